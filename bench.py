@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s (pixels x spp) of the render path on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints
+the result line.  --full adds, at N = 1, the measurements that take runs of their own: the other BASELINE
+configurations ("other_configs"), the host-buffer end-to-end figure ("end_to_end") and the CPU baseline with
+the per-pixel RMSE of the timed frame against it ("cpu_baseline", "rmse_vs_cpu", "parity_vs_cpu"); each can
+still be left out with its --no-* option.
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 as .npy files (float64 / float32, at
+most 64 MB): sums.npy, the frame's exact per-pixel radiance sums [rows j bottom-up, W, 3] (u64 fixed point
+times 2^-32: exact in float64), and rgba8.npy, the resolved RGBA8 bytes of the same frame rows [j, W, 4].
+A frame too large for the budget is cut to a fixed, seeded sample of its rows, listed in rows.npy.  The
+inputs (scene seed 1, sample seed 1) are fixed, so two builds can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process starts the N ranks itself
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` as a
@@ -11,8 +23,8 @@ child's exit code; started by an external torch.distributed.run it is one of tho
 Workloads (BASELINE.json):
   N = 1   book-1 final scene, 1200x675, 500 spp, depth 50 -- the configuration the north_star
           target (>= 1 Gsample/s) is quoted on.  configs[1] (100 spp), configs[2] (3840x2160x500)
-          and configs[3] (10k spheres, 1920x1080x256) are timed after it and reported under
-          "other_configs".
+          and configs[3] (10k spheres, 1920x1080x256) are timed after it with --full and reported
+          under "other_configs".
   N > 1   SURVEY.md 8(e)'s weak-scaling pair: configs[4]'s geometry (7680x4320) with 125 x N spp,
           rows dealt round-robin to the N ranks (N = 8 is configs[4] itself: 1000 spp); every GPU
           traces 4.147 G pixel-samples per step, exactly configs[2]'s count on one GPU.
@@ -26,7 +38,7 @@ The JSON also carries
                 events on the launch stream; counters that need rocprofv3 --pmc are replayed from
                 profiles/ and labelled with their source (null when the kernel sources differ
                 from the profiled ones);
-  cpu_baseline  Oracle A (the literal f64 CPU restatement of the reference,
+  cpu_baseline  (--full) Oracle A (the literal f64 CPU restatement of the reference,
                 oracle/oracle_f64.c) timed on this host's cores on a bounded row
                 subset of the same frame (rank 0, N=1 only).
 """
@@ -251,6 +263,30 @@ def weak_efficiency(ms_per_step, samples_per_gpu, sha, rehearsal):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, d_fix, d_rgba):
+    """--dump-outputs: the last timed step's frame as float .npy files (module docstring).  d_fix: exact sums [H, W, 3]
+    (int64 holding u64, frame rows j bottom-up); d_rgba: the resolved RGBA8 frame [H, W, 4], flipped (image row y = H-1-j)."""
+    import torch
+    H, W = int(d_fix.shape[0]), int(d_fix.shape[1])
+    row_bytes = W * 3 * 8 + W * 4 * 4
+    os.makedirs(out_dir, exist_ok=True)
+    rows = None
+    if H * row_bytes > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(H, DUMP_BUDGET_BYTES // row_bytes, replace=False))
+        idx = torch.as_tensor(rows, device=d_fix.device)
+        d_fix = d_fix.index_select(0, idx)
+        d_rgba = d_rgba.index_select(0, torch.as_tensor(H - 1 - rows, device=d_rgba.device))
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    else:
+        d_rgba = d_rgba.flip(0)                                     # frame row order, as the sums
+    sums = d_fix.cpu().numpy().view(np.uint64).astype(np.float64) * (1.0 / 4294967296.0)
+    np.save(os.path.join(out_dir, "sums.npy"), sums)
+    np.save(os.path.join(out_dir, "rgba8.npy"), d_rgba.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -262,9 +298,14 @@ def main():
                     help="samples per pixel PER GPU-share (frame spp = spp x N); default: 500 at N=1, 125 at N>1")
     ap.add_argument("--tile-rows", type=int, default=1,
                     help="rows per shard tile; 1 balances the ranks to within one row of each other")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also time the other BASELINE configurations, the host-buffer end-to-end calls and the CPU "
+                         "baseline with the RMSE of the timed frame against it (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame (exact sums, RGBA8) as float .npy files into DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: leave out the other configurations")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: leave out the end-to-end figure")
     ap.add_argument("--weak-baseline", action="store_true",
                     help="N=1 only: the single-GPU half of SURVEY.md 8(e)'s weak-scaling pair -- BASELINE configs[2], "
                          "3840x2160x500 = 4.147 G samples, the per-GPU share of the N>1 runs -- as a whole step "
@@ -276,6 +317,8 @@ def main():
                     help="N>1 logic check on a 1-GPU box: every rank renders on cuda:0 and the gather runs "
                          "over gloo on CPU tensors (RCCL refuses two ranks on one device); not a measurement")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_other_configs = args.no_end_to_end = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -399,6 +442,8 @@ def main():
                     "gather_ms": [round(float(q[2].item()), 3) for q in parts]}
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, step.last_full, d_rgba)
         frame_samples = W * H * spp_frame
         value = frame_samples * args.steps / elapsed / 1e6
         k_ms = float(np.mean(kernel_ms))

@@ -143,3 +143,35 @@ def test_weak_efficiency_is_formed_against_the_committed_single_gpu_line():
     assert abs(e["value"] - 0.95) < 1e-3 and "cross-run" in e["kind"] and e["baseline_source"].startswith("profiles/")
     assert bench.weak_efficiency(600.0, spg, "x", True)["value"] is None      # rehearsal
     assert bench.weak_efficiency(600.0, spg // 2, "x", False)["value"] is None
+
+
+def test_help_lists_full_and_dump_outputs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_writes_the_frame_exactly_and_samples_a_large_one(tmp_path, monkeypatch):
+    """--dump-outputs on host tensors standing in for the device frame: sums.npy = the u64 sums x 2^-32 in float64 (exact),
+    rgba8.npy = the flipped RGBA8 frame back in frame-row order as float32; over the byte budget a seeded row sample, the
+    same on every call, listed in rows.npy."""
+    import numpy as np
+    import torch
+    H, W = 12, 5
+    rng = np.random.default_rng(7)
+    fix = rng.integers(0, 1 << 50, (H, W, 3), dtype=np.int64)
+    rgba = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), torch.from_numpy(fix), torch.from_numpy(rgba))
+    assert sorted(os.listdir(tmp_path / "a")) == ["rgba8.npy", "sums.npy"]
+    sums, got = np.load(tmp_path / "a" / "sums.npy"), np.load(tmp_path / "a" / "rgba8.npy")
+    assert sums.dtype == np.float64 and got.dtype == np.float32
+    assert np.array_equal((sums * 4294967296.0).astype(np.int64), fix)
+    assert np.array_equal(got.astype(np.uint8), rgba[::-1])
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 5 * W * (3 * 8 + 4 * 4))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), torch.from_numpy(fix), torch.from_numpy(rgba))
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 5 and np.array_equal(rows, np.load(tmp_path / "c" / "rows.npy"))
+    j = rows.astype(np.int64)
+    assert np.all(np.diff(j) > 0) and 0 <= j[0] and j[-1] < H
+    assert np.array_equal((np.load(tmp_path / "b" / "sums.npy") * 4294967296.0).astype(np.int64), fix[j])
+    assert np.array_equal(np.load(tmp_path / "b" / "rgba8.npy").astype(np.uint8), rgba[::-1][j])

@@ -226,6 +226,24 @@ def test_bench_two_ranks_rehearsed_on_one_gpu_give_the_single_gpu_frame():
     assert two["scaling"] == "weak" and two["value"] > 0 and one["rmse_vs_cpu"] is None
 
 
+def test_bench_plain_run_dumps_the_oracle_frame(tmp_path, oracle_mod, book1_flat):
+    """A plain `bench.py --dump-outputs DIR` (no --full): the line has the headline fields and none of --full's extras, its
+    `steps` are the steps asked for, and the dumped frame is Oracle B's exact sums (x 2^-32) and RGBA8 bytes, in frame-row order."""
+    w, h, spp = 96, 54, 6
+    d = _bench("--width", str(w), "--height", str(h), "--spp", str(spp), "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["rmse_vs_cpu"] is None
+    assert not any(k in d for k in ("cpu_baseline", "other_configs", "end_to_end", "parity_vs_cpu"))
+    fb, _ = oracle_frame(oracle_mod, book1_flat, rt.book1_camera(w, h), w, h, spp)
+    sums = np.load(tmp_path / "sums.npy")
+    assert sums.dtype == np.float64 and np.array_equal(sums * 4294967296.0, fb.astype(np.float64))
+    rgba = np.load(tmp_path / "rgba8.npy")
+    assert rgba.dtype == np.float32 and np.array_equal(rgba, oracle_mod.resolve_b(fb, spp, flip=False).astype(np.float32))
+    assert not os.path.exists(tmp_path / "rows.npy")
+
+
 # ---- material / geometry corners the reference allows and no other GPU test reaches ------------------------------------------
 
 def _hand(spheres):

@@ -139,14 +139,22 @@ def test_read_png_decodes_every_row_filter(tmp_path):
 
 def test_read_png_on_the_references_own_render():
     """The one image the reference ships (rtiow_part1_final.png, written by the `image` crate's encoder): read_png() must give the sky rows
-    the committed fixture holds (tests/golden/ref_png_sky_rows.json, extracted with PIL).  Runs where the reference is present."""
+    the committed fixture holds (tests/golden/ref_png_sky_rows.json, extracted with PIL).  The input is that render's top rows,
+    tests/golden/ref_png_head.png (tests/golden/make_ref_png_head.py): the encoder's own filtered scanlines, every filter type it
+    used among them, re-deflated."""
     import json
-    src = "/root/reference/rtiow_part1_final.png"
-    if not os.path.exists(src):
-        pytest.skip("the reference tree is not on this machine")
+    import struct
+    import zlib
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    src = os.path.join(golden, "ref_png_head.png")
+    data = open(src, "rb").read()
+    rows, = struct.unpack(">I", data[20:24])                          # IHDR height
+    stride = 1 + 1200 * 4
+    raw = zlib.decompress(data[8 + 25 + 8:-12 - 4])                    # the one IDAT chunk's payload
+    assert sorted(set(raw[y * stride] for y in range(rows))) == [1, 2, 3, 4]   # Sub, Up, Average, Paeth: all undone by read_png
     im = rt.read_png(src)
-    fx = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_png_sky_rows.json")))
-    assert im.shape == (fx["height"], fx["width"], 4) and (im[:, :, 3] == 255).all()
+    fx = json.load(open(os.path.join(golden, "ref_png_sky_rows.json")))
+    assert rows <= fx["height"] and im.shape == (rows, fx["width"], 4) and (im[:, :, 3] == 255).all()
     for y, rgb in fx["constant_rows"].items():
         assert (im[int(y), :, :3] == np.array(rgb, dtype=np.uint8)).all()
     for pt in fx["points"]:
