@@ -264,8 +264,8 @@ int rt_quantize_device(rt_context *ctx, const double *x, int32_t n, uint64_t *ou
  * random_in_unit_disk's (vec3.rs:59-68) for (u11(wx), u11(wy)), as the retry loops decide them (on the integers behind the draws,
  * with the f64 expression where its roundings could decide: DESIGN.md section 3); out_uniforms[k] = (u01(wx), u11(wx), u11(wy), u11(wz)). */
 int rt_unit_accept_device(rt_context *ctx, const uint32_t *words, int32_t n, uint32_t *out_accept, double *out_uniforms);
-/* Known-answer hooks of the EARLIER matrix-pipe forms of the filter (scan modes 2-4).
- * They exist only in a library built with -DRTIOW_CROSSCHECK_MODES (tools/librtiow_hip_xcheck.so, a test
+/* Known-answer hooks of the EARLIER matrix-pipe forms of the filter (scan modes 2-4), and of the
+ * shipped mode's tile-grid footprint (kept out of the product ABI).  They exist only in a library built with -DRTIOW_CROSSCHECK_MODES (tools/librtiow_hip_xcheck.so, a test
  * artefact); the product library carries scan modes 0, 1 and 5 and does not export them. */
 #ifdef RTIOW_CROSSCHECK_MODES
 /* The two K = 4 products of the scan filter exactly as the render
@@ -280,6 +280,14 @@ int rt_filter_products_device(rt_context *ctx, const float *r1, const float *r2,
  * out_C: [16][11] the per-sphere terms. */
 int rt_filter_lifted_device(rt_context *ctx, const double *o, const double *d, const rt_sphere *spheres16,
                             float *out_D, float *out_R, float *out_C);
+/* The tile grid's footprint of the shipped scan mode (rt_device.hpp, grid_cells / grid_row_run) for n rays o + t d
+ * (f64, [n][3]; rounded to f32 as the render kernel rounds them) on the grid `grid` (x0, z0, 1/cell, x1, z1, y lo,
+ * y hi, pad: rt_tile_layout_host's out_grid) of grid_dim (1..63) cells per side, with error margins for `scale`.
+ * out_rect: [n][5] = (verdict, ix0, nx, iz0, nz), verdict -1 cannot tell / 0 no cell / else nx * nz;
+ * out_runs (or NULL): [n][63][2] = (rx0, rnx), the columns of row iz0 + k for k < nz, zeros beyond.
+ * Fails when grid_cells with and without the row-by-row segment disagree on some ray. */
+int rt_grid_cells_device(rt_context *ctx, const double *o, const double *d, int32_t n, const float grid[8], int32_t grid_dim,
+                         float scale, int32_t *out_rect, int32_t *out_runs);
 #endif /* RTIOW_CROSSCHECK_MODES */
 /* One tile of the tube filter, the shipped scan mode: o, d: [64][3] f64 rays; spheres32: 32 spheres
  * (one tile of columns, built exactly as rt_upload_scene builds them, radius floor included);

@@ -77,6 +77,7 @@ SYMBOLS = [
 XCHECK_SYMBOLS = [
     ("rt_filter_products_device", C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
     ("rt_filter_lifted_device", C.c_int, [_VP, _VP, _VP, C.POINTER(rt_sphere), _VP, _VP, _VP]),
+    ("rt_grid_cells_device", C.c_int, [_VP, _VP, _VP, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float, _VP, _VP]),
 ]
 
 _lib = None

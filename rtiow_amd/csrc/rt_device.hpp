@@ -266,8 +266,8 @@ constexpr float kTubeOriginErr = 128.0f * kUnitRoundoff;
 //     clipped piece empty only if the exit parameter lies below 0.9999 of the entry parameter; the two end points
 //     carry that error on a length <= |o| + scale, and their own rounding: the rectangle is grown by g7 + 4 e;
 //   * the cell coordinates are rounded 1e-3 cells outwards;
-//   * a direction component of magnitude < 1e-30, |o| or |d| beyond 1e15, an end point beyond 1e30 or a NaN: "cannot
-//     tell" (-1).
+//   * a direction component of magnitude < 1e-30, |o|_1 or |d|_1 beyond 1e15, an end point beyond 1e30 or a NaN anywhere:
+//     "cannot tell" (-1).
 // The same footprint ROW BY ROW (large grids): the bounding rectangle of a long diagonal piece holds far more cells
 // than the line crosses (a ray that leaves a sphere nearly horizontally stays inside the slab up to the box's edge: 3 %
 // of the rays of the 10k-sphere scene, and their rectangles made 12 cells per wave-pass out of 5).  GridSeg keeps the
@@ -308,10 +308,12 @@ __device__ __forceinline__ int grid_cells(const float (&of)[3], const float (&df
 {
     const float e = 1e-6f * (o1 + scale);
     const float dmin = __builtin_fminf(__builtin_fminf(__builtin_fabsf(df[0]), __builtin_fabsf(df[1])), __builtin_fabsf(df[2]));
-    const float dmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(df[0]), __builtin_fabsf(df[1])), __builtin_fabsf(df[2]));
+    // (|d|_1, not the largest component: v_max_f32 returns the other operand of a NaN, a sum carries it -- with the largest
+    //  component a NaN component went through to a rectangle, or to "no cell" when the other two missed the box)
+    const float dn1 = (__builtin_fabsf(df[0]) + __builtin_fabsf(df[1])) + __builtin_fabsf(df[2]);
     // ONE exit: everything below is computed whatever the answer (garbage in, clamped garbage out) and the verdict is
     // selected at the end -- four early returns cost five register moves each
-    const bool cannot0 = !(dmin > 1e-30f && dmax < 1e15f && o1 < 1e15f);
+    const bool cannot0 = !(dmin > 1e-30f && dn1 < 1e15f && o1 < 1e15f);
     const float m = g[7] + e;
     const float lo[3] = {g[0] - m, g[5] - e, g[1] - m}, hi[3] = {g[3] + m, g[6] + e, g[4] + m};
     float t_in = 0.0f, t_out = __builtin_inff();

@@ -1,6 +1,7 @@
 // rt_xcheck_kernels.hpp -- part of the CROSS-CHECK build only (-DRTIOW_CROSSCHECK_MODES: tools/librtiow_hip_xcheck.so, a test artefact).
 // Scan modes 2-4 are the earlier matrix-pipe forms of the sphere-scan filter; the product library carries modes 0, 1
-// and 5 and never includes this file.  Known-answer kernels of modes 2-4 (rt_filter_products_device, rt_filter_lifted_device).
+// and 5 and never includes this file.  Known-answer kernels of modes 2-4 (rt_filter_products_device, rt_filter_lifted_device) and of
+// the shipped mode's grid footprint (rt_grid_cells_device).
 #pragma once
 namespace rt {
 // Known-answer hook for the matrix forms of the filter: one wave, 64 ray rows x 16 sphere
@@ -56,6 +57,34 @@ __global__ __launch_bounds__(64) void lifted_products_kernel(const double *o, co
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[G][1], b1, acc, 0, 0, 0);
         for (int i = 0; i < 4; ++i) D_out[(16 * G + 4 * quad + i) * 16 + col] = acc[i];
     }
+}
+
+struct GridArgs { float g[8]; };
+// Known-answer hook for the tile grid's footprint (rt_device.hpp, grid_cells and grid_row_run -- the functions themselves, not a copy):
+// ray i = o[i] + t d[i] (f64), rounded to f32 by ray_f32 exactly as the render kernel rounds it.  rect[i] = (verdict, ix0, nx, iz0, nz),
+// verdict -1 cannot tell / 0 no cell / nx * nz; runs (may be NULL): [n][63][2], (rx0, rnx) of row iz0 + k for k < nz, zeros beyond.
+// grid_cells runs twice, with and without the row-by-row GridSeg (the two kernel instantiations call it both ways): a ray on which
+// their verdicts or rectangles differ sets *disagree (the host turns it into an error).
+__global__ __launch_bounds__(256) void grid_cells_kernel(const double *o, const double *d, int n, GridArgs ga, int G, float scale,
+                                                       int *rect, int *runs, int *disagree)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float of[3], df[3], o1;
+    ray_f32(mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), of, df, o1);
+    int ix0 = 0, nx = 0, iz0 = 0, nz = 0, jx0 = 0, jnx = 0, jz0 = 0, jnz = 0;
+    GridSeg seg;
+    const int cnt = grid_cells(of, df, o1, ga.g, G, scale, ix0, nx, iz0, nz, &seg);
+    const int cnt2 = grid_cells(of, df, o1, ga.g, G, scale, jx0, jnx, jz0, jnz, nullptr);
+    if (cnt != cnt2 || ix0 != jx0 || nx != jnx || iz0 != jz0 || nz != jnz) atomicOr(disagree, 1);
+    rect[5 * i] = cnt; rect[5 * i + 1] = ix0; rect[5 * i + 2] = nx; rect[5 * i + 3] = iz0; rect[5 * i + 4] = nz;
+    if (runs)
+        for (int k = 0; k < 63; ++k) {                  // (a fixed trip count: the writes stay inside the ray's 63 rows whatever nz is)
+            int rx0 = 0, rnx = 0;
+            if (k < nz) grid_row_run(seg, ix0, ix0 + nx - 1, (float)(iz0 + k), rx0, rnx);
+            runs[(size_t)i * 126 + 2 * k] = rx0;
+            runs[(size_t)i * 126 + 2 * k + 1] = rnx;
+        }
 }
 
 } // namespace rt

@@ -233,6 +233,23 @@ class Renderer:
                                                      Cc.ctypes.data_as(C.c_void_p)), "rt_filter_lifted_device")
         return D, R, Cc
 
+    def grid_cells(self, o, d, grid, grid_dim, scale, runs=True):
+        """The tile grid's footprint of n rays as the shipped kernel computes it (rt_device.hpp grid_cells / grid_row_run;
+        cross-check build only).  o, d: (n, 3) f64; grid: the 8 f32 of tile_layout_host.
+        Returns rect (n, 5) i32 = (verdict, ix0, nx, iz0, nz) and, with runs, (n, 63, 2) i32 = (rx0, rnx) of row iz0 + k."""
+        if not _ffi.has_crosscheck_modes():
+            raise _ffi.RtiowHipError("rt_grid_cells_device needs the -DRTIOW_CROSSCHECK_MODES build (RTIOW_HIP_LIB)")
+        o = np.ascontiguousarray(o, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(d, dtype=np.float64).reshape(-1, 3)
+        assert o.shape == d.shape
+        g = (C.c_float * 8)(*[float(v) for v in np.asarray(grid, dtype=np.float32)])
+        rect = np.zeros((len(o), 5), dtype=np.int32)
+        rr = np.zeros((len(o), 63, 2), dtype=np.int32) if runs else None
+        _ffi.check(self._lib.rt_grid_cells_device(self._h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), len(o), g,
+                                                  int(grid_dim), float(scale), rect.ctypes.data_as(C.c_void_p),
+                                                  rr.ctypes.data_as(C.c_void_p) if runs else None), "rt_grid_cells_device")
+        return (rect, rr) if runs else rect
+
     def filter_tube(self, o, d, spheres32):
         """One tile of the tube filter (the shipped scan mode), as the kernel evaluates it.
 

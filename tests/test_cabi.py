@@ -22,7 +22,9 @@ def header_functions(crosscheck=False):
     return (names(xsrc) if crosscheck else names(src))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_and_the_three_crosscheck_hooks():
+    """The product library exports the whole product header and the binding covers it; the cross-check block declares exactly
+    the three known-answer hooks (scan modes 2-4, and the grid footprint) and the product library exports none of them."""
     lib = _ffi.load()
     names = header_functions()
     assert len(names) >= 15
@@ -30,13 +32,14 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), f"{n} declared in include/rtiow_hip.h but not exported"
     assert sorted(n for n, _, _ in _ffi.SYMBOLS) == names      # the binding covers the whole header
     xnames = header_functions(crosscheck=True)
-    assert sorted(n for n, _, _ in _ffi.XCHECK_SYMBOLS) == xnames and len(xnames) == 2
-    if "RTIOW_HIP_LIB" not in os.environ:                      # the product library does not carry modes 2-4
+    assert sorted(n for n, _, _ in _ffi.XCHECK_SYMBOLS) == xnames and len(xnames) == 3
+    if "RTIOW_HIP_LIB" not in os.environ:                      # the product library does not carry modes 2-4 nor the footprint hook
         assert not any(hasattr(lib, n) for n in xnames) and not _ffi.has_crosscheck_modes()
+        assert not hasattr(lib, "rt_grid_cells_device")
 
 
 def test_crosscheck_library_exports_the_whole_header():
-    """tools/librtiow_hip_xcheck.so (built by __graft_entry__.build()) = the product ABI + the two hooks."""
+    """tools/librtiow_hip_xcheck.so (built by __graft_entry__.build()) = the product ABI + the three hooks."""
     path = os.path.join(ROOT, "tools", "librtiow_hip_xcheck.so")
     if not os.path.exists(path):
         pytest.skip("cross-check library not built")

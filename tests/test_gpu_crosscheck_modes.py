@@ -30,13 +30,14 @@ def needs_xcheck():
 
 
 def test_crosscheck_build_in_a_subprocess():
-    """The cross-check build: its known-answer tests, then bit-exact parity vs Oracle B under each of the
-    scan modes 2, 3, 4 (and 1, 5 of the same build)."""
+    """The cross-check build: its known-answer tests (modes 2-4, and the grid footprint of the shipped mode:
+    test_gpu_grid_footprint.py), then bit-exact parity vs Oracle B under each of the scan modes 2, 3, 4 (and 1, 5 of the same build)."""
     if _ffi.has_crosscheck_modes():
         pytest.skip("already inside the cross-check run")
     assert os.path.exists(XCHECK_LIB), "tools/librtiow_hip_xcheck.so missing: run __graft_entry__.build()"
     base = dict(os.environ, RTIOW_HIP_LIB=XCHECK_LIB)
-    runs = [("5", ["tests/test_gpu_crosscheck_modes.py", "tests/test_gpu_properties.py::test_all_scan_filters_give_the_same_bits"])]
+    runs = [("5", ["tests/test_gpu_crosscheck_modes.py", "tests/test_gpu_grid_footprint.py",
+                   "tests/test_gpu_properties.py::test_all_scan_filters_give_the_same_bits"])]
     parity = ["tests/test_gpu_parity.py", "-k", "bit_exact or tie_rule or filter_never or tenk or tie_between"]
     runs += [(m, parity) for m in ("2", "3", "4", "1")]
     for mode, what in runs:

@@ -2,7 +2,9 @@
 sizes and seeds; every frame must equal Oracle B bit for bit.  Usage: fuzz_parity.py [cases] [seed0]
 FUZZ_LARGE=p: share of scenes with enough spheres for a grid of more than 64 cells (default 0.15);
 FUZZ_U53=p: share of cases rendered with RT_FLAG_UNIFORM53 (default 0); FUZZ_HIGH_SPP=p: share of cases with 69..400 samples per
-pixel on a tiny image (with RTIOW_LARGE_BLOCK_MIN_ITEMS=0 those launches use the work blocks of 1 024 pixel-samples)."""
+pixel on a tiny image (with RTIOW_LARGE_BLOCK_MIN_ITEMS=0 those launches use the work blocks of 1 024 pixel-samples);
+FUZZ_VIEWS=p: share of cases whose camera has a random unit vup and its look_from anywhere -- below the ground, inside spheres
+(default 0; the other cases' draws are unchanged)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -47,6 +49,18 @@ for case in range(cases):
     la = rng.uniform(-spread, spread, 3) * 0.3
     cam = rt.Camera(lf, la, rt.Vec3(0, 1, 0), float(rng.uniform(5, 120)), W / H, float(rng.uniform(0.0, 0.5)) * spread / 10,
                     float(np.linalg.norm(lf - la)) + 1e-3)
+    views = float(os.environ.get("FUZZ_VIEWS", "0"))
+    if views > 0 and rng.random() < views:
+        lf = rng.uniform(-spread, spread, 3) * rng.choice([0.3, 1.0, 3.0])        # anywhere: below the ground too
+        if rng.random() < 0.3:                                                   # inside (or on) one of the spheres
+            k = int(rng.integers(0, len(flat)))
+            lf = flat["center"][k] + rng.normal(size=3) * 0.5 * abs(flat["radius"][k]) / np.sqrt(3)
+        la = lf + rng.normal(size=3)
+        vup = rng.normal(size=3)
+        while np.linalg.norm(np.cross(vup, la - lf)) < 1e-3 * np.linalg.norm(vup) * np.linalg.norm(la - lf):
+            vup = rng.normal(size=3)
+        cam = rt.Camera(lf, la, vup / np.linalg.norm(vup), float(rng.uniform(5, 170)), W / H,
+                        float(rng.uniform(0.0, 0.5)) * spread / 10, float(np.linalg.norm(lf - la)))
     seed = int(rng.integers(1, 2 ** 62))
     u53 = rng.random() < float(os.environ.get("FUZZ_U53", "0"))
     r.upload_scene(flat)
