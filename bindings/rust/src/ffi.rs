@@ -108,6 +108,17 @@ pub struct rt_stats {
     pub direct_samples: u64,
 }
 
+/// Adaptive sampling (`rt_render_adaptive`, `rt_select_pixels_*`): `step` samples per pass; a pixel stops once its error
+/// estimate -- the mean absolute difference of its two half-buffer means over sqrt(max(mean, dark_floor)) -- is <= threshold.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_adaptive {
+    pub step: i32,
+    pub reserved: i32,
+    pub threshold: f64,
+    pub dark_floor: f64,
+}
+
 // Layout assertions: the numbers tests/test_cabi.py asserts on the C side (ctypes mirrors of the header).
 const _: () = assert!(size_of::<rt_sphere>() == 72);
 const _: () = assert!(offset_of!(rt_sphere, kind) == 64);
@@ -117,6 +128,8 @@ const _: () = assert!(offset_of!(rt_params, t_min) == 24);
 const _: () = assert!(offset_of!(rt_params, seed) == 32);
 const _: () = assert!(size_of::<rt_stats>() == 584);
 const _: () = assert!(offset_of!(rt_stats, live_per_bounce) == 64);
+const _: () = assert!(offset_of!(rt_adaptive, threshold) == 8);
+const _: () = assert!(offset_of!(rt_adaptive, dark_floor) == 16);
 
 #[link(name = "rtiow_hip")]
 extern "C" {
@@ -138,6 +151,25 @@ extern "C" {
                             spp: i64, flip: i32, out_rgba: *mut u8) -> i32;
     pub fn rt_render_rgba8(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, flip: i32,
                            out_rgba: *mut u8, stats: *mut rt_stats) -> i32;
+    /// src/main.rs:122-139 for a LIST of pixels (g = j * width + i, j = 0 the bottom row); d_fix: [n_pixels][3] u64, entry k for d_pixels[k].
+    pub fn rt_render_pixels_device(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, d_pixels: *const u32,
+                                   n_pixels: i64, d_fix: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_render_pixels(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, pixels: *const u32,
+                            n_pixels: i64, out_fix: *mut u64, stats: *mut rt_stats) -> i32;
+    /// Which pixels still need samples after a round that brought them to `n` (ascending pixel numbers).
+    pub fn rt_select_pixels_device(ctx: *mut rt_context, d_fix: *const c_void, d_half: *const c_void, d_count: *const c_void,
+                                   width: i32, height: i32, n: i32, a: *const rt_adaptive, d_list_out: *mut c_void,
+                                   d_n_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_select_pixels_host(fix: *const u64, half: *const u64, count: *const u32, width: i32, height: i32, n: i32,
+                                 a: *const rt_adaptive, list_out: *mut u32, n_out: *mut i64) -> i32;
+    /// src/main.rs:130-137 with a per-pixel number of samples; `p.spp` is the most a pixel may get.
+    pub fn rt_render_adaptive(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, a: *const rt_adaptive,
+                              out_fix: *mut u64, out_half: *mut u64, out_count: *mut u32, stats: *mut rt_stats) -> i32;
+    /// `Color::to_rgba` (src/vec3.rs:403-421) with each pixel's own sample count.
+    pub fn rt_resolve_rgba8_counts_device(ctx: *mut rt_context, d_fix: *const c_void, d_count: *const c_void, width: i32,
+                                          rows: i32, flip: i32, d_rgba: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_resolve_rgba8_counts(ctx: *mut rt_context, fix: *const u64, count: *const u32, width: i32, rows: i32,
+                                   flip: i32, out_rgba: *mut u8) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -5,6 +5,7 @@
 //   rtiow_render [--width W] [--height H] [--spp N] [--depth D] [--seed S] [--scene-seed S]
 //                [--grid LO HI] [--device K] [--out image.png|image.ppm] [--dump-scene scene.bin] [--scene scene.bin]
 //                [--devices 0,1,..  [--tile-rows T] [--force-rccl]] [--uniform53] [--two-calls] [--passes N]
+//                [--adaptive THRESHOLD [--step N]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -13,6 +14,9 @@
 // --passes N: main.rs:130-137's sample loop as N additive launches (sample_begin, RT_FLAG_ACCUMULATE | RT_FLAG_OVERLAPPED) issued alternately on TWO streams of one
 // context, so that pass k + 1 fills the end-of-launch tail of pass k (a context holds two launches' state); the sums are exact integers, so the
 // image is the one the single call gives, byte for byte.
+// --adaptive THRESHOLD [--step N, default 8]: main.rs:130-137 with a per-pixel number of samples (rt_render_adaptive: passes of N samples, a pixel
+// stops once its error estimate is <= THRESHOLD; --spp is the most a pixel may get, a multiple of 2 N) and Color::to_rgba with each pixel's own
+// count (rt_resolve_rgba8_counts); the summary line adds the mean / min / max samples per pixel.  Single device.
 // --devices: the frame's rows are dealt round-robin to one rt_context per listed device, each driven by
 // its own host thread, and gathered with ONE RCCL ncclGather to the first device (host/rtiow_multi.hpp).
 // A device may be listed more than once (two contexts on one GPU from two threads: the threading rule of
@@ -41,6 +45,9 @@ int main(int argc, char **argv)
     bool force_rccl = false, uniform53 = false, two_calls = false;
     int passes = 1;
     int tile_rows = 1;
+    bool adaptive = false;
+    double threshold = 0.0;
+    int step = 8;
     if (argc == 5 && !std::strcmp(argv[1], "--reassembly-plan")) {
         const int H = std::atoi(argv[2]), T = std::atoi(argv[3]), n = std::atoi(argv[4]);
         if (H < 1 || T < 1 || n < 1) { std::fprintf(stderr, "--reassembly-plan H T N: all >= 1\n"); return 2; }
@@ -77,6 +84,8 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--uniform53")) uniform53 = true;
         else if (!std::strcmp(argv[i], "--two-calls")) two_calls = true;
         else if (arg("--passes")) passes = std::atoi(argv[++i]);
+        else if (arg("--adaptive")) { adaptive = true; threshold = std::atof(argv[++i]); }
+        else if (arg("--step")) step = std::atoi(argv[++i]);
         else if (arg("--dump-scene")) dump = argv[++i];
         else if (arg("--scene")) scene_file = argv[++i];
         else if (!std::strcmp(argv[i], "--grid") && i + 2 < argc) { lo = std::atoi(argv[++i]); hi = std::atoi(argv[++i]); }
@@ -112,6 +121,11 @@ int main(int argc, char **argv)
     const rt_camera rc_cam = cam.flat();
     std::vector<uint8_t> rgba(npix * 4);
     rt_stats st{};
+    std::string count_note;
+    if (adaptive && (!devices.empty() || passes > 1 || two_calls || uniform53)) {
+        std::fprintf(stderr, "--adaptive runs on one device and goes with none of --devices, --passes, --two-calls, --uniform53\n");
+        return 2;
+    }
     if (!devices.empty()) {
         // one rt_context per listed device, each driven by its own host thread; rows dealt round-robin;
         // one RCCL gather of the exact sums to the first device (main.rs:122-123 + the ordered collect() :139)
@@ -129,7 +143,22 @@ int main(int argc, char **argv)
         if (rc) return die("rt_create", rc);
         rc = rt_upload_scene(ctx, flat.data(), (int32_t)flat.size());
         if (rc) return die("rt_upload_scene", rc);
-        if (passes > 1) {
+        if (adaptive) {
+            rt_adaptive ad{};
+            ad.step = step; ad.reserved = 0; ad.threshold = threshold; ad.dark_floor = 0.01;
+            std::vector<uint64_t> fix(npix * 3);
+            std::vector<uint32_t> count(npix);
+            rc = rt_render_adaptive(ctx, &rc_cam, &p, &ad, fix.data(), nullptr, count.data(), &st);
+            if (rc) return die("rt_render_adaptive", rc);
+            rc = rt_resolve_rgba8_counts(ctx, fix.data(), count.data(), width, height, 1, rgba.data());
+            if (rc) return die("rt_resolve_rgba8_counts", rc);
+            uint32_t cmin = count[0], cmax = count[0];
+            for (uint32_t c : count) { cmin = c < cmin ? c : cmin; cmax = c > cmax ? c : cmax; }
+            char note[160];
+            std::snprintf(note, sizeof(note), " adaptive threshold %g step %d: %.1f samples per pixel (min %u, max %u),", threshold, step,
+                          (double)st.samples / (double)npix, cmin, cmax);
+            count_note = note;
+        } else if (passes > 1) {
             // progressive passes, overlapped: device buffers, two streams, every pass adds its samples to the same exact sums
             if (passes > spp) { std::fprintf(stderr, "--passes %d: more passes than samples per pixel\n", passes); return 2; }
             auto hip_die = [](hipError_t e, const char *what) { std::fprintf(stderr, "%s: %s\n", what, hipGetErrorString(e)); return 1; };
@@ -185,7 +214,8 @@ int main(int argc, char **argv)
         for (size_t k = 0; k < npix; ++k) std::fwrite(&rgba[4 * k], 1, 3, f);
         std::fclose(f);
     }
-    std::printf("%dx%d spp %d: %llu rays, kernel %.3f ms (%.1f Msamples/s) -> %s\n", width, height, spp,
-                (unsigned long long)st.rays_traced, st.kernel_ms, npix * (double)spp / st.kernel_ms / 1e3, out.c_str());
+    std::printf("%dx%d spp %d:%s %llu rays, kernel %.3f ms (%.1f Msamples/s) -> %s\n", width, height, spp, count_note.c_str(),
+                (unsigned long long)st.rays_traced, st.kernel_ms,
+                (adaptive ? (double)st.samples : npix * (double)spp) / st.kernel_ms / 1e3, out.c_str());
     return 0;
 }

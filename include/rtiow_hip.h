@@ -136,7 +136,8 @@ typedef struct {
     int32_t  kernel_variant;     /* which instantiation of the kernel ran, as bits: 1 the scan_mode-5 kernel for scenes whose
                                     tile grid has <= 64 cells (else the general one, and every other scan mode); 2 the
                                     RT_FLAG_UNIFORM53 instantiation; 4 work blocks of 1 024 pixel-samples instead of 256 (launches of
-                                    >= 2 x 10^8 pixel-samples at >= 147 samples per pixel; >= 69 on the small-grid kernel) */
+                                    >= 2 x 10^8 pixel-samples at >= 147 samples per pixel; >= 69 on the small-grid kernel); 8 the
+                                    pixel-list variant (rt_render_pixels_device) */
     uint64_t live_per_bounce[64]; /* rays traced at bounce index k (0 = camera ray; indices >= 63 share the
                                     last slot); sums to rays_traced (RT_FLAG_DIAG_STATS, else 0) */
     uint64_t direct_samples;     /* samples added to the frame buffer one by one instead of through their block's
@@ -242,6 +243,80 @@ int rt_resolve_rgba8(rt_context *ctx, const uint64_t *fix, int32_t width, int32_
  * (RT_FLAG_ACCUMULATE is ignored, as in rt_render); synchronous.  stats may be NULL. */
 int rt_render_rgba8(rt_context *ctx, const rt_camera *cam, const rt_params *p, int32_t flip,
                     uint8_t *out_rgba, rt_stats *stats);
+
+/* ---- pixel lists: main.rs:122-139 for SOME pixels of the frame ------------- */
+
+/* Renders p->spp samples of the n_pixels listed pixels of the p->width x p->height frame (crop windows, masks, re-rendering a
+ * region, picking; the passes of rt_render_adaptive).  d_pixels: device [n_pixels] u32 global pixel numbers g = j * width + i
+ * (j = 0 the BOTTOM row, as everywhere), each < width * height, in any order, duplicates allowed.  d_fix: device
+ * [n_pixels][3] u64 exact sums, COMPACT: entry k belongs to d_pixels[k].
+ * Sample s of listed pixel g is exactly the sample a dense render gives that pixel -- the body of main.rs:130-136 with
+ * Philox key (g, sample_begin + s) and u, v (main.rs:131-132) from the pixel's own (i, j) over the FULL frame's width - 1,
+ * height - 1 --, so entry k equals the dense render's sums at (j, i): a list is still ONE Oracle-B render of those samples.
+ * Honours spp, sample_begin, max_depth, t_min, seed and RT_FLAG_ACCUMULATE (which adds to d_fix -- not with duplicates in flight
+ * on two streams unless d_fix was zeroed first, as for rt_render_device); RT_FLAG_OVERLAPPED is accepted and ignored.
+ * Runs the shipped kernel's pixel-list variant only: RT_FLAG_UNIFORM53, RT_FLAG_DIAG_STATS, RT_FLAG_NO_FILTER, a context created
+ * under RTIOW_SCAN_MODE=1 and shard_count != 1 are RT_ERR_INVALID_ARGUMENT, found before anything is touched (tile_rows and
+ * shard_index are unused).  n_pixels == 0 succeeds and does nothing.  Asynchronous on `stream`; shares the context's two
+ * per-launch slots with rt_render_device, and rt_last_stats reports on it (samples = n_pixels * spp).  Lists in ascending
+ * order keep a wave's 64 camera rays on neighbouring pixels, which the tile grid relies on for speed (not for correctness). */
+int rt_render_pixels_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const uint32_t *d_pixels,
+                            int64_t n_pixels, void *d_fix, void *stream);
+/* Host-buffer form, synchronous, starts from zero (RT_FLAG_ACCUMULATE is ignored); a listed number >= width * height is
+ * RT_ERR_INVALID_ARGUMENT.  stats may be NULL. */
+int rt_render_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, const uint32_t *pixels, int64_t n_pixels,
+                     uint64_t *out_fix, rt_stats *stats);
+
+/* ---- adaptive sampling: main.rs:130-137 with a per-pixel number of samples -- */
+
+/* The reference gives every pixel samples_per_pixel samples (main.rs:27,130).  Here a pixel stops when its error estimate
+ * is small.  State per frame: fix [H][W][3] u64 (all samples), half [H][W][3] u64 (the samples of the EVEN-numbered passes
+ * only), count [H][W] u32 (samples in fix).  Pass k renders samples [k step, (k + 1) step) of the pixels active in its
+ * round; a round is two passes, so half always holds exactly count / 2 samples.  After a round that brought the active
+ * pixels to n samples, for every pixel with count == n (a "candidate"):
+ *     d_c  = | 2 half_c - fix_c |                       exact integers, c = r, g, b
+ *     D    = ((double)d_r + (double)d_g) + (double)d_b
+ *     S    = ((double)fix_r + (double)fix_g) + (double)fix_b
+ *     sc   = 1.0 / ((double)n * 4294967296.0)
+ *     err  = (D * sc) / sqrt(max(S * sc, dark_floor))
+ *     noisy = candidate && !(err <= threshold)
+ *     active_next = candidate && (a pixel of the 3x3 neighbourhood, clipped at the frame's edges, is noisy)
+ * in IEEE binary64, this operation order, no fused multiply-add.  D sc is the mean absolute difference of the two half
+ * means (an estimate of the standard error of the pixel's mean); the denominator makes it relative for bright pixels.
+ * A pixel that leaves the active set never returns. */
+typedef struct {
+    int32_t step;                /* samples per pass, >= 1                           */
+    int32_t reserved;            /* 0                                                */
+    double  threshold;           /* >= 0; 0: every pixel goes on to the cap          */
+    double  dark_floor;          /* > 0: the least mean radiance (r + g + b) the error is taken relative to */
+} rt_adaptive;                   /* 24 bytes */
+
+/* The selection on device buffers, asynchronous on `stream`.  d_fix, d_half: [height][width][3] u64; d_count:
+ * [height][width] u32; n: even, 2 <= n <= 32766.  d_list_out: capacity width * height u32, receives the active pixels'
+ * numbers g in ASCENDING order (the same list on every run: an ordered compaction, no atomics); d_n_out: one u32, their number. */
+int rt_select_pixels_device(rt_context *ctx, const void *d_fix, const void *d_half, const void *d_count, int32_t width,
+                            int32_t height, int32_t n, const rt_adaptive *a, void *d_list_out, void *d_n_out, void *stream);
+/* The same selection on host buffers, no device needed: the library's own CPU statement of the rule. */
+int rt_select_pixels_host(const uint64_t *fix, const uint64_t *half, const uint32_t *count, int32_t width, int32_t height,
+                          int32_t n, const rt_adaptive *a, uint32_t *list_out, int64_t *n_out);
+
+/* The loop.  p->spp = the MOST samples a pixel may get: a multiple of 2 * step and <= 32766 (so that n * 2^48 < 2^63 and the
+ * differences above fit a signed 64-bit integer whatever the scene); p->sample_begin == 0; shard_count == 1; the flags
+ * rt_render_pixels_device rejects are rejected.  Round 1 renders every pixel (2 passes of `step`); then select, render the
+ * list, add back, until the list is empty or count == p->spp.  Everything stays on the device between passes; per round the
+ * host reads back one word (the list's length).  out_fix, out_half: [height][width][3] u64 (out_half may be NULL);
+ * out_count: [height][width] u32.  stats (may be NULL): samples and rays_traced summed over the passes (samples ==
+ * the sum of out_count), kernel_ms the sum of the render kernels, the launch shape of the last pass.  Synchronous. */
+int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_adaptive *a,
+                       uint64_t *out_fix, uint64_t *out_half, uint32_t *out_count, rt_stats *stats);
+
+/* Color::to_rgba with each pixel's OWN sample count (vec3.rs:403-421 with samples_per_pixel = count[p]) + the row flip
+ * (main.rs:141-145): the resolve of an adaptive frame.  d_count: device [rows][width] u32, every entry >= 1. */
+int rt_resolve_rgba8_counts_device(rt_context *ctx, const void *d_fix, const void *d_count, int32_t width, int32_t rows,
+                                   int32_t flip, void *d_rgba, void *stream);
+/* Host-buffer form (copies in, resolves on the device, copies out). */
+int rt_resolve_rgba8_counts(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int32_t width, int32_t rows,
+                            int32_t flip, uint8_t *out_rgba);
 
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);

@@ -38,6 +38,10 @@ class rt_stats(C.Structure):
                 ("live_per_bounce", C.c_uint64 * 64), ("direct_samples", C.c_uint64)]
 
 
+class rt_adaptive(C.Structure):
+    _fields_ = [("step", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double), ("dark_floor", C.c_double)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -60,6 +64,13 @@ SYMBOLS = [
     ("rt_resolve_rgba8_device", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _VP, _VP]),
     ("rt_resolve_rgba8", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _VP]),
     ("rt_render_rgba8", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.c_int32, _VP, C.POINTER(rt_stats)]),
+    ("rt_render_pixels_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, C.c_int64, _VP, _VP]),
+    ("rt_render_pixels", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, C.c_int64, _VP, C.POINTER(rt_stats)]),
+    ("rt_select_pixels_device", C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(rt_adaptive), _VP, _VP, _VP]),
+    ("rt_select_pixels_host", C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(rt_adaptive), _VP, C.POINTER(C.c_int64)]),
+    ("rt_render_adaptive", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive), _VP, _VP, _VP, C.POINTER(rt_stats)]),
+    ("rt_resolve_rgba8_counts_device", C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP]),
+    ("rt_resolve_rgba8_counts", C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -93,6 +93,10 @@ struct rt_context {
     void *d_stage_sum = nullptr; size_t stage_sum_bytes = 0;
     void *d_stage_rgba = nullptr; size_t stage_rgba_bytes = 0;
     int blocks_per_cu = 0;     // 0 = occupancy query
+    // rt_select_pixels_device's scratch (noisy / active flags, the workgroups' counts) and rt_render_adaptive's frame state
+    void *d_sel = nullptr; size_t sel_bytes = 0;
+    void *d_adapt = nullptr; size_t adapt_bytes = 0;
+    void *d_stage_list = nullptr; size_t stage_list_bytes = 0;   // rt_render_pixels: the list on the device
     int ring_min_spp = 0;                 // RTIOW_RING_MIN_SPP (diagnostic): spp per launch from which block sums are kept in LDS (0: the kernel's own minimum)
 };
 
@@ -280,6 +284,82 @@ int launch_render(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, in
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(ctx->ev1, stream));
     return RT_OK;
+}
+
+// the scene's tables and grid, as every render kernel reads them
+void set_scene_params(const rt_context *ctx, rt::KParams &kp)
+{
+    kp.filt = ctx->d_filt; kp.geo = ctx->d_geo; kp.mat = ctx->d_mat;
+    kp.n_tiles = ctx->n_tiles;
+#ifdef RTIOW_CROSSCHECK_MODES
+    kp.x.bmat = ctx->x.d_bmat; kp.x.kpt = ctx->x.d_kpt;
+    kp.x.bmat16 = ctx->x.d_bmat16; kp.x.kpt16 = ctx->x.d_kpt16; kp.x.bmatL = ctx->x.d_bmatL;
+#endif
+    kp.btube = ctx->d_btube; kp.tube_rho = ctx->tube_rho;
+    kp.geo_slot = ctx->d_geo_slot; kp.slot_orig = ctx->d_slot_orig;
+    kp.n_global = ctx->n_global; kp.grid_dim = ctx->grid_dim;
+    kp.grid_rows = 0ull;
+    for (int k = 0; ctx->grid_dim > 0 && (k + 1) * ctx->grid_dim <= 64; ++k) kp.grid_rows |= 1ull << (k * ctx->grid_dim);
+    for (int k = 0; k < 8; ++k) kp.grid[k] = ctx->grid[k];
+    kp.scene_scale = ctx->scene_scale;
+    kp.n_always = ctx->n_always;
+    for (int e = 0; e < 8; ++e) kp.always_idx[e] = ctx->always_idx[e];
+}
+
+// Takes the other slot of per-launch state for a launch on `stream`; if the launch that used it last is still running (on another
+// stream), `stream` waits for it -- the host does not.  (A call is validated BEFORE it takes a slot.)
+int next_launch_slot(rt_context *ctx, hipStream_t stream, rt::KParams &kp)
+{
+    ctx->cur = (ctx->cur + 1) % rt_context::kSlots;
+    ctx->d_queue = ctx->q_slots[ctx->cur]; ctx->d_stats = ctx->s_slots[ctx->cur];
+    ctx->ev0 = ctx->e0_slots[ctx->cur]; ctx->ev1 = ctx->e1_slots[ctx->cur];
+    if (ctx->slot_used[ctx->cur]) RT_HIP(hipStreamWaitEvent(stream, ctx->ev1, 0));
+    ctx->slot_used[ctx->cur] = true;
+    kp.queue = ctx->d_queue; kp.stats = ctx->d_stats;
+    return RT_OK;
+}
+
+// what a pixel-list render accepts beyond validate_params: checked before anything is touched.  The checks that need no context come
+// first (so a caller -- and a test -- without a device still gets the precise message), then the context's own.
+int validate_pixel_list(const rt_context *ctx, const rt_camera *cam, const rt_params *p, int64_t n_pixels)
+{
+    int rc = validate_params(p);
+    if (rc) return rc;
+    if (p->flags & (RT_FLAG_UNIFORM53 | RT_FLAG_DIAG_STATS | RT_FLAG_NO_FILTER))
+        return fail(RT_ERR_INVALID_ARGUMENT, "pixel-list renders run the shipped kernel only: RT_FLAG_UNIFORM53, RT_FLAG_DIAG_STATS and "
+                    "RT_FLAG_NO_FILTER are not available on them (flags 0x%x)", p->flags);
+    if (p->shard_count != 1)
+        return fail(RT_ERR_INVALID_ARGUMENT, "pixel-list renders are not sharded: shard_count must be 1 (is %d)", p->shard_count);
+    if (n_pixels < 0 || n_pixels > 0x7fffffffLL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "n_pixels %lld out of range [0, 2^31)", (long long)n_pixels);
+    if (!ctx || !cam) return fail(RT_ERR_INVALID_ARGUMENT, "ctx/cam is NULL");
+    if (ctx->scan_mode != 5)
+        return fail(RT_ERR_INVALID_ARGUMENT, "pixel-list renders need the shipped scan mode 5; this context was created under RTIOW_SCAN_MODE=%d", ctx->scan_mode);
+    return RT_OK;
+}
+
+int validate_adaptive(const rt_adaptive *a)
+{
+    if (!a) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive is NULL");
+    if (a->step < 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.step must be >= 1 (is %d)", a->step);
+    if (a->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.reserved must be 0");
+    if (!(a->threshold >= 0.0)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.threshold must be >= 0 (and not a NaN)");
+    if (!(a->dark_floor > 0.0) || !(a->dark_floor < INFINITY))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.dark_floor must be > 0 and finite (with a zero floor a black pixel's error is 0/0)");
+    return RT_OK;
+}
+
+constexpr int kAdaptiveMaxSpp = 32766;     // n * 2^48 < 2^63: the half-buffer differences fit a signed 64-bit integer whatever the scene
+
+int validate_select(const void *fix, const void *half, const void *count, int32_t width, int32_t height, int32_t n, const rt_adaptive *a,
+                    const void *list_out, const void *n_out)
+{
+    if (!fix || !half || !count || !list_out || !n_out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_select_pixels: a buffer is NULL");
+    if (width < 1 || height < 1 || (long long)width * height > 0x7fffffffLL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_select_pixels: bad width/height");
+    if (n < 2 || n > kAdaptiveMaxSpp || (n & 1))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_select_pixels: n = %d samples must be even (two halves) and in [2, %d]", n, kAdaptiveMaxSpp);
+    return validate_adaptive(a);
 }
 
 // MODE 5 numbers candidates by table column in 26 bits (the pool word of rt_kernels.hpp is column << 6 | ray), and the
@@ -504,6 +584,7 @@ int rt_destroy(rt_context *ctx)
         if (ctx->e1_slots[k]) (void)hipEventDestroy(ctx->e1_slots[k]);
     }
     (void)hipFree(ctx->d_stage_fix); (void)hipFree(ctx->d_stage_sum); (void)hipFree(ctx->d_stage_rgba);
+    (void)hipFree(ctx->d_sel); (void)hipFree(ctx->d_adapt); (void)hipFree(ctx->d_stage_list);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return RT_OK;
@@ -707,30 +788,12 @@ int rt_render_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
     kp.magic_spp = magic_for(p->spp); kp.magic_width = magic_for(p->width); kp.magic_tile = magic_for(p->tile_rows);
     kp.use_ring = use_ring ? 1 : 0;
     kp.block_items = item_block;
-    kp.filt = ctx->d_filt; kp.geo = ctx->d_geo; kp.mat = ctx->d_mat;
-    kp.n_tiles = ctx->n_tiles;
-#ifdef RTIOW_CROSSCHECK_MODES
-    kp.x.bmat = ctx->x.d_bmat; kp.x.kpt = ctx->x.d_kpt;
-    kp.x.bmat16 = ctx->x.d_bmat16; kp.x.kpt16 = ctx->x.d_kpt16; kp.x.bmatL = ctx->x.d_bmatL;
-#endif
-    kp.btube = ctx->d_btube; kp.tube_rho = ctx->tube_rho;
-    kp.geo_slot = ctx->d_geo_slot; kp.slot_orig = ctx->d_slot_orig;
-    kp.n_global = ctx->n_global; kp.grid_dim = ctx->grid_dim;
-    kp.grid_rows = 0ull;
-    for (int k = 0; ctx->grid_dim > 0 && (k + 1) * ctx->grid_dim <= 64; ++k) kp.grid_rows |= 1ull << (k * ctx->grid_dim);
-    for (int k = 0; k < 8; ++k) kp.grid[k] = ctx->grid[k];
-    kp.scene_scale = ctx->scene_scale;
-    kp.n_always = ctx->n_always;
-    for (int e = 0; e < 8; ++e) kp.always_idx[e] = ctx->always_idx[e];
+    set_scene_params(ctx, kp);
     kp.fix = (unsigned long long *)d_fix;
     // the other slot of per-launch state; if the launch that used it last is still running (on another stream), THIS stream waits for
     // it -- the host does not -- before the counters are cleared
-    ctx->cur = (ctx->cur + 1) % rt_context::kSlots;
-    ctx->d_queue = ctx->q_slots[ctx->cur]; ctx->d_stats = ctx->s_slots[ctx->cur];
-    ctx->ev0 = ctx->e0_slots[ctx->cur]; ctx->ev1 = ctx->e1_slots[ctx->cur];
-    if (ctx->slot_used[ctx->cur]) RT_HIP(hipStreamWaitEvent(stream, ctx->ev1, 0));
-    ctx->slot_used[ctx->cur] = true;
-    kp.queue = ctx->d_queue; kp.stats = ctx->d_stats;
+    rc = next_launch_slot(ctx, stream, kp);
+    if (rc) return rc;
 
     if (!(p->flags & RT_FLAG_ACCUMULATE) && npix > 0)
         RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(unsigned long long), stream));
@@ -956,6 +1019,306 @@ int rt_render_rgba8(rt_context *ctx, const rt_camera *cam, const rt_params *p, i
         RT_HIP(hipStreamSynchronize(ctx->own_stream));
     }
     if (stats) return rt_last_stats(ctx, stats);
+    return RT_OK;
+}
+
+// ---- pixel lists -------------------------------------------------------------------------------------------------------------
+int rt_render_pixels_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const uint32_t *d_pixels,
+                            int64_t n_pixels, void *d_fix, void *stream_v)
+{
+    int rc = validate_pixel_list(ctx, cam, p, n_pixels);
+    if (rc) return rc;
+    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (n_pixels == 0) return RT_OK;
+    if (!d_pixels || !d_fix) return fail(RT_ERR_INVALID_ARGUMENT, "d_pixels/d_fix is NULL");
+    const unsigned long long total_items = (unsigned long long)n_pixels * (unsigned long long)p->spp;
+    // work blocks as rt_render_device picks them for the shipped kernel's ring of 2 x 16 pixel slots: 256 pixel-samples from 17 samples per
+    // pixel on, the largest multiple of 64 whose pixels fit the slots down to 5, every sample on its own below (never the blocks of 1 024)
+    unsigned small_block = 0;
+    for (unsigned items = rt::kItemBlock; items >= 64u && p->spp >= 1; items -= 64u)
+        if ((items - 1u + (unsigned)p->spp - 1u) / (unsigned)p->spp + 1u <= 2u * (unsigned)rt::kRingSlots) { small_block = items; break; }
+    const bool use_ring = small_block != 0u && p->spp >= ctx->ring_min_spp;
+    const unsigned item_block = use_ring ? small_block : rt::kItemBlock;
+    const unsigned long long n_blocks = (total_items + item_block - 1) / item_block;
+    if (n_blocks > 0x7fffffffULL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "n_pixels*spp = %llu pixel-samples in one launch: at most 2^31 blocks of %d", total_items, (int)item_block);
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+
+    rt::KParams kp;
+    memset(&kp, 0, sizeof(kp));
+    memcpy(&kp.cam, cam, sizeof(rt_camera));
+    kp.width = p->width; kp.height = p->height;
+    kp.spp = p->spp; kp.sample_begin = p->sample_begin; kp.max_depth = p->max_depth;
+    kp.t_min = p->t_min;
+    kp.k0 = (uint32_t)p->seed; kp.k1 = (uint32_t)(p->seed >> 32);
+    kp.tile_rows = 1; kp.shard_index = 0; kp.shard_count = 1;            // (unused by the variant)
+    kp.rows = 1; kp.n_spheres = ctx->n_spheres;
+    kp.npix = (uint32_t)n_pixels; kp.total_items = total_items; kp.n_blocks = (uint32_t)n_blocks;
+    kp.inv_spp = p->spp > 0 ? 1.0 / (double)p->spp : 0.0;
+    kp.inv_width = 1.0 / (double)p->width;
+    kp.magic_spp = (p->spp <= 1 || p->spp >= 32768) ? 0u : (uint32_t)(0x100000000ULL / (unsigned long long)p->spp + 1ULL);   // udiv_small
+    kp.use_ring = use_ring ? 1 : 0;
+    kp.block_items = item_block;
+    set_scene_params(ctx, kp);
+    kp.fix = (unsigned long long *)d_fix;
+    kp.pix_list = d_pixels;
+    rc = next_launch_slot(ctx, stream, kp);
+    if (rc) return rc;
+
+    if (!(p->flags & RT_FLAG_ACCUMULATE))
+        RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)n_pixels * 3 * sizeof(unsigned long long), stream));
+    RT_HIP(hipMemsetAsync(ctx->d_queue, 0, 64, stream));
+    RT_HIP(hipMemsetAsync(ctx->d_stats, 0, 1024, stream));
+    memset(&ctx->last, 0, sizeof(ctx->last));
+    ctx->last.n_spheres = ctx->n_spheres;
+    ctx->last.block_threads = rt::kBlock;
+    ctx->zero_depth_samples = 0;
+    if (p->max_depth == 0 || total_items == 0) {                         // (as rt_render_device: black without tracing, nothing to launch)
+        RT_HIP(hipEventRecord(ctx->ev0, stream));
+        RT_HIP(hipEventRecord(ctx->ev1, stream));
+        ctx->zero_depth_samples = total_items;
+        ctx->launched = true;
+        return RT_OK;
+    }
+    int grid = 0;
+    const bool small_grid = ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64;
+    ctx->last.scan_mode = 5;
+    ctx->last.kernel_variant = 8 | (small_grid ? 1 : 0);
+    rc = small_grid ? launch_render<5, false, true, false, rt::kItemBlockList>(ctx, kp, stream, &grid)      // (the pixel-list instantiations)
+                    : launch_render<5, false, false, false, rt::kItemBlockList>(ctx, kp, stream, &grid);
+    if (rc) return rc;
+    ctx->launched = true;
+    ctx->last.grid_blocks = grid;
+    return RT_OK;
+}
+
+int rt_render_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, const uint32_t *pixels, int64_t n_pixels,
+                     uint64_t *out_fix, rt_stats *stats)
+{
+    int rc = validate_pixel_list(ctx, cam, p, n_pixels);
+    if (rc) return rc;
+    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (n_pixels == 0) return RT_OK;
+    if (!pixels || !out_fix) return fail(RT_ERR_INVALID_ARGUMENT, "pixels/out_fix is NULL");
+    const long long npix_frame = (long long)p->width * p->height;
+    for (int64_t k = 0; k < n_pixels; ++k)
+        if ((long long)pixels[k] >= npix_frame)
+            return fail(RT_ERR_INVALID_ARGUMENT, "pixels[%lld] = %u is not a pixel of a %d x %d frame", (long long)k, pixels[k], p->width, p->height);
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t count = (size_t)n_pixels * 3;
+    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, count * sizeof(uint64_t));
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_list, &ctx->stage_list_bytes, (size_t)n_pixels * sizeof(uint32_t));
+    if (rc) return rc;
+    RT_HIP(hipMemcpyAsync(ctx->d_stage_list, pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->own_stream));
+    rt_params q = *p;
+    q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
+    rc = rt_render_pixels_device(ctx, cam, &q, (const uint32_t *)ctx->d_stage_list, n_pixels, ctx->d_stage_fix, ctx->own_stream);
+    if (rc) return rc;
+    RT_HIP(hipMemcpyAsync(out_fix, ctx->d_stage_fix, count * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->own_stream));
+    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    if (stats) return rt_last_stats(ctx, stats);
+    return RT_OK;
+}
+
+// ---- adaptive sampling -------------------------------------------------------------------------------------------------------
+int rt_select_pixels_host(const uint64_t *fix, const uint64_t *half, const uint32_t *count, int32_t width, int32_t height,
+                          int32_t n, const rt_adaptive *a, uint32_t *list_out, int64_t *n_out)
+{
+    int rc = validate_select(fix, half, count, width, height, n, a, list_out, n_out);
+    if (rc) return rc;
+    const size_t npix = (size_t)width * height;
+    std::vector<char> noisy(npix);
+    const double sc = 1.0 / ((double)n * 4294967296.0);
+    for (size_t p = 0; p < npix; ++p)
+        noisy[p] = count[p] == (uint32_t)n &&
+                   rt::select_noisy((const unsigned long long *)fix + p * 3, (const unsigned long long *)half + p * 3, sc, a->threshold, a->dark_floor);
+    int64_t m = 0;
+    for (int j = 0; j < height; ++j)
+        for (int i = 0; i < width; ++i) {
+            const size_t p = (size_t)j * width + i;
+            if (count[p] != (uint32_t)n) continue;
+            bool act = false;
+            for (int jj = std::max(j - 1, 0); jj <= std::min(j + 1, height - 1); ++jj)
+                for (int ii = std::max(i - 1, 0); ii <= std::min(i + 1, width - 1); ++ii) act = act || noisy[(size_t)jj * width + ii];
+            if (act) list_out[m++] = (uint32_t)p;
+        }
+    *n_out = m;
+    return RT_OK;
+}
+
+int rt_select_pixels_device(rt_context *ctx, const void *d_fix, const void *d_half, const void *d_count, int32_t width,
+                            int32_t height, int32_t n, const rt_adaptive *a, void *d_list_out, void *d_n_out, void *stream_v)
+{
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    int rc = validate_select(d_fix, d_half, d_count, width, height, n, a, d_list_out, d_n_out);
+    if (rc) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const uint32_t npix = (uint32_t)((long long)width * height);
+    const uint32_t blocks = (npix + rt::kSelBlock - 1) / rt::kSelBlock;
+    // scratch: noisy[npix], active[npix] (bytes, each rounded up to 256), the workgroups' counts [blocks]
+    const size_t flags_bytes = ((size_t)npix + 255) / 256 * 256;
+    rc = ensure(&ctx->d_sel, &ctx->sel_bytes, 2 * flags_bytes + (size_t)blocks * sizeof(uint32_t));
+    if (rc) return rc;
+    uint8_t *noisy = (uint8_t *)ctx->d_sel, *active = noisy + flags_bytes;
+    uint32_t *block_count = (uint32_t *)(active + flags_bytes);
+    const double sc = 1.0 / ((double)n * 4294967296.0);
+    hipLaunchKernelGGL(rt::select_noisy_kernel, dim3(blocks), dim3(rt::kSelBlock), 0, stream, (const unsigned long long *)d_fix,
+                       (const unsigned long long *)d_half, (const uint32_t *)d_count, npix, (uint32_t)n, sc, a->threshold, a->dark_floor, noisy);
+    hipLaunchKernelGGL(rt::select_active_kernel, dim3(blocks), dim3(rt::kSelBlock), 0, stream, (const uint8_t *)noisy,
+                       (const uint32_t *)d_count, (int)width, (int)height, (uint32_t)n, active, block_count);
+    hipLaunchKernelGGL(rt::select_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, blocks, (uint32_t *)d_n_out);
+    hipLaunchKernelGGL(rt::select_write_kernel, dim3(blocks), dim3(rt::kSelBlock), 0, stream, (const uint8_t *)active,
+                       (const uint32_t *)block_count, npix, (uint32_t *)d_list_out);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_adaptive *a,
+                       uint64_t *out_fix, uint64_t *out_half, uint32_t *out_count, rt_stats *stats)
+{
+    int rc = validate_params(p);
+    if (rc) return rc;
+    rc = validate_adaptive(a);
+    if (rc) return rc;
+    if (p->sample_begin != 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive numbers its own passes: sample_begin must be 0 (is %d)", p->sample_begin);
+    if (p->spp < 2 * (long long)a->step || p->spp % (2 * (long long)a->step) != 0 || p->spp > kAdaptiveMaxSpp)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive: spp = %d (the most samples a pixel may get) must be a multiple of 2 * step = %lld "
+                    "and <= %d", p->spp, 2 * (long long)a->step, kAdaptiveMaxSpp);
+    rc = validate_pixel_list(ctx, cam, p, 0);
+    if (rc) return rc;
+    if (!out_fix || !out_count) return fail(RT_ERR_INVALID_ARGUMENT, "out_fix/out_count is NULL");
+    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->own_stream;
+    const size_t npix = (size_t)p->width * p->height;
+    const size_t sums = npix * 3 * sizeof(uint64_t);
+    // the frame's state, all on the device: fix | half | one pass's compact sums | count | list | list length | running counters (5 x u64)
+    rc = ensure(&ctx->d_adapt, &ctx->adapt_bytes, 3 * sums + 2 * npix * sizeof(uint32_t) + 64);
+    if (rc) return rc;
+    char *base = (char *)ctx->d_adapt;
+    void *d_fix = base, *d_half = base + sums, *d_pass = base + 2 * sums;
+    uint32_t *d_count = (uint32_t *)(base + 3 * sums), *d_list = d_count + npix;
+    unsigned long long *d_total = (unsigned long long *)(d_list + npix);
+    uint32_t *d_n = (uint32_t *)(d_total + 5);
+    RT_HIP(hipMemsetAsync(d_total, 0, 64, st));
+
+    const uint32_t step = (uint32_t)a->step;
+    float kernel_ms = 0.0f;
+    unsigned long long zero_depth = 0;
+    rt_stats shape{};                                                    // grid, variant ... of the latest launch
+    int round_slots[2] = {0, 0};
+    auto after_pass = [&](int k) -> int {                                // the launch's counters -> the running total; remember its events
+        hipLaunchKernelGGL(rt::stats_accumulate_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)ctx->d_stats, d_total);
+        RT_HIP(hipGetLastError());
+        zero_depth += ctx->zero_depth_samples;
+        round_slots[k] = ctx->cur;
+        shape = ctx->last;
+        return RT_OK;
+    };
+    auto round_time = [&]() -> int {                                     // (after the round's synchronise: both passes have finished)
+        for (int k = 0; k < 2; ++k) {
+            float ms = 0.0f;
+            RT_HIP(hipEventElapsedTime(&ms, ctx->e0_slots[round_slots[k]], ctx->e1_slots[round_slots[k]]));
+            kernel_ms += ms;
+        }
+        return RT_OK;
+    };
+    rt_params q = *p;
+    q.spp = (int32_t)step;
+    // round 1: every pixel, through the dense kernel.  Pass 0 -> fix, a copy of it is `half`, pass 1 is added to fix.
+    q.sample_begin = 0; q.flags = p->flags & ~RT_FLAG_ACCUMULATE;
+    rc = rt_render_device(ctx, cam, &q, d_fix, st);
+    if (rc) return rc;
+    if ((rc = after_pass(0))) return rc;
+    RT_HIP(hipMemcpyAsync(d_half, d_fix, sums, hipMemcpyDeviceToDevice, st));
+    q.sample_begin = (int32_t)step; q.flags = p->flags | RT_FLAG_ACCUMULATE;
+    rc = rt_render_device(ctx, cam, &q, d_fix, st);
+    if (rc) return rc;
+    if ((rc = after_pass(1))) return rc;
+    hipLaunchKernelGGL(rt::fill_u32_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, d_count, 2u * step, (uint32_t)npix);
+    RT_HIP(hipGetLastError());
+    q.flags = p->flags & ~RT_FLAG_ACCUMULATE;
+    for (uint32_t n = 2u * step; ; n += 2u * step) {
+        uint32_t n_list = 0;
+        if (n < (uint32_t)p->spp) {
+            rc = rt_select_pixels_device(ctx, d_fix, d_half, d_count, p->width, p->height, (int32_t)n, a, d_list, d_n, st);
+            if (rc) return rc;
+            RT_HIP(hipMemcpyAsync(&n_list, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));    // the round's ONE word
+        }
+        RT_HIP(hipStreamSynchronize(st));
+        if ((rc = round_time())) return rc;
+        if (n_list == 0u) break;
+        for (int k = 0; k < 2; ++k) {                                    // passes n / step (even: also into half) and n / step + 1
+            q.sample_begin = (int32_t)(n + (uint32_t)k * step);
+            rc = rt_render_pixels_device(ctx, cam, &q, d_list, (int64_t)n_list, d_pass, st);
+            if (rc) return rc;
+            if ((rc = after_pass(k))) return rc;
+            hipLaunchKernelGGL(rt::add_back_kernel, dim3((n_list + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)d_list, n_list,
+                               (const unsigned long long *)d_pass, (unsigned long long *)d_fix,
+                               k == 0 ? (unsigned long long *)d_half : (unsigned long long *)nullptr, d_count, step);
+            RT_HIP(hipGetLastError());
+        }
+    }
+    unsigned long long total[5];
+    RT_HIP(hipMemcpyAsync(out_fix, d_fix, sums, hipMemcpyDeviceToHost, st));
+    if (out_half) RT_HIP(hipMemcpyAsync(out_half, d_half, sums, hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(out_count, d_count, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    RT_HIP(hipMemcpyAsync(total, d_total, sizeof(total), hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->n_spheres = shape.n_spheres; stats->grid_blocks = shape.grid_blocks; stats->block_threads = shape.block_threads;
+        stats->scan_mode = shape.scan_mode; stats->kernel_variant = shape.kernel_variant;
+        stats->rays_traced = total[0];
+        stats->samples = total[1] + zero_depth;
+        stats->direct_samples = total[4];
+        stats->sphere_tests = total[0] * (unsigned long long)(shape.n_spheres > 0 ? shape.n_spheres : 0);
+        stats->kernel_ms = kernel_ms;
+    }
+    return RT_OK;
+}
+
+int rt_resolve_rgba8_counts_device(rt_context *ctx, const void *d_fix, const void *d_count, int32_t width, int32_t rows,
+                                   int32_t flip, void *d_rgba, void *stream_v)
+{
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (width < 1 || rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad width/rows");
+    if (rows == 0) return RT_OK;
+    if (!d_fix || !d_count || !d_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "bad buffers");
+    RT_HIP(hipSetDevice(ctx->device));
+    const long long npix = (long long)width * rows;
+    long long blocks = (npix + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(rt::resolve_rgba8_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_v,
+                       (const unsigned long long *)d_fix, (const uint32_t *)d_count, (uint8_t *)d_rgba, (int)width, (int)rows, (int)flip);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_resolve_rgba8_counts(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int32_t width, int32_t rows,
+                            int32_t flip, uint8_t *out_rgba)
+{
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (width < 1 || rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad width/rows");
+    if (rows == 0) return RT_OK;
+    if (!fix || !count || !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "bad buffers");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)width * rows;
+    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, npix * 3 * sizeof(uint64_t));
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_rgba, &ctx->stage_rgba_bytes, npix * 4);
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_list, &ctx->stage_list_bytes, npix * sizeof(uint32_t));
+    if (rc) return rc;
+    RT_HIP(hipMemcpyAsync(ctx->d_stage_fix, fix, npix * 3 * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->own_stream));
+    RT_HIP(hipMemcpyAsync(ctx->d_stage_list, count, npix * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->own_stream));
+    rc = rt_resolve_rgba8_counts_device(ctx, ctx->d_stage_fix, ctx->d_stage_list, width, rows, flip, ctx->d_stage_rgba, ctx->own_stream);
+    if (rc) return rc;
+    RT_HIP(hipMemcpyAsync(out_rgba, ctx->d_stage_rgba, npix * 4, hipMemcpyDeviceToHost, ctx->own_stream));
+    RT_HIP(hipStreamSynchronize(ctx->own_stream));
     return RT_OK;
 }
 

@@ -91,6 +91,8 @@ struct KParams {
     unsigned long long *fix;   // [rows][width][3] exact sums
     unsigned int *queue;       // work counter
     unsigned long long *stats; // [0] rays [1] samples [2] candidates [3] exact roots [4] samples sent to the frame buffer one by one [8..15] diagnostic builds [16..79] rays per bounce index (DIAG)
+    const uint32_t *pix_list;  // pixel-list launches (ITEMS = kItemBlockList): [npix] global pixel numbers g = j * width + i; `fix` is then [npix][3], entry k for pix_list[k] (last member: the
+                               // offsets of everything render_kernel reads stay where they were)
 };
 
 constexpr int RT_KIND_LAMBERTIAN = 0, RT_KIND_METAL = 1, RT_KIND_DIALECTRIC = 2;
@@ -104,6 +106,7 @@ constexpr int kItemBlock = 256;     // pixel-samples a wave reserves per atomic 
 // a quarter of both (1200x675x500: 52.7 -> 51.3 ms; 10k spheres 1920x1080x256: 93.7 -> 91.5 ms).  Smaller launches keep 256: their last
 // blocks are the end-of-launch tail (1200x675x147 is 5 % slower with 1 024).
 constexpr int kItemBlockLarge = 1024;
+constexpr int kItemBlockList = -kItemBlock;   // as the ITEMS of render_kernel: work blocks of kItemBlock pixel-samples over a pixel list (render_kernel below)
 static_assert(kItemBlockLarge + 32768 < 65536, "udiv_small: numerators x < d + kItemBlockLarge with d < 2^15 keep x * d < 2^32");
 constexpr int kLargeMinSpp = 147;
 constexpr int kLargeMinSppSmallGrid = 69;
@@ -164,6 +167,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // of one word's 32 bits: same draw order, same runs; the rejection tests run in f64 as the reference writes them (the
 // integer form needs the 2^-31 lattice of single words).  An optional mode: ~2x the Philox work of the retry loops.
 // ITEMS: pixel-samples per work block (kItemBlock, or kItemBlockLarge for launches with enough samples: see rt_api.hip).
+// ... or kItemBlockList = -kItemBlock: blocks of kItemBlock pixel-samples over a PIXEL LIST (rt_render_pixels_device).  The launch is then a "virtual
+// image" of P.npix pixels in the order of P.pix_list; local pixel k is pixel g = P.pix_list[k] of the frame.  Only the start of a sample
+// differs (local pixel -> g -> (i, j)); the work blocks, the queue, the block sums and their write-out address pixels by their local number, so
+// the output is compact: entry k belongs to pix_list[k].  The variant is an instantiation of its own -- a __global__ with its own symbol,
+// rt::render_kernel<5, false, SMALLGRID, false, -256> -- of this one body, and the text of the body stays where it was: wrapping it into
+// a __forceinline__ function shared by two __global__ entries moves opcodes in EVERY existing instantiation (tried: all 14 ops-sha of
+// tools/isa_fingerprint.py change), a sixth template parameter would rename the kernels bench.py and the profiles spell.  As built, the existing
+// instantiations' machine code is unchanged (profiles/isa_fingerprint_{before,after}_pixel_lists.txt).
 template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITEMS = 256>
 // second launch bound = waves per SIMD the register allocator must leave room for: the bounce loop
 // is latency-bound, and the 4th wave is worth more than the few cold values it spills.  Only the shipped kernel
@@ -171,6 +182,8 @@ template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITE
 // diagnostic variant and the cross-check modes 2-4 carry 1-14 KB more and run three.
 __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 : 5) void render_kernel(const KParams P)
 {
+    constexpr bool PIXLIST = ITEMS < 0;
+    static_assert(!PIXLIST || (MODE == 5 && !DIAG && !U53 && ITEMS == kItemBlockList), "pixel lists: the shipped kernel, 32-bit uniforms, blocks of 256");
     // The block sums' ring (s_ring below) has the same 768 bytes per wave in both shapes: 4 blocks x 8 pixels, or -- the shipped scan mode's
     // kernels, all but the large-grid kernel's instantiation for blocks of 1 024 -- 2 blocks x 16 pixels.  Two blocks in flight are enough: a block of 256 lasts ~11 passes, one of
     // 1 024 ~43, and the samples of the block before the previous one that are still open when a block begins (paths of more than
@@ -180,7 +193,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     // 48.74 ms, 1200x675x100 10.53 -> 10.49 ms, 10k spheres 1920x1080 x20 7.78 -> 7.50 ms, x100 34.98 -> 34.88 ms; the large-grid kernel ON LARGE
     // BLOCKS is 0.7 % slower with the same ring (10k spheres 1920x1080x256: 85.99 -> 86.58 ms, fewer instructions, another schedule) and
     // keeps 4 x 8 and kLargeMinSpp = 147.  The cross-check scan modes and the diagnostic-counter kernels keep 4 x 8 too.
-    constexpr bool kWideRing = SMALLGRID || (MODE == 5 && !DIAG && ITEMS == kItemBlock);
+    constexpr bool kWideRing = SMALLGRID || (MODE == 5 && !DIAG && (ITEMS == kItemBlock || ITEMS == kItemBlockList));
     constexpr int kRingDepth = kWideRing ? 2 : 4;
     constexpr int kRingSlots = kWideRing ? 16 : 8;
     static_assert(kRingDepth * kRingSlots == rt::kRingDepth * rt::kRingSlots, "same LDS either way");
@@ -338,11 +351,13 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     else if (rem >= (long long)P.spp) { p0 += 1u; rem -= (long long)P.spp; }
                     blk_pix0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)p0);
                     blk_s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rem);
+                    if constexpr (!PIXLIST) {
                     uint32_t rr0 = (uint32_t)((double)blk_pix0 * P.inv_width);     // pixel / width the same way
                     int i0 = (int)(blk_pix0 - rr0 * (uint32_t)P.width);
                     if (i0 < 0) { rr0 -= 1u; i0 += P.width; } else if (i0 >= P.width) { rr0 += 1u; i0 -= P.width; }
                     blk_rr0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)rr0);                  // (keeps them in SGPRs)
                     blk_i0 = (uint32_t)__builtin_amdgcn_readfirstlane(i0);
+                    }
                     blk_next = 0u; blk_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_items);
                     blk_seq += 1u;
                     if (P.use_ring) {
@@ -366,14 +381,25 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     // item blk_next + lane of the block: sample blk_s0 + that of pixel blk_pix0, carried over into the next pixels
                     const uint32_t s_rel = blk_s0 + blk_next + (uint32_t)lane;
                     const uint32_t dq = udiv_small(s_rel, (uint32_t)P.spp, P.magic_spp);   // pixel slot within the block (< kRingSlots when use_ring)
+                    uint32_t i, j, g_pix;
+                    if constexpr (PIXLIST) {
+                        // local pixel blk_pix0 + dq of the list (< P.npix: the item exists) -> its pixel of the frame -> (i, j).  g < 2^31 is no
+                        // udiv_small numerator: g / width in f64 (exact product, one rounding) and one correction step, as the block decode above
+                        g_pix = P.pix_list[blk_pix0 + dq];
+                        uint32_t jq = (uint32_t)((double)g_pix * P.inv_width);
+                        int ir = (int)(g_pix - jq * (uint32_t)P.width);
+                        if (ir < 0) { jq -= 1u; ir += P.width; } else if (ir >= P.width) { jq += 1u; ir -= P.width; }
+                        i = (uint32_t)ir; j = jq;
+                    } else {
                     const uint32_t col = blk_i0 + dq;
                     const uint32_t rq = udiv_small(col, (uint32_t)P.width, P.magic_width);
-                    const uint32_t i = col - rq * (uint32_t)P.width;
+                    i = col - rq * (uint32_t)P.width;
                     const uint32_t rr = blk_rr0 + rq;
                     const uint32_t lt = udiv_small(rr, (uint32_t)P.tile_rows, P.magic_tile);   // local tile
-                    const uint32_t j = (lt * (uint32_t)P.shard_count + (uint32_t)P.shard_index) * (uint32_t)P.tile_rows
+                    j = (lt * (uint32_t)P.shard_count + (uint32_t)P.shard_index) * (uint32_t)P.tile_rows
                                        + (rr - lt * (uint32_t)P.tile_rows);
-                    const uint32_t g_pix = j * (uint32_t)P.width + i;
+                    g_pix = j * (uint32_t)P.width + i;
+                    }
                     const uint32_t g_s = (uint32_t)P.sample_begin + (s_rel - dq * (uint32_t)P.spp);
                     U4 w = philox4x32_10(g_pix, g_s, 0u, 0u, P.k0, P.k1);
                     uint32_t g_ev = 1u;
@@ -1339,6 +1365,155 @@ __global__ void resolve_rgba8_kernel(const unsigned long long *__restrict__ fix,
         px.w = 255;
         reinterpret_cast<uchar4 *>(out)[(long long)dst * width + i] = px;
     }
+}
+
+// Color::to_rgba with each pixel's OWN sample count (vec3.rs:403-421 with samples_per_pixel = count[p]) + the row flip: the resolve of
+// an adaptive frame.  A pixel without samples (count 0) divides by zero as the reference would: 0 * inf = NaN -> byte 0.
+__global__ void resolve_rgba8_counts_kernel(const unsigned long long *__restrict__ fix, const uint32_t *__restrict__ count,
+                                            uint8_t *__restrict__ out, int width, int rows, int flip)
+{
+    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long npix = (long long)width * rows;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; k < npix; k += stride) {
+        const int r = (int)(k / width);
+        const int i = (int)(k - (long long)r * width);
+        const int dst = flip ? rows - 1 - r : r;
+        const unsigned long long *q = fix + k * 3;
+        const double scale = 1.0 / (double)count[k];            // vec3.rs:409
+        uchar4 px;
+        px.x = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[0])), 0.0, 0.999));
+        px.y = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[1])), 0.0, 0.999));
+        px.z = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[2])), 0.0, 0.999));
+        px.w = 255;
+        reinterpret_cast<uchar4 *>(out)[(long long)dst * width + i] = px;
+    }
+}
+
+// ---- adaptive sampling: error estimate, selection, add-back (rtiow_hip.h, rt_select_pixels_device) ----
+// The rule, stated once for the device and the host (rt_select_pixels_host compiles this very function): is pixel p, whose sums hold n
+// samples of which `half` holds n / 2, still noisy?  Integers for the differences, then binary64 in the written order (-ffp-contract=off).
+__host__ __device__ inline bool select_noisy(const unsigned long long *fix, const unsigned long long *half, double sc, double threshold,
+                                             double dark_floor)
+{
+    double D = 0.0, S = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        const long long t = (long long)(2ull * half[c] - fix[c]);          // fits: n <= 32766 samples of <= 2^48 each
+        const unsigned long long d = t < 0 ? (unsigned long long)(-t) : (unsigned long long)t;
+        D = c == 0 ? (double)d : D + (double)d;                             // ((d_r + d_g) + d_b)
+        S = c == 0 ? (double)fix[c] : S + (double)fix[c];
+    }
+    const double m = S * sc;
+    const double err = (D * sc) / __builtin_sqrt(m > dark_floor ? m : dark_floor);
+    return !(err <= threshold);
+}
+
+constexpr int kSelBlock = 256;      // pixels per workgroup of the selection kernels (consecutive pixel numbers)
+
+// (1) noisy[p] = candidate && !(err <= threshold)
+__global__ __launch_bounds__(kSelBlock) void select_noisy_kernel(const unsigned long long *__restrict__ fix, const unsigned long long *__restrict__ half,
+                                                                 const uint32_t *__restrict__ count, uint32_t npix, uint32_t n, double sc,
+                                                                 double threshold, double dark_floor, uint8_t *__restrict__ noisy)
+{
+    const uint32_t p = blockIdx.x * (uint32_t)kSelBlock + threadIdx.x;
+    if (p >= npix) return;
+    noisy[p] = (count[p] == n && select_noisy(fix + (size_t)p * 3u, half + (size_t)p * 3u, sc, threshold, dark_floor)) ? 1 : 0;
+}
+
+// (2) active[p] = candidate && (a pixel of the 3x3 neighbourhood, clipped at the frame's edges, is noisy); block_count[b] = how many in workgroup b
+__global__ __launch_bounds__(kSelBlock) void select_active_kernel(const uint8_t *__restrict__ noisy, const uint32_t *__restrict__ count,
+                                                                  int width, int height, uint32_t n, uint8_t *__restrict__ active,
+                                                                  uint32_t *__restrict__ block_count)
+{
+    __shared__ uint32_t s_cnt[kSelBlock / 64];
+    const uint32_t npix = (uint32_t)width * (uint32_t)height;
+    const uint32_t p = blockIdx.x * (uint32_t)kSelBlock + threadIdx.x;
+    bool act = false;
+    if (p < npix && count[p] == n) {
+        const int j = (int)(p / (uint32_t)width), i = (int)(p - (uint32_t)j * (uint32_t)width);
+        const int j0 = j > 0 ? j - 1 : 0, j1 = j < height - 1 ? j + 1 : height - 1;
+        const int i0 = i > 0 ? i - 1 : 0, i1 = i < width - 1 ? i + 1 : width - 1;
+        for (int jj = j0; jj <= j1; ++jj)
+            for (int ii = i0; ii <= i1; ++ii) act = act || noisy[(size_t)jj * (size_t)width + (size_t)ii] != 0;
+    }
+    if (p < npix) active[p] = act ? 1 : 0;
+    const unsigned long long m = __ballot(act);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// (3) exclusive scan of the workgroups' counts, in place, by ONE workgroup (chunks of 1 024 with a running carry); the total -> *n_out
+__global__ __launch_bounds__(1024) void select_scan_kernel(uint32_t *__restrict__ block_count, uint32_t n_blocks, uint32_t *__restrict__ n_out)
+{
+    __shared__ uint32_t s_wave[16];
+    __shared__ uint32_t s_carry;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid == 0) s_carry = 0u;
+    __syncthreads();
+    for (uint32_t base = 0; base < n_blocks; base += 1024u) {
+        const uint32_t k = base + tid;
+        const uint32_t v = k < n_blocks ? block_count[k] : 0u;
+        uint32_t x = v;                                                     // inclusive scan within the wave
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)x, d);
+            if (lane >= (uint32_t)d) x += y;
+        }
+        if (lane == 63u) s_wave[wave] = x;
+        __syncthreads();
+        uint32_t before = s_carry;
+        for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
+        if (k < n_blocks) block_count[k] = before + x - v;
+        __syncthreads();
+        if (tid == 1023u) s_carry = before + x;
+        __syncthreads();
+    }
+    if (tid == 0) *n_out = s_carry;
+}
+
+// (4) the active pixels' numbers, ascending: workgroup offset + the waves before this one + the rank within the wave (ballot + v_mbcnt)
+__global__ __launch_bounds__(kSelBlock) void select_write_kernel(const uint8_t *__restrict__ active, const uint32_t *__restrict__ block_offset,
+                                                                 uint32_t npix, uint32_t *__restrict__ list)
+{
+    __shared__ uint32_t s_cnt[kSelBlock / 64];
+    const uint32_t p = blockIdx.x * (uint32_t)kSelBlock + threadIdx.x;
+    const bool act = p < npix && active[p] != 0;
+    const unsigned long long m = __ballot(act);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t at = block_offset[blockIdx.x];
+    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) at += s_cnt[w];
+    at += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (act) list[at] = p;                                                  // (at < the total <= npix = the list's capacity)
+}
+
+// One pass's compact sums back into the frame's state at the listed pixels (no duplicates in a selection's list): fix += pass,
+// half += pass on the even-numbered passes (half != nullptr), count += step.
+__global__ void add_back_kernel(const uint32_t *__restrict__ list, uint32_t n_list, const unsigned long long *__restrict__ pass,
+                                unsigned long long *__restrict__ fix, unsigned long long *__restrict__ half, uint32_t *__restrict__ count,
+                                uint32_t step)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_list) return;
+    const size_t g = list[k];
+    for (int c = 0; c < 3; ++c) {
+        const unsigned long long v = pass[(size_t)k * 3u + c];
+        fix[g * 3u + c] += v;
+        if (half) half[g * 3u + c] += v;
+    }
+    count[g] += step;
+}
+
+__global__ void fill_u32_kernel(uint32_t *__restrict__ dst, uint32_t value, uint32_t n)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) dst[k] = value;
+}
+
+// a launch's counters (KParams::stats [0..4]) added to a running total: rt_render_adaptive reads the total once, at the end
+__global__ void stats_accumulate_kernel(const unsigned long long *__restrict__ stats, unsigned long long *__restrict__ total)
+{
+    if (threadIdx.x < 5) total[threadIdx.x] += stats[threadIdx.x];
 }
 
 __global__ void philox_kat_kernel(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

@@ -19,6 +19,29 @@ def make_params(width, height, spp, *, sample_begin=0, max_depth=50, t_min=1e-4,
     return p
 
 
+def make_adaptive(step, threshold, dark_floor=0.01):
+    """rt_adaptive: `step` samples per pass, stop below `threshold` (relative to max(mean radiance, dark_floor))."""
+    a = _ffi.rt_adaptive()
+    a.step, a.reserved, a.threshold, a.dark_floor = int(step), 0, float(threshold), float(dark_floor)
+    return a
+
+
+def select_pixels_host(fix, half, count, n, adaptive):
+    """The adaptive selection on host arrays (rt_select_pixels_host, no GPU): fix, half u64 [H,W,3], count u32 [H,W] ->
+    the active pixels' numbers g = j * W + i, ascending (u32)."""
+    lib = _ffi.load()
+    fix = np.ascontiguousarray(fix, dtype=np.uint64)
+    half = np.ascontiguousarray(half, dtype=np.uint64)
+    count = np.ascontiguousarray(count, dtype=np.uint32)
+    h, w = count.shape
+    assert fix.shape == (h, w, 3) and half.shape == (h, w, 3)
+    out = np.zeros(h * w, dtype=np.uint32)
+    m = C.c_int64(0)
+    _ffi.check(lib.rt_select_pixels_host(fix.ctypes.data_as(C.c_void_p), half.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+                                         w, h, int(n), C.byref(adaptive), out.ctypes.data_as(C.c_void_p), C.byref(m)), "rt_select_pixels_host")
+    return out[:m.value].copy()
+
+
 def shard_rows(params):
     lib = _ffi.load()
     rows = C.c_int32(0)
@@ -156,6 +179,74 @@ class Renderer:
         st = _ffi.rt_stats()
         _ffi.check(self._lib.rt_last_stats(self._h, C.byref(st)), "rt_last_stats")
         return stats_dict(st)
+
+    # -- pixel lists and adaptive sampling ---------------------------------------
+    def render_pixels(self, cam, params, pixels):
+        """params.spp samples of the listed pixels (g = j * W + i, j = 0 the bottom row; any order, duplicates allowed) through
+        rt_render_pixels: returns (fix u64 [n,3], entry k for pixels[k] -- the dense render's sums at that pixel --, stats dict)."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        out = np.zeros((len(px), 3), dtype=np.uint64)
+        st = _ffi.rt_stats()
+        _ffi.check(self._lib.rt_render_pixels(self._h, C.byref(rc), C.byref(params), px.ctypes.data_as(C.c_void_p), len(px),
+                                              out.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_pixels")
+        return out, (stats_dict(st) if len(px) else None)
+
+    def render_pixels_device(self, cam, params, d_pixels_ptr, n_pixels, d_fix_ptr, stream=0):
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        _ffi.check(self._lib.rt_render_pixels_device(self._h, C.byref(rc), C.byref(params), C.c_void_p(d_pixels_ptr), int(n_pixels),
+                                                     C.c_void_p(d_fix_ptr), C.c_void_p(stream)), "rt_render_pixels_device")
+
+    def select_pixels_device(self, d_fix_ptr, d_half_ptr, d_count_ptr, width, height, n, adaptive, d_list_ptr, d_n_ptr, stream=0):
+        _ffi.check(self._lib.rt_select_pixels_device(self._h, C.c_void_p(d_fix_ptr), C.c_void_p(d_half_ptr), C.c_void_p(d_count_ptr),
+                                                     int(width), int(height), int(n), C.byref(adaptive), C.c_void_p(d_list_ptr),
+                                                     C.c_void_p(d_n_ptr), C.c_void_p(stream)), "rt_select_pixels_device")
+
+    def select_pixels(self, fix, half, count, n, adaptive):
+        """The adaptive selection ON THE DEVICE (rt_select_pixels_device) for host arrays: the state goes up through torch
+        tensors, the list comes back.  Same result as select_pixels_host."""
+        import torch
+        count = np.ascontiguousarray(count, dtype=np.uint32)
+        h, w = count.shape
+        dev = torch.device("cuda", torch.cuda.current_device())
+        up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t).copy()).to(dev)
+        d_fix = up(np.asarray(fix, dtype=np.uint64).reshape(h, w, 3), np.int64)
+        d_half = up(np.asarray(half, dtype=np.uint64).reshape(h, w, 3), np.int64)
+        d_count = up(count, np.int32)
+        d_list = torch.zeros(h * w, dtype=torch.int32, device=dev)
+        d_n = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        self.select_pixels_device(d_fix.data_ptr(), d_half.data_ptr(), d_count.data_ptr(), w, h, n, adaptive,
+                                  d_list.data_ptr(), d_n.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        m = int(d_n.cpu().numpy().view(np.uint32)[0])
+        return d_list.cpu().numpy().view(np.uint32)[:m].copy()
+
+    select_pixels_host = staticmethod(select_pixels_host)
+
+    def render_adaptive(self, cam, params, adaptive, want_half=True):
+        """rt_render_adaptive: params.spp is the cap.  Returns (fix u64 [H,W,3], half u64 [H,W,3] or None, count u32 [H,W], stats dict)."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        h, w = params.height, params.width
+        fix = np.zeros((h, w, 3), dtype=np.uint64)
+        half = np.zeros((h, w, 3), dtype=np.uint64) if want_half else None
+        count = np.zeros((h, w), dtype=np.uint32)
+        st = _ffi.rt_stats()
+        _ffi.check(self._lib.rt_render_adaptive(self._h, C.byref(rc), C.byref(params), C.byref(adaptive), fix.ctypes.data_as(C.c_void_p),
+                                                half.ctypes.data_as(C.c_void_p) if want_half else None,
+                                                count.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_adaptive")
+        return fix, half, count, stats_dict(st)
+
+    def resolve_rgba8_counts(self, fix, count, flip=True):
+        """fix u64 [rows,W,3], count u32 [rows,W] -> RGBA8 [rows,W,4]: Color::to_rgba with each pixel's own sample count."""
+        fix = np.ascontiguousarray(fix, dtype=np.uint64)
+        count = np.ascontiguousarray(count, dtype=np.uint32)
+        rows, width = fix.shape[0], fix.shape[1]
+        assert count.shape == (rows, width)
+        out = np.zeros((rows, width, 4), dtype=np.uint8)
+        _ffi.check(self._lib.rt_resolve_rgba8_counts(self._h, fix.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), width, rows,
+                                                     int(bool(flip)), out.ctypes.data_as(C.c_void_p)), "rt_resolve_rgba8_counts")
+        return out
 
     # -- to_rgba + flip --------------------------------------------------------
     def resolve_rgba8(self, fix, spp, flip=True):
