@@ -170,6 +170,15 @@ extern "C" {
                                           rows: i32, flip: i32, d_rgba: *mut c_void, stream: *mut c_void) -> i32;
     pub fn rt_resolve_rgba8_counts(ctx: *mut rt_context, fix: *const u64, count: *const u32, width: i32, rows: i32,
                                    flip: i32, out_rgba: *mut u8) -> i32;
+    /// Frame batches: src/main.rs:108-139 once per camera, in ONE launch.  `d_cams`: DEVICE [n_frames] rt_camera; `d_fix`: device
+    /// [n_frames][height][width][3] u64.  Frame f is the dense render of camera f with `sample_begin + f * sample_stride`.
+    pub fn rt_render_frames_device(ctx: *mut rt_context, d_cams: *const rt_camera, n_frames: i32, sample_stride: i32,
+                                   p: *const rt_params, d_fix: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_render_frames(ctx: *mut rt_context, cams: *const rt_camera, n_frames: i32, sample_stride: i32,
+                            p: *const rt_params, out_fix: *mut u64, stats: *mut rt_stats) -> i32;
+    /// ... + `Color::to_rgba` and the row flip per frame: `out_rgba` is [n_frames][height][width][4].
+    pub fn rt_render_frames_rgba8(ctx: *mut rt_context, cams: *const rt_camera, n_frames: i32, sample_stride: i32,
+                                  p: *const rt_params, flip: i32, out_rgba: *mut u8, stats: *mut rt_stats) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -122,6 +122,18 @@ impl GpuRenderer {
         check(rc, "rt_render_rgba8")?;
         Ok((out, stats))
     }
+
+    /// src/main.rs:108-145 once per camera, all cameras in ONE launch (`rt_render_frames_rgba8`): frame f is what `render_rgba8`
+    /// gives for `cams[f]` with `sample_begin + f * sample_stride`; the bytes of the frames follow one another.
+    pub fn render_frames(&mut self, cams: &[Camera], p: &rt_params, sample_stride: i32, flip: bool) -> Result<(Vec<u8>, rt_stats), String> {
+        let flat: Vec<rt_camera> = cams.iter().map(|c| c.to_rt()).collect();
+        let mut out = vec![0u8; flat.len() * p.height as usize * p.width as usize * 4];
+        let mut stats: rt_stats = unsafe { std::mem::zeroed() };
+        let rc = unsafe { rt_render_frames_rgba8(self.ctx, flat.as_ptr(), flat.len() as i32, sample_stride, p, flip as i32,
+                                                 out.as_mut_ptr(), &mut stats) };
+        check(rc, "rt_render_frames_rgba8")?;
+        Ok((out, stats))
+    }
 }
 
 impl Drop for GpuRenderer {

@@ -172,6 +172,49 @@ inline HittableList random_scene(uint64_t seed = 1, int lo = -11, int hi = 11)
     return world;
 }
 
+// ---- cameras of a frame batch (rt_render_frames) -------------------------------------------------------------------
+// A turntable of n cameras: frame f is the book camera (main.rs:108-118) with look_from turned about the y axis by
+// th = 2 pi f / n (frame 0 is the book camera itself).  f64, the written order, no contraction: rtiow_amd/scene.py's
+// orbit_cameras builds the same bytes (tests/test_frames_host.py).
+inline std::vector<rt_camera> orbit_cameras(int n, int width, int height)
+{
+    std::vector<rt_camera> cams;
+    for (int f = 0; f < n; ++f) {
+        const double th = 2.0 * 3.14159265358979323846 * (double)f / (double)n;
+        const double x = 13.0 * std::cos(th) + 3.0 * std::sin(th);
+        const double z = -13.0 * std::sin(th) + 3.0 * std::cos(th);
+        cams.push_back(Camera(Point3(x, 2.0, z), Point3(0, 0, 0), Vec3(0, 1, 0), 20.0, (double)width / (double)height, 0.1, 10.0).flat());
+    }
+    return cams;
+}
+
+// A camera file: raw little-endian rt_camera records (152 bytes each), no header -- exactly like the flat scene file.
+inline bool save_cameras(const char *path, const std::vector<rt_camera> &cams)
+{
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return false;
+    const bool ok = std::fwrite(cams.data(), sizeof(rt_camera), cams.size(), f) == cams.size();
+    return (std::fclose(f) == 0) && ok;
+}
+// false (and `cams` empty) for a file that cannot be read or is not a whole number of records
+inline bool load_cameras(const char *path, std::vector<rt_camera> &cams)
+{
+    cams.clear();
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return false;
+    std::fseek(f, 0, SEEK_END);
+    const long bytes = std::ftell(f);
+    std::fseek(f, 0, SEEK_SET);
+    bool ok = bytes >= 0 && bytes % (long)sizeof(rt_camera) == 0;
+    if (ok) {
+        cams.resize((size_t)bytes / sizeof(rt_camera));
+        ok = std::fread(cams.data(), sizeof(rt_camera), cams.size(), f) == cams.size();
+    }
+    std::fclose(f);
+    if (!ok) cams.clear();
+    return ok;
+}
+
 // ---- output stage: main.rs:147,177 `image_buffer.save("image.png")` ------------------------------------------------
 // An 8-bit RGBA PNG, rows top first (the order main.rs:141-145 produces), alpha as to_rgba() set it (255): the colour
 // type, bit depth and pixels of the file the reference saves through the `image` crate.  No zlib in the build: the

@@ -6,6 +6,7 @@
 //                [--grid LO HI] [--device K] [--out image.png|image.ppm] [--dump-scene scene.bin] [--scene scene.bin]
 //                [--devices 0,1,..  [--tile-rows T] [--force-rccl]] [--uniform53] [--two-calls] [--passes N]
 //                [--adaptive THRESHOLD [--step N]]
+//                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -17,6 +18,11 @@
 // --adaptive THRESHOLD [--step N, default 8]: main.rs:130-137 with a per-pixel number of samples (rt_render_adaptive: passes of N samples, a pixel
 // stops once its error estimate is <= THRESHOLD; --spp is the most a pixel may get, a multiple of 2 N) and Color::to_rgba with each pixel's own
 // count (rt_resolve_rgba8_counts); the summary line adds the mean / min / max samples per pixel.  Single device.
+// --cameras FILE (raw 152-byte rt_camera records, as --dump-cameras and rtiow_amd.save_cameras write them) or --orbit N (a turntable of N
+// cameras about the y axis, frame 0 = the book camera): a FRAME BATCH -- every camera in ONE launch (rt_render_frames_rgba8: main.rs:108-145
+// once per camera; the sums stay on the device) -- written as PREFIX_0000.png, PREFIX_0001.png, ... for --out PREFIX (.ppm if PREFIX ends in
+// .ppm; a trailing .png is dropped from the prefix).  Frame f renders the samples [f S, f S + spp), S = --sample-stride (default: spp, every
+// frame its own random numbers; 0: the same ones for all).  Single device, one call.
 // --devices: the frame's rows are dealt round-robin to one rt_context per listed device, each driven by
 // its own host thread, and gathered with ONE RCCL ncclGather to the first device (host/rtiow_multi.hpp).
 // A device may be listed more than once (two contexts on one GPU from two threads: the threading rule of
@@ -48,6 +54,8 @@ int main(int argc, char **argv)
     bool adaptive = false;
     double threshold = 0.0;
     int step = 8;
+    std::string cameras_file, dump_cameras;
+    int orbit = 0, sample_stride = -1;           // (-1: spp)
     if (argc == 5 && !std::strcmp(argv[1], "--reassembly-plan")) {
         const int H = std::atoi(argv[2]), T = std::atoi(argv[3]), n = std::atoi(argv[4]);
         if (H < 1 || T < 1 || n < 1) { std::fprintf(stderr, "--reassembly-plan H T N: all >= 1\n"); return 2; }
@@ -87,6 +95,10 @@ int main(int argc, char **argv)
         else if (arg("--adaptive")) { adaptive = true; threshold = std::atof(argv[++i]); }
         else if (arg("--step")) step = std::atoi(argv[++i]);
         else if (arg("--dump-scene")) dump = argv[++i];
+        else if (arg("--cameras")) cameras_file = argv[++i];
+        else if (arg("--orbit")) orbit = std::atoi(argv[++i]);
+        else if (arg("--sample-stride")) sample_stride = std::atoi(argv[++i]);
+        else if (arg("--dump-cameras")) dump_cameras = argv[++i];
         else if (arg("--scene")) scene_file = argv[++i];
         else if (!std::strcmp(argv[i], "--grid") && i + 2 < argc) { lo = std::atoi(argv[++i]); hi = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -110,6 +122,66 @@ int main(int argc, char **argv)
         std::fwrite(flat.data(), sizeof(rt_sphere), flat.size(), f);
         std::fclose(f);
         std::printf("%zu spheres -> %s\n", flat.size(), dump.c_str());
+        return 0;
+    }
+    const bool batch = !cameras_file.empty() || orbit != 0;
+    if (batch && (!devices.empty() || passes > 1 || adaptive || uniform53 || two_calls)) {
+        std::fprintf(stderr, "--cameras / --orbit render a frame batch on one device and go with none of --devices, --passes, --adaptive, --uniform53, --two-calls\n");
+        return 2;
+    }
+    if (!cameras_file.empty() && orbit != 0) { std::fprintf(stderr, "--cameras and --orbit: one or the other\n"); return 2; }
+    if (orbit < 0) { std::fprintf(stderr, "--orbit N: N >= 1\n"); return 2; }
+    if (!dump_cameras.empty()) {                 // the camera file: 152-byte records (the --orbit turntable, or the book camera alone)
+        const std::vector<rt_camera> cams = rtiow::orbit_cameras(orbit > 0 ? orbit : 1, width, height);
+        if (!rtiow::save_cameras(dump_cameras.c_str(), cams)) { std::perror(dump_cameras.c_str()); return 1; }
+        std::printf("%zu cameras -> %s\n", cams.size(), dump_cameras.c_str());
+        return 0;
+    }
+    if (batch) {
+        std::vector<rt_camera> cams;
+        if (orbit > 0) cams = rtiow::orbit_cameras(orbit, width, height);
+        else if (!rtiow::load_cameras(cameras_file.c_str(), cams) || cams.empty()) {
+            std::fprintf(stderr, "%s: cannot read a whole number (>= 1) of 152-byte camera records\n", cameras_file.c_str());
+            return 1;
+        }
+        rt_params p{};
+        p.width = width; p.height = height; p.spp = spp; p.sample_begin = 0; p.max_depth = depth;
+        p.t_min = 0.0001; p.seed = seed; p.tile_rows = 8; p.shard_index = 0; p.shard_count = 1; p.flags = 0u;
+        const int stride = sample_stride < 0 ? spp : sample_stride;
+        const size_t npix = (size_t)width * height;
+        std::vector<uint8_t> rgba(npix * 4 * cams.size());
+        rt_stats st{};
+        rt_context *ctx = nullptr;
+        int rc = rt_create(device, &ctx);
+        if (rc) return die("rt_create", rc);
+        rc = rt_upload_scene(ctx, flat.data(), (int32_t)flat.size());
+        if (rc) { die("rt_upload_scene", rc); rt_destroy(ctx); return 1; }
+        rc = rt_render_frames_rgba8(ctx, cams.data(), (int32_t)cams.size(), stride, &p, 1, rgba.data(), &st);
+        if (rc) { die("rt_render_frames_rgba8", rc); rt_destroy(ctx); return 1; }
+        rt_destroy(ctx);
+        std::string prefix = out, ext = ".png";
+        if (prefix.size() >= 4 && (prefix.compare(prefix.size() - 4, 4, ".png") == 0 || prefix.compare(prefix.size() - 4, 4, ".ppm") == 0)) {
+            ext = prefix.substr(prefix.size() - 4);
+            prefix.resize(prefix.size() - 4);
+        }
+        for (size_t f = 0; f < cams.size(); ++f) {
+            char num[32];
+            std::snprintf(num, sizeof(num), "_%04zu", f);
+            const std::string name = prefix + num + ext;
+            const uint8_t *px = rgba.data() + f * npix * 4;
+            if (ext == ".png") {
+                if (!rtiow::write_png(name.c_str(), px, width, height)) { std::perror(name.c_str()); return 1; }
+            } else {
+                FILE *fo = std::fopen(name.c_str(), "wb");
+                if (!fo) { std::perror(name.c_str()); return 1; }
+                std::fprintf(fo, "P6\n%d %d\n255\n", width, height);
+                for (size_t k = 0; k < npix; ++k) std::fwrite(&px[4 * k], 1, 3, fo);
+                std::fclose(fo);
+            }
+        }
+        std::printf("%zu frames of %dx%d spp %d, sample stride %d, one launch: %llu rays, kernel %.3f ms (%.1f Msamples/s) -> %s_0000%s ...\n",
+                    cams.size(), width, height, spp, stride, (unsigned long long)st.rays_traced, st.kernel_ms,
+                    (double)st.samples / st.kernel_ms / 1e3, prefix.c_str(), ext.c_str());
         return 0;
     }
     const rtiow::Camera cam(rtiow::Point3(13, 2, 3), rtiow::Point3(0, 0, 0), rtiow::Vec3(0, 1, 0), 20.0,

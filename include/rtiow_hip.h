@@ -137,7 +137,8 @@ typedef struct {
                                     tile grid has <= 64 cells (else the general one, and every other scan mode); 2 the
                                     RT_FLAG_UNIFORM53 instantiation; 4 work blocks of 1 024 pixel-samples instead of 256 (launches of
                                     >= 2 x 10^8 pixel-samples at >= 147 samples per pixel; >= 69 on the small-grid kernel); 8 the
-                                    pixel-list variant (rt_render_pixels_device) */
+                                    pixel-list variant (rt_render_pixels_device); 16 the frame-batch variant
+                                    (rt_render_frames_device) */
     uint64_t live_per_bounce[64]; /* rays traced at bounce index k (0 = camera ray; indices >= 63 share the
                                     last slot); sums to rays_traced (RT_FLAG_DIAG_STATS, else 0) */
     uint64_t direct_samples;     /* samples added to the frame buffer one by one instead of through their block's
@@ -317,6 +318,44 @@ int rt_resolve_rgba8_counts_device(rt_context *ctx, const void *d_fix, const voi
 /* Host-buffer form (copies in, resolves on the device, copies out). */
 int rt_resolve_rgba8_counts(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int32_t width, int32_t rows,
                             int32_t flip, uint8_t *out_rgba);
+
+/* ---- frame batches: main.rs:108-145 once per camera, in ONE launch ---------- */
+
+/* A batch is n_frames cameras over the uploaded scene -- a turntable, a fly-through, a stereo pair, a contact sheet of
+ * viewpoints -- with the same rt_params (width, height, spp, max_depth, t_min, seed) and a sample_stride >= 0:
+ *     frame f equals, bit for bit, the dense render of cams[f] with sample_begin' = p->sample_begin + f * sample_stride
+ * -- the exact sums rt_render gives for that camera and those parameters.  The Philox key stays p->seed and the counter stays
+ * (pixel g = j * width + i of the frame's OWN image, sample index, event, 0): the frame number enters nothing but the sample
+ * index.  sample_stride = 0 gives every frame the same random numbers (common random numbers: stereo pairs, differences
+ * between viewpoints); sample_stride >= the samples a pixel gets in all gives every frame a stream of its own (no
+ * fixed-pattern noise across an animation).  Why one launch: a launch ends when the longest path among its last samples does
+ * (~650 us for a 50-bounce path whatever the frame size), so a sequence of small frames rendered one launch each is mostly
+ * tails; the persistent grid does not care which frame a work block belongs to, and a batch has ONE tail.
+ *
+ * Device form (stands in for main.rs:108-139, once per camera).  d_cams: DEVICE [n_frames] rt_camera, alive until the launch
+ * has finished (as d_pixels of rt_render_pixels_device).  d_fix: device [n_frames][height][width][3] u64, frame after frame,
+ * rows as rt_render_device's with shard_count 1.  Honours spp, sample_begin, max_depth, t_min, seed and RT_FLAG_ACCUMULATE;
+ * RT_FLAG_OVERLAPPED is accepted and ignored; tile_rows and shard_index are unused.  Runs the shipped kernel's frame-batch
+ * variant only.  RT_ERR_INVALID_ARGUMENT, found before anything is touched (no buffer zeroed, no launch slot taken,
+ * rt_last_stats unchanged): RT_FLAG_UNIFORM53, RT_FLAG_DIAG_STATS, RT_FLAG_NO_FILTER, unknown flag bits, a context created
+ * under RTIOW_SCAN_MODE=1, shard_count != 1, n_frames < 0, sample_stride < 0, n_frames * width * height > 2^31,
+ * sample_begin + (n_frames - 1) * sample_stride + spp > 2^31 - 1, more than 2^31 - 1 work blocks (a frame has
+ * ceil(width * height * spp / 256) of them; blocks of 192 / 128 / 64 pixel-samples below 17 / 13 / 9 samples per pixel), NULL
+ * pointers with n_frames > 0; RT_ERR_NO_SCENE before an upload.  n_frames == 0 succeeds and does nothing; max_depth == 0 gives
+ * black frames without a launch, as rt_render_device does.  Asynchronous on `stream`; shares the context's two per-launch slots
+ * with rt_render_device and rt_render_pixels_device, and rt_last_stats reports on it: samples = n_frames * width * height * spp,
+ * rays_traced = the sum over the frames, scan_mode 5, kernel_variant bit 16. */
+int rt_render_frames_device(rt_context *ctx, const rt_camera *d_cams, int32_t n_frames, int32_t sample_stride,
+                            const rt_params *p, void *d_fix, void *stream);
+/* Host-buffer form: host cameras, host sums out_fix [n_frames][height][width][3]; synchronous; starts from zero
+ * (RT_FLAG_ACCUMULATE is ignored); stats may be NULL. */
+int rt_render_frames(rt_context *ctx, const rt_camera *cams, int32_t n_frames, int32_t sample_stride,
+                     const rt_params *p, uint64_t *out_fix, rt_stats *stats);
+/* ... + Color::to_rgba with p->spp samples (main.rs:137, vec3.rs:403-421) and the row flip (main.rs:141-145, flip != 0) PER
+ * FRAME: out_rgba is [n_frames][height][width][4] u8, frame f holds exactly the bytes rt_render_rgba8 gives for cams[f] and
+ * sample_begin + f * sample_stride; the sums never leave the device.  Needs spp >= 1.  Synchronous; stats may be NULL. */
+int rt_render_frames_rgba8(rt_context *ctx, const rt_camera *cams, int32_t n_frames, int32_t sample_stride,
+                           const rt_params *p, int32_t flip, uint8_t *out_rgba, rt_stats *stats);
 
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);

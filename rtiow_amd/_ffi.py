@@ -71,6 +71,9 @@ SYMBOLS = [
     ("rt_render_adaptive", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive), _VP, _VP, _VP, C.POINTER(rt_stats)]),
     ("rt_resolve_rgba8_counts_device", C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP]),
     ("rt_resolve_rgba8_counts", C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP]),
+    ("rt_render_frames_device", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.POINTER(rt_params), _VP, _VP]),
+    ("rt_render_frames", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.POINTER(rt_params), _VP, C.POINTER(rt_stats)]),
+    ("rt_render_frames_rgba8", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.POINTER(rt_params), C.c_int32, _VP, C.POINTER(rt_stats)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

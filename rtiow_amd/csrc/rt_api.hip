@@ -13,32 +13,11 @@
 #include <cstring>
 #include <vector>
 
-#include "rtiow_hip.h"
-#include "rt_kernels.hpp"
-#ifdef RTIOW_CROSSCHECK_MODES
-#include "xcheck/rt_xcheck_host_ctx.hpp"
-#endif
+#include "rt_host.hpp"          // rtiow_hip.h, rt_kernels.hpp, rt_context, launch_render: what rt_frames.hip shares with this file
 
 namespace {
 
 thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define RT_HIP(call)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP,        \
-                        "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 int env_int(const char *name, int dflt)
 {
@@ -49,60 +28,18 @@ int env_int(const char *name, int dflt)
 
 } // namespace
 
-struct rt_context {
-    int device = 0;
-    int cu_count = 0;
-    float *d_filt = nullptr;       // [n][4] f32 filter records (MODE 1)
-    double *d_geo = nullptr;       // [n][4] exact geometry
-    double *d_mat = nullptr;       // [n][kMatStride] exact materials
-    uint4 *d_btube = nullptr;      // [tiles/2 + 1][64] MODE 5 (tube filter) B operands
-    float tube_rho = 1.0f;         // MODE 5 radius floor
-    double *d_geo_slot = nullptr;  // MODE 5: [slots][4] exact geometry in table (slot) order
-    uint32_t *d_slot_orig = nullptr;   // MODE 5: [slots] list index of the sphere in each column of the table
-    int n_global = 0;              // MODE 5: tiles [0, n_global) are scanned for every ray; the rest are grid cells
-    int grid_dim = 0;              // MODE 5: cells per side of the xz grid (0: no grid, every tile is scanned)
-    float grid[8] = {};            // x0, z0, 1/cell, x1, z1, y lo, y hi, pad (rt_device.hpp, grid_cells)
-    float scene_scale = 0.0f;      // MODE 5: KParams::scene_scale
-#ifdef RTIOW_CROSSCHECK_MODES
-    XcheckScene x;                 // device tables of scan modes 2-4 (xcheck/rt_xcheck_host_ctx.hpp)
-#endif
-    int n_tiles = 0;
-    int n_always = 0;
-    int always_idx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int scan_mode = 5;             // filter: 5 tube bf16x2 MFMA (default, shipped), 1 VALU + scalar loads (cross-check);
-                                   // with -DRTIOW_CROSSCHECK_MODES also 2 f32 MFMA, 3 bf16x3 MFMA, 4 lifted bf16x3 MFMA
-    int n_spheres = -1;
-    // Per-launch state -- the work counter, the statistics words and the two events -- exists kSlots times, used in turn: a context
-    // may have kSlots renders in flight (on different streams: the second fills the first one's end-of-launch tail); the fields
-    // below name the slot of the LATEST launch, which is what rt_last_stats reports on.
-    static constexpr int kSlots = 2;
-    unsigned int *q_slots[kSlots] = {nullptr, nullptr};
-    unsigned long long *s_slots[kSlots] = {nullptr, nullptr};
-    hipEvent_t e0_slots[kSlots] = {nullptr, nullptr}, e1_slots[kSlots] = {nullptr, nullptr};
-    bool slot_used[kSlots] = {false, false};
-    int cur = 0;
-    unsigned int *d_queue = nullptr;
-    unsigned long long *d_stats = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipStream_t own_stream = nullptr;
-    bool launched = false;
-    unsigned long long zero_depth_samples = 0;
-    rt_stats last{};
-    // staging for the host-buffer entry points
-    void *d_stage_fix = nullptr; size_t stage_fix_bytes = 0;
-    void *d_stage_sum = nullptr; size_t stage_sum_bytes = 0;
-    void *d_stage_rgba = nullptr; size_t stage_rgba_bytes = 0;
-    int blocks_per_cu = 0;     // 0 = occupancy query
-    // rt_select_pixels_device's scratch (noisy / active flags, the workgroups' counts) and rt_render_adaptive's frame state
-    void *d_sel = nullptr; size_t sel_bytes = 0;
-    void *d_adapt = nullptr; size_t adapt_bytes = 0;
-    void *d_stage_list = nullptr; size_t stage_list_bytes = 0;   // rt_render_pixels: the list on the device
-    int ring_min_spp = 0;                 // RTIOW_RING_MIN_SPP (diagnostic): spp per launch from which block sums are kept in LDS (0: the kernel's own minimum)
-};
+int rt_host::fail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
 
-namespace {
+using namespace rt_host;
 
-int validate_params(const rt_params *p)
+int rt_host::validate_params(const rt_params *p)
 {
     if (!p) return fail(RT_ERR_INVALID_ARGUMENT, "params is NULL");
     if (p->width < 2 || p->height < 2)
@@ -124,6 +61,8 @@ int validate_params(const rt_params *p)
     return RT_OK;
 }
 
+namespace {
+
 // rows owned by a shard: tiles t = shard_index, shard_index+shard_count, ...
 int shard_rows(const rt_params *p)
 {
@@ -137,7 +76,9 @@ int shard_rows(const rt_params *p)
     return (int)rows;
 }
 
-int ensure(void **ptr, size_t *have, size_t need)
+} // namespace
+
+int rt_host::ensure(void **ptr, size_t *have, size_t need)
 {
     if (*have >= need && *ptr) return RT_OK;
     if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; *have = 0; }
@@ -145,6 +86,8 @@ int ensure(void **ptr, size_t *have, size_t need)
     *have = need;
     return RT_OK;
 }
+
+namespace {
 
 // K' of the scan filter for one sphere (rt_device.hpp):
 // |c|^2 (1-kappa) - r^2 (1+2 kappa) in f64, rounded DOWN to f32 (a smaller K' keeps more);
@@ -264,30 +207,10 @@ int upload_table(T **dst, const T *src, size_t count)
     return RT_OK;
 }
 
-template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITEMS = rt::kItemBlock>
-int launch_render(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, int *grid_out)
-{
-    int per_cu = ctx->blocks_per_cu;
-    if (per_cu <= 0) {
-        int occ = 0;
-        RT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, rt::render_kernel<MODE, DIAG, SMALLGRID, U53, ITEMS>, rt::kBlock, 0));
-        per_cu = occ < 1 ? 1 : (occ > 8 ? 8 : occ);
-    }
-    // persistent grid, but never more lanes than there are work items
-    long long grid = (long long)ctx->cu_count * per_cu;
-    const long long need = (long long)((kp.total_items + rt::kBlock - 1) / rt::kBlock);
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    *grid_out = (int)grid;
-    RT_HIP(hipEventRecord(ctx->ev0, stream));
-    hipLaunchKernelGGL((rt::render_kernel<MODE, DIAG, SMALLGRID, U53, ITEMS>), dim3((unsigned)grid), dim3(rt::kBlock), 0, stream, kp);
-    RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(ctx->ev1, stream));
-    return RT_OK;
-}
+} // namespace
 
 // the scene's tables and grid, as every render kernel reads them
-void set_scene_params(const rt_context *ctx, rt::KParams &kp)
+void rt_host::set_scene_params(const rt_context *ctx, rt::KParams &kp)
 {
     kp.filt = ctx->d_filt; kp.geo = ctx->d_geo; kp.mat = ctx->d_mat;
     kp.n_tiles = ctx->n_tiles;
@@ -308,7 +231,7 @@ void set_scene_params(const rt_context *ctx, rt::KParams &kp)
 
 // Takes the other slot of per-launch state for a launch on `stream`; if the launch that used it last is still running (on another
 // stream), `stream` waits for it -- the host does not.  (A call is validated BEFORE it takes a slot.)
-int next_launch_slot(rt_context *ctx, hipStream_t stream, rt::KParams &kp)
+int rt_host::next_launch_slot(rt_context *ctx, hipStream_t stream, rt::KParams &kp)
 {
     ctx->cur = (ctx->cur + 1) % rt_context::kSlots;
     ctx->d_queue = ctx->q_slots[ctx->cur]; ctx->d_stats = ctx->s_slots[ctx->cur];
@@ -318,6 +241,8 @@ int next_launch_slot(rt_context *ctx, hipStream_t stream, rt::KParams &kp)
     kp.queue = ctx->d_queue; kp.stats = ctx->d_stats;
     return RT_OK;
 }
+
+namespace {
 
 // what a pixel-list render accepts beyond validate_params: checked before anything is touched.  The checks that need no context come
 // first (so a caller -- and a test -- without a device still gets the precise message), then the context's own.
@@ -584,7 +509,7 @@ int rt_destroy(rt_context *ctx)
         if (ctx->e1_slots[k]) (void)hipEventDestroy(ctx->e1_slots[k]);
     }
     (void)hipFree(ctx->d_stage_fix); (void)hipFree(ctx->d_stage_sum); (void)hipFree(ctx->d_stage_rgba);
-    (void)hipFree(ctx->d_sel); (void)hipFree(ctx->d_adapt); (void)hipFree(ctx->d_stage_list);
+    (void)hipFree(ctx->d_sel); (void)hipFree(ctx->d_adapt); (void)hipFree(ctx->d_stage_list); (void)hipFree(ctx->d_stage_cams);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return RT_OK;

@@ -1,0 +1,210 @@
+// rt_frames.hip -- frame batches: n_frames cameras over the uploaded scene in ONE launch (rtiow_hip.h, "frame batches").
+//
+// The second translation unit of librtiow_hip.so.  It owns the frame-batch instantiations of the render kernel,
+// rt::render_kernel<5, false, SMALLGRID, false, rt::kItemBlockFrames> (rt_kernels.hpp), and the three entry points that launch
+// them; the context, the validation helpers and the per-launch slots are rt_api.hip's, shared through rt_host.hpp.  Every other
+// kernel of the library stays in rt_api.hip, whose device code this file leaves untouched.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: render_kernel and what it needs; the resolve / selection / known-answer kernels are rt_api.hip's
+#include "rt_host.hpp"
+
+using namespace rt_host;
+
+namespace {
+
+// work blocks as rt_render_pixels_device picks them for the shipped kernel's ring of 2 x 16 pixel slots: 256 pixel-samples from 17
+// samples per pixel on, the largest multiple of 64 whose pixels fit the slots down to 5, every sample on its own below
+unsigned frames_block_items(int spp, int ring_min_spp, bool *use_ring)
+{
+    unsigned small_block = 0;
+    for (unsigned items = rt::kItemBlock; items >= 64u && spp >= 1; items -= 64u)
+        if ((items - 1u + (unsigned)spp - 1u) / (unsigned)spp + 1u <= 2u * (unsigned)rt::kRingSlots) { small_block = items; break; }
+    *use_ring = small_block != 0u && spp >= ring_min_spp;
+    return *use_ring ? small_block : (unsigned)rt::kItemBlock;
+}
+
+// What a frame batch accepts beyond validate_params: checked before anything is touched.  The checks that need no context come first
+// (a caller without a device still gets the precise message), then the context's own.
+int validate_frames(const rt_context *ctx, int32_t n_frames, int32_t sample_stride, const rt_params *p)
+{
+    int rc = validate_params(p);
+    if (rc) return rc;
+    if (p->flags & (RT_FLAG_UNIFORM53 | RT_FLAG_DIAG_STATS | RT_FLAG_NO_FILTER))
+        return fail(RT_ERR_INVALID_ARGUMENT, "frame batches run the shipped kernel only: RT_FLAG_UNIFORM53, RT_FLAG_DIAG_STATS and "
+                    "RT_FLAG_NO_FILTER are not available on them (flags 0x%x)", p->flags);
+    if (p->shard_count != 1)
+        return fail(RT_ERR_INVALID_ARGUMENT, "frame batches are not sharded: shard_count must be 1 (is %d)", p->shard_count);
+    if (n_frames < 0) return fail(RT_ERR_INVALID_ARGUMENT, "n_frames must be >= 0 (is %d)", n_frames);
+    if (sample_stride < 0) return fail(RT_ERR_INVALID_ARGUMENT, "sample_stride must be >= 0 (is %d)", sample_stride);
+    const long long frame_pix = (long long)p->width * p->height;
+    if ((long long)n_frames * frame_pix > 0x80000000LL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "n_frames*width*height = %lld pixels in one batch: at most 2^31", (long long)n_frames * frame_pix);
+    if (n_frames > 0 && (long long)p->sample_begin + (long long)(n_frames - 1) * sample_stride + p->spp > 0x7fffffffLL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "sample_begin + (n_frames-1)*sample_stride + spp = %lld: the last frame's sample indices must stay "
+                    "below 2^31", (long long)p->sample_begin + (long long)(n_frames - 1) * sample_stride + p->spp);
+    bool use_ring = false;
+    const unsigned item_block = frames_block_items(p->spp, ctx ? ctx->ring_min_spp : 0, &use_ring);
+    const unsigned long long frame_blocks = ((unsigned long long)frame_pix * (unsigned long long)p->spp + item_block - 1) / item_block;
+    if (frame_blocks * (unsigned long long)n_frames > 0x7fffffffULL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "n_frames*ceil(width*height*spp / %u) = %llu work blocks in one batch: at most 2^31 - 1 "
+                    "(split the batch, or the samples with sample_begin and RT_FLAG_ACCUMULATE)", item_block, frame_blocks * (unsigned long long)n_frames);
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (ctx->scan_mode != 5)
+        return fail(RT_ERR_INVALID_ARGUMENT, "frame batches need the shipped scan mode 5; this context was created under RTIOW_SCAN_MODE=%d", ctx->scan_mode);
+    return RT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// main.rs:108-139, once per camera, in one launch
+int rt_render_frames_device(rt_context *ctx, const rt_camera *d_cams, int32_t n_frames, int32_t sample_stride,
+                            const rt_params *p, void *d_fix, void *stream_v)
+{
+    int rc = validate_frames(ctx, n_frames, sample_stride, p);
+    if (rc) return rc;
+    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (n_frames == 0) return RT_OK;
+    if (!d_cams || !d_fix) return fail(RT_ERR_INVALID_ARGUMENT, "d_cams/d_fix is NULL");
+    const unsigned long long frame_pix = (unsigned long long)p->width * (unsigned long long)p->height;
+    const unsigned long long frame_items = frame_pix * (unsigned long long)p->spp;
+    const unsigned long long total_items = frame_items * (unsigned long long)n_frames;
+    bool use_ring = false;
+    const unsigned item_block = frames_block_items(p->spp, ctx->ring_min_spp, &use_ring);
+    // a work block never straddles two frames: every frame has its own ceil(frame_items / item_block) blocks, the last one short
+    const unsigned long long frame_blocks = (frame_items + item_block - 1) / item_block;
+    const unsigned long long n_blocks = frame_blocks * (unsigned long long)n_frames;      // (<= 2^31 - 1: validate_frames)
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+
+    rt::KParams kp;
+    memset(&kp, 0, sizeof(kp));
+    static_assert(sizeof(rt::KCamera) == sizeof(rt_camera) && sizeof(rt_camera) == 19 * sizeof(double), "camera layouts must match");
+    kp.width = p->width; kp.height = p->height;
+    kp.spp = p->spp; kp.sample_begin = p->sample_begin; kp.max_depth = p->max_depth;
+    kp.t_min = p->t_min;
+    kp.k0 = (uint32_t)p->seed; kp.k1 = (uint32_t)(p->seed >> 32);
+    kp.tile_rows = 1; kp.shard_index = 0; kp.shard_count = 1;            // (unused by the variant)
+    kp.rows = p->height; kp.n_spheres = ctx->n_spheres;
+    kp.npix = (uint32_t)(frame_pix * (unsigned long long)n_frames);      // (the kernel does not read it)
+    kp.total_items = total_items; kp.n_blocks = (uint32_t)n_blocks;
+    kp.inv_spp = p->spp > 0 ? 1.0 / (double)p->spp : 0.0;
+    kp.inv_width = 1.0 / (double)p->width;
+    // udiv_small (rt_kernels.hpp): the numerators are < d + kItemBlock
+    auto magic_for = [](long long d) -> uint32_t {
+        return (d <= 1 || d >= 32768) ? 0u : (uint32_t)(0x100000000ULL / (unsigned long long)d + 1ULL);
+    };
+    kp.magic_spp = magic_for(p->spp); kp.magic_width = magic_for(p->width);
+    kp.use_ring = use_ring ? 1 : 0;
+    kp.block_items = item_block;
+    set_scene_params(ctx, kp);
+    kp.fix = (unsigned long long *)d_fix;
+    kp.cams = reinterpret_cast<const rt::KCamera *>(d_cams);
+    kp.frame_items = frame_items;
+    kp.frame_blocks = (uint32_t)frame_blocks;
+    kp.inv_frame_blocks = frame_blocks > 0 ? 1.0 / (double)frame_blocks : 0.0;
+    kp.frame_pix = (uint32_t)frame_pix;
+    kp.sample_stride = sample_stride;
+    rc = next_launch_slot(ctx, stream, kp);
+    if (rc) return rc;
+
+    if (!(p->flags & RT_FLAG_ACCUMULATE))
+        RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)(frame_pix * (unsigned long long)n_frames) * 3 * sizeof(unsigned long long), stream));
+    RT_HIP(hipMemsetAsync(ctx->d_queue, 0, 64, stream));
+    RT_HIP(hipMemsetAsync(ctx->d_stats, 0, 1024, stream));
+    memset(&ctx->last, 0, sizeof(ctx->last));
+    ctx->last.n_spheres = ctx->n_spheres;
+    ctx->last.block_threads = rt::kBlock;
+    ctx->zero_depth_samples = 0;
+    if (p->max_depth == 0 || total_items == 0) {                         // (as rt_render_device: black without tracing, nothing to launch)
+        RT_HIP(hipEventRecord(ctx->ev0, stream));
+        RT_HIP(hipEventRecord(ctx->ev1, stream));
+        ctx->zero_depth_samples = total_items;
+        ctx->last.scan_mode = 5;
+        ctx->launched = true;
+        return RT_OK;
+    }
+    int grid = 0;
+    const bool small_grid = ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64;
+    ctx->last.scan_mode = 5;
+    ctx->last.kernel_variant = 16 | (small_grid ? 1 : 0);
+    rc = small_grid ? launch_render<5, false, true, false, rt::kItemBlockFrames>(ctx, kp, stream, &grid)      // (the frame-batch instantiations)
+                    : launch_render<5, false, false, false, rt::kItemBlockFrames>(ctx, kp, stream, &grid);
+    if (rc) return rc;
+    ctx->launched = true;
+    ctx->last.grid_blocks = grid;
+    return RT_OK;
+}
+
+int rt_render_frames(rt_context *ctx, const rt_camera *cams, int32_t n_frames, int32_t sample_stride,
+                     const rt_params *p, uint64_t *out_fix, rt_stats *stats)
+{
+    int rc = validate_frames(ctx, n_frames, sample_stride, p);
+    if (rc) return rc;
+    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (n_frames == 0) return RT_OK;
+    if (!cams || !out_fix) return fail(RT_ERR_INVALID_ARGUMENT, "cams/out_fix is NULL");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t count = (size_t)n_frames * p->width * p->height * 3;
+    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, count * sizeof(uint64_t));
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_cams, &ctx->stage_cams_bytes, (size_t)n_frames * sizeof(rt_camera));
+    if (rc) return rc;
+    RT_HIP(hipMemcpyAsync(ctx->d_stage_cams, cams, (size_t)n_frames * sizeof(rt_camera), hipMemcpyHostToDevice, ctx->own_stream));
+    rt_params q = *p;
+    q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
+    rc = rt_render_frames_device(ctx, (const rt_camera *)ctx->d_stage_cams, n_frames, sample_stride, &q, ctx->d_stage_fix, ctx->own_stream);
+    if (rc) return rc;
+    RT_HIP(hipMemcpyAsync(out_fix, ctx->d_stage_fix, count * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->own_stream));
+    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    if (stats) return rt_last_stats(ctx, stats);
+    return RT_OK;
+}
+
+// main.rs:108-145 once per camera: the sums stay on the device, 4 bytes per pixel come back
+int rt_render_frames_rgba8(rt_context *ctx, const rt_camera *cams, int32_t n_frames, int32_t sample_stride,
+                           const rt_params *p, int32_t flip, uint8_t *out_rgba, rt_stats *stats)
+{
+    int rc = validate_frames(ctx, n_frames, sample_stride, p);
+    if (rc) return rc;
+    if (p->spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_frames_rgba8 needs spp >= 1 (to_rgba divides by the sample count, vec3.rs:409)");
+    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (n_frames == 0) return RT_OK;
+    if (!cams || !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "cams/out_rgba is NULL");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t frame_pix = (size_t)p->width * p->height;
+    const size_t npix = frame_pix * (size_t)n_frames;
+    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, npix * 3 * sizeof(uint64_t));
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_rgba, &ctx->stage_rgba_bytes, npix * 4);
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_cams, &ctx->stage_cams_bytes, (size_t)n_frames * sizeof(rt_camera));
+    if (rc) return rc;
+    RT_HIP(hipMemcpyAsync(ctx->d_stage_cams, cams, (size_t)n_frames * sizeof(rt_camera), hipMemcpyHostToDevice, ctx->own_stream));
+    rt_params q = *p;
+    q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
+    rc = rt_render_frames_device(ctx, (const rt_camera *)ctx->d_stage_cams, n_frames, sample_stride, &q, ctx->d_stage_fix, ctx->own_stream);
+    if (rc) return rc;
+    // Color::to_rgba is per pixel; only the flip knows about frames.  Unflipped, the batch is one image of n_frames * height rows;
+    // flipped, every frame is resolved on its own (the resolve kernel is rt_api.hip's: this file adds none)
+    if (!flip && (long long)n_frames * p->height <= 0x7fffffffLL) {
+        rc = rt_resolve_rgba8_device(ctx, ctx->d_stage_fix, p->width, n_frames * p->height, (int64_t)p->spp, 0, ctx->d_stage_rgba, ctx->own_stream);
+        if (rc) return rc;
+    } else {
+        for (int32_t f = 0; f < n_frames; ++f) {
+            rc = rt_resolve_rgba8_device(ctx, (const uint64_t *)ctx->d_stage_fix + (size_t)f * frame_pix * 3, p->width, p->height, (int64_t)p->spp,
+                                         flip, (uint8_t *)ctx->d_stage_rgba + (size_t)f * frame_pix * 4, ctx->own_stream);
+            if (rc) return rc;
+        }
+    }
+    RT_HIP(hipMemcpyAsync(out_rgba, ctx->d_stage_rgba, npix * 4, hipMemcpyDeviceToHost, ctx->own_stream));
+    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    if (stats) return rt_last_stats(ctx, stats);
+    return RT_OK;
+}
+
+} // extern "C"

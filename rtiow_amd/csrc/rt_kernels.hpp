@@ -93,6 +93,14 @@ struct KParams {
     unsigned long long *stats; // [0] rays [1] samples [2] candidates [3] exact roots [4] samples sent to the frame buffer one by one [8..15] diagnostic builds [16..79] rays per bounce index (DIAG)
     const uint32_t *pix_list;  // pixel-list launches (ITEMS = kItemBlockList): [npix] global pixel numbers g = j * width + i; `fix` is then [npix][3], entry k for pix_list[k] (last member: the
                                // offsets of everything render_kernel reads stay where they were)
+    // frame-batch launches (ITEMS = kItemBlockFrames; after pix_list for the same reason).  n_blocks = n_frames * frame_blocks and
+    // total_items = n_frames * frame_items; `fix` is [n_frames][height][width][3]
+    const KCamera *cams;       // [n_frames] cameras, DEVICE memory
+    unsigned long long frame_items;    // width * height * spp: pixel-samples of one frame
+    double inv_frame_blocks;   // 1.0 / frame_blocks (block -> frame)
+    uint32_t frame_blocks;     // work blocks per frame = ceil(frame_items / block_items): no block straddles two frames
+    uint32_t frame_pix;        // width * height: virtual pixel f * frame_pix + g is pixel g of frame f
+    int32_t sample_stride;     // frame f renders the samples [sample_begin + f * sample_stride, ... + spp)
 };
 
 constexpr int RT_KIND_LAMBERTIAN = 0, RT_KIND_METAL = 1, RT_KIND_DIALECTRIC = 2;
@@ -107,6 +115,7 @@ constexpr int kItemBlock = 256;     // pixel-samples a wave reserves per atomic 
 // blocks are the end-of-launch tail (1200x675x147 is 5 % slower with 1 024).
 constexpr int kItemBlockLarge = 1024;
 constexpr int kItemBlockList = -kItemBlock;   // as the ITEMS of render_kernel: work blocks of kItemBlock pixel-samples over a pixel list (render_kernel below)
+constexpr int kItemBlockFrames = -2 * kItemBlock;   // ... and over a BATCH OF FRAMES, one camera each (rt_render_frames_device; instantiated from rt_frames.hip only)
 static_assert(kItemBlockLarge + 32768 < 65536, "udiv_small: numerators x < d + kItemBlockLarge with d < 2^15 keep x * d < 2^32");
 constexpr int kLargeMinSpp = 147;
 constexpr int kLargeMinSppSmallGrid = 69;
@@ -175,6 +184,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // a __forceinline__ function shared by two __global__ entries moves opcodes in EVERY existing instantiation (tried: all 14 ops-sha of
 // tools/isa_fingerprint.py change), a sixth template parameter would rename the kernels bench.py and the profiles spell.  As built, the existing
 // instantiations' machine code is unchanged (profiles/isa_fingerprint_{before,after}_pixel_lists.txt).
+// ... or kItemBlockFrames = -2 * kItemBlock: blocks of (at most) kItemBlock pixel-samples over a BATCH OF FRAMES (rt_render_frames_device).  The launch is a
+// virtual image of n_frames * height rows: frame f owns the virtual pixels [f * P.frame_pix, (f + 1) * P.frame_pix) and the work blocks
+// [f * P.frame_blocks, (f + 1) * P.frame_blocks) -- a block never straddles two frames, so its frame f, hence its camera P.cams[f] and its
+// first sample index P.sample_begin + f * P.sample_stride, are wave-uniform.  The work blocks, the queue, the block sums and their
+// write-out address pixels by their virtual number (the output is [n_frames][height][width][3]); the Philox counter takes the pixel's
+// number g in its OWN frame.  Only the block decode, the start of a sample and the camera differ; the bounce loop is the dense kernel's.
+// Same method as the pixel lists (`if constexpr` where the body stands), and the instantiations live in a translation unit of their own
+// (rt_frames.hip): rt_api.hip's kernels are the same set with the same machine code (profiles/isa_fingerprint_{before,after}_frame_batches.txt).
 template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITEMS = 256>
 // second launch bound = waves per SIMD the register allocator must leave room for: the bounce loop
 // is latency-bound, and the 4th wave is worth more than the few cold values it spills.  Only the shipped kernel
@@ -182,8 +199,10 @@ template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITE
 // diagnostic variant and the cross-check modes 2-4 carry 1-14 KB more and run three.
 __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 : 5) void render_kernel(const KParams P)
 {
-    constexpr bool PIXLIST = ITEMS < 0;
-    static_assert(!PIXLIST || (MODE == 5 && !DIAG && !U53 && ITEMS == kItemBlockList), "pixel lists: the shipped kernel, 32-bit uniforms, blocks of 256");
+    constexpr bool PIXLIST = ITEMS == kItemBlockList;
+    constexpr bool FRAMES = ITEMS == kItemBlockFrames;
+    static_assert(ITEMS > 0 || PIXLIST || FRAMES, "ITEMS: a block size, kItemBlockList or kItemBlockFrames");
+    static_assert(!(PIXLIST || FRAMES) || (MODE == 5 && !DIAG && !U53), "pixel lists and frame batches: the shipped kernel, 32-bit uniforms, blocks of 256");
     // The block sums' ring (s_ring below) has the same 768 bytes per wave in both shapes: 4 blocks x 8 pixels, or -- the shipped scan mode's
     // kernels, all but the large-grid kernel's instantiation for blocks of 1 024 -- 2 blocks x 16 pixels.  Two blocks in flight are enough: a block of 256 lasts ~11 passes, one of
     // 1 024 ~43, and the samples of the block before the previous one that are still open when a block begins (paths of more than
@@ -193,7 +212,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     // 48.74 ms, 1200x675x100 10.53 -> 10.49 ms, 10k spheres 1920x1080 x20 7.78 -> 7.50 ms, x100 34.98 -> 34.88 ms; the large-grid kernel ON LARGE
     // BLOCKS is 0.7 % slower with the same ring (10k spheres 1920x1080x256: 85.99 -> 86.58 ms, fewer instructions, another schedule) and
     // keeps 4 x 8 and kLargeMinSpp = 147.  The cross-check scan modes and the diagnostic-counter kernels keep 4 x 8 too.
-    constexpr bool kWideRing = SMALLGRID || (MODE == 5 && !DIAG && (ITEMS == kItemBlock || ITEMS == kItemBlockList));
+    constexpr bool kWideRing = SMALLGRID || (MODE == 5 && !DIAG && (ITEMS == kItemBlock || ITEMS == kItemBlockList || ITEMS == kItemBlockFrames));
     constexpr int kRingDepth = kWideRing ? 2 : 4;
     constexpr int kRingSlots = kWideRing ? 16 : 8;
     static_assert(kRingDepth * kRingSlots == rt::kRingDepth * rt::kRingSlots, "same LDS either way");
@@ -260,6 +279,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     bool dead = false, alive = false;
     uint32_t pix_local = 0, pix_global = 0;
     int s = 0;
+    uint32_t my_frame = 0;                         // FRAMES: frame of the sample this lane has just taken (PHASE 1 -> PHASE 2 only)
     uint32_t my_blk = 0;                           // sequence number (within this wave) of the block of this lane's sample << 4 | its pixel slot
     D3 o = mk(0, 0, 0), d = mk(0, 0, 1);
     int depth = 0;
@@ -269,6 +289,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     // this wave's current block of work items (all wave-uniform): items [blk_next, blk_end) of it are still to be dealt;
     // its first item is sample blk_s0 of compact pixel blk_pix0 = row blk_rr0, column blk_i0 of the shard
     uint32_t blk_next = 0, blk_end = 0, blk_seq = 0xFFFFFFFFu, blk_pix0 = 0, blk_s0 = 0, blk_rr0 = 0, blk_i0 = 0;
+    uint32_t blk_frame = 0, blk_sbase = (uint32_t)P.sample_begin;   // FRAMES: the current block's frame and the index of that frame's first sample (wave-uniform)
     bool queue_empty = false;
     // the wave's queue of camera rays: entries [q_head, q_head + q_count) of s_qray / s_qid (wave-uniform)
     uint32_t q_head = 0, q_count = 0;
@@ -342,8 +363,19 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                         break;
                     }
                     // first item of the block -> (pixel, sample): W0 / spp in f64 (W0 < 2^39: exact), one correction step
-                    const unsigned long long W0 = (unsigned long long)nb * (unsigned long long)P.block_items;     // (block_items <= ITEMS)
-                    const unsigned long long left = P.total_items - W0;
+                    uint32_t nb_f = nb;                             // FRAMES: the block's number within its frame
+                    if constexpr (FRAMES) {
+                        // block -> (frame, block of the frame): nb / frame_blocks in f64 (nb < 2^31: exact product, one rounding), one correction step
+                        uint32_t fr = (uint32_t)((double)nb * P.inv_frame_blocks);
+                        long long br = (long long)nb - (long long)fr * (long long)P.frame_blocks;
+                        if (br < 0) { fr -= 1u; br += (long long)P.frame_blocks; }
+                        else if (br >= (long long)P.frame_blocks) { fr += 1u; br -= (long long)P.frame_blocks; }
+                        blk_frame = (uint32_t)__builtin_amdgcn_readfirstlane((int)fr);
+                        nb_f = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)br);
+                        blk_sbase = (uint32_t)P.sample_begin + blk_frame * (uint32_t)P.sample_stride;
+                    }
+                    const unsigned long long W0 = (unsigned long long)nb_f * (unsigned long long)P.block_items;     // (block_items <= ITEMS; FRAMES: first item WITHIN the frame)
+                    const unsigned long long left = (FRAMES ? P.frame_items : P.total_items) - W0;
                     const uint32_t n_items = left < (unsigned long long)P.block_items ? (uint32_t)left : P.block_items;
                     uint32_t p0 = (uint32_t)((double)W0 * P.inv_spp);
                     long long rem = (long long)(W0 - (unsigned long long)p0 * (unsigned long long)(uint32_t)P.spp);
@@ -358,6 +390,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     blk_rr0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)rr0);                  // (keeps them in SGPRs)
                     blk_i0 = (uint32_t)__builtin_amdgcn_readfirstlane(i0);
                     }
+                    if constexpr (FRAMES) blk_pix0 += blk_frame * P.frame_pix;     // (row and column above are the frame's own; from here on the VIRTUAL pixel)
                     blk_next = 0u; blk_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_items);
                     blk_seq += 1u;
                     if (P.use_ring) {
@@ -390,6 +423,13 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                         int ir = (int)(g_pix - jq * (uint32_t)P.width);
                         if (ir < 0) { jq -= 1u; ir += P.width; } else if (ir >= P.width) { jq += 1u; ir -= P.width; }
                         i = (uint32_t)ir; j = jq;
+                    } else if constexpr (FRAMES) {
+                        // (a frame is never sharded: row blk_rr0 + rq of the frame IS image row j)
+                        const uint32_t col = blk_i0 + dq;
+                        const uint32_t rq = udiv_small(col, (uint32_t)P.width, P.magic_width);
+                        i = col - rq * (uint32_t)P.width;
+                        j = blk_rr0 + rq;
+                        g_pix = j * (uint32_t)P.width + i;              // the Philox counter's pixel: of the sample's OWN frame
                     } else {
                     const uint32_t col = blk_i0 + dq;
                     const uint32_t rq = udiv_small(col, (uint32_t)P.width, P.magic_width);
@@ -400,7 +440,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                                        + (rr - lt * (uint32_t)P.tile_rows);
                     g_pix = j * (uint32_t)P.width + i;
                     }
-                    const uint32_t g_s = (uint32_t)P.sample_begin + (s_rel - dq * (uint32_t)P.spp);
+                    const uint32_t g_s = (FRAMES ? blk_sbase : (uint32_t)P.sample_begin) + (s_rel - dq * (uint32_t)P.spp);
                     U4 w = philox4x32_10(g_pix, g_s, 0u, 0u, P.k0, P.k1);
                     uint32_t g_ev = 1u;
                     const double u = ((double)i + (U53 ? u01_53(w.x, w.y) : u01(w.x))) / wm1;     // main.rs:131
@@ -451,6 +491,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 ev = meta >> 8;
                 pix_local = blk_pix0 + (meta & 255u);
                 my_blk = (blk_seq << 4) | (meta & 15u);
+                if constexpr (FRAMES) my_frame = blk_frame;
                 fresh = true;
             }
             const uint32_t cnt = (uint32_t)__popcll(m);
@@ -465,14 +506,43 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 const U4 lb = philox4x32_10(pix_global, (uint32_t)s, ev - 1u, 0u, P.k0, P.k1);
                 lx = u11_53(lb.x, lb.y); ly = u11_53(lb.z, lb.w);
             }
+            if constexpr (!FRAMES) {
             const D3 cam_origin = ld3(P.cam.origin);
             const D3 rd = mk(lx, ly, 0.0) * P.cam.lens_radius;
             const D3 offset = ld3(P.cam.u) * rd.x + ld3(P.cam.v) * rd.y;
             o = cam_origin + offset;
             d = (((ld3(P.cam.llc) + ld3(P.cam.horizontal) * cam_u) + ld3(P.cam.vertical) * cam_v) - cam_origin) - offset;
+            }
             s_thr[0][tid] = 1.0; s_thr[1][tid] = 1.0; s_thr[2][tid] = 1.0;
             depth = P.max_depth;
             alive = true;
+        }
+        if constexpr (FRAMES) {
+            // The camera of a frame batch.  The lanes that took a sample in this pass took it from the wave's current block -- or, when the
+            // queue ran empty and was refilled in the middle of PHASE 1, some from the block before it, which may be the last of the previous
+            // frame.  So the wave goes through the frames its fresh lanes belong to (one, rarely two): the frame number is wave-uniform in each
+            // turn, and the 19 doubles of P.cams[f] come through the constant address space as SCALAR loads -- no per-lane copy of a camera.
+            // The arithmetic is camera.rs:47-54 as above, operation for operation.
+            for (unsigned long long todo = __ballot(fresh); todo != 0ull;) {
+                const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)my_frame, (int)__builtin_ctzll(todo));
+                const bool mine = fresh && my_frame == f;
+                // (the address through v_readfirstlane, half by half: the compiler then KNOWS it is wave-uniform and selects scalar loads)
+                const unsigned long long ca = (unsigned long long)(uintptr_t)P.cams + (unsigned long long)f * sizeof(KCamera);
+                const double __attribute__((address_space(4))) *c = (const double __attribute__((address_space(4))) *)(uintptr_t)(
+                    (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ca) |
+                    ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ca >> 32)) << 32));
+                // (loaded by the WAVE, outside the lanes' branch: wave-uniform address, scalar loads)
+                double cc[sizeof(KCamera) / sizeof(double)];
+                for (int k = 0; k < (int)(sizeof(KCamera) / sizeof(double)); ++k) cc[k] = c[k];
+                if (mine) {
+                    const D3 cam_origin = mk(cc[0], cc[1], cc[2]);
+                    const D3 rd = mk(u11(lens_wx), u11(lens_wy), 0.0) * cc[18];
+                    const D3 offset = mk(cc[12], cc[13], cc[14]) * rd.x + mk(cc[15], cc[16], cc[17]) * rd.y;
+                    o = cam_origin + offset;
+                    d = (((mk(cc[3], cc[4], cc[5]) + mk(cc[6], cc[7], cc[8]) * cam_u) + mk(cc[9], cc[10], cc[11]) * cam_v) - cam_origin) - offset;
+                }
+                todo &= ~__ballot(mine);
+            }
         }
 
         RT_STAMP(9);
@@ -1320,6 +1390,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     }
 }
 
+#ifndef RT_RENDER_KERNEL_ONLY       // (a second translation unit that instantiates render_kernel -- rt_frames.hip -- leaves the other kernels to rt_api.hip)
 // exact sum -> f64 value (one rounding above 2^53)
 __device__ __forceinline__ double fix_to_f64(unsigned long long q)
 {
@@ -1579,8 +1650,10 @@ __global__ void unit_accept_kernel(const uint32_t *w, int n, uint32_t *acc, doub
     }
 }
 
+#endif // RT_RENDER_KERNEL_ONLY
+
 } // namespace rt
 
-#ifdef RTIOW_CROSSCHECK_MODES
+#if defined(RTIOW_CROSSCHECK_MODES) && !defined(RT_RENDER_KERNEL_ONLY)
 #include "xcheck/rt_xcheck_kernels.hpp"    // known-answer kernels of modes 2-4
 #endif

@@ -248,6 +248,41 @@ class Renderer:
                                                      int(bool(flip)), out.ctypes.data_as(C.c_void_p)), "rt_resolve_rgba8_counts")
         return out
 
+    # -- frame batches: many cameras, one launch -----------------------------------
+    @staticmethod
+    def _camera_array(cams):
+        """Cameras (scene.Camera, rt_camera, or a float64 array [F,19]) -> contiguous float64 [F,19]: the rt_camera records."""
+        if isinstance(cams, np.ndarray):
+            a = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 19)
+        else:
+            from .scene import cameras_to_array
+            a = cameras_to_array(cams)
+        return a
+
+    def render_frames(self, cams, params, sample_stride=0):
+        """rt_render_frames: every camera of `cams` over the uploaded scene in ONE launch; frame f is the dense render of cams[f]
+        with sample_begin + f * sample_stride.  Returns (fix u64 [F,H,W,3], stats dict -- None for an empty batch)."""
+        a = self._camera_array(cams)
+        out = np.zeros((len(a), params.height, params.width, 3), dtype=np.uint64)
+        st = _ffi.rt_stats()
+        _ffi.check(self._lib.rt_render_frames(self._h, a.ctypes.data_as(C.c_void_p), len(a), int(sample_stride), C.byref(params),
+                                              out.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_frames")
+        return out, (stats_dict(st) if len(a) else None)
+
+    def render_frames_rgba8(self, cams, params, sample_stride=0, flip=True):
+        """rt_render_frames_rgba8: the batch + Color::to_rgba + the row flip per frame, the sums kept on the device.
+        Returns (RGBA8 [F,H,W,4], stats dict -- None for an empty batch)."""
+        a = self._camera_array(cams)
+        out = np.zeros((len(a), params.height, params.width, 4), dtype=np.uint8)
+        st = _ffi.rt_stats()
+        _ffi.check(self._lib.rt_render_frames_rgba8(self._h, a.ctypes.data_as(C.c_void_p), len(a), int(sample_stride), C.byref(params),
+                                                    int(bool(flip)), out.ctypes.data_as(C.c_void_p), C.byref(st)), "rt_render_frames_rgba8")
+        return out, (stats_dict(st) if len(a) else None)
+
+    def render_frames_device(self, d_cams_ptr, n_frames, sample_stride, params, d_fix_ptr, stream=0):
+        _ffi.check(self._lib.rt_render_frames_device(self._h, C.c_void_p(d_cams_ptr), int(n_frames), int(sample_stride), C.byref(params),
+                                                     C.c_void_p(d_fix_ptr), C.c_void_p(stream)), "rt_render_frames_device")
+
     # -- to_rgba + flip --------------------------------------------------------
     def resolve_rgba8(self, fix, spp, flip=True):
         """fix: exact sums u64 [rows,W,3] -> RGBA8 [rows,W,4] (vec3.rs:403-421, main.rs:141-145)."""

@@ -182,6 +182,51 @@ def book1_camera(width, height):
                   float(width) / float(height), 0.1, 10.0)
 
 
+# ---- cameras of a frame batch (rt_render_frames) ------------------------------------------
+# A camera file is raw little-endian rt_camera records (152 bytes = 19 f64 each: origin, lower_left_corner, horizontal,
+# vertical, u, v, lens_radius; include/rtiow_hip.h), no header -- exactly like the flat scene file.
+# host/rtiow_render --dump-cameras writes the same bytes.
+
+CAMERA_DOUBLES = 19
+
+
+def cameras_to_array(cams):
+    """A sequence of Camera / rt_camera -> float64 [F,19], the rt_camera records in order."""
+    out = np.zeros((len(cams), CAMERA_DOUBLES), dtype="<f8")
+    for f, cam in enumerate(cams):
+        c = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        out[f, 0:3], out[f, 3:6], out[f, 6:9] = list(c.origin), list(c.lower_left_corner), list(c.horizontal)
+        out[f, 9:12], out[f, 12:15], out[f, 15:18] = list(c.vertical), list(c.u), list(c.v)
+        out[f, 18] = c.lens_radius
+    return out
+
+
+def orbit_cameras(n, width, height):
+    """A turntable of n cameras: frame f is book1_camera with look_from turned about the y axis by th = 2 pi f / n
+    (frame 0 is book1_camera itself).  f64, the written order; host/rtiow_host.hpp's orbit_cameras writes the same bytes."""
+    cams = []
+    for f in range(int(n)):
+        th = 2.0 * math.pi * float(f) / float(n)
+        x = 13.0 * math.cos(th) + 3.0 * math.sin(th)
+        z = -13.0 * math.sin(th) + 3.0 * math.cos(th)
+        cams.append(Camera(Point3(x, 2.0, z), Point3(0, 0, 0), Vec3(0, 1, 0), 20.0, float(width) / float(height), 0.1, 10.0))
+    return cams
+
+
+def save_cameras(path, cams):
+    a = cams if isinstance(cams, np.ndarray) else cameras_to_array(cams)
+    np.ascontiguousarray(a, dtype="<f8").reshape(-1, CAMERA_DOUBLES).tofile(path)
+
+
+def load_cameras(path):
+    """-> float64 [F,19] (what Renderer.render_frames takes)."""
+    import os
+    size = os.path.getsize(path)
+    if size % (8 * CAMERA_DOUBLES):
+        raise ValueError(f"{path}: {size} bytes is not a whole number of 152-byte camera records")
+    return np.fromfile(path, dtype="<f8").reshape(-1, CAMERA_DOUBLES)
+
+
 # ---- flat scene file: the step immediately before the path (SURVEY 8f-1) ---------------
 # Raw little-endian rt_sphere records (72 bytes each, include/rtiow_hip.h), list order kept.
 # host/rtiow_render --dump-scene writes the same bytes.

@@ -4,10 +4,10 @@ set -e
 cd "$(dirname "$0")/.."
 REV=$1; NAME=$2
 TMP=$(mktemp -d)
-mkdir -p $TMP/csrc $TMP/include
-for f in rt_api.hip rt_device.hpp rt_kernels.hpp; do git show $REV:rtiow_amd/csrc/$f > $TMP/csrc/$f; done
-git show $REV:include/rtiow_hip.h > $TMP/include/rtiow_hip.h
+git archive $REV rtiow_amd/csrc include | tar -x -C $TMP
+SRCS=$TMP/rtiow_amd/csrc/rt_api.hip
+[ -f $TMP/rtiow_amd/csrc/rt_frames.hip ] && SRCS="$SRCS $TMP/rtiow_amd/csrc/rt_frames.hip"      # (the second translation unit, from the frame batches on)
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -mllvm -amdgpu-mfma-vgpr-form \
-  -fPIC -shared -I $TMP/include -I $TMP/csrc -o tools/var_$NAME.so $TMP/csrc/rt_api.hip
+  -fPIC -shared -I $TMP/include -I $TMP/rtiow_amd/csrc -o tools/var_$NAME.so $SRCS
 rm -rf $TMP
 ls -la tools/var_$NAME.so

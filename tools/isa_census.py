@@ -8,7 +8,8 @@ rules are in PHASES below).  static count x frequency x measured cycles per enco
 per SIMD) = modelled SIMD cycles per phase, to be read against the stamped shares (profiles/r04_phase_shares.txt) and against the
 hardware's instruction counters (SQ_INSTS_VALU per wave-bounce).
 
-usage: tools/isa_census.py [--kernel SUBSTR] [--tenk] [-D...]   default kernel: render_kernelILi5ELb0ELb1ELb0ELi256 (shipped, small grid)
+usage: tools/isa_census.py [--kernel SUBSTR] [--tenk] [--frames] [-D...]   default kernel: render_kernelILi5ELb0ELb1ELb0ELi256 (shipped, small grid)
+       --frames: the frame-batch instantiation of the small-grid kernel (render_kernelILi5ELb0ELb1ELb0ELin512, compiled from rt_frames.hip)
 """
 import collections, json, os, re, subprocess, sys
 
@@ -18,12 +19,15 @@ SRC = os.path.join(ROOT, "rtiow_amd", "csrc")
 TMP = "/tmp/_isa_census"
 
 
-def build(extra):
+def build(extra, src="rtiow_amd/csrc/rt_api.hip"):
+    """Device code of one translation unit of the library (default: rt_api.hip, every kernel but the frame-batch instantiations,
+    which are rtiow_amd/csrc/rt_frames.hip's)."""
     os.makedirs(TMP, exist_ok=True)
-    obj, elf = f"{TMP}/dev.o", f"{TMP}/dev.elf"
+    tag = "dev" if src.endswith("rt_api.hip") else "dev_" + os.path.splitext(os.path.basename(src))[0]
+    obj, elf = f"{TMP}/{tag}.o", f"{TMP}/{tag}.elf"
     subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
                     "-mllvm", "-amdgpu-mfma-vgpr-form", "-I", "include", "-I", "rtiow_amd/csrc", "--cuda-device-only", "-c",
-                    "-gline-tables-only", *extra, "-o", obj, "rtiow_amd/csrc/rt_api.hip"], cwd=ROOT, check=True, stderr=subprocess.DEVNULL)
+                    "-gline-tables-only", *extra, "-o", obj, src], cwd=ROOT, check=True, stderr=subprocess.DEVNULL)
     subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={obj}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
                     f"--output={elf}"], check=True)
     dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", elf], check=True, capture_output=True, text=True).stdout
@@ -216,13 +220,18 @@ def main():
     elif tenk:
         want = "render_kernelILi5ELb0ELb0ELb0ELi1024"
     extra = [a for a in args if a.startswith("-D")]
+    src = "rtiow_amd/csrc/rt_api.hip"
+    if "--frames" in args:
+        src = "rtiow_amd/csrc/rt_frames.hip"
+        if "--kernel" not in args:
+            want = "render_kernelILi5ELb0ELb1ELb0ELin512"
     # measured trips per wave-bounce (profiles/r04_block_counts.txt: 1200x675x100; r04_block_counts_cfg4.txt: 10k spheres)
     counts = ({"looks": 20.0, "keeps": 14.03, "halves": 21.56, "pool_rounds": 1.90, "enum_trips": 5.6, "tiles": 8.43, "refills": 0.355,
                "retry_blocks": 3.8, "flushes": 0.36 / 16.0, "always_extra": 0.3}
               if tenk else
               {"looks": 15.22, "keeps": 10.18, "halves": 16.24, "pool_rounds": 1.62, "enum_trips": 4.6, "tiles": 5.35, "refills": 0.377,
                "retry_blocks": 3.72, "flushes": 0.377 / 4.0, "always_extra": 0.1})
-    elf, dis = build(extra)
+    elf, dis = build(extra, src)
     ins = kernel_instructions(dis, want)
     if not ins:
         raise SystemExit(f"no kernel matching {want}")

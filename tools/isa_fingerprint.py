@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Static fingerprint of the product kernels' ISA (no GPU): per instantiation of render_kernel, the number of instructions by class
 (vector / scalar / branch / LDS / vector memory / MFMA) and a hash over the opcode sequence.  A source refactoring that is meant to
-leave the machine code alone is checked with it: tools/isa_fingerprint.py > before.txt ... > after.txt; diff."""
+leave the machine code alone is checked with it: tools/isa_fingerprint.py > before.txt ... > after.txt; diff.
+The default output lists the kernels of rt_api.hip; --frames adds, after them, the frame-batch instantiations (rt_frames.hip)."""
 import collections, hashlib, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(root, "tools"))
 import isa_census as ic
-elf, dis = ic.build([a for a in sys.argv[1:] if a.startswith("-D")])
+defs = [a for a in sys.argv[1:] if a.startswith("-D")]
+elf, dis = ic.build(defs)
+if "--frames" in sys.argv[1:]:
+    dis += "\n" + ic.build(defs, "rtiow_amd/csrc/rt_frames.hip")[1]
 cur, seqs = None, collections.OrderedDict()
 for line in dis.splitlines():
     m = re.match(r"^([0-9a-f]+) <(\S+)>:", line)
