@@ -179,6 +179,17 @@ extern "C" {
     /// ... + `Color::to_rgba` and the row flip per frame: `out_rgba` is [n_frames][height][width][4].
     pub fn rt_render_frames_rgba8(ctx: *mut rt_context, cams: *const rt_camera, n_frames: i32, sample_stride: i32,
                                   p: *const rt_params, flip: i32, out_rgba: *mut u8, stats: *mut rt_stats) -> i32;
+    /// Feature buffers: what the FIRST hit of every camera ray shows (bounce 0 of `ray_color`, src/main.rs:38-57).  `d_feat`: device
+    /// [height][width][8] u64 exact sums (albedo rgb, normal xyz as two's complement, depth t, hits); `d_ids`: device
+    /// [height][width] i32 (list index of the first sample's hit, -1 for a miss) or null.
+    pub fn rt_render_features_device(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, d_feat: *mut c_void,
+                                     d_ids: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_render_features(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, out_feat: *mut u64,
+                              out_ids: *mut i32, kernel_ms: *mut f32) -> i32;
+    /// ... -> f32 [rows][width][8]: mean albedo, mean normal, mean depth over the hitting samples, alpha = hits / spp.
+    pub fn rt_features_to_f32_device(ctx: *mut rt_context, d_feat: *const c_void, width: i32, rows: i32, spp: i64,
+                                     d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_features_to_f32(ctx: *mut rt_context, feat: *const u64, width: i32, rows: i32, spp: i64, out: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

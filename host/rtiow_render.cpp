@@ -6,7 +6,7 @@
 //                [--grid LO HI] [--device K] [--out image.png|image.ppm] [--dump-scene scene.bin] [--scene scene.bin]
 //                [--devices 0,1,..  [--tile-rows T] [--force-rccl]] [--uniform53] [--two-calls] [--passes N]
 //                [--adaptive THRESHOLD [--step N]]
-//                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin]
+//                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -23,6 +23,10 @@
 // once per camera; the sums stay on the device) -- written as PREFIX_0000.png, PREFIX_0001.png, ... for --out PREFIX (.ppm if PREFIX ends in
 // .ppm; a trailing .png is dropped from the prefix).  Frame f renders the samples [f S, f S + spp), S = --sample-stride (default: spp, every
 // frame its own random numbers; 0: the same ones for all).  Single device, one call.
+// --features FILE: next to the image, the first-hit feature buffers of the same frame and samples (rt_render_features, then rt_features_to_f32:
+// mean albedo rgb, mean normal xyz, mean depth t over the hitting samples, alpha = hits / spp) as a NumPy .npy file: a 128-byte header and the
+// f32 [H][W][8] array, rows as the ABI has them (j = 0, the BOTTOM row, first), little-endian.  Single device; not with --uniform53, and
+// not with --adaptive (whose image gives every pixel its own number of samples: the features would not be those samples').
 // --devices: the frame's rows are dealt round-robin to one rt_context per listed device, each driven by
 // its own host thread, and gathered with ONE RCCL ncclGather to the first device (host/rtiow_multi.hpp).
 // A device may be listed more than once (two contexts on one GPU from two threads: the threading rule of
@@ -42,6 +46,25 @@ static int die(const char *what, int rc)
     return 1;
 }
 
+// a NumPy .npy file (format version 1.0) of a little-endian f32 [h][w][c] array: the magic, the version, the header's length (118:
+// the whole preamble is 128 bytes), the dict padded with spaces up to a closing newline, then the raw floats
+static bool write_npy_f32(const char *path, const float *data, int h, int w, int c)
+{
+    char head[128];
+    std::memset(head, ' ', sizeof(head));
+    std::memcpy(head, "\x93NUMPY\x01\x00\x76\x00", 10);
+    char dict[118];
+    const int n = std::snprintf(dict, sizeof(dict), "{'descr': '<f4', 'fortran_order': False, 'shape': (%d, %d, %d), }", h, w, c);
+    if (n < 0 || n >= (int)sizeof(dict)) return false;
+    std::memcpy(head + 10, dict, (size_t)n);
+    head[127] = '\n';
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return false;
+    const size_t count = (size_t)h * w * c;
+    const bool ok = std::fwrite(head, 1, sizeof(head), f) == sizeof(head) && std::fwrite(data, sizeof(float), count, f) == count;
+    return std::fclose(f) == 0 && ok;
+}
+
 int main(int argc, char **argv)
 {
     int width = 400, height = 225, spp = 10, depth = 50, device = 0, lo = -11, hi = 11;
@@ -54,7 +77,7 @@ int main(int argc, char **argv)
     bool adaptive = false;
     double threshold = 0.0;
     int step = 8;
-    std::string cameras_file, dump_cameras;
+    std::string cameras_file, dump_cameras, features_file;
     int orbit = 0, sample_stride = -1;           // (-1: spp)
     if (argc == 5 && !std::strcmp(argv[1], "--reassembly-plan")) {
         const int H = std::atoi(argv[2]), T = std::atoi(argv[3]), n = std::atoi(argv[4]);
@@ -99,6 +122,7 @@ int main(int argc, char **argv)
         else if (arg("--orbit")) orbit = std::atoi(argv[++i]);
         else if (arg("--sample-stride")) sample_stride = std::atoi(argv[++i]);
         else if (arg("--dump-cameras")) dump_cameras = argv[++i];
+        else if (arg("--features")) features_file = argv[++i];
         else if (arg("--scene")) scene_file = argv[++i];
         else if (!std::strcmp(argv[i], "--grid") && i + 2 < argc) { lo = std::atoi(argv[++i]); hi = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -125,6 +149,10 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool batch = !cameras_file.empty() || orbit != 0;
+    if (!features_file.empty() && (!devices.empty() || !cameras_file.empty() || orbit != 0 || uniform53 || adaptive)) {
+        std::fprintf(stderr, "--features renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --adaptive\n");
+        return 2;
+    }
     if (batch && (!devices.empty() || passes > 1 || adaptive || uniform53 || two_calls)) {
         std::fprintf(stderr, "--cameras / --orbit render a frame batch on one device and go with none of --devices, --passes, --adaptive, --uniform53, --two-calls\n");
         return 2;
@@ -274,6 +302,19 @@ int main(int argc, char **argv)
             // main.rs:122-145 in one call: the sums stay on the device, the flipped RGBA8 bytes come back
             rc = rt_render_rgba8(ctx, &rc_cam, &p, 1, rgba.data(), &st);
             if (rc) return die("rt_render_rgba8", rc);
+        }
+        if (!features_file.empty()) {
+            // what the first hit of the frame's camera rays shows: the same pixels and sample indices as the image
+            std::vector<uint64_t> feat(npix * RT_FEATURE_WORDS);
+            std::vector<float> f32(npix * RT_FEATURE_WORDS);
+            float feat_ms = 0.0f;
+            rc = rt_render_features(ctx, &rc_cam, &p, feat.data(), nullptr, &feat_ms);
+            if (rc) return die("rt_render_features", rc);
+            rc = rt_features_to_f32(ctx, feat.data(), width, height, spp, f32.data());
+            if (rc) return die("rt_features_to_f32", rc);
+            if (!write_npy_f32(features_file.c_str(), f32.data(), height, width, RT_FEATURE_WORDS)) { std::perror(features_file.c_str()); return 1; }
+            std::printf("features %dx%dx%d f32 (albedo, normal, depth, alpha), kernel %.3f ms -> %s\n", height, width, RT_FEATURE_WORDS, feat_ms,
+                        features_file.c_str());
         }
         rt_destroy(ctx);
     }

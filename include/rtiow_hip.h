@@ -357,6 +357,55 @@ int rt_render_frames(rt_context *ctx, const rt_camera *cams, int32_t n_frames, i
 int rt_render_frames_rgba8(rt_context *ctx, const rt_camera *cams, int32_t n_frames, int32_t sample_stride,
                            const rt_params *p, int32_t flip, uint8_t *out_rgba, rt_stats *stats);
 
+/* ---- feature buffers: what the FIRST hit of every camera ray shows ----------- */
+
+/* Denoiser guides (first-hit albedo, normal, depth), alpha / coverage and an object id, from a kernel of its own that traces
+ * bounce 0 of ray_color only (main.rs:131-134 + HittableList::hit, mod.rs:54-70) and keeps the hit record.  DESIGN.md section 14.
+ *
+ * The camera ray of pixel g = j * width + i (j = 0 the BOTTOM row) and sample index s in [sample_begin, sample_begin + spp) is the
+ * one the dense render traces for (g, s): Philox key `seed`, counter (g, s, block, 0); words 0, 1 of block 0 are the u01 draws of
+ * u = (i + e0) / (width - 1), v = (j + e1) / (height - 1); words 2, 3 the first random_in_unit_disk try (symmetric draws); every retry
+ * takes the next two consecutive words, on into blocks 1, 2, ...; accepted when length_squared < 1.0 in f64; then Camera::get_ray
+ * (camera.rs:47-54) in f64, reference operation order, no fused multiply-add.  The FIRST HIT is HittableList::hit(ray, t_min, +inf)
+ * over the whole list: Sphere::hit as written, the later sphere winning on equal t -- exactly bounce 0 of ray_color; rays with
+ * zero / NaN / infinite directions take the list in list order as written, NaN roots included, as the render kernel does.
+ *
+ * A pixel has RT_FEATURE_WORDS = 8 exact sums, u64 with quantum 2^-32, wrap-free within the 65 535-sample bound above.  A sample
+ * that hits sphere k adds (a miss adds nothing):
+ *   words 0-2  albedo   quantize(a_c): a = the sphere's albedo for RT_LAMBERTIAN / RT_METAL, (1, 1, 1) for RT_DIALECTRIC (its
+ *                       attenuation, materials.rs:103) -- BY KIND: the albedo field of a Dialectric is not read
+ *   words 3-5  normal   qs(n_c): n = HitRecord::new's normal (mod.rs:20-30: outward = (p - c) * (1/r), flipped against the ray; a
+ *                       negative radius flips it as the reference does); qs(x) = 0 for a NaN, else
+ *                       (int64) floor(clamp(x, -65536, 65536) * 2^32), added modulo 2^64 (two's complement)
+ *   word  6    depth    quantize(t), the C5 rule above (clamp RT_SAMPLE_CLAMP)
+ *   word  7    hits     1
+ * The lens offset is perpendicular to the view axis and the image plane lies at focus_dist: t * focus_dist is the z-depth along
+ * the view axis, t = 1 the focus plane.  hits / spp is alpha: the share of the pixel's camera rays that hit anything, for
+ * compositing over another background than the reference's sky.
+ * The id buffer (optional, i32 per pixel): the list index of the first hit of sample index p->sample_begin (the call's first
+ * sample), -1 for a miss; written, never accumulated. */
+#define RT_FEATURE_WORDS 8
+/* Device form, asynchronous on `stream`.  d_feat: device [height][width][8] u64; d_ids: device [height][width] i32 or NULL.
+ * Honours width, height, spp (>= 1 here), sample_begin, t_min, seed and RT_FLAG_ACCUMULATE; max_depth, tile_rows, shard_index and
+ * RT_FLAG_OVERLAPPED are unused or ignored.  RT_FLAG_ACCUMULATE adds to d_feat: a pixel is owned by ONE lane and added with a plain
+ * load / add / store (no atomics), so two feature launches must NOT add to the same buffer concurrently -- order them on one
+ * stream or with events (unlike rt_render_device's passes, which may overlap).
+ * RT_ERR_INVALID_ARGUMENT, found before anything is touched (nothing written, rt_last_stats unchanged; the checks that need no
+ * context come first): RT_FLAG_UNIFORM53, RT_FLAG_DIAG_STATS, RT_FLAG_NO_FILTER, unknown flag bits, a context created under
+ * RTIOW_SCAN_MODE=1, shard_count != 1, spp < 1, NULL cam or d_feat; RT_ERR_NO_SCENE before an upload.
+ * A feature launch takes NONE of the context's two launch slots and rt_last_stats does not report on it. */
+int rt_render_features_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, void *d_feat, void *d_ids, void *stream);
+/* Host form: synchronous, starts from zero (RT_FLAG_ACCUMULATE is ignored); out_feat [height][width][8], out_ids [height][width]
+ * or NULL; kernel_ms (may be NULL): the kernel's time, from a pair of events the call creates and destroys itself. */
+int rt_render_features(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *out_feat, int32_t *out_ids, float *kernel_ms);
+/* Exact sums -> what a denoiser takes: d_out device [rows][width][8] f32.  With v = the sum's value in f64 (hi/lo form:
+ * ((f64)(q >> 32) * 2^32 + (f64)(u32)q) * 2^-32) and IEEE f64 throughout: albedo = (f32)(v / spp); normal = (f32)(+-v(|q|) / spp), q read
+ * as a two's-complement integer; depth = hits ? (f32)(v / hits) : 0, the mean over the HITTING samples; word 7 = (f32)(hits / spp).
+ * spp = the samples in the sums, >= 1. */
+int rt_features_to_f32_device(rt_context *ctx, const void *d_feat, int32_t width, int32_t rows, int64_t spp, void *d_out, void *stream);
+/* Host-buffer form (copies in, converts on the device, copies out). */
+int rt_features_to_f32(rt_context *ctx, const uint64_t *feat, int32_t width, int32_t rows, int64_t spp, float *out);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

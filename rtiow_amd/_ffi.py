@@ -48,6 +48,7 @@ RT_FLAG_DIAG_STATS = 0x4
 RT_FLAG_UNIFORM53 = 0x8
 RT_FLAG_OVERLAPPED = 0x10
 RT_FLAG_KNOWN = 0x1f
+RT_FEATURE_WORDS = 8        # u64 sums per pixel of a feature buffer: albedo rgb, normal xyz, depth, hits
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
@@ -74,6 +75,10 @@ SYMBOLS = [
     ("rt_render_frames_device", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.POINTER(rt_params), _VP, _VP]),
     ("rt_render_frames", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.POINTER(rt_params), _VP, C.POINTER(rt_stats)]),
     ("rt_render_frames_rgba8", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.POINTER(rt_params), C.c_int32, _VP, C.POINTER(rt_stats)]),
+    ("rt_render_features_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, _VP, _VP]),
+    ("rt_render_features", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, _VP, C.POINTER(C.c_float)]),
+    ("rt_features_to_f32_device", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, _VP, _VP]),
+    ("rt_features_to_f32", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, _VP]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

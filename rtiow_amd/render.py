@@ -283,6 +283,42 @@ class Renderer:
         _ffi.check(self._lib.rt_render_frames_device(self._h, C.c_void_p(d_cams_ptr), int(n_frames), int(sample_stride), C.byref(params),
                                                      C.c_void_p(d_fix_ptr), C.c_void_p(stream)), "rt_render_frames_device")
 
+    # -- feature buffers: first-hit albedo, normal, depth, hit count, object id ------
+    def render_features(self, cam, params, want_ids=True):
+        """rt_render_features: what the first hit of every camera ray of the dense render shows.  Returns (feat u64 [H,W,8] -- exact
+        sums of albedo rgb, normal xyz (two's complement), depth t and the hit count --, ids i32 [H,W] or None -- the list index the
+        call's first sample hits, -1 for a miss --, the kernel's time in ms)."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        h, w = params.height, params.width
+        feat = np.zeros((h, w, _ffi.RT_FEATURE_WORDS), dtype=np.uint64)
+        ids = np.zeros((h, w), dtype=np.int32) if want_ids else None
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_render_features(self._h, C.byref(rc), C.byref(params), feat.ctypes.data_as(C.c_void_p),
+                                                ids.ctypes.data_as(C.c_void_p) if want_ids else None, C.byref(ms)), "rt_render_features")
+        return feat, ids, float(ms.value)
+
+    def render_features_device(self, cam, params, d_feat_ptr, d_ids_ptr=0, stream=0):
+        """rt_render_features_device: d_feat_ptr device [H,W,8] u64, d_ids_ptr device [H,W] i32 or 0; asynchronous on `stream`."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        _ffi.check(self._lib.rt_render_features_device(self._h, C.byref(rc), C.byref(params), C.c_void_p(d_feat_ptr),
+                                                       C.c_void_p(d_ids_ptr) if d_ids_ptr else None, C.c_void_p(stream)),
+                   "rt_render_features_device")
+
+    def features_to_f32(self, feat, spp):
+        """rt_features_to_f32: exact sums u64 [rows,W,8] of `spp` samples -> f32 [rows,W,8] = mean albedo rgb, mean normal xyz, mean
+        depth over the hitting samples (0 without one), alpha = hits / spp."""
+        feat = np.ascontiguousarray(feat, dtype=np.uint64)
+        rows, width = feat.shape[0], feat.shape[1]
+        assert feat.shape == (rows, width, _ffi.RT_FEATURE_WORDS)
+        out = np.zeros((rows, width, _ffi.RT_FEATURE_WORDS), dtype=np.float32)
+        _ffi.check(self._lib.rt_features_to_f32(self._h, feat.ctypes.data_as(C.c_void_p), width, rows, int(spp),
+                                                out.ctypes.data_as(C.c_void_p)), "rt_features_to_f32")
+        return out
+
+    def features_to_f32_device(self, d_feat_ptr, width, rows, spp, d_out_ptr, stream=0):
+        _ffi.check(self._lib.rt_features_to_f32_device(self._h, C.c_void_p(d_feat_ptr), int(width), int(rows), int(spp),
+                                                       C.c_void_p(d_out_ptr), C.c_void_p(stream)), "rt_features_to_f32_device")
+
     # -- to_rgba + flip --------------------------------------------------------
     def resolve_rgba8(self, fix, spp, flip=True):
         """fix: exact sums u64 [rows,W,3] -> RGBA8 [rows,W,4] (vec3.rs:403-421, main.rs:141-145)."""
