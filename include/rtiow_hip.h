@@ -156,7 +156,11 @@ typedef struct {
  *   RTIOW_RING_MIN_SPP=n           rt_create: no per-block pixel sums in LDS below n samples per pixel (default: wherever a block's pixels fit the sums' slots,
  *                                  i.e. from 5 samples per pixel on; 9 with RT_FLAG_NO_FILTER / RT_FLAG_DIAG_STATS)
  *   RTIOW_LARGE_BLOCK_MIN_ITEMS=n  per launch: work blocks of 1 024 pixel-samples instead of 256 from n pixel-samples per launch on
- *                                  (default 2 x 10^8; also needs >= 147 samples per pixel, 69 on the small-grid kernel; rt_stats.kernel_variant bit 2 says which ran) */
+ *                                  (default 2 x 10^8; also needs >= 147 samples per pixel, 69 on the small-grid kernel; rt_stats.kernel_variant bit 2 says which ran)
+ *   RTIOW_DENSE_BODY=classic|capped   per launch: rt_render_device's shipped kernel (scan mode 5 without RT_FLAG_DIAG_STATS / RT_FLAG_UNIFORM53) with the unbounded
+ *                                  unit-sphere redraw loop (classic) or with at most four tries per scatter and pass, a lane without an accepted try keeping its
+ *                                  ray for the next pass (capped); default: per kernel, whichever measured faster.  kernel_variant is the same either way;
+ *                                  rt_last_dense_body (rtiow_hip_diag.h) says which ran */
 
 /* ---- lifetime -------------------------------------------------------------- */
 

@@ -99,6 +99,11 @@ XCHECK_SYMBOLS = [
     ("rt_grid_cells_device", C.c_int, [_VP, _VP, _VP, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float, _VP, _VP]),
 ]
 
+# include/rtiow_hip_diag.h: diagnostics outside the C ABI of rtiow_hip.h
+DIAG_SYMBOLS = [
+    ("rt_last_dense_body", C.c_int32, [_VP]),
+]
+
 _lib = None
 
 
@@ -126,6 +131,10 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, res, args in SYMBOLS:
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
+        fn.restype = res
+        fn.argtypes = args
+    for name, res, args in DIAG_SYMBOLS:
+        fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
     for name, res, args in XCHECK_SYMBOLS:

@@ -744,6 +744,7 @@ int rt_render_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
     const int mode = (p->flags & RT_FLAG_NO_FILTER) ? 0 : ctx->scan_mode;
     ctx->last.scan_mode = mode;
     ctx->last.kernel_variant = 0;
+    ctx->last_dense_body = 0;
     const bool small_grid = small_grid_scene;
     if (p->flags & RT_FLAG_UNIFORM53) {
         // 53-bit uniforms: instantiated for the shipped scan mode (both grid variants) and for RT_FLAG_NO_FILTER
@@ -774,6 +775,13 @@ int rt_render_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
     case 9: rc = launch_render<4, true>(ctx, kp, stream, &grid); break;
 #endif
     case 10:        // (the shipped kernel has a leaner instantiation for scenes whose tile grid has <= 64 cells)
+        // the same launch on the capped-redraw body (rt_dense.hip; RTIOW_DENSE_BODY=classic: the kernels below): kernel_variant says the same
+        if (dense_body_is_capped(small_grid, large_blocks)) {
+            rc = launch_dense_capped(ctx, kp, stream, small_grid, large_blocks, &grid);
+            ctx->last.kernel_variant = (small_grid ? 1 : 0) | (large_blocks ? 4 : 0);
+            ctx->last_dense_body = 1;
+            break;
+        }
         if (small_grid) {
             rc = large_blocks ? launch_render<5, false, true, false, rt::kItemBlockLarge>(ctx, kp, stream, &grid)
                               : launch_render<5, false, true>(ctx, kp, stream, &grid);

@@ -6,7 +6,7 @@
 //   -DRT_BLOCK_COUNTS    wave-level execution counts of the main blocks into stats[8..15] (tools/block_counts.py); with
 //                        -DRT_COUNT_ROWS counters 1 and 6 count the large grid's footprint-row and list-emission trips, with
 //                        -DRT_COUNT_ENUM the enumeration's trips and the candidates it pushes, with -DRT_COUNT_REDRAW the lanes that draw a unit-sphere
-//                        sample and those that fail try 0, instead of refills and redraw trips
+//                        sample and those that fail try 0, with -DRT_COUNT_PARKS the capped body's parked lanes (and the redraw blocks of either body), instead of refills and redraw trips
 //   -DRT_EXIT_TIMES      when the first / last / average wave leaves the kernel (100 MHz real-time clock; tools/exit_times.py)
 //   -DRT_LDS_CONFLICTS   a software model of the LDS bank serialisation at every LDS site of the kernel (tools/lds_conflicts.py)
 //
@@ -33,6 +33,7 @@
 #define RT_COUNT_ROWS_TRIP(k) RT_DIAG_NOTHING           /* ... as the large grid's footprint-row / list-emission trips (-DRT_COUNT_ROWS) */
 #define RT_COUNT_ENUM_TRIP(m) RT_DIAG_NOTHING           /* ... as the enumeration's trips and pushed candidates (-DRT_COUNT_ENUM) */
 #define RT_COUNT_REDRAW_LANES(ok) RT_DIAG_NOTHING       /* ... as the lanes that draw a unit-sphere sample and those that fail try 0 (-DRT_COUNT_REDRAW) */
+#define RT_COUNT_CAPPED_PARKS(n) RT_DIAG_NOTHING        /* ... counter 1 as the capped body's parked lanes, counter 6 the redraw blocks of either body (-DRT_COUNT_PARKS) */
 #define RT_LDS(site, BYTES, ATOMIC, LOAD64, ptr, active) RT_DIAG_NOTHING
 #define RT_LDS_N(site, n, BYTES, ATOMIC, LOAD64, byte_addr, active) RT_DIAG_NOTHING
 #define RT_LDS_QUEUE_READS(take, entry) RT_DIAG_NOTHING
@@ -84,6 +85,11 @@
 #undef RT_COUNT_REDRAW_LANES
 #define RT_COUNT_REDRAW_LANES(ok) do { const unsigned n1_ = (unsigned)__popcll(__ballot(true)), n6_ = (unsigned)__popcll(__ballot(!(ok))); \
                                        RT_COUNT_N(1, n1_); RT_COUNT_N(6, n6_); } while (0)      /* (the ballots BEFORE RT_COUNT_N narrows to its leader lane) */
+#elif defined(RT_COUNT_PARKS)
+#undef RT_COUNT_CAPPED_PARKS
+#undef RT_COUNT_MAIN
+#define RT_COUNT_CAPPED_PARKS(n) RT_COUNT_N(1, n)
+#define RT_COUNT_MAIN(k) do { if ((k) == 6) RT_COUNT(k); } while (0)
 #else
 #undef RT_COUNT_MAIN
 #define RT_COUNT_MAIN(k) RT_COUNT(k)

@@ -1,6 +1,6 @@
 // rt_host.hpp -- what the translation units of librtiow_hip.so share: the context, the error path, parameter validation, the per-launch
 // slots and the launch of one instantiation of the render kernel.  rt_api.hip defines the functions declared here (and every kernel
-// but the frame-batch instantiations of render_kernel, which rt_frames.hip owns).
+// but the frame-batch instantiations of render_kernel, which rt_frames.hip owns, and the capped dense ones, which rt_dense.hip owns).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,6 +71,7 @@ struct rt_context {
     void *d_adapt = nullptr; size_t adapt_bytes = 0;
     void *d_stage_list = nullptr; size_t stage_list_bytes = 0;   // rt_render_pixels: the list on the device
     void *d_stage_cams = nullptr; size_t stage_cams_bytes = 0;   // rt_render_frames / rt_render_frames_rgba8: the cameras on the device
+    int last_dense_body = 0;              // rt_last_dense_body (rtiow_hip_diag.h): 1 when the latest rt_render_device launch ran a capped-redraw kernel of rt_dense.hip, else 0
     int ring_min_spp = 0;                 // RTIOW_RING_MIN_SPP (diagnostic): spp per launch from which block sums are kept in LDS (0: the kernel's own minimum)
 };
 
@@ -102,5 +103,14 @@ int launch_render(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, in
     RT_HIP(hipEventRecord(ctx->ev1, stream));
     return RT_OK;
 }
+
+// rt_dense.hip: the dense launch's instantiations with the capped unit-sphere redraw (ITEMS = kItemBlockDense / kItemBlockDenseLarge).
+// kDenseCappedDefault[small grid][blocks of 1 024]: the launches that take them when RTIOW_DENSE_BODY is not set.  Measured, interleaved with the
+// classic body in both orders (profiles/capped_redraw_ab.txt): small grid on blocks of 1 024 (1200x675x500) -1.1 .. -1.3 %: the default; small grid on
+// blocks of 256 -0.8 .. -0.9 % at 1200x675x100 but +0.4 .. +1.5 % on the 0.65 ms launch 400x225x10, large grid +0.3 % (blocks of 1 024) and +0.6 %
+// (blocks of 256): those three stay on the classic body and keep the capped one behind RTIOW_DENSE_BODY=capped.
+constexpr bool kDenseCappedDefault[2][2] = {{false, false}, {false, true}};
+bool dense_body_is_capped(bool small_grid, bool large_blocks);
+int launch_dense_capped(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, bool small_grid, bool large_blocks, int *grid_out);
 
 } // namespace rt_host

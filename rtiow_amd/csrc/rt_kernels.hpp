@@ -116,6 +116,10 @@ constexpr int kItemBlock = 256;     // pixel-samples a wave reserves per atomic 
 constexpr int kItemBlockLarge = 1024;
 constexpr int kItemBlockList = -kItemBlock;   // as the ITEMS of render_kernel: work blocks of kItemBlock pixel-samples over a pixel list (render_kernel below)
 constexpr int kItemBlockFrames = -2 * kItemBlock;   // ... and over a BATCH OF FRAMES, one camera each (rt_render_frames_device; instantiated from rt_frames.hip only)
+// ... and the dense launch once more, with the CAPPED unit-sphere redraw (render_kernel below, PHASE 4): blocks of kItemBlock /
+// of kItemBlockLarge pixel-samples, decoded, queued and summed exactly as ITEMS = kItemBlock / kItemBlockLarge (instantiated from rt_dense.hip only)
+constexpr int kItemBlockDense = -3 * kItemBlock;
+constexpr int kItemBlockDenseLarge = -4 * kItemBlock;
 static_assert(kItemBlockLarge + 32768 < 65536, "udiv_small: numerators x < d + kItemBlockLarge with d < 2^15 keep x * d < 2^32");
 constexpr int kLargeMinSpp = 147;
 constexpr int kLargeMinSppSmallGrid = 69;
@@ -192,6 +196,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // number g in its OWN frame.  Only the block decode, the start of a sample and the camera differ; the bounce loop is the dense kernel's.
 // Same method as the pixel lists (`if constexpr` where the body stands), and the instantiations live in a translation unit of their own
 // (rt_frames.hip): rt_api.hip's kernels are the same set with the same machine code (profiles/isa_fingerprint_{before,after}_frame_batches.txt).
+// ... or kItemBlockDense / kItemBlockDenseLarge: the DENSE launch on blocks of kItemBlock / kItemBlockLarge with the capped redraw.  A scatter draws at most
+// four unit-sphere tries -- the three blocks ev, ev + 1, ev + 2 of the stream contract's period, in straight-line code -- and a lane that accepted none
+// of them PARKS: it advances ev by 3 and keeps its ray, depth and throughput, so the next pass traces the same ray to the same hit and its shared first
+// block is block ev + 3, "try 0 of the next three blocks".  The accepted words and the final ev are the unbounded loop's; only the pass moves, and the
+// per-pixel sums are integer sums.  The wave no longer draws until its unluckiest lane accepts.  Only PHASE 4 differs from the dense kernel; same method
+// as the two variants above, instantiations in rt_dense.hip.
 template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITEMS = 256>
 // second launch bound = waves per SIMD the register allocator must leave room for: the bounce loop
 // is latency-bound, and the 4th wave is worth more than the few cold values it spills.  Only the shipped kernel
@@ -201,8 +211,10 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
 {
     constexpr bool PIXLIST = ITEMS == kItemBlockList;
     constexpr bool FRAMES = ITEMS == kItemBlockFrames;
-    static_assert(ITEMS > 0 || PIXLIST || FRAMES, "ITEMS: a block size, kItemBlockList or kItemBlockFrames");
+    constexpr bool CAPPED = ITEMS == kItemBlockDense || ITEMS == kItemBlockDenseLarge;
+    static_assert(ITEMS > 0 || PIXLIST || FRAMES || CAPPED, "ITEMS: a block size, kItemBlockList, kItemBlockFrames, kItemBlockDense or kItemBlockDenseLarge");
     static_assert(!(PIXLIST || FRAMES) || (MODE == 5 && !DIAG && !U53), "pixel lists and frame batches: the shipped kernel, 32-bit uniforms, blocks of 256");
+    static_assert(!CAPPED || (MODE == 5 && !DIAG && !U53), "the capped redraw: the shipped kernel, 32-bit uniforms (a 53-bit try is six words: another period)");
     // The block sums' ring (s_ring below) has the same 768 bytes per wave in both shapes: 4 blocks x 8 pixels, or -- the shipped scan mode's
     // kernels, all but the large-grid kernel's instantiation for blocks of 1 024 -- 2 blocks x 16 pixels.  Two blocks in flight are enough: a block of 256 lasts ~11 passes, one of
     // 1 024 ~43, and the samples of the block before the previous one that are still open when a block begins (paths of more than
@@ -212,7 +224,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     // 48.74 ms, 1200x675x100 10.53 -> 10.49 ms, 10k spheres 1920x1080 x20 7.78 -> 7.50 ms, x100 34.98 -> 34.88 ms; the large-grid kernel ON LARGE
     // BLOCKS is 0.7 % slower with the same ring (10k spheres 1920x1080x256: 85.99 -> 86.58 ms, fewer instructions, another schedule) and
     // keeps 4 x 8 and kLargeMinSpp = 147.  The cross-check scan modes and the diagnostic-counter kernels keep 4 x 8 too.
-    constexpr bool kWideRing = SMALLGRID || (MODE == 5 && !DIAG && (ITEMS == kItemBlock || ITEMS == kItemBlockList || ITEMS == kItemBlockFrames));
+    constexpr bool kWideRing = SMALLGRID || (MODE == 5 && !DIAG && (ITEMS == kItemBlock || ITEMS == kItemBlockList || ITEMS == kItemBlockFrames || ITEMS == kItemBlockDense));
     constexpr int kRingDepth = kWideRing ? 2 : 4;
     constexpr int kRingSlots = kWideRing ? 16 : 8;
     static_assert(kRingDepth * kRingSlots == rt::kRingDepth * rt::kRingSlots, "same LDS either way");
@@ -1138,6 +1150,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
         // ==== PHASE 4: shade ===================================================================================================
         // ---- (e) shade: main.rs:44-56 + materials.rs ----------------------------
         bool finished = false;                                          // this lane's sample ended in this pass
+        bool parked = false;                                            // CAPPED: this lane's scatter accepted none of its four tries in this pass
         D3 radiance = mk(0.0, 0.0, 0.0);
         if (alive) {
             bool done = false;
@@ -1199,6 +1212,38 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     }
                     ev += nblk;
                     sp = mk(sx, sy, sz);
+                  } else {
+                    inv_param = mD_.x; r0_front = mD_.y; r0_back = mE_.x;
+                  }
+                } else if constexpr (CAPPED) {
+                  if (kind != RT_KIND_DIALECTRIC) {
+                    // vec3.rs:37-45 with a budget of one period of the stream contract per pass: tries 0-3 use every word of the blocks
+                    // ev, ev + 1, ev + 2 and leave none over.  No loop, no carried word; the two wave-level branches stay (nearly always taken).
+                    uint32_t tx = w.x, ty = w.y, tz = w.z, nblk = 1u;
+                    bool ok = unit_sphere_accepts(tx, ty, tz);
+                    RT_COUNT_REDRAW_LANES(ok);
+                    if (!ok) {
+                        RT_COUNT_MAIN(6);
+                        U4 b = philox4x32_10(pix_global, (uint32_t)s, ev + 1u, 0u, P.k0, P.k1);
+                        nblk = 2u;
+                        tx = w.w; ty = b.x; tz = b.y;                            // try 1
+                        ok = unit_sphere_accepts(tx, ty, tz);
+                        if (!ok) {
+                            RT_COUNT_MAIN(6);
+                            const uint32_t c1 = b.z, c2 = b.w;
+                            b = philox4x32_10(pix_global, (uint32_t)s, ev + 2u, 0u, P.k0, P.k1);
+                            nblk = 3u;
+                            tx = c1; ty = c2; tz = b.x;                          // try 2
+                            ok = unit_sphere_accepts(tx, ty, tz);
+                            if (!ok) {
+                                tx = b.y; ty = b.z; tz = b.w;                    // try 3: no new block
+                                ok = unit_sphere_accepts(tx, ty, tz);
+                            }
+                        }
+                    }
+                    parked = !ok;                                                // (then nblk == 3: the next pass starts at "try 0 of the next three blocks")
+                    ev += nblk;
+                    sp = mk(u11(tx), u11(ty), u11(tz));
                   } else {
                     inv_param = mD_.x; r0_front = mD_.y; r0_back = mE_.x;
                   }
@@ -1287,6 +1332,21 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     }
                     ndir = do_refract ? refract(uV, nrm, ratio) : reflect(uV, nrm);
                 }
+                if constexpr (CAPPED) {
+                    // a parked lane (Lambertian or Metal) has not scattered: ray, depth and throughput stay, and it is neither done nor finished
+                    if (parked) done = false;
+                    else {
+                        if (kind != RT_KIND_DIALECTRIC) {
+                            s_thr[0][tid] = s_thr[0][tid] * albedo.x;
+                            s_thr[1][tid] = s_thr[1][tid] * albedo.y;
+                            s_thr[2][tid] = s_thr[2][tid] * albedo.z;
+                        }
+                        o = p;
+                        d = ndir;
+                        depth -= 1;
+                        if (depth <= 0) done = true;
+                    }
+                } else {
                 if (kind != RT_KIND_DIALECTRIC) {                                // Dialectric: (1,1,1), x * 1.0 == x
                     s_thr[0][tid] = s_thr[0][tid] * albedo.x;
                     s_thr[1][tid] = s_thr[1][tid] * albedo.y;
@@ -1296,12 +1356,19 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 d = ndir;
                 depth -= 1;
                 if (depth <= 0) done = true;                                    // main.rs:40-42: L = 0
+                }
             }
             if (done) {
                 alive = false;
                 finished = true;
                 radiance = L;
             }
+        }
+        if constexpr (CAPPED) {
+            // the parked lanes' rays were counted at the top of this pass and will be counted again in the next one: scalar work only
+            const uint32_t n_parked = (uint32_t)__popcll(__ballot(parked));
+            RT_COUNT_CAPPED_PARKS(n_parked);
+            n_rays -= n_parked;
         }
         RT_STAMP(13);
         __builtin_amdgcn_s_setprio(1);
@@ -1390,7 +1457,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     }
 }
 
-#ifndef RT_RENDER_KERNEL_ONLY       // (a second translation unit that instantiates render_kernel -- rt_frames.hip -- leaves the other kernels to rt_api.hip)
+#ifndef RT_RENDER_KERNEL_ONLY       // (a further translation unit that instantiates render_kernel -- rt_frames.hip, rt_dense.hip -- leaves the other kernels to rt_api.hip)
 // exact sum -> f64 value (one rounding above 2^53)
 __device__ __forceinline__ double fix_to_f64(unsigned long long q)
 {

@@ -7,6 +7,8 @@ TMP=$(mktemp -d)
 git archive $REV rtiow_amd/csrc include | tar -x -C $TMP
 SRCS=$TMP/rtiow_amd/csrc/rt_api.hip
 [ -f $TMP/rtiow_amd/csrc/rt_frames.hip ] && SRCS="$SRCS $TMP/rtiow_amd/csrc/rt_frames.hip"      # (the second translation unit, from the frame batches on)
+[ -f $TMP/rtiow_amd/csrc/rt_features.hip ] && SRCS="$SRCS $TMP/rtiow_amd/csrc/rt_features.hip"  # (... the feature kernel's)
+[ -f $TMP/rtiow_amd/csrc/rt_dense.hip ] && SRCS="$SRCS $TMP/rtiow_amd/csrc/rt_dense.hip"        # (... the capped dense kernels')
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -mllvm -amdgpu-mfma-vgpr-form \
   -fPIC -shared -I $TMP/include -I $TMP/rtiow_amd/csrc -o tools/var_$NAME.so $SRCS
 rm -rf $TMP

@@ -8,8 +8,9 @@ rules are in PHASES below).  static count x frequency x measured cycles per enco
 per SIMD) = modelled SIMD cycles per phase, to be read against the stamped shares (profiles/r04_phase_shares.txt) and against the
 hardware's instruction counters (SQ_INSTS_VALU per wave-bounce).
 
-usage: tools/isa_census.py [--kernel SUBSTR] [--tenk] [--frames] [-D...]   default kernel: render_kernelILi5ELb0ELb1ELb0ELi256 (shipped, small grid)
+usage: tools/isa_census.py [--kernel SUBSTR] [--tenk] [--frames] [--dense] [-D...]   default kernel: render_kernelILi5ELb0ELb1ELb0ELi256 (shipped, small grid)
        --frames: the frame-batch instantiation of the small-grid kernel (render_kernelILi5ELb0ELb1ELb0ELin512, compiled from rt_frames.hip)
+       --dense: the capped-redraw instantiation of the small-grid kernel on blocks of 1 024 (render_kernelILi5ELb0ELb1ELb0ELin1024, compiled from rt_dense.hip)
 """
 import collections, json, os, re, subprocess, sys
 
@@ -21,7 +22,7 @@ TMP = "/tmp/_isa_census"
 
 def build(extra, src="rtiow_amd/csrc/rt_api.hip"):
     """Device code of one translation unit of the library (default: rt_api.hip, every kernel but the frame-batch instantiations,
-    which are rtiow_amd/csrc/rt_frames.hip's)."""
+    which are rtiow_amd/csrc/rt_frames.hip's, and the capped dense ones, rtiow_amd/csrc/rt_dense.hip's)."""
     os.makedirs(TMP, exist_ok=True)
     tag = "dev" if src.endswith("rt_api.hip") else "dev_" + os.path.splitext(os.path.basename(src))[0]
     obj, elf = f"{TMP}/{tag}.o", f"{TMP}/{tag}.elf"
@@ -225,6 +226,10 @@ def main():
         src = "rtiow_amd/csrc/rt_frames.hip"
         if "--kernel" not in args:
             want = "render_kernelILi5ELb0ELb1ELb0ELin512"
+    if "--dense" in args:
+        src = "rtiow_amd/csrc/rt_dense.hip"
+        if "--kernel" not in args:
+            want = "render_kernelILi5ELb0ELb1ELb0ELin1024"
     # measured trips per wave-bounce (profiles/r04_block_counts.txt: 1200x675x100; r04_block_counts_cfg4.txt: 10k spheres)
     counts = ({"looks": 20.0, "keeps": 14.03, "halves": 21.56, "pool_rounds": 1.90, "enum_trips": 5.6, "tiles": 8.43, "refills": 0.355,
                "retry_blocks": 3.8, "flushes": 0.36 / 16.0, "always_extra": 0.3}

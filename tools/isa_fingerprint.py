@@ -2,7 +2,8 @@
 """Static fingerprint of the product kernels' ISA (no GPU): per instantiation of render_kernel, the number of instructions by class
 (vector / scalar / branch / LDS / vector memory / MFMA) and a hash over the opcode sequence.  A source refactoring that is meant to
 leave the machine code alone is checked with it: tools/isa_fingerprint.py > before.txt ... > after.txt; diff.
-The default output lists the kernels of rt_api.hip; --frames adds, after them, the frame-batch instantiations (rt_frames.hip)."""
+The default output lists the kernels of rt_api.hip; --frames adds, after them, the frame-batch instantiations (rt_frames.hip),
+--dense the dense launch's instantiations with the capped unit-sphere redraw (rt_dense.hip)."""
 import collections, hashlib, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(root, "tools"))
@@ -11,6 +12,8 @@ defs = [a for a in sys.argv[1:] if a.startswith("-D")]
 elf, dis = ic.build(defs)
 if "--frames" in sys.argv[1:]:
     dis += "\n" + ic.build(defs, "rtiow_amd/csrc/rt_frames.hip")[1]
+if "--dense" in sys.argv[1:]:
+    dis += "\n" + ic.build(defs, "rtiow_amd/csrc/rt_dense.hip")[1]
 cur, seqs = None, collections.OrderedDict()
 for line in dis.splitlines():
     m = re.match(r"^([0-9a-f]+) <(\S+)>:", line)

@@ -5,12 +5,15 @@
 # configs[2] (3840x2160x500, tag "weak": the N = 1 half of the weak-scaling pair, `bench.py --weak-baseline`).  Output under gpurun_out/prof_<tag>/; summaries are copied
 # into profiles/ by tools/summarize_profile.py.  Every run has a time limit of its own (LIMIT seconds), and the first run that fails,
 # faults or times out ends the script: nothing more is started on the GPU after it.
+# CONFIGS="target cfg2" profiles only those tags; SUFFIX=_classic writes to prof_<tag>_classic beside prof_<tag> (e.g. with RTIOW_DENSE_BODY=classic
+# in the environment: the same bench on the classic body of the dense kernel, the "before" of a before/after pair).
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 LIMIT=${LIMIT:-300}
 run_cfg() {
   TAG=$1; shift
   OUT=gpurun_out/prof_$TAG
+  OUT=$OUT$SUFFIX
   rm -rf $OUT; mkdir -p $OUT
   STEPS=5; [ "$TAG" = weak ] && STEPS=2
   ARGS="bench.py --steps $STEPS --warmup 1 --no-cpu-baseline --no-other-configs --no-end-to-end $@"
@@ -31,7 +34,12 @@ run_cfg() {
     [ $rc -eq 0 ] || { tail -5 $OUT/pmc$i.log; exit 1; }
   done
 }
-run_cfg target &&
-run_cfg cfg2 --width 1200 --height 675 --spp 100 &&
-run_cfg tenk --tenk &&
-run_cfg weak --weak-baseline
+for c in ${CONFIGS:-target cfg2 tenk weak}; do
+  case $c in
+    target) run_cfg target ;;
+    cfg2) run_cfg cfg2 --width 1200 --height 675 --spp 100 ;;
+    tenk) run_cfg tenk --tenk ;;
+    weak) run_cfg weak --weak-baseline ;;
+    *) echo "unknown configuration $c"; exit 2 ;;
+  esac || exit 1
+done
