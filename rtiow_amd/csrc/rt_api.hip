@@ -229,9 +229,27 @@ void rt_host::set_scene_params(const rt_context *ctx, rt::KParams &kp)
     for (int e = 0; e < 8; ++e) kp.always_idx[e] = ctx->always_idx[e];
 }
 
-// Takes the other slot of per-launch state for a launch on `stream`; if the launch that used it last is still running (on another
-// stream), `stream` waits for it -- the host does not.  (A call is validated BEFORE it takes a slot.)
-int rt_host::next_launch_slot(rt_context *ctx, hipStream_t stream, rt::KParams &kp)
+void rt_host::fill_common_params(const rt_context *ctx, const rt_params *p, const LaunchPlan &plan, unsigned long long npix,
+                                 unsigned long long total_items, unsigned long long n_blocks, void *d_fix, rt::KParams &kp)
+{
+    memset(&kp, 0, sizeof(kp));
+    kp.width = p->width; kp.height = p->height;
+    kp.spp = p->spp; kp.sample_begin = p->sample_begin; kp.max_depth = p->max_depth;
+    kp.t_min = p->t_min;
+    kp.k0 = (uint32_t)p->seed; kp.k1 = (uint32_t)(p->seed >> 32);
+    kp.tile_rows = 1; kp.shard_index = 0; kp.shard_count = 1;
+    kp.n_spheres = ctx->n_spheres;
+    kp.npix = (uint32_t)npix; kp.total_items = total_items; kp.n_blocks = (uint32_t)n_blocks;
+    kp.inv_spp = p->spp > 0 ? 1.0 / (double)p->spp : 0.0;
+    kp.inv_width = 1.0 / (double)p->width;
+    kp.magic_spp = magic_for(p->spp);
+    kp.use_ring = plan.use_ring ? 1 : 0;
+    kp.block_items = plan.block_items;
+    set_scene_params(ctx, kp);
+    kp.fix = (unsigned long long *)d_fix;
+}
+
+int rt_host::begin_launch(rt_context *ctx, hipStream_t stream, rt::KParams &kp, int max_depth, size_t clear_bytes, int untraced_scan_mode, bool *trace)
 {
     ctx->cur = (ctx->cur + 1) % rt_context::kSlots;
     ctx->d_queue = ctx->q_slots[ctx->cur]; ctx->d_stats = ctx->s_slots[ctx->cur];
@@ -239,6 +257,21 @@ int rt_host::next_launch_slot(rt_context *ctx, hipStream_t stream, rt::KParams &
     if (ctx->slot_used[ctx->cur]) RT_HIP(hipStreamWaitEvent(stream, ctx->ev1, 0));
     ctx->slot_used[ctx->cur] = true;
     kp.queue = ctx->d_queue; kp.stats = ctx->d_stats;
+
+    if (clear_bytes) RT_HIP(hipMemsetAsync(kp.fix, 0, clear_bytes, stream));
+    RT_HIP(hipMemsetAsync(ctx->d_queue, 0, 64, stream));
+    RT_HIP(hipMemsetAsync(ctx->d_stats, 0, 1024, stream));
+    memset(&ctx->last, 0, sizeof(ctx->last));
+    ctx->last.n_spheres = ctx->n_spheres;
+    ctx->last.block_threads = rt::kBlock;
+    ctx->zero_depth_samples = 0;
+    *trace = max_depth != 0 && kp.total_items != 0;
+    if (*trace) return RT_OK;
+    RT_HIP(hipEventRecord(ctx->ev0, stream));
+    RT_HIP(hipEventRecord(ctx->ev1, stream));
+    ctx->zero_depth_samples = kp.total_items;
+    ctx->last.scan_mode = untraced_scan_mode;
+    ctx->launched = true;
     return RT_OK;
 }
 
@@ -431,6 +464,46 @@ TileLayout tile_layout(const rt_sphere *spheres, int n, const char *never)
 #ifdef RTIOW_CROSSCHECK_MODES
 #include "xcheck/rt_xcheck_host.inc"       // B operands of scan modes 2-4
 #endif
+
+// The dense launch's kernel: the one place that maps (mode, diag, u53, small grid, blocks of 1 024) to an instantiation, and says
+// which one ran (rt_stats::kernel_variant: 1 small grid, 2 U53, 4 blocks of 1 024; rt_last_dense_body).  The shipped kernel has a leaner
+// instantiation for scenes whose tile grid has <= 64 cells, and a second body with the capped unit-sphere redraw (rt_dense.hip;
+// RTIOW_DENSE_BODY=classic: the kernels below): kernel_variant says the same for both.
+int launch_dense(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, int mode, bool diag, bool u53, bool small_grid, bool large_blocks, int *grid)
+{
+    const bool shipped = mode == 5 && !diag;
+    ctx->last.kernel_variant = (shipped && small_grid ? 1 : 0) | (u53 ? 2 : 0) | (shipped && large_blocks ? 4 : 0);
+    ctx->last_dense_body = shipped && !u53 && dense_body_is_capped(small_grid, large_blocks) ? 1 : 0;
+    if (ctx->last_dense_body) return launch_dense_capped(ctx, kp, stream, small_grid, large_blocks, grid);
+    if (u53) {
+        if (mode == 0) return launch_render<0, false, false, true>(ctx, kp, stream, grid);
+        if (small_grid) return large_blocks ? launch_render<5, false, true, true, rt::kItemBlockLarge>(ctx, kp, stream, grid)
+                                            : launch_render<5, false, true, true>(ctx, kp, stream, grid);
+        return large_blocks ? launch_render<5, false, false, true, rt::kItemBlockLarge>(ctx, kp, stream, grid)
+                            : launch_render<5, false, false, true>(ctx, kp, stream, grid);
+    }
+    if (shipped) {
+        if (small_grid) return large_blocks ? launch_render<5, false, true, false, rt::kItemBlockLarge>(ctx, kp, stream, grid)
+                                            : launch_render<5, false, true>(ctx, kp, stream, grid);
+        return large_blocks ? launch_render<5, false, false, false, rt::kItemBlockLarge>(ctx, kp, stream, grid)
+                            : launch_render<5, false>(ctx, kp, stream, grid);
+    }
+    switch (mode * 2 + (diag ? 1 : 0)) {
+    case 0: return launch_render<0, false>(ctx, kp, stream, grid);
+    case 1: return launch_render<0, true>(ctx, kp, stream, grid);
+    case 2: return launch_render<1, false>(ctx, kp, stream, grid);
+    case 3: return launch_render<1, true>(ctx, kp, stream, grid);
+#ifdef RTIOW_CROSSCHECK_MODES
+    case 4: return launch_render<2, false>(ctx, kp, stream, grid);
+    case 5: return launch_render<2, true>(ctx, kp, stream, grid);
+    case 6: return launch_render<3, false>(ctx, kp, stream, grid);
+    case 7: return launch_render<3, true>(ctx, kp, stream, grid);
+    case 8: return launch_render<4, false>(ctx, kp, stream, grid);
+    case 9: return launch_render<4, true>(ctx, kp, stream, grid);
+#endif
+    default: return launch_render<5, true>(ctx, kp, stream, grid);
+    }
+}
 
 } // namespace
 
@@ -661,141 +734,35 @@ int rt_render_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
 
     const long long npix = (long long)rows * p->width;
     // Work items are single pixel-samples in pixel-major order (item w = pixel * spp + sample), handed out in
-    // blocks of kItemBlock consecutive items; the work counter counts blocks.
+    // blocks of consecutive items (plan_launch, rt_host.hpp); the work counter counts blocks.
     const unsigned long long total_items = (unsigned long long)npix * (unsigned long long)p->spp;
-    // Blocks of kItemBlockLarge for launches that are long enough for their last blocks not to matter (rt_kernels.hpp): the shipped
-    // scan mode without the diagnostic counters, block sums in LDS, >= 147 samples per pixel (69 for scenes on the small-grid kernel), >= 2 x 10^8 pixel-samples.  RTIOW_LARGE_BLOCK_MIN_ITEMS
-    // moves the last threshold (tests: 0 = every launch that qualifies otherwise; a huge value = never).
-    const int mode_now = (p->flags & RT_FLAG_NO_FILTER) ? 0 : ctx->scan_mode;
+    const int mode = (p->flags & RT_FLAG_NO_FILTER) ? 0 : ctx->scan_mode;
+    const bool diag = (p->flags & RT_FLAG_DIAG_STATS) != 0, u53 = (p->flags & RT_FLAG_UNIFORM53) != 0;
+    const bool small_grid = small_grid_scene(ctx);
+    // RTIOW_LARGE_BLOCK_MIN_ITEMS moves the blocks of 1 024's last threshold (tests: 0 = every launch that qualifies otherwise; a huge value = never)
     const char *lb_env = getenv("RTIOW_LARGE_BLOCK_MIN_ITEMS");
     const unsigned long long lb_min = (lb_env && *lb_env) ? strtoull(lb_env, nullptr, 0)
                                     : (p->flags & RT_FLAG_OVERLAPPED) ? 0ull : rt::kLargeMinItems;   // (overlapped passes: the next pass fills the tail)
-    const bool small_grid_scene = ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64;
-    // Block sums in LDS: a block's consecutive samples must touch no more pixels than its sums have slots -- ceil((items - 1) / spp) + 1 <= 8,
-    // or 16 on the shipped scan mode's kernels --: blocks of 256 from 37 (17) samples per pixel on, and below that the largest multiple of 64 (a block
-    // is started 64 samples at a time) that fits: 192, 128 or 64 pixel-samples, down to 9 (5) samples per pixel.  Fewer: every sample is added
-    // to the frame buffer with three 64-bit atomics of its own -- a quarter of the frame time at 20-32 samples per pixel (1200x675x32: 5.46 ms
-    // that way, 4.04 ms with block sums).  RTIOW_RING_MIN_SPP=n (tests): no block sums below n samples per pixel.
-    // (the large-grid kernel's instantiation for blocks of 1 024 keeps 4 x 8: a launch that will take large blocks is sized for 8 slots)
-    const bool shipped_kernel = mode_now == 5 && !(p->flags & RT_FLAG_DIAG_STATS);
-    const bool large_candidate = shipped_kernel && !small_grid_scene && p->spp >= rt::kLargeMinSpp && total_items >= lb_min && p->spp >= ctx->ring_min_spp;
-    const bool wide_ring = shipped_kernel && !large_candidate;
-    const unsigned ring_slots = wide_ring ? 2u * (unsigned)rt::kRingSlots : (unsigned)rt::kRingSlots;
-    unsigned small_block = 0;
-    for (unsigned items = rt::kItemBlock; items >= 64u && p->spp >= 1; items -= 64u)
-        if ((items - 1u + (unsigned)p->spp - 1u) / (unsigned)p->spp + 1u <= ring_slots) { small_block = items; break; }
-    const bool use_ring = small_block != 0u && p->spp >= ctx->ring_min_spp;
-    const bool large_blocks = mode_now == 5 && !(p->flags & RT_FLAG_DIAG_STATS) && use_ring && small_block == (unsigned)rt::kItemBlock &&
-                              p->spp >= (small_grid_scene ? rt::kLargeMinSppSmallGrid : rt::kLargeMinSpp) && total_items >= lb_min;
-    const unsigned item_block = large_blocks ? rt::kItemBlockLarge : use_ring ? small_block : rt::kItemBlock;
-    const unsigned long long n_blocks = (total_items + item_block - 1) / item_block;
+    const LaunchPlan plan = plan_launch(p->spp, ctx->ring_min_spp, mode == 5 && !diag, small_grid, true, total_items, lb_min);
+    const unsigned long long n_blocks = (total_items + plan.block_items - 1) / plan.block_items;
     if (n_blocks > 0x7fffffffULL)
         return fail(RT_ERR_INVALID_ARGUMENT, "rows*width*spp = %llu pixel-samples in one launch: at most 2^31 blocks of %d "
-                    "(split the samples over several launches with sample_begin and RT_FLAG_ACCUMULATE)", total_items, (int)item_block);
+                    "(split the samples over several launches with sample_begin and RT_FLAG_ACCUMULATE)", total_items, (int)plan.block_items);
+    // 53-bit uniforms: instantiated for the shipped scan mode (both grid variants) and for RT_FLAG_NO_FILTER
+    if (u53 && (diag || (mode != 0 && mode != 5)))
+        return fail(RT_ERR_INVALID_ARGUMENT, "RT_FLAG_UNIFORM53 runs with scan mode 5 (the default) or RT_FLAG_NO_FILTER, without RT_FLAG_DIAG_STATS");
     rt::KParams kp;
-    memset(&kp, 0, sizeof(kp));
+    fill_common_params(ctx, p, plan, (unsigned long long)npix, total_items, n_blocks, d_fix, kp);
     static_assert(sizeof(rt::KCamera) == sizeof(rt_camera), "camera layouts must match");
     memcpy(&kp.cam, cam, sizeof(rt_camera));
-    kp.width = p->width; kp.height = p->height;
-    kp.spp = p->spp; kp.sample_begin = p->sample_begin; kp.max_depth = p->max_depth;
-    kp.t_min = p->t_min;
-    kp.k0 = (uint32_t)p->seed; kp.k1 = (uint32_t)(p->seed >> 32);
     kp.tile_rows = p->tile_rows; kp.shard_index = p->shard_index; kp.shard_count = p->shard_count;
-    kp.rows = rows; kp.n_spheres = ctx->n_spheres;
-    kp.npix = (uint32_t)npix; kp.total_items = total_items; kp.n_blocks = (uint32_t)n_blocks;
-    kp.inv_spp = p->spp > 0 ? 1.0 / (double)p->spp : 0.0;
-    kp.inv_width = 1.0 / (double)p->width;
-    // udiv_small (rt_kernels.hpp): numerators are < d + kItemBlockLarge (spp, width) or < 65536 (rows / tile_rows), so for
-    // d < 2^15 the product x * d stays below 2^32 and floor(x * M / 2^32) is the exact quotient
-    auto magic_for = [](long long d) -> uint32_t {
-        return (d <= 1 || d >= 32768) ? 0u : (uint32_t)(0x100000000ULL / (unsigned long long)d + 1ULL);
-    };
-    kp.magic_spp = magic_for(p->spp); kp.magic_width = magic_for(p->width); kp.magic_tile = magic_for(p->tile_rows);
-    kp.use_ring = use_ring ? 1 : 0;
-    kp.block_items = item_block;
-    set_scene_params(ctx, kp);
-    kp.fix = (unsigned long long *)d_fix;
-    // the other slot of per-launch state; if the launch that used it last is still running (on another stream), THIS stream waits for
-    // it -- the host does not -- before the counters are cleared
-    rc = next_launch_slot(ctx, stream, kp);
-    if (rc) return rc;
-
-    if (!(p->flags & RT_FLAG_ACCUMULATE) && npix > 0)
-        RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(unsigned long long), stream));
-    RT_HIP(hipMemsetAsync(ctx->d_queue, 0, 64, stream));
-    RT_HIP(hipMemsetAsync(ctx->d_stats, 0, 1024, stream));
-
-    memset(&ctx->last, 0, sizeof(ctx->last));
-    ctx->last.n_spheres = ctx->n_spheres;
-    ctx->last.block_threads = rt::kBlock;
-    ctx->zero_depth_samples = 0;
-    if (p->max_depth == 0 || kp.total_items == 0) {
-        // ray_color(depth <= 0) returns black without tracing (main.rs:40-42): the sums stay
-        // as they are and no ray is cast; nothing to launch.
-        RT_HIP(hipEventRecord(ctx->ev0, stream));
-        RT_HIP(hipEventRecord(ctx->ev1, stream));
-        ctx->zero_depth_samples = (unsigned long long)npix * (unsigned long long)p->spp;
-        ctx->launched = true;
-        return RT_OK;
-    }
-
-    int grid = 0;
-    const bool diag = (p->flags & RT_FLAG_DIAG_STATS) != 0;
-    const int mode = (p->flags & RT_FLAG_NO_FILTER) ? 0 : ctx->scan_mode;
-    ctx->last.scan_mode = mode;
-    ctx->last.kernel_variant = 0;
-    ctx->last_dense_body = 0;
-    const bool small_grid = small_grid_scene;
-    if (p->flags & RT_FLAG_UNIFORM53) {
-        // 53-bit uniforms: instantiated for the shipped scan mode (both grid variants) and for RT_FLAG_NO_FILTER
-        if (diag || (mode != 0 && mode != 5))
-            return fail(RT_ERR_INVALID_ARGUMENT, "RT_FLAG_UNIFORM53 runs with scan mode 5 (the default) or RT_FLAG_NO_FILTER, without RT_FLAG_DIAG_STATS");
-        if (mode == 0) rc = launch_render<0, false, false, true>(ctx, kp, stream, &grid);
-        else if (small_grid) rc = large_blocks ? launch_render<5, false, true, true, rt::kItemBlockLarge>(ctx, kp, stream, &grid)
-                                              : launch_render<5, false, true, true>(ctx, kp, stream, &grid);
-        else rc = large_blocks ? launch_render<5, false, false, true, rt::kItemBlockLarge>(ctx, kp, stream, &grid)
-                               : launch_render<5, false, false, true>(ctx, kp, stream, &grid);
-        if (rc) return rc;
-        ctx->last.kernel_variant = 2 | ((mode == 5 && small_grid) ? 1 : 0) | (mode == 5 && large_blocks ? 4 : 0);
-        ctx->launched = true;
-        ctx->last.grid_blocks = grid;
-        return RT_OK;
-    }
-    switch (mode * 2 + (diag ? 1 : 0)) {
-    case 0: rc = launch_render<0, false>(ctx, kp, stream, &grid); break;
-    case 1: rc = launch_render<0, true>(ctx, kp, stream, &grid); break;
-    case 2: rc = launch_render<1, false>(ctx, kp, stream, &grid); break;
-    case 3: rc = launch_render<1, true>(ctx, kp, stream, &grid); break;
-#ifdef RTIOW_CROSSCHECK_MODES
-    case 4: rc = launch_render<2, false>(ctx, kp, stream, &grid); break;
-    case 5: rc = launch_render<2, true>(ctx, kp, stream, &grid); break;
-    case 6: rc = launch_render<3, false>(ctx, kp, stream, &grid); break;
-    case 7: rc = launch_render<3, true>(ctx, kp, stream, &grid); break;
-    case 8: rc = launch_render<4, false>(ctx, kp, stream, &grid); break;
-    case 9: rc = launch_render<4, true>(ctx, kp, stream, &grid); break;
-#endif
-    case 10:        // (the shipped kernel has a leaner instantiation for scenes whose tile grid has <= 64 cells)
-        // the same launch on the capped-redraw body (rt_dense.hip; RTIOW_DENSE_BODY=classic: the kernels below): kernel_variant says the same
-        if (dense_body_is_capped(small_grid, large_blocks)) {
-            rc = launch_dense_capped(ctx, kp, stream, small_grid, large_blocks, &grid);
-            ctx->last.kernel_variant = (small_grid ? 1 : 0) | (large_blocks ? 4 : 0);
-            ctx->last_dense_body = 1;
-            break;
-        }
-        if (small_grid) {
-            rc = large_blocks ? launch_render<5, false, true, false, rt::kItemBlockLarge>(ctx, kp, stream, &grid)
-                              : launch_render<5, false, true>(ctx, kp, stream, &grid);
-            ctx->last.kernel_variant = 1;
-        } else rc = large_blocks ? launch_render<5, false, false, false, rt::kItemBlockLarge>(ctx, kp, stream, &grid)
-                                 : launch_render<5, false>(ctx, kp, stream, &grid);
-        if (large_blocks) ctx->last.kernel_variant |= 4;
-        break;
-    default: rc = launch_render<5, true>(ctx, kp, stream, &grid); break;
-    }
-    if (rc) return rc;
-    ctx->launched = true;
-    ctx->last.grid_blocks = grid;
-    return RT_OK;
+    kp.rows = rows;
+    kp.magic_width = magic_for(p->width); kp.magic_tile = magic_for(p->tile_rows);
+    const size_t clear_bytes = (p->flags & RT_FLAG_ACCUMULATE) ? 0 : (size_t)npix * 3 * sizeof(unsigned long long);
+    return run_launch(ctx, stream, kp, p->max_depth, clear_bytes, 0, [&](int *grid) {
+        ctx->last.scan_mode = mode;
+        return launch_dense(ctx, kp, stream, mode, diag, u53, small_grid, plan.large_blocks, grid);
+    });
 }
 
 int rt_last_stats(rt_context *ctx, rt_stats *stats)
@@ -965,65 +932,27 @@ int rt_render_pixels_device(rt_context *ctx, const rt_camera *cam, const rt_para
     if (n_pixels == 0) return RT_OK;
     if (!d_pixels || !d_fix) return fail(RT_ERR_INVALID_ARGUMENT, "d_pixels/d_fix is NULL");
     const unsigned long long total_items = (unsigned long long)n_pixels * (unsigned long long)p->spp;
-    // work blocks as rt_render_device picks them for the shipped kernel's ring of 2 x 16 pixel slots: 256 pixel-samples from 17 samples per
-    // pixel on, the largest multiple of 64 whose pixels fit the slots down to 5, every sample on its own below (never the blocks of 1 024)
-    unsigned small_block = 0;
-    for (unsigned items = rt::kItemBlock; items >= 64u && p->spp >= 1; items -= 64u)
-        if ((items - 1u + (unsigned)p->spp - 1u) / (unsigned)p->spp + 1u <= 2u * (unsigned)rt::kRingSlots) { small_block = items; break; }
-    const bool use_ring = small_block != 0u && p->spp >= ctx->ring_min_spp;
-    const unsigned item_block = use_ring ? small_block : rt::kItemBlock;
-    const unsigned long long n_blocks = (total_items + item_block - 1) / item_block;
+    // work blocks as the shipped kernel's ring of 2 x 16 pixel slots takes them (plan_launch), never the blocks of 1 024
+    const LaunchPlan plan = plan_launch(p->spp, ctx->ring_min_spp, true, false, false, total_items, 0);
+    const unsigned long long n_blocks = (total_items + plan.block_items - 1) / plan.block_items;
     if (n_blocks > 0x7fffffffULL)
-        return fail(RT_ERR_INVALID_ARGUMENT, "n_pixels*spp = %llu pixel-samples in one launch: at most 2^31 blocks of %d", total_items, (int)item_block);
+        return fail(RT_ERR_INVALID_ARGUMENT, "n_pixels*spp = %llu pixel-samples in one launch: at most 2^31 blocks of %d", total_items, (int)plan.block_items);
     RT_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
 
     rt::KParams kp;
-    memset(&kp, 0, sizeof(kp));
+    fill_common_params(ctx, p, plan, (unsigned long long)n_pixels, total_items, n_blocks, d_fix, kp);
     memcpy(&kp.cam, cam, sizeof(rt_camera));
-    kp.width = p->width; kp.height = p->height;
-    kp.spp = p->spp; kp.sample_begin = p->sample_begin; kp.max_depth = p->max_depth;
-    kp.t_min = p->t_min;
-    kp.k0 = (uint32_t)p->seed; kp.k1 = (uint32_t)(p->seed >> 32);
-    kp.tile_rows = 1; kp.shard_index = 0; kp.shard_count = 1;            // (unused by the variant)
-    kp.rows = 1; kp.n_spheres = ctx->n_spheres;
-    kp.npix = (uint32_t)n_pixels; kp.total_items = total_items; kp.n_blocks = (uint32_t)n_blocks;
-    kp.inv_spp = p->spp > 0 ? 1.0 / (double)p->spp : 0.0;
-    kp.inv_width = 1.0 / (double)p->width;
-    kp.magic_spp = (p->spp <= 1 || p->spp >= 32768) ? 0u : (uint32_t)(0x100000000ULL / (unsigned long long)p->spp + 1ULL);   // udiv_small
-    kp.use_ring = use_ring ? 1 : 0;
-    kp.block_items = item_block;
-    set_scene_params(ctx, kp);
-    kp.fix = (unsigned long long *)d_fix;
+    kp.rows = 1;                                                         // (rows and the sharding fields are unused by the variant; no magic_width)
     kp.pix_list = d_pixels;
-    rc = next_launch_slot(ctx, stream, kp);
-    if (rc) return rc;
-
-    if (!(p->flags & RT_FLAG_ACCUMULATE))
-        RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)n_pixels * 3 * sizeof(unsigned long long), stream));
-    RT_HIP(hipMemsetAsync(ctx->d_queue, 0, 64, stream));
-    RT_HIP(hipMemsetAsync(ctx->d_stats, 0, 1024, stream));
-    memset(&ctx->last, 0, sizeof(ctx->last));
-    ctx->last.n_spheres = ctx->n_spheres;
-    ctx->last.block_threads = rt::kBlock;
-    ctx->zero_depth_samples = 0;
-    if (p->max_depth == 0 || total_items == 0) {                         // (as rt_render_device: black without tracing, nothing to launch)
-        RT_HIP(hipEventRecord(ctx->ev0, stream));
-        RT_HIP(hipEventRecord(ctx->ev1, stream));
-        ctx->zero_depth_samples = total_items;
-        ctx->launched = true;
-        return RT_OK;
-    }
-    int grid = 0;
-    const bool small_grid = ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64;
-    ctx->last.scan_mode = 5;
-    ctx->last.kernel_variant = 8 | (small_grid ? 1 : 0);
-    rc = small_grid ? launch_render<5, false, true, false, rt::kItemBlockList>(ctx, kp, stream, &grid)      // (the pixel-list instantiations)
-                    : launch_render<5, false, false, false, rt::kItemBlockList>(ctx, kp, stream, &grid);
-    if (rc) return rc;
-    ctx->launched = true;
-    ctx->last.grid_blocks = grid;
-    return RT_OK;
+    const size_t clear_bytes = (p->flags & RT_FLAG_ACCUMULATE) ? 0 : (size_t)n_pixels * 3 * sizeof(unsigned long long);
+    return run_launch(ctx, stream, kp, p->max_depth, clear_bytes, 0, [&](int *grid) {
+        const bool small_grid = small_grid_scene(ctx);
+        ctx->last.scan_mode = 5;
+        ctx->last.kernel_variant = 8 | (small_grid ? 1 : 0);
+        return small_grid ? launch_render<5, false, true, false, rt::kItemBlockList>(ctx, kp, stream, grid)      // (the pixel-list instantiations)
+                          : launch_render<5, false, false, false, rt::kItemBlockList>(ctx, kp, stream, grid);
+    });
 }
 
 int rt_render_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, const uint32_t *pixels, int64_t n_pixels,

@@ -2,8 +2,9 @@
 // DESIGN.md section 5.3).
 //
 // The fourth translation unit of librtiow_hip.so.  It owns four instantiations of the render kernel,
-// rt::render_kernel<5, false, SMALLGRID, false, rt::kItemBlockDense | rt::kItemBlockDenseLarge>, the function rt_render_device reaches them
-// through, and the diagnostic that says which body the last dense launch ran (rtiow_hip_diag.h).  Every other kernel of the library stays
+// rt::render_kernel<5, false, SMALLGRID, false, rt::kItemBlockDense | rt::kItemBlockDenseLarge>, the function the dense launch's one dispatch
+// (launch_dense, rt_api.hip) reaches them through, and the diagnostic that says which body the last dense launch ran (rtiow_hip_diag.h).  The
+// launch itself -- plan, KParams, slot, clears, tail -- is the shared path of rt_host.hpp: nothing of it is here.  Every other kernel of the library stays
 // where it was: rt_api.hip's and rt_frames.hip's device code is untouched, and the classic dense kernels remain in the library
 // (RTIOW_DENSE_BODY=classic runs them for the same launch: the same frame, the A/B baseline).
 #include <hip/hip_runtime.h>

@@ -2,8 +2,9 @@
 //
 // The second translation unit of librtiow_hip.so.  It owns the frame-batch instantiations of the render kernel,
 // rt::render_kernel<5, false, SMALLGRID, false, rt::kItemBlockFrames> (rt_kernels.hpp), and the three entry points that launch
-// them; the context, the validation helpers and the per-launch slots are rt_api.hip's, shared through rt_host.hpp.  Every other
-// kernel of the library stays in rt_api.hip, whose device code this file leaves untouched.
+// them: their validation, the frame fields of KParams and the kernel choice.  The context, validate_params and the launch path that
+// the dense and the pixel-list renders take as well (plan_launch, fill_common_params, run_launch) are shared through rt_host.hpp.
+// Every other kernel of the library stays in rt_api.hip, whose device code this file leaves untouched.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -15,16 +16,8 @@ using namespace rt_host;
 
 namespace {
 
-// work blocks as rt_render_pixels_device picks them for the shipped kernel's ring of 2 x 16 pixel slots: 256 pixel-samples from 17
-// samples per pixel on, the largest multiple of 64 whose pixels fit the slots down to 5, every sample on its own below
-unsigned frames_block_items(int spp, int ring_min_spp, bool *use_ring)
-{
-    unsigned small_block = 0;
-    for (unsigned items = rt::kItemBlock; items >= 64u && spp >= 1; items -= 64u)
-        if ((items - 1u + (unsigned)spp - 1u) / (unsigned)spp + 1u <= 2u * (unsigned)rt::kRingSlots) { small_block = items; break; }
-    *use_ring = small_block != 0u && spp >= ring_min_spp;
-    return *use_ring ? small_block : (unsigned)rt::kItemBlock;
-}
+// work blocks as rt_render_pixels_device takes them: the shipped kernel's ring of 2 x 16 pixel slots, never the blocks of 1 024
+LaunchPlan frames_plan(int spp, int ring_min_spp) { return plan_launch(spp, ring_min_spp, true, false, false, 0, 0); }
 
 // What a frame batch accepts beyond validate_params: checked before anything is touched.  The checks that need no context come first
 // (a caller without a device still gets the precise message), then the context's own.
@@ -45,8 +38,7 @@ int validate_frames(const rt_context *ctx, int32_t n_frames, int32_t sample_stri
     if (n_frames > 0 && (long long)p->sample_begin + (long long)(n_frames - 1) * sample_stride + p->spp > 0x7fffffffLL)
         return fail(RT_ERR_INVALID_ARGUMENT, "sample_begin + (n_frames-1)*sample_stride + spp = %lld: the last frame's sample indices must stay "
                     "below 2^31", (long long)p->sample_begin + (long long)(n_frames - 1) * sample_stride + p->spp);
-    bool use_ring = false;
-    const unsigned item_block = frames_block_items(p->spp, ctx ? ctx->ring_min_spp : 0, &use_ring);
+    const unsigned item_block = frames_plan(p->spp, ctx ? ctx->ring_min_spp : 0).block_items;
     const unsigned long long frame_blocks = ((unsigned long long)frame_pix * (unsigned long long)p->spp + item_block - 1) / item_block;
     if (frame_blocks * (unsigned long long)n_frames > 0x7fffffffULL)
         return fail(RT_ERR_INVALID_ARGUMENT, "n_frames*ceil(width*height*spp / %u) = %llu work blocks in one batch: at most 2^31 - 1 "
@@ -73,71 +65,34 @@ int rt_render_frames_device(rt_context *ctx, const rt_camera *d_cams, int32_t n_
     const unsigned long long frame_pix = (unsigned long long)p->width * (unsigned long long)p->height;
     const unsigned long long frame_items = frame_pix * (unsigned long long)p->spp;
     const unsigned long long total_items = frame_items * (unsigned long long)n_frames;
-    bool use_ring = false;
-    const unsigned item_block = frames_block_items(p->spp, ctx->ring_min_spp, &use_ring);
-    // a work block never straddles two frames: every frame has its own ceil(frame_items / item_block) blocks, the last one short
-    const unsigned long long frame_blocks = (frame_items + item_block - 1) / item_block;
+    const LaunchPlan plan = frames_plan(p->spp, ctx->ring_min_spp);
+    // a work block never straddles two frames: every frame has its own ceil(frame_items / block_items) blocks, the last one short
+    const unsigned long long frame_blocks = (frame_items + plan.block_items - 1) / plan.block_items;
     const unsigned long long n_blocks = frame_blocks * (unsigned long long)n_frames;      // (<= 2^31 - 1: validate_frames)
     RT_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = (hipStream_t)stream_v;
 
     rt::KParams kp;
-    memset(&kp, 0, sizeof(kp));
     static_assert(sizeof(rt::KCamera) == sizeof(rt_camera) && sizeof(rt_camera) == 19 * sizeof(double), "camera layouts must match");
-    kp.width = p->width; kp.height = p->height;
-    kp.spp = p->spp; kp.sample_begin = p->sample_begin; kp.max_depth = p->max_depth;
-    kp.t_min = p->t_min;
-    kp.k0 = (uint32_t)p->seed; kp.k1 = (uint32_t)(p->seed >> 32);
-    kp.tile_rows = 1; kp.shard_index = 0; kp.shard_count = 1;            // (unused by the variant)
-    kp.rows = p->height; kp.n_spheres = ctx->n_spheres;
-    kp.npix = (uint32_t)(frame_pix * (unsigned long long)n_frames);      // (the kernel does not read it)
-    kp.total_items = total_items; kp.n_blocks = (uint32_t)n_blocks;
-    kp.inv_spp = p->spp > 0 ? 1.0 / (double)p->spp : 0.0;
-    kp.inv_width = 1.0 / (double)p->width;
-    // udiv_small (rt_kernels.hpp): the numerators are < d + kItemBlock
-    auto magic_for = [](long long d) -> uint32_t {
-        return (d <= 1 || d >= 32768) ? 0u : (uint32_t)(0x100000000ULL / (unsigned long long)d + 1ULL);
-    };
-    kp.magic_spp = magic_for(p->spp); kp.magic_width = magic_for(p->width);
-    kp.use_ring = use_ring ? 1 : 0;
-    kp.block_items = item_block;
-    set_scene_params(ctx, kp);
-    kp.fix = (unsigned long long *)d_fix;
+    fill_common_params(ctx, p, plan, frame_pix * (unsigned long long)n_frames, total_items, n_blocks, d_fix, kp);   // (the kernel does not read npix)
+    kp.rows = p->height;                                                 // (rows and the sharding fields are unused by the variant; no magic_tile)
+    kp.magic_width = magic_for(p->width);
     kp.cams = reinterpret_cast<const rt::KCamera *>(d_cams);
     kp.frame_items = frame_items;
     kp.frame_blocks = (uint32_t)frame_blocks;
     kp.inv_frame_blocks = frame_blocks > 0 ? 1.0 / (double)frame_blocks : 0.0;
     kp.frame_pix = (uint32_t)frame_pix;
     kp.sample_stride = sample_stride;
-    rc = next_launch_slot(ctx, stream, kp);
-    if (rc) return rc;
-
-    if (!(p->flags & RT_FLAG_ACCUMULATE))
-        RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)(frame_pix * (unsigned long long)n_frames) * 3 * sizeof(unsigned long long), stream));
-    RT_HIP(hipMemsetAsync(ctx->d_queue, 0, 64, stream));
-    RT_HIP(hipMemsetAsync(ctx->d_stats, 0, 1024, stream));
-    memset(&ctx->last, 0, sizeof(ctx->last));
-    ctx->last.n_spheres = ctx->n_spheres;
-    ctx->last.block_threads = rt::kBlock;
-    ctx->zero_depth_samples = 0;
-    if (p->max_depth == 0 || total_items == 0) {                         // (as rt_render_device: black without tracing, nothing to launch)
-        RT_HIP(hipEventRecord(ctx->ev0, stream));
-        RT_HIP(hipEventRecord(ctx->ev1, stream));
-        ctx->zero_depth_samples = total_items;
+    const size_t clear_bytes = (p->flags & RT_FLAG_ACCUMULATE) ? 0 : (size_t)(frame_pix * (unsigned long long)n_frames) * 3 * sizeof(unsigned long long);
+    // The untraced exit (max_depth 0) reports scan_mode 5 here, where the dense and the pixel-list launches report 0: nobody chose the
+    // difference, and rt_last_stats keeps it.
+    return run_launch(ctx, stream, kp, p->max_depth, clear_bytes, 5, [&](int *grid) {
+        const bool small_grid = small_grid_scene(ctx);
         ctx->last.scan_mode = 5;
-        ctx->launched = true;
-        return RT_OK;
-    }
-    int grid = 0;
-    const bool small_grid = ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64;
-    ctx->last.scan_mode = 5;
-    ctx->last.kernel_variant = 16 | (small_grid ? 1 : 0);
-    rc = small_grid ? launch_render<5, false, true, false, rt::kItemBlockFrames>(ctx, kp, stream, &grid)      // (the frame-batch instantiations)
-                    : launch_render<5, false, false, false, rt::kItemBlockFrames>(ctx, kp, stream, &grid);
-    if (rc) return rc;
-    ctx->launched = true;
-    ctx->last.grid_blocks = grid;
-    return RT_OK;
+        ctx->last.kernel_variant = 16 | (small_grid ? 1 : 0);
+        return small_grid ? launch_render<5, false, true, false, rt::kItemBlockFrames>(ctx, kp, stream, grid)      // (the frame-batch instantiations)
+                          : launch_render<5, false, false, false, rt::kItemBlockFrames>(ctx, kp, stream, grid);
+    });
 }
 
 int rt_render_frames(rt_context *ctx, const rt_camera *cams, int32_t n_frames, int32_t sample_stride,

@@ -1,6 +1,9 @@
-// rt_host.hpp -- what the translation units of librtiow_hip.so share: the context, the error path, parameter validation, the per-launch
-// slots and the launch of one instantiation of the render kernel.  rt_api.hip defines the functions declared here (and every kernel
-// but the frame-batch instantiations of render_kernel, which rt_frames.hip owns, and the capped dense ones, which rt_dense.hip owns).
+// rt_host.hpp -- what the translation units of librtiow_hip.so share: the context, the error path, parameter validation and the ONE
+// launch path of the render kernel, which the dense, the pixel-list and the frame-batch entry points all take: plan_launch (work-block
+// size, ring, blocks of 1 024: a pure function of a few integers), magic_for, fill_common_params, run_launch (slot, clears, the
+// "nothing to trace" exit, the kernel, the tail) and launch_render (one instantiation).  An entry point keeps its own validation, its
+// own few KParams fields and its kernel choice.  rt_api.hip defines the functions declared here (and every kernel but the frame-batch
+// instantiations of render_kernel, which rt_frames.hip owns, and the capped dense ones, which rt_dense.hip owns).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,7 +83,74 @@ namespace rt_host {
 int validate_params(const rt_params *p);
 int ensure(void **ptr, size_t *have, size_t need);
 void set_scene_params(const rt_context *ctx, rt::KParams &kp);
-int next_launch_slot(rt_context *ctx, hipStream_t stream, rt::KParams &kp);
+
+// the shipped kernel has a leaner instantiation for scenes whose tile grid (with the tiles every ray scans) has <= 64 cells
+inline bool small_grid_scene(const rt_context *ctx) { return ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64; }
+
+// udiv_small (rt_kernels.hpp): numerators are < d + kItemBlockLarge (spp, width) or < 65536 (rows / tile_rows), so for
+// d < 2^15 the product x * d stays below 2^32 and floor(x * M / 2^32) is the exact quotient
+inline uint32_t magic_for(long long d)
+{
+    return (d <= 1 || d >= 32768) ? 0u : (uint32_t)(0x100000000ULL / (unsigned long long)d + 1ULL);
+}
+
+// How a launch is cut into work blocks.  Block sums in LDS (use_ring): a block's consecutive samples must touch no more pixels than
+// its sums have slots -- ceil((items - 1) / spp) + 1 <= 8, or 16 on the shipped kernels (scan mode 5 without the diagnostic counters)
+// --: blocks of 256 from 37 (17) samples per pixel on, and below that the largest multiple of 64 (a block is started 64 samples at a
+// time) that fits: 192, 128 or 64 pixel-samples, down to 9 (5) samples per pixel.  Fewer, or fewer than ring_min_spp
+// (RTIOW_RING_MIN_SPP, tests): every sample is added to the frame buffer with three 64-bit atomics of its own -- a quarter of the frame
+// time at 20-32 samples per pixel (1200x675x32: 5.46 ms that way, 4.04 ms with block sums) -- in blocks of 256.
+// Blocks of kItemBlockLarge (large_blocks) for launches that are long enough for their last blocks not to matter (rt_kernels.hpp): the
+// shipped kernel, block sums in LDS, >= 147 samples per pixel (69 for scenes on the small-grid kernel), >= large_min_items
+// pixel-samples; never on pixel lists and frame batches (large_allowed).  The large-grid kernel's instantiation for blocks of 1 024
+// keeps a ring of 4 x 8: a launch that will take it is sized for 8 slots.
+struct LaunchPlan {
+    bool use_ring;
+    unsigned block_items;      // KParams::block_items: kItemBlockLarge with large_blocks, else the ring's block, else kItemBlock
+    bool large_blocks;
+};
+inline LaunchPlan plan_launch(int spp, int ring_min_spp, bool shipped_kernel, bool small_grid, bool large_allowed,
+                              unsigned long long total_items, unsigned long long large_min_items)
+{
+    const bool large_fits = shipped_kernel && large_allowed && spp >= ring_min_spp && total_items >= large_min_items &&
+                            spp >= (small_grid ? rt::kLargeMinSppSmallGrid : rt::kLargeMinSpp);
+    const unsigned slots = (shipped_kernel && (small_grid || !large_fits) ? 2u : 1u) * (unsigned)rt::kRingSlots;
+    unsigned ring_block = 0;
+    for (unsigned items = rt::kItemBlock; items >= 64u && spp >= 1; items -= 64u)
+        if ((items - 1u + (unsigned)spp - 1u) / (unsigned)spp + 1u <= slots) { ring_block = items; break; }
+    LaunchPlan plan;
+    plan.use_ring = ring_block != 0u && spp >= ring_min_spp;
+    plan.large_blocks = large_fits && plan.use_ring && ring_block == (unsigned)rt::kItemBlock;
+    plan.block_items = plan.large_blocks ? rt::kItemBlockLarge : plan.use_ring ? ring_block : (unsigned)rt::kItemBlock;
+    return plan;
+}
+
+// The KParams fields every launch path fills the same way (the rest is zero): image size, samples, depth, key, the plan, the item and
+// block counts, the scene's tables and the sums.  The sharding fields say "one shard" (rt_render_device overwrites them); rows,
+// magic_width, magic_tile, the camera(s), pix_list and the frame fields are the caller's.
+void fill_common_params(const rt_context *ctx, const rt_params *p, const LaunchPlan &plan, unsigned long long npix,
+                        unsigned long long total_items, unsigned long long n_blocks, void *d_fix, rt::KParams &kp);
+// What every launch does before its kernel: takes the other slot of per-launch state (if the launch that used it last is still running
+// on another stream, `stream` waits for it -- the host does not; a call is validated BEFORE it takes a slot), clears clear_bytes of
+// d_fix (0: RT_FLAG_ACCUMULATE) and the slot's counters, resets what rt_last_stats reports.  *trace: there is something
+// to trace; else (max_depth 0 or no items: ray_color(depth <= 0) is black without tracing, main.rs:40-42) both events are
+// recorded, the launch counts as made and reports untraced_scan_mode.
+int begin_launch(rt_context *ctx, hipStream_t stream, rt::KParams &kp, int max_depth, size_t clear_bytes, int untraced_scan_mode, bool *trace);
+
+// One launch from slot to tail; launch(&grid) picks and starts the kernel (launch_render) and sets ctx->last.scan_mode / kernel_variant.
+template <class Launch>
+int run_launch(rt_context *ctx, hipStream_t stream, rt::KParams &kp, int max_depth, size_t clear_bytes, int untraced_scan_mode, Launch launch)
+{
+    bool trace = false;
+    int grid = 0;
+    int rc = begin_launch(ctx, stream, kp, max_depth, clear_bytes, untraced_scan_mode, &trace);
+    if (rc || !trace) return rc;
+    rc = launch(&grid);
+    if (rc) return rc;
+    ctx->launched = true;
+    ctx->last.grid_blocks = grid;
+    return RT_OK;
+}
 
 template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITEMS = rt::kItemBlock>
 int launch_render(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, int *grid_out)

@@ -14,6 +14,7 @@ import sys
 import rtiow_amd as rt  # noqa: F401
 from rtiow_amd import _ffi
 from rtiow_amd.philox import philox4x32_10
+from isa_pins import fingerprint_lines as _fingerprint_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEY = (0x2545F491, 0x9E3779B1)
@@ -127,15 +128,6 @@ def test_four_tries_then_resume_is_the_unbounded_schedule():
     assert n == 40000 and two >= 40 and three >= 2, (two, three)
     # (0.4764^4 = 5.15 % of the scatters park at least once: 2 060 +- 5 sigma of 45)
     assert 1800 < total_parks < 2500, total_parks
-
-
-def _fingerprint_lines(text):
-    out = {}
-    for line in text.splitlines():
-        if " n=" in line and "ops-sha=" in line:
-            name, rest = line.split(" n=", 1)
-            out[name.strip()] = "n=" + " ".join(rest.split())
-    return out
 
 
 NEW = ["void rt::render_kernel<5, false, false, false, -1024>", "void rt::render_kernel<5, false, false, false, -768>",

@@ -12,6 +12,7 @@ import pytest
 
 import rtiow_amd as rt
 from rtiow_amd import _ffi
+from isa_pins import fingerprint_lines as _fingerprint_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -104,15 +105,6 @@ def test_cli_dumps_the_cameras_the_python_mirror_builds(tmp_path):
 
 
 # ---- the existing kernels' machine code --------------------------------------------------------------------------------
-
-def _fingerprint_lines(text):
-    out = {}
-    for line in text.splitlines():
-        if " n=" in line and "ops-sha=" in line:
-            name, rest = line.split(" n=", 1)
-            out[name.strip()] = "n=" + " ".join(rest.split())
-    return out
-
 
 def test_frame_batches_leave_every_existing_kernel_alone():
     """A fresh run of tools/isa_fingerprint.py (its default output: the kernels of rt_api.hip) equals, line for line, what the tool

@@ -12,6 +12,7 @@ import pytest
 
 import rtiow_amd as rt
 from rtiow_amd import _ffi
+from isa_pins import fingerprint_lines as _fingerprint_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -236,15 +237,6 @@ def test_null_arguments_of_the_new_entries_are_errors_not_crashes():
 
 
 # ---- the existing kernels' machine code --------------------------------------------------------------------------------
-
-def _fingerprint_lines(text):
-    out = {}
-    for line in text.splitlines():
-        if " n=" in line and "ops-sha=" in line:
-            name, rest = line.split(" n=", 1)
-            out[name.strip()] = "n=" + " ".join(rest.split())
-    return out
-
 
 def test_existing_kernels_keep_their_machine_code():
     """Every kernel that exists on the parent commit has the instruction counts and the opcode-sequence hash the PARENT's
