@@ -119,6 +119,23 @@ pub struct rt_adaptive {
     pub dark_floor: f64,
 }
 
+/// The denoiser's options (`rt_denoise`, `rt_denoise_device`, `rt_denoise_host`): `levels` a-trous levels with hole step 2^l,
+/// `flags` = `RT_DENOISE_DEMODULATE` or 0, and the widths of the three edge-stops (colour, halved per level; normal; relative depth).
+/// (The C header spells the type `struct rt_denoise`: it shares its name with the host-buffer entry point.)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_denoise {
+    pub levels: i32,
+    pub flags: u32,
+    pub sigma_color: f64,
+    pub sigma_normal: f64,
+    pub sigma_depth: f64,
+}
+
+pub const RT_DENOISE_DEMODULATE: u32 = 0x1;
+pub const RT_DENOISE_MAX_LEVELS: i32 = 8;
+pub const RT_DENOISE_ALBEDO_FLOOR: f64 = 0.015625;
+
 // Layout assertions: the numbers tests/test_cabi.py asserts on the C side (ctypes mirrors of the header).
 const _: () = assert!(size_of::<rt_sphere>() == 72);
 const _: () = assert!(offset_of!(rt_sphere, kind) == 64);
@@ -130,6 +147,9 @@ const _: () = assert!(size_of::<rt_stats>() == 584);
 const _: () = assert!(offset_of!(rt_stats, live_per_bounce) == 64);
 const _: () = assert!(offset_of!(rt_adaptive, threshold) == 8);
 const _: () = assert!(offset_of!(rt_adaptive, dark_floor) == 16);
+const _: () = assert!(offset_of!(rt_denoise, sigma_color) == 8);
+const _: () = assert!(offset_of!(rt_denoise, sigma_depth) == 24);
+const _: () = assert!(32 == size_of::<rt_denoise>());
 
 #[link(name = "rtiow_hip")]
 extern "C" {
@@ -190,6 +210,18 @@ extern "C" {
     pub fn rt_features_to_f32_device(ctx: *mut rt_context, d_feat: *const c_void, width: i32, rows: i32, spp: i64,
                                      d_out: *mut c_void, stream: *mut c_void) -> i32;
     pub fn rt_features_to_f32(ctx: *mut rt_context, feat: *const u64, width: i32, rows: i32, spp: i64, out: *mut f32) -> i32;
+    /// The denoiser: an edge-avoiding a-trous filter on the radiance sums, driven by the feature sums of the same camera; the result is a
+    /// ONE-SAMPLE frame of exact sums (resolve it with spp = 1).  `d_count` / `count`: each pixel's own number of samples (the adaptive
+    /// frame) or null (every pixel has `spp`).  `d_work`: `rt_denoise_workspace_bytes` bytes of device memory, the caller's.
+    pub fn rt_denoise_workspace_bytes(width: i32, height: i32, out_bytes: *mut i64) -> i32;
+    pub fn rt_denoise_device(ctx: *mut rt_context, d_fix: *const c_void, d_count: *const c_void, spp: i64, d_feat: *const c_void,
+                             feat_spp: i64, width: i32, height: i32, dn: *const rt_denoise, d_work: *mut c_void,
+                             d_out_fix: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_denoise(ctx: *mut rt_context, fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64,
+                      width: i32, height: i32, dn: *const rt_denoise, out_fix: *mut u64, kernel_ms: *mut f32) -> i32;
+    /// The same filter on host buffers, no device needed.
+    pub fn rt_denoise_host(fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64, width: i32, height: i32,
+                           dn: *const rt_denoise, out_fix: *mut u64) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

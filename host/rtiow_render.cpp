@@ -7,6 +7,7 @@
 //                [--devices 0,1,..  [--tile-rows T] [--force-rccl]] [--uniform53] [--two-calls] [--passes N]
 //                [--adaptive THRESHOLD [--step N]]
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
+//                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -27,6 +28,10 @@
 // mean albedo rgb, mean normal xyz, mean depth t over the hitting samples, alpha = hits / spp) as a NumPy .npy file: a 128-byte header and the
 // f32 [H][W][8] array, rows as the ABI has them (j = 0, the BOTTOM row, first), little-endian.  Single device; not with --uniform53, and
 // not with --adaptive (whose image gives every pixel its own number of samples: the features would not be those samples').
+// --denoise: renders the frame's exact sums (rt_render, or rt_render_adaptive with --adaptive), renders the first-hit features of the same camera
+// with --feature-spp N samples (default 8; rt_render_features), filters (rt_denoise: --denoise-levels, default 4, and the three sigmas, defaults
+// 0.35 / 1.0 / 0.2, demodulated; with --adaptive the count buffer goes in, every pixel divided by its own number of samples), resolves the
+// one-sample result (rt_resolve_rgba8 with spp = 1) and saves that.  Single device; not with --uniform53, --passes, --two-calls, --features.
 // --devices: the frame's rows are dealt round-robin to one rt_context per listed device, each driven by
 // its own host thread, and gathered with ONE RCCL ncclGather to the first device (host/rtiow_multi.hpp).
 // A device may be listed more than once (two contexts on one GPU from two threads: the threading rule of
@@ -79,6 +84,10 @@ int main(int argc, char **argv)
     int step = 8;
     std::string cameras_file, dump_cameras, features_file;
     int orbit = 0, sample_stride = -1;           // (-1: spp)
+    bool denoise = false;
+    int feature_spp = 8;
+    struct rt_denoise dn{};
+    dn.levels = 4; dn.flags = RT_DENOISE_DEMODULATE; dn.sigma_color = 0.35; dn.sigma_normal = 1.0; dn.sigma_depth = 0.2;
     if (argc == 5 && !std::strcmp(argv[1], "--reassembly-plan")) {
         const int H = std::atoi(argv[2]), T = std::atoi(argv[3]), n = std::atoi(argv[4]);
         if (H < 1 || T < 1 || n < 1) { std::fprintf(stderr, "--reassembly-plan H T N: all >= 1\n"); return 2; }
@@ -123,6 +132,12 @@ int main(int argc, char **argv)
         else if (arg("--sample-stride")) sample_stride = std::atoi(argv[++i]);
         else if (arg("--dump-cameras")) dump_cameras = argv[++i];
         else if (arg("--features")) features_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+        else if (arg("--feature-spp")) feature_spp = std::atoi(argv[++i]);
+        else if (arg("--denoise-levels")) dn.levels = std::atoi(argv[++i]);
+        else if (arg("--sigma-color")) dn.sigma_color = std::atof(argv[++i]);
+        else if (arg("--sigma-normal")) dn.sigma_normal = std::atof(argv[++i]);
+        else if (arg("--sigma-depth")) dn.sigma_depth = std::atof(argv[++i]);
         else if (arg("--scene")) scene_file = argv[++i];
         else if (!std::strcmp(argv[i], "--grid") && i + 2 < argc) { lo = std::atoi(argv[++i]); hi = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -151,6 +166,10 @@ int main(int argc, char **argv)
     const bool batch = !cameras_file.empty() || orbit != 0;
     if (!features_file.empty() && (!devices.empty() || !cameras_file.empty() || orbit != 0 || uniform53 || adaptive)) {
         std::fprintf(stderr, "--features renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --adaptive\n");
+        return 2;
+    }
+    if (denoise && (!devices.empty() || batch || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
+        std::fprintf(stderr, "--denoise renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --passes, --two-calls, --features\n");
         return 2;
     }
     if (batch && (!devices.empty() || passes > 1 || adaptive || uniform53 || two_calls)) {
@@ -243,6 +262,8 @@ int main(int argc, char **argv)
         if (rc) return die("rt_create", rc);
         rc = rt_upload_scene(ctx, flat.data(), (int32_t)flat.size());
         if (rc) return die("rt_upload_scene", rc);
+        std::vector<uint64_t> dn_fix;                // --denoise: the frame's sums ...
+        std::vector<uint32_t> dn_count;              // ... and, with --adaptive, every pixel's own number of samples
         if (adaptive) {
             rt_adaptive ad{};
             ad.step = step; ad.reserved = 0; ad.threshold = threshold; ad.dark_floor = 0.01;
@@ -250,14 +271,21 @@ int main(int argc, char **argv)
             std::vector<uint32_t> count(npix);
             rc = rt_render_adaptive(ctx, &rc_cam, &p, &ad, fix.data(), nullptr, count.data(), &st);
             if (rc) return die("rt_render_adaptive", rc);
-            rc = rt_resolve_rgba8_counts(ctx, fix.data(), count.data(), width, height, 1, rgba.data());
-            if (rc) return die("rt_resolve_rgba8_counts", rc);
+            if (!denoise) {
+                rc = rt_resolve_rgba8_counts(ctx, fix.data(), count.data(), width, height, 1, rgba.data());
+                if (rc) return die("rt_resolve_rgba8_counts", rc);
+            }
             uint32_t cmin = count[0], cmax = count[0];
             for (uint32_t c : count) { cmin = c < cmin ? c : cmin; cmax = c > cmax ? c : cmax; }
             char note[160];
             std::snprintf(note, sizeof(note), " adaptive threshold %g step %d: %.1f samples per pixel (min %u, max %u),", threshold, step,
                           (double)st.samples / (double)npix, cmin, cmax);
             count_note = note;
+            if (denoise) { dn_fix.swap(fix); dn_count.swap(count); }
+        } else if (denoise) {
+            dn_fix.resize(npix * 3);
+            rc = rt_render(ctx, &rc_cam, &p, nullptr, dn_fix.data(), &st);               // main.rs:122-136
+            if (rc) return die("rt_render", rc);
         } else if (passes > 1) {
             // progressive passes, overlapped: device buffers, two streams, every pass adds its samples to the same exact sums
             if (passes > spp) { std::fprintf(stderr, "--passes %d: more passes than samples per pixel\n", passes); return 2; }
@@ -302,6 +330,21 @@ int main(int argc, char **argv)
             // main.rs:122-145 in one call: the sums stay on the device, the flipped RGBA8 bytes come back
             rc = rt_render_rgba8(ctx, &rc_cam, &p, 1, rgba.data(), &st);
             if (rc) return die("rt_render_rgba8", rc);
+        }
+        if (denoise) {
+            // the guides: the first hits of the same camera's rays, feature_spp samples per pixel; then the filter and the one-sample resolve
+            rt_params fp = p;
+            fp.spp = feature_spp;
+            std::vector<uint64_t> feat(npix * RT_FEATURE_WORDS), clean(npix * 3);
+            float feat_ms = 0.0f, dn_ms = 0.0f;
+            rc = rt_render_features(ctx, &rc_cam, &fp, feat.data(), nullptr, &feat_ms);
+            if (rc) return die("rt_render_features", rc);
+            rc = rt_denoise(ctx, dn_fix.data(), adaptive ? dn_count.data() : nullptr, spp, feat.data(), feature_spp, width, height, &dn, clean.data(), &dn_ms);
+            if (rc) return die("rt_denoise", rc);
+            rc = rt_resolve_rgba8(ctx, clean.data(), width, height, 1, 1, rgba.data());
+            if (rc) return die("rt_resolve_rgba8", rc);
+            std::printf("denoised: %d levels, sigmas %g / %g / %g, features at %d spp (kernel %.3f ms), filter kernels %.3f ms\n", dn.levels,
+                        dn.sigma_color, dn.sigma_normal, dn.sigma_depth, feature_spp, feat_ms, dn_ms);
         }
         if (!features_file.empty()) {
             // what the first hit of the frame's camera rays shows: the same pixels and sample indices as the image

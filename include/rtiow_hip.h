@@ -410,6 +410,69 @@ int rt_features_to_f32_device(rt_context *ctx, const void *d_feat, int32_t width
 /* Host-buffer form (copies in, converts on the device, copies out). */
 int rt_features_to_f32(rt_context *ctx, const uint64_t *feat, int32_t width, int32_t rows, int64_t spp, float *out);
 
+/* ---- denoiser: an edge-avoiding a-trous filter driven by the first-hit guides ---- */
+
+/* Turns the radiance sums of a low-spp (or adaptively stopped) frame and the feature sums of the same camera into a filtered
+ * ONE-SAMPLE frame of exact sums: rt_resolve_rgba8(..., spp = 1, ...) makes the picture of it, rt_fix_to_f32_device its f32 form.
+ * DESIGN.md section 15.  Buffers, all full frames, j = 0 the BOTTOM row:
+ *   fix    [H][W][3] u64   the radiance sums any render entry point gives
+ *   count  [H][W] u32 or NULL: each pixel's own number of samples, every entry >= 1 (the adaptive frame); NULL: every pixel has
+ *          `spp` samples (>= 1); when given, spp is ignored
+ *   feat   [H][W][8] u64   the sums of rt_render_features over feat_spp >= 1 samples
+ *   out    [H][W][3] u64   the denoised mean radiance on the 2^-32 grid (one sample)
+ *
+ * The contract: IEEE binary64 throughout, in this operation order, no fused multiply-add.  v(q) = the sum's value, hi/lo form
+ * (above).  Pixel p = (i, j).
+ *   Prepare.  c_ch = v(fix_ch) / (double)count_p;  alb_ch = v(feat_ch) / (double)feat_spp;  n_ch = +-v(|q|) / (double)feat_spp for
+ *     words 3-5 read as two's complement (the rule of rt_features_to_f32 without the cast);  hits = word 7;
+ *     z = hits ? v(word 6) / (double)hits : 0.0;  alpha = (double)hits / (double)feat_spp.  With RT_DENOISE_DEMODULATE
+ *     m_ch = alb_ch + (1.0 - alpha) (the part of a pixel that sees the sky counts as albedo 1), then
+ *     m_ch = m_ch < RT_DENOISE_ALBEDO_FLOOR ? RT_DENOISE_ALBEDO_FLOOR : m_ch; without it m_ch = 1.0.  The filter runs on c / m.
+ *   Level l = 0 .. levels - 1, hole step s = 2^l:  scl = sigma_color * 0.5^l, ic = 1.0 / (scl * scl),
+ *     in = 1.0 / (sigma_normal * sigma_normal), sz2 = sigma_depth * sigma_depth.
+ *     1. g_p = the 3x3 box mean of the level's input c: the in-frame neighbours summed dy = -1..1 outer, dx = -1..1 inner, from 0.0,
+ *        divided by their number as a double.  The colour edge-stop compares these means, not the noisy values.
+ *     2. izp = 1.0 / (sz2 * (z_p * z_p) + 1e-12).  For dy = -2..2 outer, dx = -2..2 inner, q = p + s (dx, dy), taps outside the
+ *        frame skipped:  k = h[dy + 2] * h[dx + 2], h = (1/16, 1/4, 3/8, 1/4, 1/16);  xc = ((dr dr + dg dg) + db db) * ic with
+ *        d = g_p - g_q;  xn likewise on n_p - n_q, times in;  xz = ((z_p - z_q) * (z_p - z_q)) * izp;
+ *        t(x) = x < 1.0 ? 1.0 - x : 0.0 (a NaN gives 0);  w = ((k * (tc * tc)) * (tn * tn)) * (tz * tz);
+ *        acc_ch = acc_ch + w * c_q,ch and ws = ws + w, both from 0.0;  c'_p,ch = acc_ch / ws (the centre tap gives ws >= 9/64).
+ *   Finish.  out_ch = quantize(c_ch * m_ch), the C5 rule above.
+ * The result is a pure function of the inputs: the same bits from the device forms, from rt_denoise_host, and from either form of
+ * the level kernel (RTIOW_DENOISE_LEVEL_KERNEL=gather|tile, a diagnostic knob read per call).
+ *
+ * The struct shares its name with the host-buffer entry point, as stat does: write `struct rt_denoise`. */
+struct rt_denoise {
+    int32_t  levels;        /* 1 .. RT_DENOISE_MAX_LEVELS (8): level l uses hole step 2^l */
+    uint32_t flags;         /* RT_DENOISE_DEMODULATE; every other bit is an error       */
+    double   sigma_color;   /* > 0, finite; halves with every level                     */
+    double   sigma_normal;  /* > 0, finite                                              */
+    double   sigma_depth;   /* > 0, finite; relative to the centre pixel's depth        */
+};                          /* 32 bytes */
+#define RT_DENOISE_DEMODULATE   0x1u
+#define RT_DENOISE_MAX_LEVELS   8
+#define RT_DENOISE_ALBEDO_FLOOR 0.015625
+
+/* RT_ERR_INVALID_ARGUMENT from every form, found before anything is touched, the checks that need no context first: NULL dn, fix,
+ * feat, out or workspace; levels out of range; unknown flag bits; a sigma <= 0 or not finite; width or height < 1;
+ * width * height > 2^31; spp < 1 with a NULL count; feat_spp < 1. */
+
+/* The bytes of workspace the device form needs for a width x height frame (16 doubles per pixel). */
+int rt_denoise_workspace_bytes(int32_t width, int32_t height, int64_t *out_bytes);
+/* Device form, asynchronous on `stream`.  Every pointer is a device pointer, 8-byte aligned; the buffers must not overlap.  d_work:
+ * rt_denoise_workspace_bytes() bytes, the caller's (contents undefined afterwards).  Takes NONE of the context's launch slots,
+ * rt_last_stats does not report on it, and it needs no uploaded scene. */
+int rt_denoise_device(rt_context *ctx, const void *d_fix, const void *d_count, int64_t spp, const void *d_feat, int64_t feat_spp,
+                      int32_t width, int32_t height, const struct rt_denoise *dn, void *d_work, void *d_out_fix, void *stream);
+/* Host-buffer form (copies in, filters on the device, copies out); synchronous.  kernel_ms (may be NULL): the kernels' time, from a
+ * pair of events the call creates and destroys itself. */
+int rt_denoise(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp,
+               int32_t width, int32_t height, const struct rt_denoise *dn, uint64_t *out_fix, float *kernel_ms);
+/* The same filter on host buffers, no device needed: the library's own CPU statement of the contract (it compiles the very
+ * functions the kernels do, rt_denoise_core.hpp). */
+int rt_denoise_host(const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp, int32_t width,
+                    int32_t height, const struct rt_denoise *dn, uint64_t *out_fix);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

@@ -42,6 +42,11 @@ class rt_adaptive(C.Structure):
     _fields_ = [("step", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double), ("dark_floor", C.c_double)]
 
 
+class rt_denoise(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("flags", C.c_uint32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -49,6 +54,9 @@ RT_FLAG_UNIFORM53 = 0x8
 RT_FLAG_OVERLAPPED = 0x10
 RT_FLAG_KNOWN = 0x1f
 RT_FEATURE_WORDS = 8        # u64 sums per pixel of a feature buffer: albedo rgb, normal xyz, depth, hits
+RT_DENOISE_DEMODULATE = 0x1
+RT_DENOISE_MAX_LEVELS = 8
+RT_DENOISE_ALBEDO_FLOOR = 0.015625
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
@@ -79,6 +87,10 @@ SYMBOLS = [
     ("rt_render_features", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, _VP, C.POINTER(C.c_float)]),
     ("rt_features_to_f32_device", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, _VP, _VP]),
     ("rt_features_to_f32", C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, _VP]),
+    ("rt_denoise_workspace_bytes", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("rt_denoise_device", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, _VP, _VP]),
+    ("rt_denoise", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, C.POINTER(C.c_float)]),
+    ("rt_denoise_host", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -42,6 +42,39 @@ def select_pixels_host(fix, half, count, n, adaptive):
     return out[:m.value].copy()
 
 
+def make_denoise(levels=4, sigma_color=0.35, sigma_normal=1.0, sigma_depth=0.2, demodulate=True):
+    """rt_denoise: `levels` a-trous levels (hole step 2^l), the edge-stop widths on colour (halved per level), normal and relative depth,
+    and whether the filter runs on radiance divided by the first-hit albedo.  The defaults are the best of the sweep in DESIGN.md section 15."""
+    d = _ffi.rt_denoise()
+    d.levels, d.flags = int(levels), _ffi.RT_DENOISE_DEMODULATE if demodulate else 0
+    d.sigma_color, d.sigma_normal, d.sigma_depth = float(sigma_color), float(sigma_normal), float(sigma_depth)
+    return d
+
+
+def _denoise_arrays(fix, feat, count):
+    fix = np.ascontiguousarray(fix, dtype=np.uint64)
+    feat = np.ascontiguousarray(feat, dtype=np.uint64)
+    h, w = fix.shape[0], fix.shape[1]
+    assert fix.shape == (h, w, 3) and feat.shape == (h, w, _ffi.RT_FEATURE_WORDS)
+    if count is not None:
+        count = np.ascontiguousarray(count, dtype=np.uint32)
+        assert count.shape == (h, w)
+    return fix, feat, count, h, w
+
+
+def denoise_host(fix, spp, feat, feat_spp, denoise=None, count=None):
+    """rt_denoise_host (no GPU): the library's CPU statement of the denoiser.  fix u64 [H,W,3] of `spp` samples (or of count[H,W] u32
+    samples per pixel), feat u64 [H,W,8] of `feat_spp` samples -> the denoised one-sample frame u64 [H,W,3]."""
+    lib = _ffi.load()
+    fix, feat, count, h, w = _denoise_arrays(fix, feat, count)
+    dn = denoise if denoise is not None else make_denoise()
+    out = np.zeros((h, w, 3), dtype=np.uint64)
+    _ffi.check(lib.rt_denoise_host(fix.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p) if count is not None else None, int(spp),
+                                   feat.ctypes.data_as(C.c_void_p), int(feat_spp), w, h, C.byref(dn), out.ctypes.data_as(C.c_void_p)),
+               "rt_denoise_host")
+    return out
+
+
 def shard_rows(params):
     lib = _ffi.load()
     rows = C.c_int32(0)
@@ -318,6 +351,33 @@ class Renderer:
     def features_to_f32_device(self, d_feat_ptr, width, rows, spp, d_out_ptr, stream=0):
         _ffi.check(self._lib.rt_features_to_f32_device(self._h, C.c_void_p(d_feat_ptr), int(width), int(rows), int(spp),
                                                        C.c_void_p(d_out_ptr), C.c_void_p(stream)), "rt_features_to_f32_device")
+
+    # -- denoiser: an edge-avoiding a-trous filter driven by the feature buffers -------
+    def denoise(self, fix, spp, feat, feat_spp, denoise=None, count=None):
+        """rt_denoise: fix u64 [H,W,3] of `spp` samples (or of count[H,W] u32 samples per pixel: the adaptive frame), feat u64 [H,W,8] of
+        `feat_spp` samples -> (the denoised ONE-SAMPLE frame u64 [H,W,3] -- resolve it with spp = 1 --, the kernels' time in ms)."""
+        fix, feat, count, h, w = _denoise_arrays(fix, feat, count)
+        dn = denoise if denoise is not None else make_denoise()
+        out = np.zeros((h, w, 3), dtype=np.uint64)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_denoise(self._h, fix.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p) if count is not None else None,
+                                        int(spp), feat.ctypes.data_as(C.c_void_p), int(feat_spp), w, h, C.byref(dn),
+                                        out.ctypes.data_as(C.c_void_p), C.byref(ms)), "rt_denoise")
+        return out, float(ms.value)
+
+    def denoise_device(self, d_fix_ptr, spp, d_feat_ptr, feat_spp, width, height, denoise, d_work_ptr, d_out_ptr, d_count_ptr=0, stream=0):
+        """rt_denoise_device: device pointers; d_work_ptr: denoise_workspace_bytes(width, height) bytes; asynchronous on `stream`."""
+        _ffi.check(self._lib.rt_denoise_device(self._h, C.c_void_p(d_fix_ptr), C.c_void_p(d_count_ptr) if d_count_ptr else None, int(spp),
+                                               C.c_void_p(d_feat_ptr), int(feat_spp), int(width), int(height), C.byref(denoise),
+                                               C.c_void_p(d_work_ptr), C.c_void_p(d_out_ptr), C.c_void_p(stream)), "rt_denoise_device")
+
+    @staticmethod
+    def denoise_workspace_bytes(width, height):
+        n = C.c_int64(0)
+        _ffi.check(_ffi.load().rt_denoise_workspace_bytes(int(width), int(height), C.byref(n)), "rt_denoise_workspace_bytes")
+        return int(n.value)
+
+    denoise_host = staticmethod(denoise_host)
 
     # -- to_rgba + flip --------------------------------------------------------
     def resolve_rgba8(self, fix, spp, flip=True):
