@@ -102,6 +102,14 @@ def render_features(ocam, flat, width, height, spp, *, sample_begin=0, seed=1, t
     return feat, ids
 
 
+def same(got, want):
+    """(feat, ids, ...) of a kernel against the reference's (feat, ids): all eight words and the ids, bit for bit."""
+    feat, ids = got[0], got[1]
+    assert feat.dtype == np.uint64 and ids.dtype == np.int32
+    assert np.array_equal(ids, want[1]), f"{int((ids != want[1]).sum())} ids differ"
+    assert np.array_equal(feat, want[0]), f"{int((feat != want[0]).any(axis=-1).sum())} pixels differ"
+
+
 def fix_to_f64(q):
     """rt_kernels.hpp fix_to_f64 on a u64 array: ((f64)(q >> 32) * 2^32 + (f64)(u32)q) * 2^-32."""
     q = np.asarray(q, dtype=np.uint64)

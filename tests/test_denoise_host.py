@@ -90,6 +90,22 @@ def test_host_equals_numpy_with_other_sigmas_and_eight_levels(cases):
         assert np.array_equal(got, want), (levels, sc, sn, sd, differing(got, want))
 
 
+@pytest.mark.parametrize("levels", [6, 7, 8])
+def test_host_equals_numpy_at_levels_six_to_eight_on_a_wide_frame(levels):
+    """150 x 9, hole steps 32, 64 and 128: the taps at +-128 of the columns 0..21 and 128..149 are inside the frame, every vertical tap
+    but the centre row's is outside it.  What the GPU's levels 6-8 are held to (tests/test_gpu_denoise.py) is pinned here at that size.
+    The colour width halves per level: at the default 0.35 these levels return their input on this frame, so the same is asked at
+    45 ~ 0.35 * 2^7, where each of them moves pixels."""
+    fix, count, spp, feat, feat_spp = dr.synthetic_case(150, 9)
+    for sigma_color in (0.35, 45.0):
+        for demodulate in (True, False):
+            for cnt in (None, count):
+                got = rt.denoise_host(fix, spp, feat, feat_spp, rt.make_denoise(levels, sigma_color, 1.0, 0.2, demodulate), count=cnt)
+                want = dr.denoise(fix, spp, feat, feat_spp, levels=levels, sigma_color=sigma_color, demodulate=demodulate, count=cnt)
+                assert np.array_equal(got, want), (sigma_color, demodulate, cnt is not None, differing(got, want))
+    assert (want != dr.denoise(fix, spp, feat, feat_spp, levels=levels - 1, sigma_color=45.0, demodulate=False, count=count)).any()
+
+
 def test_host_equals_numpy_on_an_oracle_render(oracle_mod, book1_flat):
     """Oracle B's sums and the reference's feature sums of the book scene, 37 x 19 x 4 spp."""
     w, h, spp = 37, 19, 4

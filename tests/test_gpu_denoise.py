@@ -14,6 +14,14 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [(1, 1), (5, 3), (37, 19), (70, 45)]        # 70 x 45 with 5 levels: s = 16 is wider than a 16 x 16 tile, ragged tile edges; 5 x 3 is narrower than the kernel
+# levels 6-8 (hole steps 32, 64, 128): the tile kernel's sub-lattices are 1-3 pixels wide and most of a workgroup's lanes idle.  150 x 9 at
+# s = 128: residues 0..21 hold two pixels and the rest one, nri = min(s, width) = 128 < width while nrj = 9 < s, and the taps at +-128 of
+# the columns 0..21 and 128..149 land inside the frame; at 70 x 45 nri = 64 < 70 < 128: both branches of the minimum
+DEEP_SIZES = [(70, 45), (150, 9)]
+# The colour width halves with every level: at the default 0.35 no tap of a level past the fifth carries weight on these frames (each such
+# level returns its input, by the numpy statement too), so wrong taps would not show.  At 45 ~ 0.35 * 2^7 every level that has a tap
+# inside the frame moves pixels -- asserted on the CPU statement below.
+WIDE_COLOR = 45.0
 KNOB = "RTIOW_DENOISE_LEVEL_KERNEL"
 
 
@@ -24,7 +32,7 @@ def differing(got, want):
 @pytest.fixture(scope="module")
 def cases():
     out = {}
-    for w, h in SIZES:
+    for w, h in SIZES + [(150, 9)]:
         case = dr.synthetic_case(w, h)
         for a in (case[0], case[1], case[3]):
             a.setflags(write=False)
@@ -37,11 +45,11 @@ def host_results(cases):
     """rt_denoise_host of (size, levels, demodulate, with count), computed once and shared by the three kernel choices."""
     memo = {}
 
-    def get(size, levels, demodulate, with_count):
-        key = (size, levels, demodulate, with_count)
+    def get(size, levels, demodulate, with_count, sigma_color=0.35):
+        key = (size, levels, demodulate, with_count, sigma_color)
         if key not in memo:
             fix, count, spp, feat, feat_spp = cases[size]
-            want = rt.denoise_host(fix, spp, feat, feat_spp, rt.make_denoise(levels, demodulate=demodulate), count=count if with_count else None)
+            want = rt.denoise_host(fix, spp, feat, feat_spp, rt.make_denoise(levels, sigma_color, demodulate=demodulate), count=count if with_count else None)
             want.setflags(write=False)
             memo[key] = want
         return memo[key]
@@ -71,8 +79,23 @@ def test_buffers_form_equals_host(renderer, cases, host_results, level_kernel, s
                 assert ms > 0.0                                          # the kernels' time, from the call's own events
 
 
-@pytest.mark.parametrize("size", [(5, 3), (70, 45)], ids=lambda s: f"{s[0]}x{s[1]}")
-def test_device_form_equals_host_and_stays_inside_its_buffers(renderer, cases, host_results, level_kernel, size):
+@pytest.mark.parametrize("size", DEEP_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_buffers_form_equals_host_at_levels_six_to_eight(renderer, cases, host_results, level_kernel, size):
+    fix, count, spp, feat, feat_spp = cases[size]
+    for sigma_color in (0.35, WIDE_COLOR):
+        for levels in (6, 7, 8):
+            for demodulate in (True, False):
+                for with_count in (False, True):
+                    got, _ = renderer.denoise(fix, spp, feat, feat_spp, rt.make_denoise(levels, sigma_color, demodulate=demodulate),
+                                              count=count if with_count else None)
+                    want = host_results(size, levels, demodulate, with_count, sigma_color)
+                    assert np.array_equal(got, want), (sigma_color, levels, demodulate, with_count, differing(got, want))
+    # with the wide colour term each of these levels moves the frame (70 x 45 has no tap at +-128 inside it: its eighth level is idle)
+    for levels in (6, 7, 8) if size == (150, 9) else (6, 7):
+        assert (host_results(size, levels, True, False, WIDE_COLOR) != host_results(size, levels - 1, True, False, WIDE_COLOR)).any(), levels
+
+
+def device_form(renderer, cases, host_results, size, options, sigma_color=0.35):
     import torch
     fix, count, spp, feat, feat_spp = cases[size]
     w, h = size
@@ -85,15 +108,25 @@ def test_device_form_equals_host_and_stays_inside_its_buffers(renderer, cases, h
     d_work = torch.full((words + guard,), 0x5A5A5A5A, dtype=torch.int64, device=dev)
     d_out = torch.full((h * w * 3 + guard,), 0x5A5A5A5A, dtype=torch.int64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
-    for levels, demodulate, with_count in ((5, True, True), (4, False, False), (1, True, False)):
-        renderer.denoise_device(d_fix.data_ptr(), spp, d_feat.data_ptr(), feat_spp, w, h, rt.make_denoise(levels, demodulate=demodulate),
+    for levels, demodulate, with_count in options:
+        renderer.denoise_device(d_fix.data_ptr(), spp, d_feat.data_ptr(), feat_spp, w, h, rt.make_denoise(levels, sigma_color, demodulate=demodulate),
                                 d_work.data_ptr(), d_out.data_ptr(), d_count_ptr=d_count.data_ptr() if with_count else 0, stream=stream)
         torch.cuda.synchronize()
         got = d_out[:h * w * 3].cpu().numpy().view(np.uint64).reshape(h, w, 3)
-        want = host_results(size, levels, demodulate, with_count)
+        want = host_results(size, levels, demodulate, with_count, sigma_color)
         assert np.array_equal(got, want), (levels, demodulate, with_count, differing(got, want))
     assert (d_work[words:] == 0x5A5A5A5A).all().item() and (d_out[h * w * 3:] == 0x5A5A5A5A).all().item()
     assert np.array_equal(d_fix.cpu().numpy().view(np.uint64), fix) and np.array_equal(d_feat.cpu().numpy().view(np.uint64), feat)
+
+
+@pytest.mark.parametrize("size", [(5, 3), (70, 45)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_device_form_equals_host_and_stays_inside_its_buffers(renderer, cases, host_results, level_kernel, size):
+    device_form(renderer, cases, host_results, size, ((5, True, True), (4, False, False), (1, True, False)))
+
+
+def test_device_form_with_eight_levels_on_a_wide_frame(renderer, cases, host_results, level_kernel):
+    device_form(renderer, cases, host_results, (150, 9), ((8, True, True),))
+    device_form(renderer, cases, host_results, (150, 9), ((8, True, True),), sigma_color=WIDE_COLOR)
 
 
 def test_adaptive_frame_with_its_count_buffer(renderer, book1_flat, level_kernel):

@@ -9,19 +9,13 @@ import pytest
 
 import features_ref as fr
 import rtiow_amd as rt
+from features_ref import same
 from rtiow_amd import _ffi
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOOK = dict(w=37, h=19, spp=3, begin=5)         # neither side a multiple of 8; the book camera's aperture makes lens retries run on into B_1
-
-
-def same(got, want):
-    feat, ids = got[0], got[1]
-    assert feat.dtype == np.uint64 and ids.dtype == np.int32
-    assert np.array_equal(ids, want[1]), f"{int((ids != want[1]).sum())} ids differ"
-    assert np.array_equal(feat, want[0]), f"{int((feat != want[0]).any(axis=-1).sum())} pixels differ"
 
 
 @pytest.fixture(scope="module")
@@ -195,6 +189,24 @@ def test_features_to_f32_is_the_numpy_statement(renderer, book_ref):
     assert np.array_equal(f.view(np.uint32), fr.features_to_f32(feat, BOOK["spp"]).view(np.uint32))
     hit = feat[..., 7] == BOOK["spp"]                                   # fully covered pixels: a unit normal's mean is at most 1 long
     assert hit.any() and (np.linalg.norm(f[hit][:, 3:6], axis=-1) < 1.0 + 1e-6).all() and (f[..., 7] <= 1.0).all()
+
+
+def test_features_to_f32_beyond_one_grid(renderer):
+    """rt_features_to_f32_device caps its grid at 8192 x 256 = 2 097 152 lanes and strides beyond: 2048 x 1026 pixels (a 3840 x 2160 frame
+    has four times as many) take a second trip for the last 4 096, and the hand-made pixels of synthetic_sums() sit on the last twelve."""
+    hand, spp = fr.synthetic_sums()
+    w, h, Q1 = 2048, 1026, 1 << 32
+    assert w * h > 8192 * 256 + hand.shape[0] * hand.shape[1]
+    rng = np.random.default_rng(2048)
+    q = np.zeros((h, w, 8), dtype=np.uint64)
+    q[..., 0:3] = rng.integers(0, 3 * Q1, size=(h, w, 3), dtype=np.uint64)
+    q[..., 3:6] = rng.integers(-3 * Q1, 3 * Q1, size=(h, w, 3), dtype=np.int64).view(np.uint64)
+    q[..., 7] = rng.integers(0, 4, size=(h, w), dtype=np.uint64)
+    q[..., 6] = rng.integers(0, 1 << 40, size=(h, w), dtype=np.uint64) * q[..., 7]
+    q.reshape(-1, 8)[-12:] = hand.reshape(12, 8)
+    got, want = renderer.features_to_f32(q, spp), fr.features_to_f32(q, spp)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert want.reshape(-1, 8)[8192 * 256:].any() and np.array_equal(want.reshape(-1, 8)[-12:], fr.features_to_f32(hand, spp).reshape(12, 8))
 
 
 def test_rejected_call_touches_nothing_and_dense_render_is_unchanged(renderer, oracle_mod, book1_flat):
