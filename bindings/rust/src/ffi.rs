@@ -132,6 +132,23 @@ pub struct rt_denoise {
     pub sigma_depth: f64,
 }
 
+/// The options of temporal accumulation (`rt_temporal`, `rt_temporal_device`, `rt_temporal_host`): `flags` = `RT_TEMPORAL_CLAMP` or 0,
+/// the least weight of the current frame, the widths of the normal and the relative-depth test a history tap must pass, and the scale of
+/// the neighbourhood clamp.  (The C header spells the type `struct rt_temporal`: it shares its name with the host-buffer entry point.)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_temporal {
+    pub flags: u32,
+    pub reserved: u32,
+    pub alpha_min: f64,
+    pub sigma_normal: f64,
+    pub sigma_depth: f64,
+    pub clamp_scale: f64,
+}
+
+pub const RT_TEMPORAL_CLAMP: u32 = 0x1;
+pub const RT_TEMPORAL_MAX_LEN: u32 = 65535;
+
 pub const RT_DENOISE_DEMODULATE: u32 = 0x1;
 pub const RT_DENOISE_MAX_LEVELS: i32 = 8;
 pub const RT_DENOISE_ALBEDO_FLOOR: f64 = 0.015625;
@@ -150,6 +167,9 @@ const _: () = assert!(offset_of!(rt_adaptive, dark_floor) == 16);
 const _: () = assert!(offset_of!(rt_denoise, sigma_color) == 8);
 const _: () = assert!(offset_of!(rt_denoise, sigma_depth) == 24);
 const _: () = assert!(32 == size_of::<rt_denoise>());
+const _: () = assert!(offset_of!(rt_temporal, alpha_min) == 8);
+const _: () = assert!(offset_of!(rt_temporal, clamp_scale) == 32);
+const _: () = assert!(40 == size_of::<rt_temporal>());
 
 #[link(name = "rtiow_hip")]
 extern "C" {
@@ -222,6 +242,23 @@ extern "C" {
     /// The same filter on host buffers, no device needed.
     pub fn rt_denoise_host(fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64, width: i32, height: i32,
                            dn: *const rt_denoise, out_fix: *mut u64) -> i32;
+    /// Temporal accumulation over a STATIC scene: the current frame's sums blended with the previous call's result, fetched where each
+    /// pixel's first-hit point lay in the previous camera's image.  History: all four of `prev_fix`, `prev_len`, `prev_feat`, `prev_cam`
+    /// or none (null: the first frame).  The cameras and the options are HOST pointers in every form.  `out_fix` is a ONE-SAMPLE frame of
+    /// exact sums, `out_len` the number of frames behind each pixel; they must not overlap the history (ping-pong).
+    pub fn rt_temporal_device(ctx: *mut rt_context, d_fix: *const c_void, d_count: *const c_void, spp: i64, d_feat: *const c_void,
+                              feat_spp: i64, cam: *const rt_camera, d_prev_fix: *const c_void, d_prev_len: *const c_void,
+                              d_prev_feat: *const c_void, prev_feat_spp: i64, prev_cam: *const rt_camera, width: i32, height: i32,
+                              tp: *const rt_temporal, d_out_fix: *mut c_void, d_out_len: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_temporal(ctx: *mut rt_context, fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64,
+                       cam: *const rt_camera, prev_fix: *const u64, prev_len: *const u32, prev_feat: *const u64, prev_feat_spp: i64,
+                       prev_cam: *const rt_camera, width: i32, height: i32, tp: *const rt_temporal, out_fix: *mut u64,
+                       out_len: *mut u32, kernel_ms: *mut f32) -> i32;
+    /// The same accumulation on host buffers, no device needed.
+    pub fn rt_temporal_host(fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64, cam: *const rt_camera,
+                            prev_fix: *const u64, prev_len: *const u32, prev_feat: *const u64, prev_feat_spp: i64,
+                            prev_cam: *const rt_camera, width: i32, height: i32, tp: *const rt_temporal, out_fix: *mut u64,
+                            out_len: *mut u32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -8,6 +8,7 @@
 //                [--adaptive THRESHOLD [--step N]]
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
+//                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -32,6 +33,12 @@
 // with --feature-spp N samples (default 8; rt_render_features), filters (rt_denoise: --denoise-levels, default 4, and the three sigmas, defaults
 // 0.35 / 1.0 / 0.2, demodulated; with --adaptive the count buffer goes in, every pixel divided by its own number of samples), resolves the
 // one-sample result (rt_resolve_rgba8 with spp = 1) and saves that.  Single device; not with --uniform53, --passes, --two-calls, --features.
+// --temporal (with --cameras / --orbit): the frames of the batch accumulated over time (rt_temporal).  The batch's exact sums
+// (rt_render_frames, one launch), per frame the first-hit features of its camera with --feature-spp N samples starting at the frame's own
+// sample_begin (rt_render_features), rt_temporal chained over the frames with two pairs of history buffers used in turn (--alpha-min, default 0.1;
+// --temporal-sigma-normal 0.5; --temporal-sigma-depth 0.1; --temporal-clamp X: the scale of the neighbourhood clamp, default 1, a negative X switches
+// it off), with --denoise also rt_denoise on each accumulated frame (spp = 1, the frame's own features), then the one-sample resolve; the
+// frames are written as the batch writes them.  --denoise goes with a batch only together with --temporal.
 // --devices: the frame's rows are dealt round-robin to one rt_context per listed device, each driven by
 // its own host thread, and gathered with ONE RCCL ncclGather to the first device (host/rtiow_multi.hpp).
 // A device may be listed more than once (two contexts on one GPU from two threads: the threading rule of
@@ -88,6 +95,9 @@ int main(int argc, char **argv)
     int feature_spp = 8;
     struct rt_denoise dn{};
     dn.levels = 4; dn.flags = RT_DENOISE_DEMODULATE; dn.sigma_color = 0.35; dn.sigma_normal = 1.0; dn.sigma_depth = 0.2;
+    bool temporal = false;
+    struct rt_temporal tp{};
+    tp.flags = RT_TEMPORAL_CLAMP; tp.alpha_min = 0.1; tp.sigma_normal = 0.5; tp.sigma_depth = 0.1; tp.clamp_scale = 1.0;
     if (argc == 5 && !std::strcmp(argv[1], "--reassembly-plan")) {
         const int H = std::atoi(argv[2]), T = std::atoi(argv[3]), n = std::atoi(argv[4]);
         if (H < 1 || T < 1 || n < 1) { std::fprintf(stderr, "--reassembly-plan H T N: all >= 1\n"); return 2; }
@@ -138,6 +148,14 @@ int main(int argc, char **argv)
         else if (arg("--sigma-color")) dn.sigma_color = std::atof(argv[++i]);
         else if (arg("--sigma-normal")) dn.sigma_normal = std::atof(argv[++i]);
         else if (arg("--sigma-depth")) dn.sigma_depth = std::atof(argv[++i]);
+        else if (!std::strcmp(argv[i], "--temporal")) temporal = true;
+        else if (arg("--alpha-min")) tp.alpha_min = std::atof(argv[++i]);
+        else if (arg("--temporal-sigma-normal")) tp.sigma_normal = std::atof(argv[++i]);
+        else if (arg("--temporal-sigma-depth")) tp.sigma_depth = std::atof(argv[++i]);
+        else if (arg("--temporal-clamp")) {
+            tp.clamp_scale = std::atof(argv[++i]);
+            if (tp.clamp_scale < 0.0) { tp.flags = 0u; tp.clamp_scale = 1.0; }
+        }
         else if (arg("--scene")) scene_file = argv[++i];
         else if (!std::strcmp(argv[i], "--grid") && i + 2 < argc) { lo = std::atoi(argv[++i]); hi = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -168,7 +186,11 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--features renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --adaptive\n");
         return 2;
     }
-    if (denoise && (!devices.empty() || batch || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
+    if (temporal && (!batch || !devices.empty() || passes > 1 || adaptive || uniform53 || two_calls)) {
+        std::fprintf(stderr, "--temporal accumulates a frame batch (--cameras / --orbit) on one device and goes with none of --devices, --passes, --adaptive, --uniform53, --two-calls\n");
+        return 2;
+    }
+    if (denoise && (!devices.empty() || (batch && !temporal) || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
         std::fprintf(stderr, "--denoise renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --passes, --two-calls, --features\n");
         return 2;
     }
@@ -203,8 +225,46 @@ int main(int argc, char **argv)
         if (rc) return die("rt_create", rc);
         rc = rt_upload_scene(ctx, flat.data(), (int32_t)flat.size());
         if (rc) { die("rt_upload_scene", rc); rt_destroy(ctx); return 1; }
-        rc = rt_render_frames_rgba8(ctx, cams.data(), (int32_t)cams.size(), stride, &p, 1, rgba.data(), &st);
-        if (rc) { die("rt_render_frames_rgba8", rc); rt_destroy(ctx); return 1; }
+        if (temporal) {
+            // the batch's exact sums in one launch; then frame after frame: the guides of the frame's own camera rays, the accumulation over the
+            // previous call's result (two pairs of history buffers, used in turn), optionally the spatial filter, the one-sample resolve
+            std::vector<uint64_t> fix(npix * 3 * cams.size()), feat[2], acc[2], clean;
+            std::vector<uint32_t> len[2];
+            for (int k = 0; k < 2; ++k) { feat[k].resize(npix * RT_FEATURE_WORDS); acc[k].resize(npix * 3); len[k].resize(npix); }
+            if (denoise) clean.resize(npix * 3);
+            rc = rt_render_frames(ctx, cams.data(), (int32_t)cams.size(), stride, &p, fix.data(), &st);
+            if (rc) { die("rt_render_frames", rc); rt_destroy(ctx); return 1; }
+            float tp_ms = 0.0f;
+            size_t with_history = 0, hit_pixels = 0;
+            for (size_t f = 0; f < cams.size() && !rc; ++f) {
+                const int w = (int)(f & 1), r = 1 - w;
+                rt_params fp = p;
+                fp.spp = feature_spp; fp.sample_begin = (int32_t)f * stride;
+                float ms = 0.0f;
+                rc = rt_render_features(ctx, &cams[f], &fp, feat[w].data(), nullptr, nullptr);
+                if (rc) { die("rt_render_features", rc); break; }
+                rc = rt_temporal(ctx, fix.data() + f * npix * 3, nullptr, spp, feat[w].data(), feature_spp, &cams[f], f ? acc[r].data() : nullptr,
+                                 f ? len[r].data() : nullptr, f ? feat[r].data() : nullptr, feature_spp, f ? &cams[f - 1] : nullptr, width, height, &tp,
+                                 acc[w].data(), len[w].data(), &ms);
+                if (rc) { die("rt_temporal", rc); break; }
+                tp_ms += ms;
+                if (f + 1 == cams.size())
+                    for (size_t k = 0; k < npix; ++k) { hit_pixels += feat[w][k * RT_FEATURE_WORDS + 7] != 0; with_history += len[w][k] >= 2; }
+                if (denoise) {
+                    rc = rt_denoise(ctx, acc[w].data(), nullptr, 1, feat[w].data(), feature_spp, width, height, &dn, clean.data(), nullptr);
+                    if (rc) { die("rt_denoise", rc); break; }
+                }
+                rc = rt_resolve_rgba8(ctx, denoise ? clean.data() : acc[w].data(), width, height, 1, 1, rgba.data() + f * npix * 4);
+                if (rc) die("rt_resolve_rgba8", rc);
+            }
+            if (rc) { rt_destroy(ctx); return 1; }
+            std::printf("temporal: alpha_min %g, sigmas %g / %g, clamp %s %g, features at %d spp%s; accumulation kernels %.3f ms; last frame: %zu of %zu hit pixels with history\n",
+                        tp.alpha_min, tp.sigma_normal, tp.sigma_depth, (tp.flags & RT_TEMPORAL_CLAMP) ? "on" : "off", tp.clamp_scale, feature_spp,
+                        denoise ? ", each frame denoised" : "", tp_ms, with_history, hit_pixels);
+        } else {
+            rc = rt_render_frames_rgba8(ctx, cams.data(), (int32_t)cams.size(), stride, &p, 1, rgba.data(), &st);
+            if (rc) { die("rt_render_frames_rgba8", rc); rt_destroy(ctx); return 1; }
+        }
         rt_destroy(ctx);
         std::string prefix = out, ext = ".png";
         if (prefix.size() >= 4 && (prefix.compare(prefix.size() - 4, 4, ".png") == 0 || prefix.compare(prefix.size() - 4, 4, ".ppm") == 0)) {

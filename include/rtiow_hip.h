@@ -473,6 +473,95 @@ int rt_denoise(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int6
 int rt_denoise_host(const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp, int32_t width,
                     int32_t height, const struct rt_denoise *dn, uint64_t *out_fix);
 
+/* ---- temporal accumulation: last frame's result, reprojected through the first hit ---- */
+
+/* Blends the radiance sums of the current frame of an animation over a STATIC scene with the result of the previous call, fetched where
+ * the surface each pixel shows lay in the previous camera's image.  The scene does not move, so no motion vectors are needed: the first-hit
+ * depth of a pixel gives a world point, and that point projects into the previous image.  Tests on depth and normal reject disocclusions.
+ * The result is a ONE-SAMPLE frame of exact sums, like the denoiser's: rt_denoise(..., spp = 1, the current frame's feat, ...),
+ * rt_resolve_rgba8(..., spp = 1) and rt_fix_to_f32_device take it as it is.  DESIGN.md section 16.  Buffers, all full frames, j = 0 the
+ * BOTTOM row:
+ *   current frame   fix [H][W][3] u64; count [H][W] u32 or NULL (every entry >= 1; NULL: every pixel has `spp` samples, >= 1; when
+ *                   given, spp is ignored); feat [H][W][8] u64 over feat_spp >= 1 samples; cam: the frame's rt_camera, a HOST pointer
+ *                   in every form, read during the call
+ *   history         all four or none (none = the first frame): prev_fix [H][W][3] u64 and prev_len [H][W] u32, the previous call's
+ *                   out_fix and out_len (length 0: no history at that pixel); prev_feat [H][W][8] u64 over prev_feat_spp >= 1 samples,
+ *                   the previous frame's feature sums; prev_cam, the previous frame's rt_camera (host pointer)
+ *   outputs         out_fix [H][W][3] u64, the accumulated mean radiance on the 2^-32 grid (one sample); out_len [H][W] u32, the
+ *                   number of frames behind each pixel, 1 .. RT_TEMPORAL_MAX_LEN.  They must NOT overlap the history (a pixel reads
+ *                   its neighbours' history): callers ping-pong two pairs of buffers.
+ *
+ * The contract: IEEE binary64 throughout, in this operation order, no fused multiply-add.  v(q) = the sum's value, hi/lo form (above);
+ * quantize = the C5 rule; dot(a, b) = (a0 b0 + a1 b1) + a2 b2; cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).
+ *   Constants, once per call, with Hh = prev.horizontal, Vv = prev.vertical:  L_k = prev.lower_left_corner_k - prev.origin_k;
+ *     nrm = cross(Hh, Vv);  iLn = 1.0 / dot(L, nrm);  LH = dot(L, Hh);  LV = dot(L, Vv);  iHH = 1.0 / dot(Hh, Hh);  iVV = 1.0 / dot(Vv, Vv);
+ *     wm1 = (double)(W - 1);  hm1 = (double)(H - 1);  sz2 = sigma_depth * sigma_depth;  in = 1.0 / (sigma_normal * sigma_normal).
+ *     The formulas assume horizontal and vertical are perpendicular, as Camera::new (camera.rs:17-45) makes them; they are the contract
+ *     whatever camera is passed.
+ *   Pixel p = (i, j):
+ *   1. Prepare (the denoiser's rules, no demodulation).  c_ch = v(fix_ch) / (double)count_p (or spp);  hits = word 7;
+ *      z = hits ? v(word 6) / (double)hits : 0.0;  n_ch = +-v(|q|) / (double)feat_spp for words 3-5 read as two's complement.
+ *   2. No history: out_ch = quantize(c_ch), len = 1 -- when there is no history argument, when hits == 0 (a pure sky pixel has nothing
+ *      to reproject and no noise to remove), and at every "no history" exit below.
+ *   3. The world point of the pixel centre through the lens centre.  u = ((double)i + 0.5) / wm1;  v = ((double)j + 0.5) / hm1;
+ *      d_k = ((cur.lower_left_corner_k + u * cur.horizontal_k) + v * cur.vertical_k) - cur.origin_k;  P_k = cur.origin_k + z * d_k.
+ *      (z is the ray parameter whose value 1 is the focus plane; lens offsets average out of it.)
+ *   4. Into the previous image.  e_k = P_k - prev.origin_k;  s = dot(e, nrm) * iLn (the point's ray parameter in the previous camera, the
+ *      unit of that frame's z);  no history unless s > 0.0;  is = 1.0 / s;  up = (dot(e, Hh) * is - LH) * iHH;
+ *      vp = (dot(e, Vv) * is - LV) * iVV;  fx = up * wm1 - 0.5;  fy = vp * hm1 - 0.5;  no history unless
+ *      fx >= -1.0 && fx < (double)W && fy >= -1.0 && fy < (double)H (a NaN fails);  i0 = floor(fx), a = fx - (double)i0;  j0, b likewise.
+ *   5. Four taps q, in the order (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1), with the weights kw = (1.0 - a) * (1.0 - b),
+ *      a * (1.0 - b), (1.0 - a) * b, a * b.  A tap is skipped when it lies outside the frame, when kw is not > 0.0, when prev_len_q == 0,
+ *      when the previous frame's hits_q == 0, and unless both
+ *          ((z_q - s) * (z_q - s)) < sz2 * (s * s) + 1e-12      and      ((dn0 dn0 + dn1 dn1) + dn2 dn2) * in < 1.0,  dn = n_p - n_q,
+ *      with z_q, n_q the previous frame's guides at q prepared as in step 1 over prev_feat_spp.  A kept tap adds
+ *      acc_ch = acc_ch + kw * v(prev_fix_q,ch) and ws = ws + kw, both from 0.0, and N = min(N, prev_len_q).  No history unless ws > 0.0;
+ *      h_ch = acc_ch / ws.
+ *   6. With RT_TEMPORAL_CLAMP (it limits ghosting on mirrors and glass, which first-hit reprojection does not describe): lo_ch = hi_ch =
+ *      c_p,ch, then for the other in-frame pixels q of the 3 x 3 neighbourhood of p in the CURRENT frame, dy = -1..1 outer, dx = -1..1
+ *      inner: lo = c_q < lo ? c_q : lo, hi = c_q > hi ? c_q : hi.  mid = (lo + hi) * 0.5;  ext = ((hi - lo) * 0.5) * clamp_scale;
+ *      h = h < mid - ext ? mid - ext : h;  then h = h > mid + ext ? mid + ext : h.
+ *   7. Blend.  at = 1.0 / (double)(N + 1);  at = at < alpha_min ? alpha_min : at;  out_ch = quantize(h_ch + at * (c_ch - h_ch));
+ *      len = min(N + 1, RT_TEMPORAL_MAX_LEN).
+ * The result is a pure function of the inputs: the same bits from the device forms and from rt_temporal_host.
+ *
+ * The struct shares its name with the host-buffer entry point, as rt_denoise does: write `struct rt_temporal`. */
+struct rt_temporal {
+    uint32_t flags;         /* RT_TEMPORAL_CLAMP; every other bit is an error                                   */
+    uint32_t reserved;      /* 0                                                                                */
+    double   alpha_min;     /* in (0, 1]: the least weight of the current frame (the history's memory is 1 / alpha_min frames) */
+    double   sigma_normal;  /* > 0, finite                                                                      */
+    double   sigma_depth;   /* > 0, finite; relative to the reprojected depth                                   */
+    double   clamp_scale;   /* >= 0, finite: 1 the neighbourhood's box, 0 its centre (no history survives), read with RT_TEMPORAL_CLAMP */
+};                          /* 40 bytes */
+#define RT_TEMPORAL_CLAMP   0x1u
+#define RT_TEMPORAL_MAX_LEN 65535
+
+/* RT_ERR_INVALID_ARGUMENT from every form, found before anything is touched, the checks that need no context first: NULL options, fix,
+ * feat, cam, out_fix or out_len; a partial history (some but not all of prev_fix, prev_len, prev_feat, prev_cam); unknown flag bits; an
+ * option out of range or not finite; width or height < 2 (u, v divide by W - 1, H - 1); width * height > 2^31; spp < 1 with a NULL
+ * count; feat_spp < 1; prev_feat_spp < 1 with a history. */
+
+/* Device form, asynchronous on `stream`.  Every buffer is a device pointer, 8-byte aligned (4 for the u32 ones); the two cameras and the
+ * options are host pointers read during the call.  Takes NONE of the context's launch slots, rt_last_stats does not report on it, and it
+ * needs no uploaded scene. */
+int rt_temporal_device(rt_context *ctx, const void *d_fix, const void *d_count, int64_t spp, const void *d_feat, int64_t feat_spp,
+                       const rt_camera *cam, const void *d_prev_fix, const void *d_prev_len, const void *d_prev_feat, int64_t prev_feat_spp,
+                       const rt_camera *prev_cam, int32_t width, int32_t height, const struct rt_temporal *tp, void *d_out_fix,
+                       void *d_out_len, void *stream);
+/* Host-buffer form (copies in, accumulates on the device, copies out); synchronous.  kernel_ms (may be NULL): the kernel's time, from a
+ * pair of events the call creates and destroys itself. */
+int rt_temporal(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp,
+                const rt_camera *cam, const uint64_t *prev_fix, const uint32_t *prev_len, const uint64_t *prev_feat, int64_t prev_feat_spp,
+                const rt_camera *prev_cam, int32_t width, int32_t height, const struct rt_temporal *tp, uint64_t *out_fix, uint32_t *out_len,
+                float *kernel_ms);
+/* The same accumulation on host buffers, no device needed: the library's own CPU statement of the contract (it compiles the very
+ * functions the kernel does, rt_temporal_core.hpp). */
+int rt_temporal_host(const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp, const rt_camera *cam,
+                     const uint64_t *prev_fix, const uint32_t *prev_len, const uint64_t *prev_feat, int64_t prev_feat_spp,
+                     const rt_camera *prev_cam, int32_t width, int32_t height, const struct rt_temporal *tp, uint64_t *out_fix,
+                     uint32_t *out_len);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

@@ -47,6 +47,11 @@ class rt_denoise(C.Structure):
                 ("sigma_depth", C.c_double)]
 
 
+class rt_temporal(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("alpha_min", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double), ("clamp_scale", C.c_double)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -57,6 +62,8 @@ RT_FEATURE_WORDS = 8        # u64 sums per pixel of a feature buffer: albedo rgb
 RT_DENOISE_DEMODULATE = 0x1
 RT_DENOISE_MAX_LEVELS = 8
 RT_DENOISE_ALBEDO_FLOOR = 0.015625
+RT_TEMPORAL_CLAMP = 0x1
+RT_TEMPORAL_MAX_LEN = 65535
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
@@ -91,6 +98,12 @@ SYMBOLS = [
     ("rt_denoise_device", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, _VP, _VP]),
     ("rt_denoise", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, C.POINTER(C.c_float)]),
     ("rt_denoise_host", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP]),
+    ("rt_temporal_device", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
+                                     C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, _VP]),
+    ("rt_temporal", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
+                              C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, C.POINTER(C.c_float)]),
+    ("rt_temporal_host", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
+                                   C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -1,0 +1,209 @@
+// rt_temporal.hip -- temporal accumulation across the frames of an animation by first-hit reprojection (rtiow_hip.h, "temporal
+// accumulation").
+//
+// The sixth translation unit of librtiow_hip.so.  Like the denoiser it sits wholly beside the render kernels: it reads the exact sums a
+// render and a feature launch left on the device, and the one-sample frame the previous call wrote, and writes a one-sample frame of exact
+// sums plus a history length per pixel.  rt_kernels.hpp, rt_device.hpp, rt_api.hip and the other translation units are untouched, so every
+// existing kernel keeps its machine code.  The arithmetic lives in rt_temporal_core.hpp, once, for the kernel here, for rt_temporal_host
+// and for the stand-alone sanitizer program of the tests.
+//
+// One launch, one lane per pixel: a wave covers an 8 x 8 pixel tile and a workgroup four of them (as features_kernel does), so the four
+// taps of neighbouring lanes and their 3 x 3 boxes fall into the same cache lines; a grid-stride loop over the tiles.  The constants of the
+// call -- both cameras among them -- are computed on the host by rt_tp::constants and arrive as a kernel argument (wave-uniform).  No LDS,
+// no atomics; a lane stores its three sums and its length once.  There is ONE form of the kernel: profiles/temporal.txt has the
+// measurement that says a staged form is not worth building.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <vector>
+
+#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: no kernel of rt_api.hip is instantiated here
+#include "rt_host.hpp"
+#include "rt_temporal_core.hpp"
+
+using namespace rt_host;
+
+namespace rt {
+
+constexpr int kTpBlock = 256;                       // four waves, each on pixel tiles of its own
+constexpr int kTpWaves = kTpBlock / 64;
+constexpr long long kTpMaxBlocks = 1 << 20;         // the grid-stride loop takes over beyond
+
+struct TpTiling {
+    uint32_t tiles_x;               // pixel tiles per row of tiles: ceil(width / 8)
+    uint32_t n_tiles;               // tiles_x * ceil(height / 8) <= 2^31 / 64 + 2^16
+};
+
+__global__ __launch_bounds__(kTpBlock) void temporal_kernel(const rt_tp::Const K, const rt_tp::Buffers B, const TpTiling T,
+                                                            unsigned long long *__restrict__ out_fix, uint32_t *__restrict__ out_len)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t n_waves = gridDim.x * (uint32_t)kTpWaves;
+    for (uint32_t wt = blockIdx.x * (uint32_t)kTpWaves + wave; wt < T.n_tiles; wt += n_waves) {
+        const uint32_t ty = wt / T.tiles_x, tx = wt - ty * T.tiles_x;
+        const long long i = (long long)(tx * 8u + (lane & 7u)), j = (long long)(ty * 8u + (lane >> 3));
+        if (i >= K.width || j >= K.height) continue;            // lanes past the right or top edge: nothing computed, nothing stored
+        uint64_t q[3];
+        const uint32_t len = rt_tp::pixel_at(i, j, K, B, q);
+        const unsigned long long p = (unsigned long long)(j * K.width + i);
+        out_fix[3 * p + 0] = q[0]; out_fix[3 * p + 1] = q[1]; out_fix[3 * p + 2] = q[2];
+        out_len[p] = len;
+    }
+}
+
+} // namespace rt
+
+namespace {
+
+rt_tp::Cam cam_of(const rt_camera *c)
+{
+    rt_tp::Cam k;
+    for (int a = 0; a < 3; ++a) {
+        k.origin[a] = c->origin[a]; k.llc[a] = c->lower_left_corner[a];
+        k.horizontal[a] = c->horizontal[a]; k.vertical[a] = c->vertical[a];
+    }
+    return k;
+}
+
+// What every form checks, before anything is touched; none of it needs a context.  *K: the constants of the call.
+int validate_temporal(const struct rt_temporal *tp, const void *fix, bool has_count, int64_t spp, const void *feat, int64_t feat_spp,
+                      const rt_camera *cam, const void *prev_fix, const void *prev_len, const void *prev_feat, int64_t prev_feat_spp,
+                      const rt_camera *prev_cam, int32_t width, int32_t height, const void *out_fix, const void *out_len, rt_tp::Const *K)
+{
+    if (!tp) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: the options are NULL");
+    if (!fix || !feat || !cam || !out_fix || !out_len)
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: a buffer is NULL (fix, feat, cam, out_fix or out_len)");
+    const int n_hist = (prev_fix ? 1 : 0) + (prev_len ? 1 : 0) + (prev_feat ? 1 : 0) + (prev_cam ? 1 : 0);
+    if (n_hist != 0 && n_hist != 4)
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: a partial history (%d of prev_fix, prev_len, prev_feat, prev_cam): all four or none", n_hist);
+    if (tp->flags & ~RT_TEMPORAL_CLAMP) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: unknown flags 0x%x", tp->flags);
+    if (!(tp->alpha_min > 0.0) || !(tp->alpha_min <= 1.0))
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: alpha_min must be in (0, 1] (is %g)", tp->alpha_min);
+    if (!(tp->sigma_normal > 0.0) || !(tp->sigma_depth > 0.0) || !std::isfinite(tp->sigma_normal) || !std::isfinite(tp->sigma_depth))
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: every sigma must be > 0 and finite (%g, %g)", tp->sigma_normal, tp->sigma_depth);
+    if (!(tp->clamp_scale >= 0.0) || !std::isfinite(tp->clamp_scale))
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: clamp_scale must be >= 0 and finite (is %g)", tp->clamp_scale);
+    if (width < 2 || height < 2) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: width and height must be >= 2 (%d, %d)", width, height);
+    if ((long long)width * height > (1ll << 31))
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: width * height must be <= 2^31 (is %lld)", (long long)width * height);
+    if (!has_count && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: spp >= 1 without a count buffer (is %lld)", (long long)spp);
+    if (feat_spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: feat_spp >= 1 (is %lld)", (long long)feat_spp);
+    if (n_hist && prev_feat_spp < 1)
+        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: prev_feat_spp >= 1 with a history (is %lld)", (long long)prev_feat_spp);
+    const rt_tp::Cam cur = cam_of(cam);
+    rt_tp::Cam prev;
+    if (n_hist) prev = cam_of(prev_cam);
+    *K = rt_tp::constants(cur, n_hist ? &prev : nullptr, width, height, has_count ? 1 : (long long)spp, (long long)feat_spp,
+                          n_hist ? (long long)prev_feat_spp : 1, tp->flags, tp->alpha_min, tp->sigma_normal, tp->sigma_depth, tp->clamp_scale);
+    return RT_OK;
+}
+
+rt_tp::Buffers buffers_of(const void *fix, const void *count, const void *feat, const void *prev_fix, const void *prev_len, const void *prev_feat)
+{
+    rt_tp::Buffers B;
+    B.fix = (const uint64_t *)fix; B.count = (const uint32_t *)count; B.feat = (const uint64_t *)feat;
+    B.prev_fix = (const uint64_t *)prev_fix; B.prev_len = (const uint32_t *)prev_len; B.prev_feat = (const uint64_t *)prev_feat;
+    return B;
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_temporal_device(rt_context *ctx, const void *d_fix, const void *d_count, int64_t spp, const void *d_feat, int64_t feat_spp,
+                       const rt_camera *cam, const void *d_prev_fix, const void *d_prev_len, const void *d_prev_feat, int64_t prev_feat_spp,
+                       const rt_camera *prev_cam, int32_t width, int32_t height, const struct rt_temporal *tp, void *d_out_fix, void *d_out_len,
+                       void *stream_v)
+{
+    rt_tp::Const K;
+    int rc = validate_temporal(tp, d_fix, d_count != nullptr, spp, d_feat, feat_spp, cam, d_prev_fix, d_prev_len, d_prev_feat, prev_feat_spp,
+                               prev_cam, width, height, d_out_fix, d_out_len, &K);
+    if (rc) return rc;
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    RT_HIP(hipSetDevice(ctx->device));
+    // (no launch slot: rt_last_stats does not report on an accumulation; no scene needed)
+    rt::TpTiling T;
+    T.tiles_x = ((uint32_t)width + 7u) / 8u;
+    const unsigned long long n_tiles = (unsigned long long)T.tiles_x * (((unsigned long long)height + 7ull) / 8ull);
+    T.n_tiles = (uint32_t)n_tiles;                              // width * height <= 2^31: at most 2^31 / 8 + 2^28 tiles of one row or column
+    unsigned long long grid = (n_tiles + rt::kTpWaves - 1) / rt::kTpWaves;
+    if (grid > (unsigned long long)rt::kTpMaxBlocks) grid = (unsigned long long)rt::kTpMaxBlocks;
+    hipLaunchKernelGGL(rt::temporal_kernel, dim3((unsigned)grid), dim3(rt::kTpBlock), 0, (hipStream_t)stream_v, K,
+                       buffers_of(d_fix, d_count, d_feat, d_prev_fix, d_prev_len, d_prev_feat), T, (unsigned long long *)d_out_fix,
+                       (uint32_t *)d_out_len);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_temporal(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp,
+                const rt_camera *cam, const uint64_t *prev_fix, const uint32_t *prev_len, const uint64_t *prev_feat, int64_t prev_feat_spp,
+                const rt_camera *prev_cam, int32_t width, int32_t height, const struct rt_temporal *tp, uint64_t *out_fix, uint32_t *out_len,
+                float *kernel_ms)
+{
+    rt_tp::Const K;
+    int rc = validate_temporal(tp, fix, count != nullptr, spp, feat, feat_spp, cam, prev_fix, prev_len, prev_feat, prev_feat_spp, prev_cam, width,
+                               height, out_fix, out_len, &K);
+    if (rc) return rc;
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    RT_HIP(hipSetDevice(ctx->device));
+    // the staging buffers rt_destroy frees.  d_stage_fix: the radiance sums, the feature sums and the output sums, one after the other
+    // (256-byte steps); d_stage_sum: the history's sums and feature sums; d_stage_list: the counts, the history's lengths, the output's
+    const bool hist = prev_cam != nullptr;
+    const size_t npix = (size_t)width * height;
+    const size_t up = 255;
+    const size_t fix_bytes = npix * 3 * sizeof(uint64_t), feat_bytes = npix * RT_FEATURE_WORDS * sizeof(uint64_t), len_bytes = npix * sizeof(uint32_t);
+    const size_t off_feat = (fix_bytes + up) & ~up, off_out = (off_feat + feat_bytes + up) & ~up;
+    const size_t off_plen = (len_bytes + up) & ~up, off_olen = (off_plen + len_bytes + up) & ~up;
+    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, off_out + fix_bytes);
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_sum, &ctx->stage_sum_bytes, off_feat + feat_bytes);
+    if (rc) return rc;
+    rc = ensure(&ctx->d_stage_list, &ctx->stage_list_bytes, off_olen + len_bytes);
+    if (rc) return rc;
+    char *base = (char *)ctx->d_stage_fix, *hbase = (char *)ctx->d_stage_sum, *lbase = (char *)ctx->d_stage_list;
+    RT_HIP(hipMemcpyAsync(base, fix, fix_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+    RT_HIP(hipMemcpyAsync(base + off_feat, feat, feat_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+    if (count) RT_HIP(hipMemcpyAsync(lbase, count, len_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+    if (hist) {
+        RT_HIP(hipMemcpyAsync(hbase, prev_fix, fix_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+        RT_HIP(hipMemcpyAsync(hbase + off_feat, prev_feat, feat_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+        RT_HIP(hipMemcpyAsync(lbase + off_plen, prev_len, len_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+    }
+    // the kernel is timed with a pair of events of this call's own: the context's belong to its launch slots
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    RT_HIP(hipEventCreate(&e0));
+    hipError_t he = hipEventCreate(&e1);
+    if (he == hipSuccess) he = hipEventRecord(e0, ctx->own_stream);
+    if (he == hipSuccess) {
+        rc = rt_temporal_device(ctx, base, count ? lbase : nullptr, spp, base + off_feat, feat_spp, cam, hist ? hbase : nullptr,
+                                hist ? lbase + off_plen : nullptr, hist ? hbase + off_feat : nullptr, prev_feat_spp, prev_cam, width, height, tp,
+                                base + off_out, lbase + off_olen, ctx->own_stream);
+        if (!rc) he = hipEventRecord(e1, ctx->own_stream);
+        if (!rc && he == hipSuccess) he = hipMemcpyAsync(out_fix, base + off_out, fix_bytes, hipMemcpyDeviceToHost, ctx->own_stream);
+        if (!rc && he == hipSuccess) he = hipMemcpyAsync(out_len, lbase + off_olen, len_bytes, hipMemcpyDeviceToHost, ctx->own_stream);
+        if (!rc && he == hipSuccess) he = hipStreamSynchronize(ctx->own_stream);
+        float ms = 0.0f;
+        if (!rc && he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+        if (!rc && he == hipSuccess && kernel_ms) *kernel_ms = ms;
+    }
+    (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (rc) return rc;
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "rt_temporal: %s", hipGetErrorString(he));
+    return RT_OK;
+}
+
+// the library's own CPU statement: the very functions the kernel compiles, one pixel after the other
+int rt_temporal_host(const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp, const rt_camera *cam,
+                     const uint64_t *prev_fix, const uint32_t *prev_len, const uint64_t *prev_feat, int64_t prev_feat_spp, const rt_camera *prev_cam,
+                     int32_t width, int32_t height, const struct rt_temporal *tp, uint64_t *out_fix, uint32_t *out_len)
+{
+    rt_tp::Const K;
+    int rc = validate_temporal(tp, fix, count != nullptr, spp, feat, feat_spp, cam, prev_fix, prev_len, prev_feat, prev_feat_spp, prev_cam, width,
+                               height, out_fix, out_len, &K);
+    if (rc) return rc;
+    rt_tp::accumulate_host(K, buffers_of(fix, count, feat, prev_fix, prev_len, prev_feat), out_fix, out_len);
+    return RT_OK;
+}
+
+} // extern "C"

@@ -75,6 +75,52 @@ def denoise_host(fix, spp, feat, feat_spp, denoise=None, count=None):
     return out
 
 
+def make_temporal(alpha_min=0.1, sigma_normal=0.5, sigma_depth=0.1, clamp=True, clamp_scale=1.0):
+    """rt_temporal: the least weight of the current frame, the widths of the normal and the relative-depth test that a history tap must
+    pass, and whether the history is clamped to the box of the current frame's 3 x 3 neighbourhood (scaled about its centre by
+    clamp_scale).  The defaults are those of the sweep in DESIGN.md section 16."""
+    t = _ffi.rt_temporal()
+    t.flags, t.reserved = (_ffi.RT_TEMPORAL_CLAMP if clamp else 0), 0
+    t.alpha_min, t.sigma_normal, t.sigma_depth, t.clamp_scale = float(alpha_min), float(sigma_normal), float(sigma_depth), float(clamp_scale)
+    return t
+
+
+def _rt_cam(cam):
+    return cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+
+
+def _temporal_args(fix, spp, feat, feat_spp, cam, history, count):
+    """The arguments the host-buffer forms of rt_temporal share, and what must stay alive while they are used.
+    history: None (the first frame) or (prev_fix u64 [H,W,3], prev_len u32 [H,W], prev_feat u64 [H,W,8], prev_feat_spp, prev_cam)."""
+    fix, feat, count, h, w = _denoise_arrays(fix, feat, count)
+    keep = [fix, feat, count, _rt_cam(cam)]
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    if history is None:
+        hist = (None, None, None, 0, None)
+    else:
+        pfix, plen, pfeat, pspp, pcam = history
+        pfix, pfeat, plen, ph, pw = _denoise_arrays(pfix, pfeat, plen)
+        assert (ph, pw) == (h, w) and plen is not None
+        keep += [pfix, plen, pfeat, _rt_cam(pcam)]
+        hist = (vp(pfix), vp(plen), vp(pfeat), int(pspp), C.byref(keep[-1]))
+    out_fix = np.zeros((h, w, 3), dtype=np.uint64)
+    out_len = np.zeros((h, w), dtype=np.uint32)
+    head = (vp(fix), vp(count), int(spp), vp(feat), int(feat_spp), C.byref(keep[3]), *hist, w, h)
+    return head, out_fix, out_len, keep
+
+
+def temporal_host(fix, spp, feat, feat_spp, cam, history=None, temporal=None, count=None):
+    """rt_temporal_host (no GPU): the library's CPU statement of temporal accumulation.  fix u64 [H,W,3] of `spp` samples (or of
+    count[H,W] u32 samples per pixel), feat u64 [H,W,8] of `feat_spp` samples and the frame's camera; history: None for the first frame,
+    else (prev_fix, prev_len, prev_feat, prev_feat_spp, prev_cam) -- the previous call's two results, the previous frame's feature sums
+    and camera.  Returns (the accumulated one-sample frame u64 [H,W,3], the history lengths u32 [H,W])."""
+    lib = _ffi.load()
+    tp = temporal if temporal is not None else make_temporal()
+    head, out_fix, out_len, keep = _temporal_args(fix, spp, feat, feat_spp, cam, history, count)
+    _ffi.check(lib.rt_temporal_host(*head, C.byref(tp), out_fix.ctypes.data_as(C.c_void_p), out_len.ctypes.data_as(C.c_void_p)), "rt_temporal_host")
+    return out_fix, out_len
+
+
 def shard_rows(params):
     lib = _ffi.load()
     rows = C.c_int32(0)
@@ -378,6 +424,56 @@ class Renderer:
         return int(n.value)
 
     denoise_host = staticmethod(denoise_host)
+
+    # -- temporal accumulation: the previous result, reprojected through the first hit ------
+    def temporal(self, fix, spp, feat, feat_spp, cam, history=None, temporal=None, count=None):
+        """rt_temporal: the arguments of temporal_host, on the device -> (the accumulated ONE-SAMPLE frame u64 [H,W,3], the history
+        lengths u32 [H,W], the kernel's time in ms).  Feed the two arrays back as the next frame's history (with this frame's feat and camera)."""
+        tp = temporal if temporal is not None else make_temporal()
+        head, out_fix, out_len, keep = _temporal_args(fix, spp, feat, feat_spp, cam, history, count)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_temporal(self._h, *head, C.byref(tp), out_fix.ctypes.data_as(C.c_void_p), out_len.ctypes.data_as(C.c_void_p),
+                                         C.byref(ms)), "rt_temporal")
+        return out_fix, out_len, float(ms.value)
+
+    def temporal_device(self, d_fix_ptr, spp, d_feat_ptr, feat_spp, cam, width, height, temporal, d_out_fix_ptr, d_out_len_ptr, history=None,
+                        d_count_ptr=0, stream=0):
+        """rt_temporal_device: device pointers, asynchronous on `stream`; history: None or (d_prev_fix_ptr, d_prev_len_ptr, d_prev_feat_ptr,
+        prev_feat_spp, prev_cam) -- the cameras are host objects.  The outputs must not overlap the history: ping-pong."""
+        vp = lambda q: C.c_void_p(q) if q else None
+        rc = _rt_cam(cam)
+        if history is None:
+            hist = (None, None, None, 0, None)
+        else:
+            pc = _rt_cam(history[4])
+            hist = (vp(history[0]), vp(history[1]), vp(history[2]), int(history[3]), C.byref(pc))
+        _ffi.check(self._lib.rt_temporal_device(self._h, vp(d_fix_ptr), vp(d_count_ptr), int(spp), vp(d_feat_ptr), int(feat_spp), C.byref(rc), *hist,
+                                                int(width), int(height), C.byref(temporal), vp(d_out_fix_ptr), vp(d_out_len_ptr), C.c_void_p(stream)),
+                   "rt_temporal_device")
+
+    temporal_host = staticmethod(temporal_host)
+
+    def render_sequence(self, cams, params, sample_stride, feature_spp, temporal=None, denoise=None, flip=True):
+        """An animation over the uploaded scene with temporal accumulation: render_frames (ONE launch; frame f takes the samples
+        sample_begin + f * sample_stride on), per frame render_features with that frame's sample_begin (the guides see the frame's own camera
+        rays), rt_temporal chained over the frames with ping-pong history, optionally rt_denoise on each accumulated frame (spp = 1, the frame's
+        own guides), and the one-sample resolve.  temporal: an rt_temporal (None: make_temporal()); denoise: an rt_denoise or None (no spatial
+        filter).  Returns (RGBA8 [F,H,W,4], the last frame's history lengths u32 [H,W])."""
+        a = self._camera_array(cams)
+        tp = temporal if temporal is not None else make_temporal()
+        w, h = params.width, params.height
+        fixes, _ = self.render_frames(a, params, sample_stride)
+        out = np.zeros((len(a), h, w, 4), dtype=np.uint8)
+        history, lengths = None, np.zeros((h, w), dtype=np.uint32)
+        for f in range(len(a)):
+            cam = _ffi.rt_camera.from_buffer_copy(a[f].tobytes())
+            fp = make_params(w, h, feature_spp, sample_begin=params.sample_begin + f * int(sample_stride), t_min=params.t_min, seed=params.seed)
+            feat, _, _ = self.render_features(cam, fp, want_ids=False)
+            acc, lengths, _ = self.temporal(fixes[f], params.spp, feat, feature_spp, cam, history, tp)
+            history = (acc, lengths, feat, feature_spp, cam)
+            shown = self.denoise(acc, 1, feat, feature_spp, denoise)[0] if denoise is not None else acc
+            out[f] = self.resolve_rgba8(shown, 1, flip=flip)
+        return out, lengths
 
     # -- to_rgba + flip --------------------------------------------------------
     def resolve_rgba8(self, fix, spp, flip=True):
