@@ -581,8 +581,7 @@ int rt_destroy(rt_context *ctx)
         if (ctx->e0_slots[k]) (void)hipEventDestroy(ctx->e0_slots[k]);
         if (ctx->e1_slots[k]) (void)hipEventDestroy(ctx->e1_slots[k]);
     }
-    (void)hipFree(ctx->d_stage_fix); (void)hipFree(ctx->d_stage_sum); (void)hipFree(ctx->d_stage_rgba);
-    (void)hipFree(ctx->d_sel); (void)hipFree(ctx->d_adapt); (void)hipFree(ctx->d_stage_list); (void)hipFree(ctx->d_stage_cams);
+    (void)hipFree(ctx->d_arena); (void)hipFree(ctx->d_sel);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return RT_OK;
@@ -811,9 +810,7 @@ int rt_fix_to_f32_device(rt_context *ctx, const void *d_fix, int64_t count, void
     if (count < 0 || (count > 0 && (!d_fix || !d_out_f32))) return fail(RT_ERR_INVALID_ARGUMENT, "bad buffers");
     if (count == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    long long blocks = (count + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(rt::fix_to_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_v,
+    hipLaunchKernelGGL(rt::fix_to_f32_kernel, dim3(grid_256(count)), dim3(256), 0, (hipStream_t)stream_v,
                        (const unsigned long long *)d_fix, (float *)d_out_f32, (long long)count);
     RT_HIP(hipGetLastError());
     return RT_OK;
@@ -827,11 +824,8 @@ int rt_resolve_rgba8_device(rt_context *ctx, const void *d_fix, int32_t width, i
     if (rows == 0) return RT_OK;
     if (!d_fix || !d_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "bad buffers");
     RT_HIP(hipSetDevice(ctx->device));
-    const long long npix = (long long)width * rows;
-    long long blocks = (npix + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
     const double scale = 1.0 / (double)spp;            // vec3.rs:409
-    hipLaunchKernelGGL(rt::resolve_rgba8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_v,
+    hipLaunchKernelGGL(rt::resolve_rgba8_kernel, dim3(grid_256((long long)width * rows)), dim3(256), 0, (hipStream_t)stream_v,
                        (const unsigned long long *)d_fix, (uint8_t *)d_rgba, (int)width, (int)rows, scale, (int)flip);
     RT_HIP(hipGetLastError());
     return RT_OK;
@@ -847,22 +841,20 @@ int rt_render(rt_context *ctx, const rt_camera *cam, const rt_params *p,
     const size_t count = (size_t)rows * p->width * 3;
     if (count > 0 && !out_sum && !out_fix) return fail(RT_ERR_INVALID_ARGUMENT, "no output buffer");
     RT_HIP(hipSetDevice(ctx->device));
-    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, count * sizeof(uint64_t));
-    if (rc) return rc;
-    rc = ensure(&ctx->d_stage_sum, &ctx->stage_sum_bytes, count * sizeof(float));
-    if (rc) return rc;
+    Stage st(ctx);
+    const size_t b_fix = st.add(count * sizeof(uint64_t)), b_sum = st.add(count * sizeof(float));
+    if ((rc = st.commit())) return rc;
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_device(ctx, cam, &q, ctx->d_stage_fix, ctx->own_stream);
+    rc = rt_render_device(ctx, cam, &q, st.at(b_fix), ctx->own_stream);
     if (rc) return rc;
     if (out_sum) {
-        rc = rt_fix_to_f32_device(ctx, ctx->d_stage_fix, (int64_t)count, ctx->d_stage_sum, ctx->own_stream);
+        rc = rt_fix_to_f32_device(ctx, st.at(b_fix), (int64_t)count, st.at(b_sum), ctx->own_stream);
         if (rc) return rc;
-        RT_HIP(hipMemcpyAsync(out_sum, ctx->d_stage_sum, count * sizeof(float), hipMemcpyDeviceToHost, ctx->own_stream));
+        RT_HIP(st.down(out_sum, b_sum, count * sizeof(float)));
     }
-    if (out_fix)
-        RT_HIP(hipMemcpyAsync(out_fix, ctx->d_stage_fix, count * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    if (out_fix) RT_HIP(st.down(out_fix, b_fix, count * sizeof(uint64_t)));
+    RT_HIP(st.sync());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }
@@ -876,15 +868,15 @@ int rt_resolve_rgba8(rt_context *ctx, const uint64_t *fix, int32_t width, int32_
     if (!fix || !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "bad buffers");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)width * rows;
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, npix * 3 * sizeof(uint64_t));
+    Stage st(ctx);
+    const size_t b_fix = st.add(npix * 3 * sizeof(uint64_t)), b_rgba = st.add(npix * 4);
+    int rc = st.commit();
     if (rc) return rc;
-    rc = ensure(&ctx->d_stage_rgba, &ctx->stage_rgba_bytes, npix * 4);
+    RT_HIP(st.up(b_fix, fix, npix * 3 * sizeof(uint64_t)));
+    rc = rt_resolve_rgba8_device(ctx, st.at(b_fix), width, rows, spp, flip, st.at(b_rgba), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(ctx->d_stage_fix, fix, npix * 3 * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->own_stream));
-    rc = rt_resolve_rgba8_device(ctx, ctx->d_stage_fix, width, rows, spp, flip, ctx->d_stage_rgba, ctx->own_stream);
-    if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(out_rgba, ctx->d_stage_rgba, npix * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_rgba, b_rgba, npix * 4));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -902,22 +894,19 @@ int rt_render_rgba8(rt_context *ctx, const rt_camera *cam, const rt_params *p, i
     const size_t npix = (size_t)rows * p->width;
     if (npix > 0 && !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgba is NULL");
     RT_HIP(hipSetDevice(ctx->device));
-    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, npix * 3 * sizeof(uint64_t));
-    if (rc) return rc;
-    rc = ensure(&ctx->d_stage_rgba, &ctx->stage_rgba_bytes, npix * 4);
-    if (rc) return rc;
+    Stage st(ctx);
+    const size_t b_fix = st.add(npix * 3 * sizeof(uint64_t)), b_rgba = st.add(npix * 4);
+    if ((rc = st.commit())) return rc;
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_device(ctx, cam, &q, ctx->d_stage_fix, ctx->own_stream);
+    rc = rt_render_device(ctx, cam, &q, st.at(b_fix), ctx->own_stream);
     if (rc) return rc;
     if (npix > 0) {
-        rc = rt_resolve_rgba8_device(ctx, ctx->d_stage_fix, p->width, rows, (int64_t)p->spp, flip, ctx->d_stage_rgba, ctx->own_stream);
+        rc = rt_resolve_rgba8_device(ctx, st.at(b_fix), p->width, rows, (int64_t)p->spp, flip, st.at(b_rgba), ctx->own_stream);
         if (rc) return rc;
-        RT_HIP(hipMemcpyAsync(out_rgba, ctx->d_stage_rgba, npix * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-        RT_HIP(hipStreamSynchronize(ctx->own_stream));
-    } else {
-        RT_HIP(hipStreamSynchronize(ctx->own_stream));
+        RT_HIP(st.down(out_rgba, b_rgba, npix * 4));
     }
+    RT_HIP(st.sync());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }
@@ -969,17 +958,16 @@ int rt_render_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
             return fail(RT_ERR_INVALID_ARGUMENT, "pixels[%lld] = %u is not a pixel of a %d x %d frame", (long long)k, pixels[k], p->width, p->height);
     RT_HIP(hipSetDevice(ctx->device));
     const size_t count = (size_t)n_pixels * 3;
-    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, count * sizeof(uint64_t));
-    if (rc) return rc;
-    rc = ensure(&ctx->d_stage_list, &ctx->stage_list_bytes, (size_t)n_pixels * sizeof(uint32_t));
-    if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(ctx->d_stage_list, pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->own_stream));
+    Stage st(ctx);
+    const size_t b_fix = st.add(count * sizeof(uint64_t)), b_list = st.add((size_t)n_pixels * sizeof(uint32_t));
+    if ((rc = st.commit())) return rc;
+    RT_HIP(st.up(b_list, pixels, (size_t)n_pixels * sizeof(uint32_t)));
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_pixels_device(ctx, cam, &q, (const uint32_t *)ctx->d_stage_list, n_pixels, ctx->d_stage_fix, ctx->own_stream);
+    rc = rt_render_pixels_device(ctx, cam, &q, st.at<const uint32_t>(b_list), n_pixels, st.at(b_fix), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(out_fix, ctx->d_stage_fix, count * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_fix, b_fix, count * sizeof(uint64_t)));
+    RT_HIP(st.sync());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }
@@ -1057,13 +1045,14 @@ int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p
     hipStream_t st = ctx->own_stream;
     const size_t npix = (size_t)p->width * p->height;
     const size_t sums = npix * 3 * sizeof(uint64_t);
-    // the frame's state, all on the device: fix | half | one pass's compact sums | count | list | list length | running counters (5 x u64)
-    rc = ensure(&ctx->d_adapt, &ctx->adapt_bytes, 3 * sums + 2 * npix * sizeof(uint32_t) + 64);
-    if (rc) return rc;
-    char *base = (char *)ctx->d_adapt;
-    void *d_fix = base, *d_half = base + sums, *d_pass = base + 2 * sums;
-    uint32_t *d_count = (uint32_t *)(base + 3 * sums), *d_list = d_count + npix;
-    unsigned long long *d_total = (unsigned long long *)(d_list + npix);
+    // the frame's state, all on the device: fix | half | one pass's compact sums | count | list | running counters (5 x u64), list length
+    Stage stage(ctx);
+    const size_t b_fix = stage.add(sums), b_half = stage.add(sums), b_pass = stage.add(sums);
+    const size_t b_count = stage.add(npix * sizeof(uint32_t)), b_list = stage.add(npix * sizeof(uint32_t)), b_total = stage.add(64);
+    if ((rc = stage.commit())) return rc;
+    void *d_fix = stage.at(b_fix), *d_half = stage.at(b_half), *d_pass = stage.at(b_pass);
+    uint32_t *d_count = stage.at<uint32_t>(b_count), *d_list = stage.at<uint32_t>(b_list);
+    unsigned long long *d_total = stage.at<unsigned long long>(b_total);
     uint32_t *d_n = (uint32_t *)(d_total + 5);
     RT_HIP(hipMemsetAsync(d_total, 0, 64, st));
 
@@ -1151,10 +1140,7 @@ int rt_resolve_rgba8_counts_device(rt_context *ctx, const void *d_fix, const voi
     if (rows == 0) return RT_OK;
     if (!d_fix || !d_count || !d_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "bad buffers");
     RT_HIP(hipSetDevice(ctx->device));
-    const long long npix = (long long)width * rows;
-    long long blocks = (npix + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(rt::resolve_rgba8_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_v,
+    hipLaunchKernelGGL(rt::resolve_rgba8_counts_kernel, dim3(grid_256((long long)width * rows)), dim3(256), 0, (hipStream_t)stream_v,
                        (const unsigned long long *)d_fix, (const uint32_t *)d_count, (uint8_t *)d_rgba, (int)width, (int)rows, (int)flip);
     RT_HIP(hipGetLastError());
     return RT_OK;
@@ -1169,18 +1155,16 @@ int rt_resolve_rgba8_counts(rt_context *ctx, const uint64_t *fix, const uint32_t
     if (!fix || !count || !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "bad buffers");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)width * rows;
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, npix * 3 * sizeof(uint64_t));
+    Stage st(ctx);
+    const size_t b_fix = st.add(npix * 3 * sizeof(uint64_t)), b_rgba = st.add(npix * 4), b_count = st.add(npix * sizeof(uint32_t));
+    int rc = st.commit();
     if (rc) return rc;
-    rc = ensure(&ctx->d_stage_rgba, &ctx->stage_rgba_bytes, npix * 4);
+    RT_HIP(st.up(b_fix, fix, npix * 3 * sizeof(uint64_t)));
+    RT_HIP(st.up(b_count, count, npix * sizeof(uint32_t)));
+    rc = rt_resolve_rgba8_counts_device(ctx, st.at(b_fix), st.at(b_count), width, rows, flip, st.at(b_rgba), ctx->own_stream);
     if (rc) return rc;
-    rc = ensure(&ctx->d_stage_list, &ctx->stage_list_bytes, npix * sizeof(uint32_t));
-    if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(ctx->d_stage_fix, fix, npix * 3 * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(ctx->d_stage_list, count, npix * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->own_stream));
-    rc = rt_resolve_rgba8_counts_device(ctx, ctx->d_stage_fix, ctx->d_stage_list, width, rows, flip, ctx->d_stage_rgba, ctx->own_stream);
-    if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(out_rgba, ctx->d_stage_rgba, npix * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_rgba, b_rgba, npix * 4));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -1191,17 +1175,18 @@ int rt_f64_div_sqrt_device(rt_context *ctx, const double *a, const double *b, in
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)n * sizeof(double);
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, 4 * bytes);
+    Stage st(ctx);
+    const size_t b_a = st.add(bytes), b_b = st.add(bytes), b_q = st.add(bytes), b_r = st.add(bytes);
+    int rc = st.commit();
     if (rc) return rc;
-    double *da = (double *)ctx->d_stage_fix, *db = da + n, *dq = db + n, *dr = dq + n;
-    RT_HIP(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, ctx->own_stream));
+    RT_HIP(st.up(b_a, a, bytes));
+    RT_HIP(st.up(b_b, b, bytes));
     hipLaunchKernelGGL(rt::f64_div_sqrt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream,
-                       (const double *)da, (const double *)db, (int)n, dq, dr);
+                       st.at<const double>(b_a), st.at<const double>(b_b), (int)n, st.at<double>(b_q), st.at<double>(b_r));
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(out_div, dq, bytes, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(out_sqrt, dr, bytes, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_div, b_q, bytes));
+    RT_HIP(st.down(out_sqrt, b_r, bytes));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -1211,15 +1196,16 @@ int rt_quantize_device(rt_context *ctx, const double *x, int32_t n, uint64_t *ou
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)n * sizeof(double);
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, 2 * bytes);
+    Stage st(ctx);
+    const size_t b_x = st.add(bytes), b_q = st.add(bytes);
+    int rc = st.commit();
     if (rc) return rc;
-    double *dx = (double *)ctx->d_stage_fix;
-    unsigned long long *dq = (unsigned long long *)(dx + n);
-    RT_HIP(hipMemcpyAsync(dx, x, bytes, hipMemcpyHostToDevice, ctx->own_stream));
-    hipLaunchKernelGGL(rt::quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, (const double *)dx, (int)n, dq);
+    RT_HIP(st.up(b_x, x, bytes));
+    hipLaunchKernelGGL(rt::quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.at<const double>(b_x), (int)n,
+                       st.at<unsigned long long>(b_q));
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(out, dq, bytes, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out, b_q, bytes));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -1229,16 +1215,17 @@ int rt_unit_accept_device(rt_context *ctx, const uint32_t *words, int32_t n, uin
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const size_t wb = (size_t)n * 3 * sizeof(uint32_t), ab = (size_t)n * sizeof(uint32_t), ub = (size_t)n * 4 * sizeof(double);
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, ub + wb + ab);
+    Stage st(ctx);
+    const size_t b_u = st.add(ub), b_w = st.add(wb), b_a = st.add(ab);
+    int rc = st.commit();
     if (rc) return rc;
-    double *du = (double *)ctx->d_stage_fix;
-    uint32_t *dw = (uint32_t *)(du + 4 * (size_t)n), *da = dw + 3 * (size_t)n;
-    RT_HIP(hipMemcpyAsync(dw, words, wb, hipMemcpyHostToDevice, ctx->own_stream));
-    hipLaunchKernelGGL(rt::unit_accept_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, (const uint32_t *)dw, (int)n, da, du);
+    RT_HIP(st.up(b_w, words, wb));
+    hipLaunchKernelGGL(rt::unit_accept_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.at<const uint32_t>(b_w), (int)n,
+                       st.at<uint32_t>(b_a), st.at<double>(b_u));
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(out_accept, da, ab, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(out_uniforms, du, ub, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_accept, b_a, ab));
+    RT_HIP(st.down(out_uniforms, b_u, ub));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -1271,22 +1258,20 @@ int rt_filter_tube_device(rt_context *ctx, const double *o, const double *d, con
     for (int c = 0; c < 32; ++c) col[c] = &spheres32[c];
     uint4 tile[64];
     tube_tile(col, rho, tile, out_bound);
-    const size_t in_b = 3072 + sizeof(tile), out_b = (64 * 32 * 2 + 64 * 9) * 4;
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, in_b + out_b);
+    const size_t h_b = 64 * 32 * 2 * 4, rows_b = 64 * 9 * 4;
+    Stage st(ctx);
+    const size_t b_o = st.add(1536), b_d = st.add(1536), b_tile = st.add(sizeof(tile)), b_h = st.add(h_b), b_rows = st.add(rows_b);
+    int rc = st.commit();
     if (rc) return rc;
-    char *base = (char *)ctx->d_stage_fix;
-    double *d_o = (double *)base, *d_d = d_o + 192;
-    uint4 *d_tile = (uint4 *)(base + 3072);
-    float *d_h = (float *)(base + in_b), *d_rows = d_h + 64 * 32 * 2;
-    RT_HIP(hipMemcpyAsync(d_o, o, 1536, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(d_d, d, 1536, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(d_tile, tile, sizeof(tile), hipMemcpyHostToDevice, ctx->own_stream));
+    RT_HIP(st.up(b_o, o, 1536));
+    RT_HIP(st.up(b_d, d, 1536));
+    RT_HIP(st.up(b_tile, tile, sizeof(tile)));
     hipLaunchKernelGGL(rt::tube_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
-                       (const double *)d_o, (const double *)d_d, (const uint4 *)d_tile, rho, d_h, d_rows);
+                       st.at<const double>(b_o), st.at<const double>(b_d), st.at<const uint4>(b_tile), rho, st.at<float>(b_h), st.at<float>(b_rows));
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(out_h, d_h, 64 * 32 * 2 * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(out_rows, d_rows, 64 * 9 * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_h, b_h, h_b));
+    RT_HIP(st.down(out_rows, b_rows, rows_b));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -1307,13 +1292,15 @@ int rt_philox_device(rt_context *ctx, const uint32_t ctr[4], const uint32_t key[
 {
     if (!ctx || !ctr || !key || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     RT_HIP(hipSetDevice(ctx->device));
-    int rc = ensure(&ctx->d_stage_rgba, &ctx->stage_rgba_bytes, 64);
+    Stage st(ctx);
+    const size_t b_out = st.add(16);
+    int rc = st.commit();
     if (rc) return rc;
     hipLaunchKernelGGL(rt::philox_kat_kernel, dim3(1), dim3(1), 0, ctx->own_stream,
-                       ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], (uint32_t *)ctx->d_stage_rgba);
+                       ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], st.at<uint32_t>(b_out));
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(out, ctx->d_stage_rgba, 16, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out, b_out, 16));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 

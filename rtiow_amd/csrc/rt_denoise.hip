@@ -288,44 +288,22 @@ int rt_denoise(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int6
     if (rc) return rc;
     if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
     RT_HIP(hipSetDevice(ctx->device));
-    // the staging buffers rt_destroy frees: d_stage_fix holds the radiance sums, the feature sums and the output, one after the other
-    // (256-byte steps); d_stage_sum the workspace; d_stage_list the counts
     const size_t npix = (size_t)width * height;
-    const size_t up = 255;
     const size_t fix_bytes = npix * 3 * sizeof(uint64_t), feat_bytes = npix * RT_FEATURE_WORDS * sizeof(uint64_t);
-    const size_t off_feat = (fix_bytes + up) & ~up, off_out = (off_feat + feat_bytes + up) & ~up;
-    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, off_out + fix_bytes);
-    if (rc) return rc;
-    rc = ensure(&ctx->d_stage_sum, &ctx->stage_sum_bytes, npix * rt::kDnWorkDoubles * sizeof(double));
-    if (rc) return rc;
-    if (count) {
-        rc = ensure(&ctx->d_stage_list, &ctx->stage_list_bytes, npix * sizeof(uint32_t));
-        if (rc) return rc;
-    }
-    char *base = (char *)ctx->d_stage_fix;
-    RT_HIP(hipMemcpyAsync(base, fix, fix_bytes, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(base + off_feat, feat, feat_bytes, hipMemcpyHostToDevice, ctx->own_stream));
-    if (count) RT_HIP(hipMemcpyAsync(ctx->d_stage_list, count, npix * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->own_stream));
-    // the kernels are timed with a pair of events of this call's own: the context's belong to its launch slots
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    RT_HIP(hipEventCreate(&e0));
-    hipError_t he = hipEventCreate(&e1);
-    if (he == hipSuccess) he = hipEventRecord(e0, ctx->own_stream);
-    if (he == hipSuccess) {
-        rc = rt_denoise_device(ctx, base, count ? ctx->d_stage_list : nullptr, spp, base + off_feat, feat_spp, width, height, dn, ctx->d_stage_sum,
-                               base + off_out, ctx->own_stream);
-        if (!rc) he = hipEventRecord(e1, ctx->own_stream);
-        if (!rc && he == hipSuccess) he = hipMemcpyAsync(out_fix, base + off_out, fix_bytes, hipMemcpyDeviceToHost, ctx->own_stream);
-        if (!rc && he == hipSuccess) he = hipStreamSynchronize(ctx->own_stream);
-        float ms = 0.0f;
-        if (!rc && he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-        if (!rc && he == hipSuccess && kernel_ms) *kernel_ms = ms;
-    }
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    if (he != hipSuccess) return fail(RT_ERR_HIP, "rt_denoise: %s", hipGetErrorString(he));
-    return RT_OK;
+    const size_t count_bytes = count ? npix * sizeof(uint32_t) : 0;
+    Stage st(ctx);
+    const size_t b_fix = st.add(fix_bytes), b_feat = st.add(feat_bytes), b_out = st.add(fix_bytes);
+    const size_t b_work = st.add(npix * rt::kDnWorkDoubles * sizeof(double)), b_count = st.add(count_bytes);
+    if ((rc = st.commit())) return rc;
+    RT_HIP(st.up(b_fix, fix, fix_bytes));
+    RT_HIP(st.up(b_feat, feat, feat_bytes));
+    if (count) RT_HIP(st.up(b_count, count, count_bytes));
+    return timed_section(ctx, "rt_denoise", kernel_ms,
+        [&] {
+            return rt_denoise_device(ctx, st.at(b_fix), count ? st.at(b_count) : nullptr, spp, st.at(b_feat), feat_spp, width, height, dn,
+                                     st.at(b_work), st.at(b_out), ctx->own_stream);
+        },
+        [&] { return st.down(out_fix, b_out, fix_bytes); });
 }
 
 // the library's own CPU statement of the filter: the very functions the kernels compile, one pixel after the other

@@ -389,36 +389,18 @@ int rt_render_features(rt_context *ctx, const rt_camera *cam, const rt_params *p
     if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)p->width * p->height;
-    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, npix * RT_FEATURE_WORDS * sizeof(uint64_t));
-    if (rc) return rc;
-    if (out_ids) {
-        rc = ensure(&ctx->d_stage_sum, &ctx->stage_sum_bytes, npix * sizeof(int32_t));
-        if (rc) return rc;
-    }
+    const size_t feat_bytes = npix * RT_FEATURE_WORDS * sizeof(uint64_t), ids_bytes = out_ids ? npix * sizeof(int32_t) : 0;
+    Stage st(ctx);
+    const size_t b_feat = st.add(feat_bytes), b_ids = st.add(ids_bytes);
+    if ((rc = st.commit())) return rc;
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    // the kernel is timed with a pair of events of this call's own: the context's belong to its launch slots
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    RT_HIP(hipEventCreate(&e0));
-    hipError_t he = hipEventCreate(&e1);
-    if (he == hipSuccess) he = hipEventRecord(e0, ctx->own_stream);
-    if (he == hipSuccess) {
-        rc = rt_render_features_device(ctx, cam, &q, ctx->d_stage_fix, out_ids ? ctx->d_stage_sum : nullptr, ctx->own_stream);
-        if (!rc) he = hipEventRecord(e1, ctx->own_stream);
-        if (!rc && he == hipSuccess)
-            he = hipMemcpyAsync(out_feat, ctx->d_stage_fix, npix * RT_FEATURE_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->own_stream);
-        if (!rc && he == hipSuccess && out_ids)
-            he = hipMemcpyAsync(out_ids, ctx->d_stage_sum, npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->own_stream);
-        if (!rc && he == hipSuccess) he = hipStreamSynchronize(ctx->own_stream);
-        float ms = 0.0f;
-        if (!rc && he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-        if (!rc && he == hipSuccess && kernel_ms) *kernel_ms = ms;
-    }
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    if (he != hipSuccess) return fail(RT_ERR_HIP, "rt_render_features: %s", hipGetErrorString(he));
-    return RT_OK;
+    return timed_section(ctx, "rt_render_features", kernel_ms,
+        [&] { return rt_render_features_device(ctx, cam, &q, st.at(b_feat), out_ids ? st.at(b_ids) : nullptr, ctx->own_stream); },
+        [&] {
+            const hipError_t he = st.down(out_feat, b_feat, feat_bytes);
+            return he == hipSuccess && out_ids ? st.down(out_ids, b_ids, ids_bytes) : he;
+        });
 }
 
 #ifdef RT_FEATURES_COUNT
@@ -442,9 +424,7 @@ int rt_features_to_f32_device(rt_context *ctx, const void *d_feat, int32_t width
     if (rows == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const long long npix = (long long)width * rows;
-    long long blocks = (npix + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(rt::features_to_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_v,
+    hipLaunchKernelGGL(rt::features_to_f32_kernel, dim3(grid_256(npix)), dim3(256), 0, (hipStream_t)stream_v,
                        (const unsigned long long *)d_feat, (float *)d_out, npix, (double)spp);
     RT_HIP(hipGetLastError());
     return RT_OK;
@@ -457,15 +437,14 @@ int rt_features_to_f32(rt_context *ctx, const uint64_t *feat, int32_t width, int
     if (rows == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const size_t count = (size_t)width * rows * RT_FEATURE_WORDS;
-    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, count * sizeof(uint64_t));
+    Stage st(ctx);
+    const size_t b_feat = st.add(count * sizeof(uint64_t)), b_out = st.add(count * sizeof(float));
+    if ((rc = st.commit())) return rc;
+    RT_HIP(st.up(b_feat, feat, count * sizeof(uint64_t)));
+    rc = rt_features_to_f32_device(ctx, st.at(b_feat), width, rows, spp, st.at(b_out), ctx->own_stream);
     if (rc) return rc;
-    rc = ensure(&ctx->d_stage_sum, &ctx->stage_sum_bytes, count * sizeof(float));
-    if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(ctx->d_stage_fix, feat, count * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->own_stream));
-    rc = rt_features_to_f32_device(ctx, ctx->d_stage_fix, width, rows, spp, ctx->d_stage_sum, ctx->own_stream);
-    if (rc) return rc;
-    RT_HIP(hipMemcpyAsync(out, ctx->d_stage_sum, count * sizeof(float), hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out, b_out, count * sizeof(float)));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 

@@ -4,6 +4,8 @@
 // "nothing to trace" exit, the kernel, the tail) and launch_render (one instantiation).  An entry point keeps its own validation, its
 // own few KParams fields and its kernel choice.  rt_api.hip defines the functions declared here (and every kernel but the frame-batch
 // instantiations of render_kernel, which rt_frames.hip owns, and the capped dense ones, which rt_dense.hip owns).
+// The host-buffer entry points share their plumbing here as well: StageLayout / Stage (one device arena per context, laid out per call),
+// timed_section (a pair of events of the call's own around its kernels) and grid_256.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,16 +66,13 @@ struct rt_context {
     bool launched = false;
     unsigned long long zero_depth_samples = 0;
     rt_stats last{};
-    // staging for the host-buffer entry points
-    void *d_stage_fix = nullptr; size_t stage_fix_bytes = 0;
-    void *d_stage_sum = nullptr; size_t stage_sum_bytes = 0;
-    void *d_stage_rgba = nullptr; size_t stage_rgba_bytes = 0;
+    // The staging arena of the host-buffer entry points (rt_host::Stage below): whatever the call in progress laid out in it, nothing
+    // between calls.  Device-form entry points never touch it.
+    void *d_arena = nullptr; size_t arena_bytes = 0;
     int blocks_per_cu = 0;     // 0 = occupancy query
-    // rt_select_pixels_device's scratch (noisy / active flags, the workgroups' counts) and rt_render_adaptive's frame state
+    // rt_select_pixels_device's scratch (noisy / active flags, the workgroups' counts): a device form's, on the caller's stream, so not
+    // in the arena -- rt_render_adaptive calls it while its own frame state lives there
     void *d_sel = nullptr; size_t sel_bytes = 0;
-    void *d_adapt = nullptr; size_t adapt_bytes = 0;
-    void *d_stage_list = nullptr; size_t stage_list_bytes = 0;   // rt_render_pixels: the list on the device
-    void *d_stage_cams = nullptr; size_t stage_cams_bytes = 0;   // rt_render_frames / rt_render_frames_rgba8: the cameras on the device
     int last_dense_body = 0;              // rt_last_dense_body (rtiow_hip_diag.h): 1 when the latest rt_render_device launch ran a capped-redraw kernel of rt_dense.hip, else 0
     int ring_min_spp = 0;                 // RTIOW_RING_MIN_SPP (diagnostic): spp per launch from which block sums are kept in LDS (0: the kernel's own minimum)
 };
@@ -83,6 +82,71 @@ namespace rt_host {
 int validate_params(const rt_params *p);
 int ensure(void **ptr, size_t *have, size_t need);
 void set_scene_params(const rt_context *ctx, rt::KParams &kp);
+
+// the grid of the element-wise kernels: 256 threads a block, at most 8 192 blocks (their grid-stride loops take the rest)
+inline unsigned grid_256(long long n)
+{
+    const long long blocks = (n + 255) / 256;
+    return (unsigned)(blocks > 8192 ? 8192 : blocks);
+}
+
+// Where the blocks of one host-form call lie in the arena: add(bytes) gives the byte offset of a new block.  Every block starts on a
+// 256-byte boundary (what hipMalloc gives a buffer of its own; the kernels' 16-byte loads rely on it), in the order declared; a block
+// of 0 bytes occupies nothing.  Pure arithmetic, no HIP call (tests/stage_layout_table.cpp tabulates it).
+struct StageLayout {
+    size_t total = 0;
+    size_t add(size_t bytes)
+    {
+        const size_t offset = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return offset;
+    }
+};
+
+// One host-form call's use of the arena.  THE RULE: device-form entry points never touch the arena; a host-form entry point lays its
+// blocks out once (add ... commit), before its first copy, and from then on calls only device forms -- so nothing can move or reuse a
+// block while the call's work is in flight on own_stream.  commit() grows the arena to this call's total with ensure(): never shrunk,
+// contents not preserved.  up / down / sync are hipMemcpyAsync / hipStreamSynchronize on ctx->own_stream.
+class Stage {
+public:
+    explicit Stage(rt_context *ctx) : ctx_(ctx) {}
+    size_t add(size_t bytes) { return layout_.add(bytes); }
+    int commit() { return ensure(&ctx_->d_arena, &ctx_->arena_bytes, layout_.total); }
+    template <class T = void> T *at(size_t block) const { return reinterpret_cast<T *>(static_cast<char *>(ctx_->d_arena) + block); }
+    hipError_t up(size_t block, const void *src, size_t bytes) const { return hipMemcpyAsync(at(block), src, bytes, hipMemcpyHostToDevice, ctx_->own_stream); }
+    hipError_t down(void *dst, size_t block, size_t bytes) const { return hipMemcpyAsync(dst, at(block), bytes, hipMemcpyDeviceToHost, ctx_->own_stream); }
+    hipError_t sync() const { return hipStreamSynchronize(ctx_->own_stream); }
+private:
+    rt_context *ctx_;
+    StageLayout layout_;
+};
+
+// Times what body() enqueues on ctx->own_stream with a pair of events of this call's own (the context's belong to its launch slots),
+// created here and destroyed on every path: the first is recorded before body -- after the caller's uploads --, the second after it and
+// before downloads(), so *kernel_ms (may be NULL) covers the kernels only; then the stream is synchronised.  body returns a device
+// form's code, which is passed on as it is with its own message; downloads returns a hipError_t; a HIP failure is "<name>: <error>".
+template <class Body, class Downloads>
+int timed_section(rt_context *ctx, const char *name, float *kernel_ms, Body body, Downloads downloads)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    RT_HIP(hipEventCreate(&e0));
+    int rc = RT_OK;
+    hipError_t he = hipEventCreate(&e1);
+    if (he == hipSuccess) he = hipEventRecord(e0, ctx->own_stream);
+    if (he == hipSuccess && !(rc = body())) {
+        he = hipEventRecord(e1, ctx->own_stream);
+        if (he == hipSuccess) he = downloads();
+        if (he == hipSuccess) he = hipStreamSynchronize(ctx->own_stream);
+        float ms = 0.0f;
+        if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
+        if (he == hipSuccess && kernel_ms) *kernel_ms = ms;
+    }
+    (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (rc) return rc;
+    if (he != hipSuccess) return fail(RT_ERR_HIP, "%s: %s", name, hipGetErrorString(he));
+    return RT_OK;
+}
 
 // the shipped kernel has a leaner instantiation for scenes whose tile grid (with the tiles every ray scans) has <= 64 cells
 inline bool small_grid_scene(const rt_context *ctx) { return ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64; }

@@ -146,51 +146,32 @@ int rt_temporal(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int
     if (rc) return rc;
     if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
     RT_HIP(hipSetDevice(ctx->device));
-    // the staging buffers rt_destroy frees.  d_stage_fix: the radiance sums, the feature sums and the output sums, one after the other
-    // (256-byte steps); d_stage_sum: the history's sums and feature sums; d_stage_list: the counts, the history's lengths, the output's
     const bool hist = prev_cam != nullptr;
     const size_t npix = (size_t)width * height;
-    const size_t up = 255;
     const size_t fix_bytes = npix * 3 * sizeof(uint64_t), feat_bytes = npix * RT_FEATURE_WORDS * sizeof(uint64_t), len_bytes = npix * sizeof(uint32_t);
-    const size_t off_feat = (fix_bytes + up) & ~up, off_out = (off_feat + feat_bytes + up) & ~up;
-    const size_t off_plen = (len_bytes + up) & ~up, off_olen = (off_plen + len_bytes + up) & ~up;
-    rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, off_out + fix_bytes);
-    if (rc) return rc;
-    rc = ensure(&ctx->d_stage_sum, &ctx->stage_sum_bytes, off_feat + feat_bytes);
-    if (rc) return rc;
-    rc = ensure(&ctx->d_stage_list, &ctx->stage_list_bytes, off_olen + len_bytes);
-    if (rc) return rc;
-    char *base = (char *)ctx->d_stage_fix, *hbase = (char *)ctx->d_stage_sum, *lbase = (char *)ctx->d_stage_list;
-    RT_HIP(hipMemcpyAsync(base, fix, fix_bytes, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(base + off_feat, feat, feat_bytes, hipMemcpyHostToDevice, ctx->own_stream));
-    if (count) RT_HIP(hipMemcpyAsync(lbase, count, len_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+    Stage st(ctx);
+    const size_t b_fix = st.add(fix_bytes), b_feat = st.add(feat_bytes), b_count = st.add(count ? len_bytes : 0);
+    const size_t b_pfix = st.add(hist ? fix_bytes : 0), b_pfeat = st.add(hist ? feat_bytes : 0), b_plen = st.add(hist ? len_bytes : 0);
+    const size_t b_out = st.add(fix_bytes), b_olen = st.add(len_bytes);
+    if ((rc = st.commit())) return rc;
+    RT_HIP(st.up(b_fix, fix, fix_bytes));
+    RT_HIP(st.up(b_feat, feat, feat_bytes));
+    if (count) RT_HIP(st.up(b_count, count, len_bytes));
     if (hist) {
-        RT_HIP(hipMemcpyAsync(hbase, prev_fix, fix_bytes, hipMemcpyHostToDevice, ctx->own_stream));
-        RT_HIP(hipMemcpyAsync(hbase + off_feat, prev_feat, feat_bytes, hipMemcpyHostToDevice, ctx->own_stream));
-        RT_HIP(hipMemcpyAsync(lbase + off_plen, prev_len, len_bytes, hipMemcpyHostToDevice, ctx->own_stream));
+        RT_HIP(st.up(b_pfix, prev_fix, fix_bytes));
+        RT_HIP(st.up(b_pfeat, prev_feat, feat_bytes));
+        RT_HIP(st.up(b_plen, prev_len, len_bytes));
     }
-    // the kernel is timed with a pair of events of this call's own: the context's belong to its launch slots
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    RT_HIP(hipEventCreate(&e0));
-    hipError_t he = hipEventCreate(&e1);
-    if (he == hipSuccess) he = hipEventRecord(e0, ctx->own_stream);
-    if (he == hipSuccess) {
-        rc = rt_temporal_device(ctx, base, count ? lbase : nullptr, spp, base + off_feat, feat_spp, cam, hist ? hbase : nullptr,
-                                hist ? lbase + off_plen : nullptr, hist ? hbase + off_feat : nullptr, prev_feat_spp, prev_cam, width, height, tp,
-                                base + off_out, lbase + off_olen, ctx->own_stream);
-        if (!rc) he = hipEventRecord(e1, ctx->own_stream);
-        if (!rc && he == hipSuccess) he = hipMemcpyAsync(out_fix, base + off_out, fix_bytes, hipMemcpyDeviceToHost, ctx->own_stream);
-        if (!rc && he == hipSuccess) he = hipMemcpyAsync(out_len, lbase + off_olen, len_bytes, hipMemcpyDeviceToHost, ctx->own_stream);
-        if (!rc && he == hipSuccess) he = hipStreamSynchronize(ctx->own_stream);
-        float ms = 0.0f;
-        if (!rc && he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-        if (!rc && he == hipSuccess && kernel_ms) *kernel_ms = ms;
-    }
-    (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    if (he != hipSuccess) return fail(RT_ERR_HIP, "rt_temporal: %s", hipGetErrorString(he));
-    return RT_OK;
+    return timed_section(ctx, "rt_temporal", kernel_ms,
+        [&] {
+            return rt_temporal_device(ctx, st.at(b_fix), count ? st.at(b_count) : nullptr, spp, st.at(b_feat), feat_spp, cam,
+                                      hist ? st.at(b_pfix) : nullptr, hist ? st.at(b_plen) : nullptr, hist ? st.at(b_pfeat) : nullptr, prev_feat_spp,
+                                      prev_cam, width, height, tp, st.at(b_out), st.at(b_olen), ctx->own_stream);
+        },
+        [&] {
+            const hipError_t he = st.down(out_fix, b_out, fix_bytes);
+            return he == hipSuccess ? st.down(out_len, b_olen, len_bytes) : he;
+        });
 }
 
 // the library's own CPU statement: the very functions the kernel compiles, one pixel after the other

@@ -7,20 +7,19 @@ int rt_filter_products_device(rt_context *ctx, const float *r1, const float *r2,
 {
     if (!ctx || !r1 || !r2 || !s || !out_hb || !out_q) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t in_f = 64 * 4 * 2 + 16 * 4, out_f = 64 * 16 * 2;
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, (in_f + out_f) * sizeof(float));
+    Stage st(ctx);
+    const size_t b_r1 = st.add(256 * 4), b_r2 = st.add(256 * 4), b_s = st.add(64 * 4), b_hb = st.add(1024 * 4), b_q = st.add(1024 * 4);
+    int rc = st.commit();
     if (rc) return rc;
-    float *d = (float *)ctx->d_stage_fix;
-    float *d_r1 = d, *d_r2 = d + 256, *d_s = d + 512, *d_hb = d + 576, *d_q = d + 576 + 1024;
-    RT_HIP(hipMemcpyAsync(d_r1, r1, 256 * 4, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(d_r2, r2, 256 * 4, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(d_s, s, 64 * 4, hipMemcpyHostToDevice, ctx->own_stream));
+    RT_HIP(st.up(b_r1, r1, 256 * 4));
+    RT_HIP(st.up(b_r2, r2, 256 * 4));
+    RT_HIP(st.up(b_s, s, 64 * 4));
     hipLaunchKernelGGL(rt::filter_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
-                       (const float *)d_r1, (const float *)d_r2, (const float *)d_s, (int)bf16x3, d_hb, d_q);
+                       st.at<const float>(b_r1), st.at<const float>(b_r2), st.at<const float>(b_s), (int)bf16x3, st.at<float>(b_hb), st.at<float>(b_q));
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(out_hb, d_hb, 1024 * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(out_q, d_q, 1024 * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_hb, b_hb, 1024 * 4));
+    RT_HIP(st.down(out_q, b_q, 1024 * 4));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -34,22 +33,20 @@ int rt_filter_lifted_device(rt_context *ctx, const double *o, const double *d, c
     memcpy(out_C, C, sizeof(C));
     uint4 tile[128];
     lifted_tile(C, tile);
-    const size_t in_b = 64 * 3 * 8 * 2 + sizeof(tile), out_b = (64 * 16 + 64 * rt::kLiftTerms) * 4;
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, in_b + out_b);
+    const size_t R_b = 64 * rt::kLiftTerms * 4;
+    Stage st(ctx);
+    const size_t b_o = st.add(1536), b_d = st.add(1536), b_tile = st.add(sizeof(tile)), b_D = st.add(1024 * 4), b_R = st.add(R_b);
+    int rc = st.commit();
     if (rc) return rc;
-    char *base = (char *)ctx->d_stage_fix;
-    double *d_o = (double *)base, *d_d = d_o + 192;
-    uint4 *d_tile = (uint4 *)(base + 3072);
-    float *d_D = (float *)(base + 3072 + sizeof(tile)), *d_R = d_D + 1024;
-    RT_HIP(hipMemcpyAsync(d_o, o, 1536, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(d_d, d, 1536, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(d_tile, tile, sizeof(tile), hipMemcpyHostToDevice, ctx->own_stream));
+    RT_HIP(st.up(b_o, o, 1536));
+    RT_HIP(st.up(b_d, d, 1536));
+    RT_HIP(st.up(b_tile, tile, sizeof(tile)));
     hipLaunchKernelGGL(rt::lifted_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
-                       (const double *)d_o, (const double *)d_d, (const uint4 *)d_tile, d_D, d_R);
+                       st.at<const double>(b_o), st.at<const double>(b_d), st.at<const uint4>(b_tile), st.at<float>(b_D), st.at<float>(b_R));
     RT_HIP(hipGetLastError());
-    RT_HIP(hipMemcpyAsync(out_D, d_D, 1024 * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(out_R, d_R, 64 * rt::kLiftTerms * 4, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_D, b_D, 1024 * 4));
+    RT_HIP(st.down(out_R, b_R, R_b));
+    RT_HIP(st.sync());
     return RT_OK;
 }
 
@@ -62,25 +59,24 @@ int rt_grid_cells_device(rt_context *ctx, const double *o, const double *d, int3
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const size_t ob = (size_t)n * 3 * sizeof(double), rb = (size_t)n * 5 * sizeof(int32_t), wb = out_runs ? (size_t)n * 126 * sizeof(int32_t) : 0;
-    int rc = ensure(&ctx->d_stage_fix, &ctx->stage_fix_bytes, 2 * ob + rb + wb + 16);
+    Stage st(ctx);
+    const size_t b_o = st.add(ob), b_d = st.add(ob), b_rect = st.add(rb), b_runs = st.add(wb), b_bad = st.add(sizeof(int32_t));
+    int rc = st.commit();
     if (rc) return rc;
-    char *base = (char *)ctx->d_stage_fix;
-    double *d_o = (double *)base, *d_d = (double *)(base + ob);
-    int32_t *d_rect = (int32_t *)(base + 2 * ob), *d_runs = out_runs ? (int32_t *)(base + 2 * ob + rb) : nullptr;
-    int32_t *d_bad = (int32_t *)(base + 2 * ob + rb + wb);
     rt::GridArgs ga;
     for (int k = 0; k < 8; ++k) ga.g[k] = grid[k];
-    RT_HIP(hipMemcpyAsync(d_o, o, ob, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(d_d, d, ob, hipMemcpyHostToDevice, ctx->own_stream));
-    RT_HIP(hipMemsetAsync(d_bad, 0, sizeof(int32_t), ctx->own_stream));
+    RT_HIP(st.up(b_o, o, ob));
+    RT_HIP(st.up(b_d, d, ob));
+    RT_HIP(hipMemsetAsync(st.at(b_bad), 0, sizeof(int32_t), ctx->own_stream));
     hipLaunchKernelGGL(rt::grid_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream,
-                       (const double *)d_o, (const double *)d_d, (int)n, ga, (int)grid_dim, scale, d_rect, d_runs, d_bad);
+                       st.at<const double>(b_o), st.at<const double>(b_d), (int)n, ga, (int)grid_dim, scale, st.at<int32_t>(b_rect),
+                       out_runs ? st.at<int32_t>(b_runs) : nullptr, st.at<int32_t>(b_bad));
     RT_HIP(hipGetLastError());
     int32_t bad = 0;
-    RT_HIP(hipMemcpyAsync(out_rect, d_rect, rb, hipMemcpyDeviceToHost, ctx->own_stream));
-    if (out_runs) RT_HIP(hipMemcpyAsync(out_runs, d_runs, wb, hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->own_stream));
-    RT_HIP(hipStreamSynchronize(ctx->own_stream));
+    RT_HIP(st.down(out_rect, b_rect, rb));
+    if (out_runs) RT_HIP(st.down(out_runs, b_runs, wb));
+    RT_HIP(st.down(&bad, b_bad, sizeof(int32_t)));
+    RT_HIP(st.sync());
     if (bad) return fail(RT_ERR_HIP, "rt_grid_cells_device: grid_cells with and without GridSeg disagree on some ray");
     return RT_OK;
 }

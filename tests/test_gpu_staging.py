@@ -1,0 +1,116 @@
+"""The staging arena on the GPU (rt_host::Stage, rt_host.hpp): ONE context goes through every host-buffer entry
+point, in sequence, at frame sizes that make its arena grow (7 x 5 -> 64 x 36), stay (-> 7 x 5 -> 33 x 17: smaller calls inside a larger
+arena, whose bytes are whatever the calls before left there) and be laid out differently from call to call.  Every result must equal,
+bit for bit, the same call on a context created for that call alone -- whose arena is fresh and exactly as large as the call needs.  An
+optional buffer that is absent right after a call that had it (rt_denoise without counts after one with, rt_temporal without history
+after one with) must not see the stale block: tests/test_stage_layout_host.py checks on the CPU that the denoise input used here gives
+different results with and without its counts.  The file asserts nothing about the arena itself, only about results, messages and times."""
+import ctypes as C
+import time
+
+import numpy as np
+import pytest
+
+import rtiow_amd as rt
+from rtiow_amd import _ffi
+from test_stage_layout_host import DENOISE_LEVELS, staging_inputs
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(7, 5), (64, 36), (7, 5), (33, 17)]
+ORDER = SIZES + SIZES[::-1]
+SPP, ADAPTIVE_SPP, ADAPTIVE_STEP = 2, 8, 2
+TIMED = ("features_ids", "features_no_ids", "denoise_count", "denoise_no_count", "temporal_history_count", "temporal_no_history")
+
+
+def render_fix_only(r, cam, p):
+    """rt_render with out_sum = NULL (Renderer.render always asks for the f32 sums)"""
+    out = np.zeros((p.height, p.width, 3), dtype=np.uint64)
+    c = cam.to_rt_camera()
+    _ffi.check(r._lib.rt_render(r._h, C.byref(c), C.byref(p), None, out.ctypes.data_as(C.c_void_p), None), "rt_render")
+    return out
+
+
+def calls(w, h):
+    """[(name, f(renderer) -> tuple of arrays [, kernel ms last for the names in TIMED])]: the sequence at one frame size."""
+    cam, cams = rt.book1_camera(w, h), rt.orbit_cameras(2, w, h)
+    p = rt.make_params(w, h, SPP, seed=1)
+    (fix, count, spp, feat, feat_spp), (pfix, plen, pfeat, pspp) = staging_inputs(w, h)
+    history = (pfix, plen, pfeat, pspp, rt.orbit_cameras(16, w, h)[1])
+    dn, tp = rt.make_denoise(levels=DENOISE_LEVELS), rt.make_temporal()
+    x = np.linspace(0.0, 3.0, w * h + 1)
+    return [
+        ("render_both", lambda r: r.render(cam, p)[:2]),
+        ("render_sum", lambda r: r.render(cam, p, want_fix=False)[:1]),
+        ("render_fix", lambda r: (render_fix_only(r, cam, p),)),
+        ("render_rgba8", lambda r: r.render_rgba8(cam, p)[:1]),
+        ("render_pixels", lambda r: r.render_pixels(cam, p, np.arange(0, w * h, 3))[:1]),
+        ("render_frames", lambda r: r.render_frames(cams, p, sample_stride=SPP)[:1]),
+        ("render_frames_rgba8_flip", lambda r: r.render_frames_rgba8(cams, p, flip=True)[:1]),
+        ("render_frames_rgba8", lambda r: r.render_frames_rgba8(cams, p, flip=False)[:1]),
+        ("features_ids", lambda r: r.render_features(cam, p)),
+        ("features_no_ids", lambda r: (lambda f, _, ms: (f, ms))(*r.render_features(cam, p, want_ids=False))),
+        ("features_to_f32", lambda r: (r.features_to_f32(feat, feat_spp),)),
+        ("denoise_count", lambda r: r.denoise(fix, spp, feat, feat_spp, dn, count=count)),
+        ("denoise_no_count", lambda r: r.denoise(fix, spp, feat, feat_spp, dn)),
+        ("temporal_history_count", lambda r: r.temporal(fix, spp, feat, feat_spp, cam, history, tp, count=count)),
+        ("temporal_no_history", lambda r: r.temporal(fix, spp, feat, feat_spp, cam, None, tp)),
+        ("resolve_rgba8", lambda r: (r.resolve_rgba8(fix, spp),)),
+        ("resolve_rgba8_counts", lambda r: (r.resolve_rgba8_counts(fix, count),)),
+        ("render_adaptive", lambda r: r.render_adaptive(cam, rt.make_params(w, h, ADAPTIVE_SPP, seed=1), rt.make_adaptive(ADAPTIVE_STEP, 0.05))[:3]),
+        ("quantize", lambda r: (r.quantize(x),)),
+        ("philox", lambda r: (np.array(r.philox((w, h, 3, 4), (5, 6)), dtype=np.uint64),)),
+    ]
+
+
+def arrays(name, result):
+    return result[:-1] if name in TIMED else result
+
+
+@pytest.fixture(scope="module")
+def fresh(book1_flat):
+    """(size, name) -> the call's arrays from a context created for that call alone; computed once per size."""
+    cache = {}
+
+    def get(size):
+        if size not in cache:
+            cache[size] = {}
+            for name, call in calls(*size):
+                with rt.Renderer(0) as r:
+                    r.upload_scene(book1_flat)
+                    cache[size][name] = arrays(name, call(r))
+                for a in cache[size][name]:
+                    a.setflags(write=False)
+        return cache[size]
+    return get
+
+
+def test_one_context_through_every_host_form(book1_flat, fresh):
+    bad = rt.make_denoise(levels=0)
+    with rt.Renderer(0) as r:
+        r.upload_scene(book1_flat)
+        for step, size in enumerate(ORDER):
+            want = fresh(size)
+            for name, call in calls(*size):
+                if name == "temporal_history_count":                  # a rejected call in mid-sequence: its usual message, and the next call correct
+                    (fix, _, spp, feat, feat_spp), _ = staging_inputs(*size)
+                    with pytest.raises(_ffi.RtiowHipError, match=r"denoise: levels must be 1\.\.\d+ \(is 0\)"):
+                        r.denoise(fix, spp, feat, feat_spp, bad)
+                t0 = time.perf_counter()
+                got = call(r)
+                wall_ms = (time.perf_counter() - t0) * 1e3
+                if name in TIMED:
+                    assert 0.0 < got[-1] < wall_ms, (step, size, name, got[-1], wall_ms)
+                got = arrays(name, got)
+                assert len(got) == len(want[name]) and all(g.dtype == v.dtype and np.array_equal(g, v) for g, v in zip(got, want[name])), (step, size, name)
+
+
+def test_the_sequence_tells_a_present_buffer_from_an_absent_one(fresh):
+    """(what makes the test above a test: the calls with and without the optional buffer differ on these inputs)"""
+    for size in set(SIZES):
+        want = fresh(size)
+        assert not np.array_equal(want["denoise_count"][0], want["denoise_no_count"][0])
+        assert not np.array_equal(want["temporal_history_count"][0], want["temporal_no_history"][0])
+        assert not np.array_equal(want["render_frames_rgba8_flip"][0], want["render_frames_rgba8"][0])
+    # ... and rt_render_adaptive went past its first round (selection and pixel-list passes beside its frame state in the arena)
+    assert any((fresh(size)["render_adaptive"][2] > 2 * ADAPTIVE_STEP).any() for size in set(SIZES))
