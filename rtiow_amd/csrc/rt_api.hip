@@ -89,101 +89,21 @@ int rt_host::ensure(void **ptr, size_t *have, size_t need)
 
 namespace {
 
-// K' of the scan filter for one sphere (rt_device.hpp):
-// |c|^2 (1-kappa) - r^2 (1+2 kappa) in f64, rounded DOWN to f32 (a smaller K' keeps more);
-// spheres outside f32's comfortable range get -inf: always kept.
-float filter_kprime(const rt_sphere &s, double KU)
-{
-    const double kappa = KU / (1.0 - KU);
-    const double r2 = s.radius * s.radius;
-    const double c2 = s.center[0] * s.center[0] + s.center[1] * s.center[1] + s.center[2] * s.center[2];
-    if (!(r2 > 1e-30) || !(c2 + r2 < 1e30)) return -INFINITY;
-    const double exact = c2 * (1.0 - kappa) - r2 * (1.0 + 2.0 * kappa);
-    float kp = (float)(exact - std::fabs(exact) * 1e-12);
-    if ((double)kp > exact) kp = std::nextafterf(kp, -INFINITY);
-    return kp;
-}
+// What rt_scene_core.hpp states on its own of the device side, pinned here: the one file that sees both.
+static_assert(rt_scene::kTablesVersion == 1, "the scene tables changed: bump kTablesVersion in rt_scene_core.hpp AND this assert, so that "
+              "this file -- a hashed kernel source (bench.py, kernel_source_sha) -- changes with them");
+static_assert(rt_scene::kTubeBasisErr == rt::kTubeBasisErr && rt_scene::kTubeCenterErr == rt::kTubeCenterErr && rt_scene::kFilterKU == rt::kFilterKU,
+              "rt_scene_core.hpp and rt_device.hpp disagree on a filter constant");
+static_assert(rt_scene::kMatStride == rt::kMatStride, "rt_scene_core.hpp and rt_kernels.hpp disagree on the material record");
+static_assert(sizeof(rt_scene::Word4) == sizeof(uint4) && offsetof(rt_scene::Word4, x) == offsetof(uint4, x) && offsetof(rt_scene::Word4, y) == offsetof(uint4, y) &&
+              offsetof(rt_scene::Word4, z) == offsetof(uint4, z) && offsetof(rt_scene::Word4, w) == offsetof(uint4, w), "Word4 must have uint4's layout");
 
-uint32_t host_bf16_rne(float x)
+// the two diagnostic knobs of the scene build, read at upload (rt_scene_core.hpp, tile_layout), and the context's scan mode
+rt_scene::Knobs scene_knobs(int scan_mode)
 {
-    uint32_t u; memcpy(&u, &x, 4);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-void host_split_bf16x3(float x, uint32_t p[3])
-{
-    auto back = [](uint32_t b) { uint32_t u = b << 16; float f; memcpy(&f, &u, 4); return f; };
-    p[0] = host_bf16_rne(x);
-    const float r1 = x - back(p[0]);
-    p[1] = host_bf16_rne(r1);
-    const float r2 = r1 - back(p[1]);
-    p[2] = host_bf16_rne(r2);
-}
-
-// ---- MODE 5 (tube filter, rt_device.hpp): per-sphere columns and bounds ----
-// Radius floor rho: the rows of a ray are scaled by rho / (rho + e_ray), which keeps the test sound for
-// every sphere whose bound is >= rho; smaller spheres are tested with the bound rho.  The lower quartile
-// of the radii leaves three quarters of the scene untouched and keeps the scaling close to 1.
-float tube_radius_floor(const rt_sphere *spheres, int n, const char *skip)
-{
-    std::vector<double> r;
-    for (int i = 0; i < n; ++i)
-        if (!(skip && skip[i]) && std::fabs(spheres[i].radius) > 1e-15 && std::fabs(spheres[i].radius) < 1e15)
-            r.push_back(std::fabs(spheres[i].radius));
-    if (r.empty()) return 1.0f;
-    std::nth_element(r.begin(), r.begin() + r.size() / 4, r.end());
-    return (float)r[r.size() / 4];
-}
-// bound of one sphere: max(R, rho), R = r (1+64u) + 640u |c| rounded up; +inf outside the analysed range
-float tube_bound(const rt_sphere &s, float rho)
-{
-    const double r = std::fabs(s.radius);
-    const double c2 = s.center[0] * s.center[0] + s.center[1] * s.center[1] + s.center[2] * s.center[2];
-    if (!(r * r > 1e-30) || !(c2 + r * r < 1e30)) return INFINITY;
-    const double R = r * (1.0 + (double)rt::kTubeBasisErr) + (double)rt::kTubeCenterErr * std::sqrt(c2);
-    float f = (float)(R * (1.0 + 1e-12));
-    if ((double)f < R) f = std::nextafterf(f, INFINITY);
-    return f > rho ? f : rho;
-}
-// sigma of one sphere: 2 (1 - 2^-6) / bound, rounded DOWN to a bf16 (rt_device.hpp: "kept" <=> |H| < 2);
-// 0 for a sphere outside the analysed range (bound = +inf): H = 0, always kept.  Returns the bf16 bit pattern.
-uint32_t tube_sigma_bits(float bound)
-{
-    if (!(bound < INFINITY)) return 0u;
-    const float f = (float)(2.0 * (1.0 - 1.0 / 64.0) / (double)bound);
-    uint32_t u; memcpy(&u, &f, 4);
-    return u >> 16;                                    // truncation = rounding down (sigma > 0)
-}
-// one tile of 32 columns: B operands [64] (lane l = column l&31, K-slots 8(l>>5)..+7) and, for the tests, the
-// bounds [32] the columns were scaled with.  `s[c] == nullptr`: a column no ray keeps (padding, always-exact list):
-// all zero but for K-slot 15, where 4 meets the 1 every ray carries there.
-void tube_tile(const rt_sphere *const s[32], float rho, uint4 out_b[64], float out_r[32])
-{
-    for (int c = 0; c < 32; ++c) {
-        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        out_r[c] = -1.0f;
-        if (s[c]) {
-            out_r[c] = tube_bound(*s[c], rho);
-            const uint32_t sg = tube_sigma_bits(out_r[c]);
-            uint32_t sgu = sg << 16; float sigma; memcpy(&sigma, &sgu, 4);
-            if (sg != 0u) {                            // (always-kept columns keep sigma = 0, c = 0: H = 0)
-                for (int i = 0; i < 3; ++i) {
-                    // two bf16 pieces of sigma * (the f64 centre): |sigma c - (y1 + y2)| <= 2^-16 |sigma c|
-                    const double ci = s[c]->center[i] * (double)sigma;
-                    const uint32_t y1 = host_bf16_rne((float)ci);
-                    uint32_t u1 = y1 << 16; float f1; memcpy(&f1, &u1, 4);
-                    const uint32_t y2 = host_bf16_rne((float)(ci - (double)f1));
-                    w[2 * i + 0] = y1 | (y2 << 16);
-                    w[2 * i + 1] = y1 | (y2 << 16);
-                }
-            }
-            w[6] = sg | (sg << 16);                    // sigma against the three exact pieces of t
-            w[7] = sg;
-        } else {
-            w[7] = 0x4080u << 16;                      // K-slot 15: 4.0 -> H = 4 for every ray: never kept
-        }
-        out_b[c] = make_uint4(w[0], w[1], w[2], w[3]);
-        out_b[32 + c] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
+    rt_scene::Knobs k;
+    k.scan_mode = scan_mode; k.no_grid = env_int("RTIOW_NO_GRID", 0); k.grid_dim = env_int("RTIOW_GRID_DIM", 0);
+    return k;
 }
 
 // releases every device table of the scene and marks the context as having none
@@ -213,20 +133,21 @@ int upload_table(T **dst, const T *src, size_t count)
 void rt_host::set_scene_params(const rt_context *ctx, rt::KParams &kp)
 {
     kp.filt = ctx->d_filt; kp.geo = ctx->d_geo; kp.mat = ctx->d_mat;
-    kp.n_tiles = ctx->n_tiles;
+    const rt_scene::Header &sc = ctx->scene;
+    kp.n_tiles = sc.n_tiles;
 #ifdef RTIOW_CROSSCHECK_MODES
     kp.x.bmat = ctx->x.d_bmat; kp.x.kpt = ctx->x.d_kpt;
     kp.x.bmat16 = ctx->x.d_bmat16; kp.x.kpt16 = ctx->x.d_kpt16; kp.x.bmatL = ctx->x.d_bmatL;
 #endif
-    kp.btube = ctx->d_btube; kp.tube_rho = ctx->tube_rho;
+    kp.btube = ctx->d_btube; kp.tube_rho = sc.tube_rho;
     kp.geo_slot = ctx->d_geo_slot; kp.slot_orig = ctx->d_slot_orig;
-    kp.n_global = ctx->n_global; kp.grid_dim = ctx->grid_dim;
+    kp.n_global = sc.n_global; kp.grid_dim = sc.grid_dim;
     kp.grid_rows = 0ull;
-    for (int k = 0; ctx->grid_dim > 0 && (k + 1) * ctx->grid_dim <= 64; ++k) kp.grid_rows |= 1ull << (k * ctx->grid_dim);
-    for (int k = 0; k < 8; ++k) kp.grid[k] = ctx->grid[k];
-    kp.scene_scale = ctx->scene_scale;
-    kp.n_always = ctx->n_always;
-    for (int e = 0; e < 8; ++e) kp.always_idx[e] = ctx->always_idx[e];
+    for (int k = 0; sc.grid_dim > 0 && (k + 1) * sc.grid_dim <= 64; ++k) kp.grid_rows |= 1ull << (k * sc.grid_dim);
+    for (int k = 0; k < 8; ++k) kp.grid[k] = sc.grid[k];
+    kp.scene_scale = sc.scene_scale;
+    kp.n_always = sc.n_always;
+    for (int e = 0; e < 8; ++e) kp.always_idx[e] = sc.always_idx[e];
 }
 
 void rt_host::fill_common_params(const rt_context *ctx, const rt_params *p, const LaunchPlan &plan, unsigned long long npix,
@@ -318,147 +239,6 @@ int validate_select(const void *fix, const void *half, const void *count, int32_
     if (n < 2 || n > kAdaptiveMaxSpp || (n & 1))
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_select_pixels: n = %d samples must be even (two halves) and in [2, %d]", n, kAdaptiveMaxSpp);
     return validate_adaptive(a);
-}
-
-// MODE 5 numbers candidates by table column in 26 bits (the pool word of rt_kernels.hpp is column << 6 | ray), and the
-// large-grid kernel keeps one 64-bit word per grid row in LDS with one lane per row (a run of columns is (1 << n) - 1 << x0).
-constexpr size_t kMaxColumns = (size_t)1 << 26;
-constexpr int kMaxGridDim = 63;
-
-// Where MODE 5 puts each sphere in its table of columns (tiles of 32), and the grid the kernel finds tiles with.
-struct TileLayout {
-    int grid_dim = 0, n_global = 0;
-    float grid[8] = {};             // rt_kernels.hpp, KParams::grid
-    float scale = 0.0f;             // sum over axes of the largest |coordinate| of the grid's box
-    std::vector<int> slot_of;       // column -> place in the caller's list, -1 = padding; a multiple of 32 long
-};
-
-// The spheres that skip the filter and are always tested exactly: much larger than the rest of the scene (the
-// ground), the filter would keep them for nearly every ray.  The choice only moves work, never results.
-std::vector<int> always_exact_list(const rt_sphere *spheres, int n)
-{
-    std::vector<int> out;
-    if (n <= 0) return out;
-    std::vector<double> radii(n);
-    for (int i = 0; i < n; ++i) radii[i] = std::fabs(spheres[i].radius);
-    std::vector<double> sorted = radii;
-    std::nth_element(sorted.begin(), sorted.begin() + n / 2, sorted.end());
-    const double big = 8.0 * sorted[n / 2];
-    std::vector<int> order;
-    for (int i = 0; i < n; ++i) if (radii[i] > big) order.push_back(i);
-    std::sort(order.begin(), order.end(), [&](int x, int y) { return radii[x] > radii[y]; });
-    for (size_t k = 0; k < order.size() && k < 8; ++k) out.push_back(order[k]);
-    return out;
-}
-
-TileLayout tile_layout(const rt_sphere *spheres, int n, const char *never)
-{
-    TileLayout L;
-    // ---- which column of the table holds which sphere --------------------------------------------------
-    // Spheres are put into tiles of 32 columns by WHERE they are, so that a wave only scans the tiles its rays
-    // can reach (rt_device.hpp, grid_cells): a square grid over the xz extent of the small spheres, one tile
-    // per cell (what does not fit a cell's 32 columns overflows), preceded by "global" tiles that every ray scans:
-    // spheres too large for a cell and the overflow.  The order of the columns decides nothing: ties are resolved
-    // on the spheres' positions in the caller's list (slot_orig).  Diagnostic knobs, read at upload:
-    // RTIOW_NO_GRID=1 (columns in list order, every tile scanned), RTIOW_GRID_DIM=G (cells per side).
-    std::vector<int> filtered;
-    for (int i = 0; i < n; ++i) if (!never[i]) filtered.push_back(i);
-    std::vector<int> &slot_of = L.slot_of;
-    L.grid_dim = 0; L.n_global = 0;
-    if (filtered.size() > 64 && !env_int("RTIOW_NO_GRID", 0)) {
-        std::vector<double> rr;
-        for (int i : filtered) rr.push_back(std::fabs(spheres[i].radius));
-        std::nth_element(rr.begin(), rr.begin() + rr.size() / 2, rr.end());
-        const double med = rr[rr.size() / 2];
-        double x0 = INFINITY, x1 = -INFINITY, z0 = INFINITY, z1 = -INFINITY;
-        for (int i : filtered) {
-            if (std::fabs(spheres[i].radius) > 3.0 * med) continue;
-            x0 = std::min(x0, spheres[i].center[0]); x1 = std::max(x1, spheres[i].center[0]);
-            z0 = std::min(z0, spheres[i].center[2]); z1 = std::max(z1, spheres[i].center[2]);
-        }
-        const double extent = std::max(x1 - x0, z1 - z0);
-        // The kernel finds cells with f32 arithmetic on (coordinate - x0) * (1 / cell): the grid exists only while that
-        // is meaningful -- a positive extent below 1e15 (coordinates up to 1e15 are legal, so extents up to 2e15 occur)
-        // whose cell size has a finite, normal f32 reciprocal.  extent == 0 (every small sphere above the same point):
-        // ONE cell of size 1.  Anything else: no grid, every tile scanned, columns in list order.
-        const bool one_cell = extent == 0.0;
-        const bool grid_ok = one_cell || (extent > 0.0 && extent < 1e15);
-        if (grid_ok) {
-        // cells(G): the spheres of each cell of a G x G grid, and what does not go into a cell
-        std::vector<std::vector<int>> cells;
-        std::vector<int> global;
-        double cell = 1.0;
-        auto assign = [&](int G, bool keep) -> int {       // -> number of global tiles
-            cell = one_cell ? 1.0 : extent / G;
-            std::vector<int> count((size_t)G * G, 0);
-            if (keep) { cells.assign((size_t)G * G, {}); global.clear(); }
-            size_t n_glob = 0;
-            for (int i : filtered) {
-                const double r = std::fabs(spheres[i].radius);
-                bool to_cell = !(r > 3.0 * med || r > 0.25 * cell);
-                size_t c = 0;
-                if (to_cell) {
-                    int ix = (int)std::floor((spheres[i].center[0] - x0) / cell), iz = (int)std::floor((spheres[i].center[2] - z0) / cell);
-                    ix = std::max(0, std::min(ix, G - 1)); iz = std::max(0, std::min(iz, G - 1));
-                    c = (size_t)iz * G + ix;
-                    to_cell = count[c] < 32;                        // the cell's tile is full: overflow
-                }
-                if (to_cell) { ++count[c]; if (keep) cells[c].push_back(i); }
-                else { ++n_glob; if (keep) global.push_back(i); }
-            }
-            return (int)((n_glob + 31) / 32);
-        };
-        // The grid's resolution: a wave scans the global tiles plus the cells its 64 rays touch, and rays are lines --
-        // the cells touched grow like G (measured on the book scenes: about 1.4 G - 1.6 of G x G), while coarse cells
-        // overflow into global tiles.  Take the G with the smallest  global tiles + 1.4 G.
-        int G = one_cell ? 1 : env_int("RTIOW_GRID_DIM", 0);
-        if (G <= 0) {
-            double best = INFINITY;
-            for (int g = 1; g <= kMaxGridDim; ++g) {
-                if ((double)g * g > (double)filtered.size()) break;
-                const int ng = assign(g, false);
-                if (ng > 48) continue;                              // (the kernel's list holds 126 tiles)
-                const double cost = ng + 1.4 * g;
-                if (cost < best) { best = cost; G = g; }
-            }
-        }
-        G = std::max(1, std::min(G, kMaxGridDim));          // (no G qualified: G = 1 will not either, and the grid stays off)
-        (void)assign(G, true);
-        double ylo = INFINITY, yhi = -INFINITY, pad = 0.0;
-        for (const std::vector<int> &c : cells)
-            for (int i : c) {
-                const double r = std::fabs(spheres[i].radius);
-                ylo = std::min(ylo, spheres[i].center[1] - r); yhi = std::max(yhi, spheres[i].center[1] + r);
-                pad = std::max(pad, r);
-            }
-        const int n_global = (int)((global.size() + 31) / 32);
-        const float inv_cell = (float)(1.0 / cell);
-        if (std::isnormal(inv_cell) && (size_t)(n_global + G * G) * 32 <= (size_t)kMaxColumns && n_global <= 48 && ylo <= yhi) {
-            L.grid_dim = G; L.n_global = n_global;
-            slot_of.assign((size_t)(n_global + G * G) * 32, -1);
-            for (size_t k = 0; k < global.size(); ++k) slot_of[k] = global[k];
-            for (size_t c = 0; c < cells.size(); ++c)
-                for (size_t k = 0; k < cells[c].size(); ++k) slot_of[((size_t)n_global + c) * 32 + k] = cells[c][k];
-            auto down = [](double v) { float f = (float)v; if ((double)f > v) f = std::nextafterf(f, -INFINITY); return f; };
-            auto up = [](double v) { float f = (float)v; if ((double)f < v) f = std::nextafterf(f, INFINITY); return f; };
-            L.grid[0] = down(x0); L.grid[1] = down(z0);
-            // the kernel turns a coordinate into a cell with THESE f32 values; rounding 1/cell either way only
-            // shifts cell borders by ~1e-7 cells, which the kernel's own margin (1e-3 cells) covers
-            L.grid[2] = inv_cell;
-            L.grid[3] = up(x0 + G * cell); L.grid[4] = up(z0 + G * cell);
-            L.grid[5] = down(ylo); L.grid[6] = up(yhi); L.grid[7] = up(pad);
-            // the kernel's error margins are relative to the size of what a ray can reach inside the grid's box
-            const double gs = std::max(std::fabs(x0), std::fabs(x0 + G * cell)) + pad + std::max(std::fabs(ylo), std::fabs(yhi)) +
-                              std::max(std::fabs(z0), std::fabs(z0 + G * cell)) + pad;
-            L.scale = (float)gs * 1.0001f;
-        }
-        }   // grid_ok
-    }
-    if (L.grid_dim == 0) {                              // no grid: the columns in list order, every tile scanned
-        slot_of.assign((size_t)((filtered.empty() ? 0 : filtered.back() + 1) + 31) / 32 * 32, -1);
-        for (int i : filtered) slot_of[i] = i;
-    }
-    return L;
 }
 
 #ifdef RTIOW_CROSSCHECK_MODES
@@ -609,92 +389,22 @@ int rt_upload_scene(rt_context *ctx, const rt_sphere *spheres, int32_t n)
     // the previous scene may still be in use by a launch on any stream
     RT_HIP(hipDeviceSynchronize());
     free_scene(ctx);
-    const size_t cnt = (size_t)(n > 0 ? n : 1);
-    std::vector<double> geo(cnt * 4, 0.0), mat(cnt * rt::kMatStride, 0.0);
-    for (int i = 0; i < n; ++i) {
-        const rt_sphere &s = spheres[i];
-        // exact records: radius*radius (sphere.rs:22) and 1.0/radius (vec3.rs:371-375 applied
-        // at sphere.rs:37) are per-sphere constants, each one f64 rounding, as in the reference
-        const double r2 = s.radius * s.radius;
-        geo[4 * i + 0] = s.center[0]; geo[4 * i + 1] = s.center[1]; geo[4 * i + 2] = s.center[2];
-        geo[4 * i + 3] = r2;
-        double *m = &mat[(size_t)rt::kMatStride * i];
-        m[0] = 1.0 / s.radius;
-        m[1] = s.param;
-        m[2] = s.albedo[0]; m[3] = s.albedo[1]; m[4] = s.albedo[2];
-        m[5] = (double)s.kind;
-        if (s.kind == RT_DIALECTRIC) {
-            // materials.rs:84-87 `1.0/self.ir` and :79 `((1-ri)/(1+ri)).powi(2)` for the two ratios a
-            // Dialectric can see (front: 1/ir, back: ir): the reference's own f64 operations, hoisted
-            m[6] = 1.0 / s.param;
-            double r0 = (1.0 - m[6]) / (1.0 + m[6]); m[7] = r0 * r0;
-            r0 = (1.0 - s.param) / (1.0 + s.param); m[8] = r0 * r0;
-            m[2] = 1.0; m[3] = 1.0; m[4] = 1.0;                                  // attenuation (1,1,1), :103
-        }
-    }
-    // the spheres that skip the filter (always_exact_list above)
-    ctx->n_always = 0;
-    for (int i : always_exact_list(spheres, n)) ctx->always_idx[ctx->n_always++] = i;
-    // tile count (tiles of 16 columns) rounded up to even, plus two spare tiles so the pipelined loops
-    // never branch on a table bound (padding columns are never kept)
-    const int n_tiles = 2 * ((n + 31) / 32);
-    ctx->n_tiles = n_tiles;
+    const rt_scene::Tables T = rt_scene::build(spheres, n, scene_knobs(ctx->scan_mode));
     int rc = RT_OK;
-    // Only the table of the scan mode this context runs is built (RTIOW_SCAN_MODE, read at rt_create).
-    if (ctx->scan_mode == 5) {      // the tube filter (shipped)
-        std::vector<char> never(n > 0 ? n : 1, 0);
-        for (int e = 0; e < ctx->n_always; ++e) never[ctx->always_idx[e]] = 1;
-        ctx->tube_rho = tube_radius_floor(spheres, n, never.data());
-        // which column of the table holds which sphere, and the grid the kernel finds tiles with
-        const TileLayout L = tile_layout(spheres, n, never.data());
-        const std::vector<int> &slot_of = L.slot_of;
-        ctx->grid_dim = L.grid_dim; ctx->n_global = L.n_global;
-        for (int k = 0; k < 8; ++k) ctx->grid[k] = L.grid[k];
-        ctx->scene_scale = L.scale;
-        const int n_tiles32 = (int)(slot_of.size() / 32);
-        ctx->n_tiles = 2 * n_tiles32;                          // (counted in 16-column units, as the other scan modes do)
-        const size_t ttc = (size_t)n_tiles32 + 1;              // one spare tile: the pipelined loop never branches on a table bound
-        std::vector<uint4> btube(ttc * 64);
-        std::vector<float> rtube(ttc * 32);
-        std::vector<double> geo_slot(ttc * 32 * 4, 0.0);
-        std::vector<uint32_t> slot_orig(ttc * 32, 0xFFFFFFFFu);
-        for (size_t t = 0; t < ttc; ++t) {
-            const rt_sphere *col[32];
-            for (int c = 0; c < 32; ++c) {
-                const size_t slot = 32 * t + c;
-                const int i = slot < slot_of.size() ? slot_of[slot] : -1;
-                col[c] = i >= 0 ? &spheres[i] : nullptr;
-                if (i >= 0) {
-                    slot_orig[slot] = (uint32_t)i;
-                    for (int k = 0; k < 4; ++k) geo_slot[4 * slot + k] = geo[4 * (size_t)i + k];
-                }
-            }
-            tube_tile(col, ctx->tube_rho, &btube[t * 64], &rtube[t * 32]);
-        }
-        if (!rc) rc = upload_table(&ctx->d_btube, btube.data(), btube.size());
-        if (!rc) rc = upload_table(&ctx->d_geo_slot, geo_slot.data(), geo_slot.size());
-        if (!rc) rc = upload_table(&ctx->d_slot_orig, slot_orig.data(), slot_orig.size());
-    }
-    // filter records of the f32 evaluation schemes (mode 1, and the sources of the mode 2/3 tables):
-    // centre rounded to f32 + K'
-    std::vector<float> filt(cnt * 4, 0.0f);
-    if (ctx->scan_mode >= 1 && ctx->scan_mode <= 3) {
-        for (int i = 0; i < n; ++i) {
-            const rt_sphere &s = spheres[i];
-            filt[4 * i + 0] = (float)s.center[0]; filt[4 * i + 1] = (float)s.center[1];
-            filt[4 * i + 2] = (float)s.center[2]; filt[4 * i + 3] = filter_kprime(s, (double)rt::kFilterKU);
-        }
-        if (ctx->scan_mode == 1 && !rc) rc = upload_table(&ctx->d_filt, filt.data(), filt.size());
-    }
+    if (!rc && !T.btube.empty()) rc = upload_table(&ctx->d_btube, reinterpret_cast<const uint4 *>(T.btube.data()), T.btube.size());
+    if (!rc && !T.geo_slot.empty()) rc = upload_table(&ctx->d_geo_slot, T.geo_slot.data(), T.geo_slot.size());
+    if (!rc && !T.slot_orig.empty()) rc = upload_table(&ctx->d_slot_orig, T.slot_orig.data(), T.slot_orig.size());
+    if (!rc && ctx->scan_mode == 1) rc = upload_table(&ctx->d_filt, T.filt.data(), T.filt.size());
 #ifdef RTIOW_CROSSCHECK_MODES
-    if (!rc) rc = xcheck_upload_tables(ctx, spheres, n, n_tiles, filt);
+    if (!rc) rc = xcheck_upload_tables(ctx, spheres, n, T);
 #endif
-    if (!rc) rc = upload_table(&ctx->d_geo, geo.data(), geo.size());
-    if (!rc) rc = upload_table(&ctx->d_mat, mat.data(), mat.size());
+    if (!rc) rc = upload_table(&ctx->d_geo, T.geo.data(), T.geo.size());
+    if (!rc) rc = upload_table(&ctx->d_mat, T.mat.data(), T.mat.size());
     if (rc) {                       // a failed upload leaves NO scene behind (message of the failing call kept)
         free_scene(ctx);
         return rc;
     }
+    ctx->scene = T.header;
     ctx->n_spheres = n;
     return RT_OK;
 }
@@ -1236,12 +946,8 @@ int rt_unit_accept_device(rt_context *ctx, const uint32_t *words, int32_t n, uin
 int rt_tube_tile_host(const rt_sphere *spheres32, uint32_t *out_words, float *out_bound, float *out_rho)
 {
     if (!spheres32 || !out_words || !out_bound || !out_rho) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    const float rho = tube_radius_floor(spheres32, 32, nullptr);
-    *out_rho = rho;
-    const rt_sphere *col[32];
-    for (int c = 0; c < 32; ++c) col[c] = &spheres32[c];
-    uint4 tile[64];
-    tube_tile(col, rho, tile, out_bound);
+    rt_scene::Word4 tile[64];
+    *out_rho = rt_scene::full_tile(spheres32, tile, out_bound);
     memcpy(out_words, tile, sizeof(tile));
     return RT_OK;
 }
@@ -1252,12 +958,8 @@ int rt_filter_tube_device(rt_context *ctx, const double *o, const double *d, con
     if (!ctx || !o || !d || !spheres32 || !out_h || !out_rows || !out_bound || !out_rho)
         return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     RT_HIP(hipSetDevice(ctx->device));
-    const float rho = tube_radius_floor(spheres32, 32, nullptr);
-    *out_rho = rho;
-    const rt_sphere *col[32];
-    for (int c = 0; c < 32; ++c) col[c] = &spheres32[c];
-    uint4 tile[64];
-    tube_tile(col, rho, tile, out_bound);
+    rt_scene::Word4 tile[64];
+    const float rho = *out_rho = rt_scene::full_tile(spheres32, tile, out_bound);
     const size_t h_b = 64 * 32 * 2 * 4, rows_b = 64 * 9 * 4;
     Stage st(ctx);
     const size_t b_o = st.add(1536), b_d = st.add(1536), b_tile = st.add(sizeof(tile)), b_h = st.add(h_b), b_rows = st.add(rows_b);
@@ -1278,9 +980,7 @@ int rt_filter_tube_device(rt_context *ctx, const double *o, const double *d, con
 int rt_tile_layout_host(const rt_sphere *spheres, int32_t n, int32_t out_dims[2], float out_grid[8], int32_t *out_slot_of, int32_t cap)
 {
     if (!spheres || n < 0 || n > RT_MAX_SPHERES || !out_dims || !out_grid || (!out_slot_of && cap > 0)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tile_layout_host: bad argument");
-    std::vector<char> never(n > 0 ? n : 1, 0);
-    for (int i : always_exact_list(spheres, n)) never[i] = 1;
-    const TileLayout L = tile_layout(spheres, n, never.data());
+    const rt_scene::TileLayout L = rt_scene::list_layout(spheres, n, scene_knobs(5));
     out_dims[0] = L.grid_dim; out_dims[1] = L.n_global;
     for (int k = 0; k < 8; ++k) out_grid[k] = L.grid[k];
     if ((size_t)cap < L.slot_of.size()) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tile_layout_host: out_slot_of too small");

@@ -6,11 +6,14 @@
 // instantiations of render_kernel, which rt_frames.hip owns, and the capped dense ones, which rt_dense.hip owns).
 // The host-buffer entry points share their plumbing here as well: StageLayout / Stage (one device arena per context, laid out per call),
 // timed_section (a pair of events of the call's own around its kernels) and grid_256.
+// rt_scene_core.hpp (included here for rt_context's Header) builds the scene's tables on the host, pure and HIP-free; a change to what a
+// table holds bumps its kTablesVersion and the static_assert on it in rt_api.hip, so that the hashed sources change with it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "rtiow_hip.h"
 #include "rt_kernels.hpp"
+#include "rt_scene_core.hpp"
 #ifdef RTIOW_CROSSCHECK_MODES
 #include "xcheck/rt_xcheck_host_ctx.hpp"
 #endif
@@ -34,19 +37,12 @@ struct rt_context {
     double *d_geo = nullptr;       // [n][4] exact geometry
     double *d_mat = nullptr;       // [n][kMatStride] exact materials
     uint4 *d_btube = nullptr;      // [tiles/2 + 1][64] MODE 5 (tube filter) B operands
-    float tube_rho = 1.0f;         // MODE 5 radius floor
     double *d_geo_slot = nullptr;  // MODE 5: [slots][4] exact geometry in table (slot) order
     uint32_t *d_slot_orig = nullptr;   // MODE 5: [slots] list index of the sphere in each column of the table
-    int n_global = 0;              // MODE 5: tiles [0, n_global) are scanned for every ray; the rest are grid cells
-    int grid_dim = 0;              // MODE 5: cells per side of the xz grid (0: no grid, every tile is scanned)
-    float grid[8] = {};            // x0, z0, 1/cell, x1, z1, y lo, y hi, pad (rt_device.hpp, grid_cells)
-    float scene_scale = 0.0f;      // MODE 5: KParams::scene_scale
+    rt_scene::Header scene;        // the scene's scalars: tile counts, the grid, the radius floor, the always-exact list (rt_scene_core.hpp)
 #ifdef RTIOW_CROSSCHECK_MODES
     XcheckScene x;                 // device tables of scan modes 2-4 (xcheck/rt_xcheck_host_ctx.hpp)
 #endif
-    int n_tiles = 0;
-    int n_always = 0;
-    int always_idx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int scan_mode = 5;             // filter: 5 tube bf16x2 MFMA (default, shipped), 1 VALU + scalar loads (cross-check);
                                    // with -DRTIOW_CROSSCHECK_MODES also 2 f32 MFMA, 3 bf16x3 MFMA, 4 lifted bf16x3 MFMA
     int n_spheres = -1;
@@ -149,7 +145,7 @@ int timed_section(rt_context *ctx, const char *name, float *kernel_ms, Body body
 }
 
 // the shipped kernel has a leaner instantiation for scenes whose tile grid (with the tiles every ray scans) has <= 64 cells
-inline bool small_grid_scene(const rt_context *ctx) { return ctx->grid_dim > 0 && ctx->n_global + ctx->grid_dim * ctx->grid_dim <= 64; }
+inline bool small_grid_scene(const rt_context *ctx) { return ctx->scene.grid_dim > 0 && ctx->scene.n_global + ctx->scene.grid_dim * ctx->scene.grid_dim <= 64; }
 
 // udiv_small (rt_kernels.hpp): numerators are < d + kItemBlockLarge (spp, width) or < 65536 (rows / tile_rows), so for
 // d < 2^15 the product x * d stays below 2^32 and floor(x * M / 2^32) is the exact quotient

@@ -55,7 +55,7 @@ int rt_grid_cells_device(rt_context *ctx, const double *o, const double *d, int3
                          int32_t *out_rect, int32_t *out_runs)
 {
     if (!ctx || !o || !d || !grid || !out_rect || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (grid_dim < 1 || grid_dim > kMaxGridDim) return fail(RT_ERR_INVALID_ARGUMENT, "grid_dim must be 1..%d", kMaxGridDim);
+    if (grid_dim < 1 || grid_dim > rt_scene::kMaxGridDim) return fail(RT_ERR_INVALID_ARGUMENT, "grid_dim must be 1..%d", rt_scene::kMaxGridDim);
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     const size_t ob = (size_t)n * 3 * sizeof(double), rb = (size_t)n * 5 * sizeof(int32_t), wb = out_runs ? (size_t)n * 126 * sizeof(int32_t) : 0;

@@ -1,6 +1,6 @@
 // rt_xcheck_host.inc -- part of the CROSS-CHECK build only (-DRTIOW_CROSSCHECK_MODES: tools/librtiow_hip_xcheck.so, a test artefact).
 // Host side of scan modes 2-4, the earlier matrix-pipe forms of the sphere-scan filter (DESIGN.md section 5.2); the product library carries
-// modes 0, 1 and 5 and never includes this file.  Included inside rt_api.hip's anonymous namespace (after filter_kprime, host_split_bf16x3, upload_table): the B operands of modes 2-4.
+// modes 0, 1 and 5 and never includes this file.  Included inside rt_api.hip's anonymous namespace (after upload_table; filter_kprime and host_split_bf16x3 are rt_scene_core.hpp's): the B operands of modes 2-4.
 // ---- MODE 4 (lifted form, rt_device.hpp): the per-sphere column C_0..C_10 and its 64 K-slots ----
 // `s == nullptr` (padding) or `never` (a sphere on the always-exact list): a column no ray keeps.
 // Every C_k is computed in f64 from the exact centre/radius and rounded once; C_10 = -K' is
@@ -10,7 +10,7 @@ void lifted_column(const rt_sphere *s, bool never, float C[rt::kLiftTerms])
     for (int k = 0; k < rt::kLiftTerms; ++k) C[k] = 0.0f;
     C[0] = 1.0f;
     if (!s || never) { C[10] = rt::kLiftNever; return; }
-    const float kp = filter_kprime(*s, (double)rt::kFilterKU_lifted);
+    const float kp = rt_scene::filter_kprime(*s, (double)rt::kFilterKU_lifted);
     if (!(kp > -INFINITY)) { C[10] = rt::kLiftAlways; return; }       // outside the analysed range
     const double cx = s->center[0], cy = s->center[1], cz = s->center[2];
     C[1] = (float)cx; C[2] = (float)cy; C[3] = (float)cz;
@@ -22,12 +22,12 @@ void lifted_column(const rt_sphere *s, bool never, float C[rt::kLiftTerms])
 void lifted_b_words(const float C[rt::kLiftTerms], uint32_t w[32])
 {
     for (int p = 0; p < 9; ++p) {
-        uint32_t y[3]; host_split_bf16x3(C[1 + p], y);
+        uint32_t y[3]; rt_scene::host_split_bf16x3(C[1 + p], y);
         w[3 * p + 0] = y[0] | (y[1] << 16);
         w[3 * p + 1] = y[0] | (y[2] << 16);
         w[3 * p + 2] = y[1] | (y[0] << 16);
     }
-    uint32_t k[3]; host_split_bf16x3(C[10], k);
+    uint32_t k[3]; rt_scene::host_split_bf16x3(C[10], k);
     w[27] = rt::kBf16One | (rt::kBf16One << 16);      // C_0 = 1 against the three pieces of R_0
     w[28] = rt::kBf16One | (k[0] << 16);
     w[29] = k[1] | (k[2] << 16);
@@ -48,9 +48,12 @@ void lifted_tile(const float C[16][rt::kLiftTerms], uint4 out[128])
 
 
 // the device tables of the scan mode the context runs (2: f32 B operand + K'; 3: three-piece bf16 B operand + K' at the larger KU; 4: lifted form)
-int xcheck_upload_tables(rt_context *ctx, const rt_sphere *spheres, int n, int n_tiles, const std::vector<float> &filt)
+int xcheck_upload_tables(rt_context *ctx, const rt_sphere *spheres, int n, const rt_scene::Tables &T)
 {
     int rc = RT_OK;
+    const std::vector<float> &filt = T.filt;
+    const rt_scene::Header &H = T.header;
+    const int n_tiles = H.n_tiles;
     const size_t tcnt = (size_t)n_tiles + 2;
     if (ctx->scan_mode == 2 || ctx->scan_mode == 3) {
         std::vector<float> bmat(tcnt * 64, 0.0f), kpt(tcnt * 16, NAN);
@@ -62,7 +65,7 @@ int xcheck_upload_tables(rt_context *ctx, const rt_sphere *spheres, int n, int n
                 bmat[(size_t)t * 64 + l] = v;
             }
         for (int i = 0; i < n; ++i) kpt[i] = filt[4 * i + 3];      // padding stays NaN: never kept
-        for (int e = 0; e < ctx->n_always; ++e) kpt[ctx->always_idx[e]] = NAN;
+        for (int e = 0; e < H.n_always; ++e) kpt[H.always_idx[e]] = NAN;
         if (ctx->scan_mode == 2) {
             if (!rc) rc = upload_table(&ctx->x.d_bmat, bmat.data(), bmat.size());
             if (!rc) rc = upload_table(&ctx->x.d_kpt, kpt.data(), kpt.size());
@@ -72,24 +75,23 @@ int xcheck_upload_tables(rt_context *ctx, const rt_sphere *spheres, int n, int n
             std::vector<uint4> bmat16(tcnt * 64, make_uint4(0u, 0u, 0u, 0u));
             std::vector<float> kpt16(tcnt * 16, NAN);
             for (size_t e = 0; e < bmat.size(); ++e) {
-                uint32_t y[3]; host_split_bf16x3(bmat[e], y);
+                uint32_t y[3]; rt_scene::host_split_bf16x3(bmat[e], y);
                 bmat16[e] = make_uint4(y[0] | (y[1] << 16), y[0] | (y[2] << 16), y[1] | (y[0] << 16), y[2] | (y[1] << 16));
             }
-            for (int i = 0; i < n; ++i) kpt16[i] = filter_kprime(spheres[i], (double)rt::kFilterKU_bf16x3);
-            for (int e = 0; e < ctx->n_always; ++e) kpt16[ctx->always_idx[e]] = NAN;
+            for (int i = 0; i < n; ++i) kpt16[i] = rt_scene::filter_kprime(spheres[i], (double)rt::kFilterKU_bf16x3);
+            for (int e = 0; e < H.n_always; ++e) kpt16[H.always_idx[e]] = NAN;
             if (!rc) rc = upload_table(&ctx->x.d_bmat16, bmat16.data(), bmat16.size());
             if (!rc) rc = upload_table(&ctx->x.d_kpt16, kpt16.data(), kpt16.size());
         }
     }
     if (ctx->scan_mode == 4) {
         std::vector<uint4> bmatL(tcnt * 128);
-        std::vector<char> never(n > 0 ? n : 1, 0);
-        for (int e = 0; e < ctx->n_always; ++e) never[ctx->always_idx[e]] = 1;
+        const int *always_end = H.always_idx + H.n_always;
         for (size_t t = 0; t < tcnt; ++t) {
             float C[16][rt::kLiftTerms];
             for (int c = 0; c < 16; ++c) {
                 const long i = 16 * (long)t + c;
-                lifted_column(i < n ? &spheres[i] : nullptr, i < n && never[i], C[c]);
+                lifted_column(i < n ? &spheres[i] : nullptr, i < n && std::find(H.always_idx, always_end, (int)i) != always_end, C[c]);
             }
             lifted_tile(C, &bmatL[t * 128]);
         }
