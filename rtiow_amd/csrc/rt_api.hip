@@ -158,6 +158,7 @@ void rt_host::fill_common_params(const rt_context *ctx, const rt_params *p, cons
     kp.spp = p->spp; kp.sample_begin = p->sample_begin; kp.max_depth = p->max_depth;
     kp.t_min = p->t_min;
     kp.k0 = (uint32_t)p->seed; kp.k1 = (uint32_t)(p->seed >> 32);
+    rt_keys::fill_round_keys(kp.k0, kp.k1, kp.round_keys);          // (what the capped dense kernels read instead of rebuilding it from k0, k1)
     kp.tile_rows = 1; kp.shard_index = 0; kp.shard_count = 1;
     kp.n_spheres = ctx->n_spheres;
     kp.npix = (uint32_t)npix; kp.total_items = total_items; kp.n_blocks = (uint32_t)n_blocks;

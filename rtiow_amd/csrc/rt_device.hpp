@@ -83,6 +83,42 @@ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c
     return o;
 }
 
+// The same block with the round keys READ, not rebuilt: `keys` is the launch's table of rt_round_keys.hpp (dword 2 r, 2 r + 1: the key pair of
+// round r), which the host fills once per launch and the capped dense kernels find in their kernel-argument block (KParams::round_keys): constant
+// address space, scalar loads only, nothing written.  Four dwords -- two rounds -- per load, two loads ahead: the quads of rounds 0-3 are asked for
+// before the first multiply, the quad of rounds r + 2, r + 3 before round r (r = 2, 4, 6; the empty asm ties its address to a value of the round
+// before, so the load can neither rise to the top nor sink to its use), and every load has two rounds of multiplies to arrive under.  At most eight
+// key SGPRs are live: twelve and eight in two batches cost six more parked scalars per pass (v_writelane / v_readlane) than they saved, twenty at
+// once many more.  The asm on the pointer is what the asm on the key is above: without it the loads are loop-invariant, and the compiler keeps
+// twenty SGPRs alive across the bounce loop and spills others.  18 s_add_i32 with a 32-bit literal per block become five s_load_dwordx4.
+typedef const uint32_t __attribute__((address_space(4))) *RoundKeyTable;
+__device__ __forceinline__ U4 philox4x32_10_table(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, RoundKeyTable keys)
+{
+    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef u32x4 __attribute__((aligned(4))) u32x4_any;                // (a scalar load needs dword alignment only, whatever its width)
+    typedef const u32x4_any __attribute__((address_space(4))) *Quad;
+    asm volatile("" : "+s"(keys));
+    u32x4 q[5];
+    q[0] = ((Quad)keys)[0]; q[1] = ((Quad)keys)[1];
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r >= 2 && r <= 6 && !(r & 1)) {         // before rounds 2, 4, 6: the quad of rounds r + 2, r + 3
+            RoundKeyTable late = keys;
+            asm volatile("" : "+s"(late), "+v"(c0));
+            q[r / 2 + 1] = ((Quad)late)[r / 2 + 1];
+        }
+        const uint64_t p0 = (uint64_t)M0 * c0;
+        const uint64_t p1 = (uint64_t)M1 * c2;
+        const u32x4 k = q[r / 2];
+        const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, (r & 1) ? k.z : k.x, 0x96);
+        const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, (r & 1) ? k.w : k.y, 0x96);
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    }
+    U4 o; o.x = c0; o.y = c1; o.z = c2; o.w = c3;
+    return o;
+}
+
 // word -> draw from [0,1) (gen::<f64>()): u = w * 2^-32, all 32 bits of the word (exact in f64).  (Rounds 1-4: (w >> 8) * 2^-24,
 // a leftover of the abandoned f32 plan; the shift is gone and the lattice is 256 times finer for the same Philox work.)
 __device__ __forceinline__ double u01(uint32_t w) { return (double)w * (1.0 / 4294967296.0); }

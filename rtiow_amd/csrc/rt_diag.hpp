@@ -34,6 +34,7 @@
 #define RT_COUNT_ENUM_TRIP(m) RT_DIAG_NOTHING           /* ... as the enumeration's trips and pushed candidates (-DRT_COUNT_ENUM) */
 #define RT_COUNT_REDRAW_LANES(ok) RT_DIAG_NOTHING       /* ... as the lanes that draw a unit-sphere sample and those that fail try 0 (-DRT_COUNT_REDRAW) */
 #define RT_COUNT_CAPPED_PARKS(n) RT_DIAG_NOTHING        /* ... counter 1 as the capped body's parked lanes, counter 6 the redraw blocks of either body (-DRT_COUNT_PARKS) */
+#define RT_COUNT_TILE_GROUPS(g) RT_DIAG_NOTHING         /* ... counter 1 as the tiles every group scans (mask 0xF), counter 6 the looks of the other tiles (-DRT_COUNT_MASKS) */
 #define RT_LDS(site, BYTES, ATOMIC, LOAD64, ptr, active) RT_DIAG_NOTHING
 #define RT_LDS_N(site, n, BYTES, ATOMIC, LOAD64, byte_addr, active) RT_DIAG_NOTHING
 #define RT_LDS_QUEUE_READS(take, entry) RT_DIAG_NOTHING
@@ -90,6 +91,9 @@
 #undef RT_COUNT_MAIN
 #define RT_COUNT_CAPPED_PARKS(n) RT_COUNT_N(1, n)
 #define RT_COUNT_MAIN(k) do { if ((k) == 6) RT_COUNT(k); } while (0)
+#elif defined(RT_COUNT_MASKS)
+#undef RT_COUNT_TILE_GROUPS
+#define RT_COUNT_TILE_GROUPS(g) do { if ((g) == 0xFu) RT_COUNT(1); else RT_COUNT_N(6, __builtin_popcount(g)); } while (0)
 #else
 #undef RT_COUNT_MAIN
 #define RT_COUNT_MAIN(k) RT_COUNT(k)

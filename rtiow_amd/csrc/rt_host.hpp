@@ -14,6 +14,7 @@
 #include "rtiow_hip.h"
 #include "rt_kernels.hpp"
 #include "rt_scene_core.hpp"
+#include "rt_round_keys.hpp"
 #ifdef RTIOW_CROSSCHECK_MODES
 #include "xcheck/rt_xcheck_host_ctx.hpp"
 #endif

@@ -36,6 +36,7 @@
 #include "xcheck/rt_xcheck_params.hpp"
 #endif
 #include <type_traits>
+#include <cstddef>
 
 #ifndef RT_GROUP_SKIP
 #define RT_GROUP_SKIP 1     // MODE 5: a 16-ray group skips the tiles none of its rays can reach (0: every group scans the wave's whole list)
@@ -101,6 +102,10 @@ struct KParams {
     uint32_t frame_blocks;     // work blocks per frame = ceil(frame_items / block_items): no block straddles two frames
     uint32_t frame_pix;        // width * height: virtual pixel f * frame_pix + g is pixel g of frame f
     int32_t sample_stride;     // frame f renders the samples [sample_begin + f * sample_stride, ... + spp)
+    // the capped dense kernels (ITEMS = kItemBlockDense / kItemBlockDenseLarge): the ten round-key pairs of (k0, k1), filled by the host (rt_round_keys.hpp)
+    // and read where they lie, in the kernel-argument block, with scalar loads (rt_device.hpp, philox4x32_10_table).  The last member, like pix_list and
+    // cams before it: the offsets of everything else stay where they were.  No other kernel reads it.
+    uint32_t round_keys[20];
 };
 
 constexpr int RT_KIND_LAMBERTIAN = 0, RT_KIND_METAL = 1, RT_KIND_DIALECTRIC = 2;
@@ -283,6 +288,15 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
         (const float __attribute__((address_space(4))) *)(uintptr_t)P.filt;
     const double *__restrict__ geo = P.geo;
     const double *__restrict__ mat = P.mat;
+    // one Philox block of this launch's key.  The capped dense kernels READ the ten round keys (P.round_keys, scalar loads from the kernel-argument
+    // block -- P is the kernel's first argument, at offset 0 of it: rt_device.hpp, philox4x32_10_table); every other instantiation rebuilds them from
+    // P.k0, P.k1 as before, and compiles to the code it had.
+    auto philox = [&](uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) -> U4 {
+        if constexpr (CAPPED) {
+            const char __attribute__((address_space(4))) *args = (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+            return philox4x32_10_table(c0, c1, c2, c3, (RoundKeyTable)(args + offsetof(KParams, round_keys)));
+        } else return philox4x32_10(c0, c1, c2, c3, P.k0, P.k1);
+    };
     const int n = P.n_spheres;
     const double t_min = P.t_min;
     const double wm1 = (double)(P.width - 1);
@@ -453,7 +467,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     g_pix = j * (uint32_t)P.width + i;
                     }
                     const uint32_t g_s = (FRAMES ? blk_sbase : (uint32_t)P.sample_begin) + (s_rel - dq * (uint32_t)P.spp);
-                    U4 w = philox4x32_10(g_pix, g_s, 0u, 0u, P.k0, P.k1);
+                    U4 w = philox(g_pix, g_s, 0u, 0u);
                     uint32_t g_ev = 1u;
                     const double u = ((double)i + (U53 ? u01_53(w.x, w.y) : u01(w.x))) / wm1;     // main.rs:131
                     const double v = ((double)j + (U53 ? u01_53(w.z, w.w) : u01(w.y))) / hm1;     // main.rs:132
@@ -467,13 +481,13 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                         // written.  The queue keeps no lens words: the lane that takes the sample recomputes block g_ev - 1.
                         double lx, ly;
                         do {
-                            w = philox4x32_10(g_pix, g_s, g_ev, 0u, P.k0, P.k1);
+                            w = philox(g_pix, g_s, g_ev, 0u);
                             g_ev++;
                             lx = u11_53(w.x, w.y); ly = u11_53(w.z, w.w);
                         } while (!(lx * lx + ly * ly < 1.0));
                     } else
                     while (!unit_disk_accepts(wx, wy)) {
-                        w = philox4x32_10(g_pix, g_s, g_ev, 0u, P.k0, P.k1);
+                        w = philox(g_pix, g_s, g_ev, 0u);
                         g_ev++;
                         wx = w.x; wy = w.y;
                         if (!unit_disk_accepts(wx, wy)) { wx = w.z; wy = w.w; }
@@ -515,7 +529,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
         if (fresh) {                                                // camera.rs:47-54
             double lx = u11(lens_wx), ly = u11(lens_wy);
             if constexpr (U53) {                                    // the accepted unit-disk try is the last block the start drew
-                const U4 lb = philox4x32_10(pix_global, (uint32_t)s, ev - 1u, 0u, P.k0, P.k1);
+                const U4 lb = philox(pix_global, (uint32_t)s, ev - 1u, 0u);
                 lx = u11_53(lb.x, lb.y); ly = u11_53(lb.z, lb.w);
             }
             if constexpr (!FRAMES) {
@@ -849,6 +863,12 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 // 2.7-4.9 SIMD cycles where max/min-trees took 14 of 4.3-5.4 (tools/valu_cost_table.hip: v_max/v_min*
                 // cost 4.3-5.4 cycles at four waves per SIMD, v_or/v_bitop3 2.7-3.1).
                 auto keeps = [](uint32_t x) -> bool { return __builtin_fabsf(__uint_as_float(x)) < kTubeKeepBelow; };
+                static_assert(kTubeKeepBelow == 2.0f, "the recording path's asm spells the bound as the inline constant 2.0");
+#if defined(RT_LDS_CONFLICTS)
+                constexpr bool kAsmRecord = false;              // (the conflict model reads each step's address and mask)
+#else
+                constexpr bool kAsmRecord = CAPPED;
+#endif
                 auto look_tube = [&](int G, const f32x16 &acc, int wrel) {
                     // X_bb: the AND over the four rays 8 bb + j of this lane; the wave-level branch tests X_0 & X_1
                     uint32_t X[2];
@@ -874,6 +894,37 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                         for (int bb = 0; bb < 2; ++bb) {
                             if (kh[bb] != 0ull) {
                                 RT_COUNT(4);
+                                if constexpr (kAsmRecord) {
+                                    // The capped dense kernels: ONE scalar instruction per ray step, not two.  v_cmpx narrows exec to the lanes that keep
+                                    // (it replaces the v_cmp; s_and_saveexec is gone), the ds_or runs under it, and exec comes back from the half's saved
+                                    // mask with one s_mov -- which is also what lets the next compare see the half's full mask.  5 scalar instructions
+                                    // per half where the compiler's form has 8; written as one asm block so that no step gets an exec-empty branch.
+                                    // (LDS operations of a wave complete in order: the walk's later reads of these words see them.)
+                                    typedef __attribute__((address_space(3))) unsigned int *LdsWord;
+                                    const uint32_t at = (uint32_t)(uintptr_t)(LdsWord)row;             // (the steps' words: immediate offsets, as the compiler's form has them)
+                                    uint32_t xs[4];
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) xs[j] = __float_as_uint(acc[8 * bb + j]) | __float_as_uint(acc[8 * bb + 4 + j]);
+                                    unsigned long long half_exec;
+                                    asm volatile("s_mov_b64 %[sv], exec\n\t"
+                                                 "v_cmpx_lt_f32_e64 vcc, |%[x0]|, 2.0\n\t"
+                                                 "ds_or_b32 %[at], %[bit] offset:%[o0]\n\t"
+                                                 "s_mov_b64 exec, %[sv]\n\t"
+                                                 "v_cmpx_lt_f32_e64 vcc, |%[x1]|, 2.0\n\t"
+                                                 "ds_or_b32 %[at], %[bit] offset:%[o1]\n\t"
+                                                 "s_mov_b64 exec, %[sv]\n\t"
+                                                 "v_cmpx_lt_f32_e64 vcc, |%[x2]|, 2.0\n\t"
+                                                 "ds_or_b32 %[at], %[bit] offset:%[o2]\n\t"
+                                                 "s_mov_b64 exec, %[sv]\n\t"
+                                                 "v_cmpx_lt_f32_e64 vcc, |%[x3]|, 2.0\n\t"
+                                                 "ds_or_b32 %[at], %[bit] offset:%[o3]\n\t"
+                                                 "s_mov_b64 exec, %[sv]"
+                                                 : [sv] "=&s"(half_exec)
+                                                 : [x0] "v"(xs[0]), [x1] "v"(xs[1]), [x2] "v"(xs[2]), [x3] "v"(xs[3]), [at] "v"(at), [bit] "v"(bit),
+                                                   [o0] "i"(4 * (16 * G + 8 * bb)), [o1] "i"(4 * (16 * G + 8 * bb + 1)), [o2] "i"(4 * (16 * G + 8 * bb + 2)),
+                                                   [o3] "i"(4 * (16 * G + 8 * bb + 3))
+                                                 : "vcc", "memory");
+                                } else
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) {
                                     RT_LDS(0, 4, true, false, &row[16 * G + 8 * bb + j],
@@ -1043,6 +1094,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     auto do_tile = [&](int w, const bf16x8 &b, unsigned groups) {
                         RT_COUNT(7);
                         RT_COUNT_N(2, __builtin_popcount(groups));      // (counter 2: matrix instructions + looks executed)
+                        RT_COUNT_TILE_GROUPS(groups);
 #if RT_GROUP_SKIP
                         if (groups != 0xFu) {
                             // some groups cannot reach this tile (none of their rays' footprints holds its cell): only the others
@@ -1073,8 +1125,25 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     };
                     {
                         // B operands ping-pong between two register sets, each fetched a tile ahead.
-                        bf16x8 bp = load_b(tile_at(0)), bq;
+                        bf16x8 bp, bq;
                         int w = 0;
+                        if constexpr (CAPPED) {
+                            // (the capped dense kernels: a list entry is read ONCE -- its tile when the B operand is asked for, its groups a tile later from
+                            //  the same scalar -- not once for each: one v_readlane and its index less per tile)
+                            auto entry_at = [&](int j) -> unsigned { return (unsigned)__builtin_amdgcn_readlane(listv, j); };
+                            unsigned ep = entry_at(0), eq;
+                            bp = load_b((int)(ep & 0x0FFFFFFFu));
+                            for (; w + 1 < nwords; w += 2) {
+                                eq = entry_at(w + 1);
+                                bq = load_b((int)(eq & 0x0FFFFFFFu));
+                                do_tile(w, bp, ep >> 28);
+                                ep = entry_at(w + 2);
+                                bp = load_b((int)(ep & 0x0FFFFFFFu));
+                                do_tile(w + 1, bq, eq >> 28);
+                            }
+                            if (w < nwords) do_tile(w, bp, ep >> 28);
+                        } else {
+                        bp = load_b(tile_at(0));
                         for (; w + 1 < nwords; w += 2) {
                             bq = load_b(tile_at(w + 1));
                             do_tile(w, bp, groups_at(w));
@@ -1082,6 +1151,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                             do_tile(w + 1, bq, groups_at(w + 1));
                         }
                         if (w < nwords) do_tile(w, bp, groups_at(w));
+                        }
                     }
                     __builtin_amdgcn_wave_barrier();
                     RT_STAMP(6);
@@ -1174,7 +1244,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 // ahead, consumed (ev++) only if the draw is really made -- the Dialectric's reflectance draw.  One wave-level call,
                 // not two; and it runs HERE, between asking for the sphere's records and using them: it needs nothing from memory,
                 // so its ~160 issue cycles pass under the loads' latency (-0.45 % frame time; the empty asm pins the order).
-                U4 w = philox4x32_10(pix_global, (uint32_t)s, ev, 0u, P.k0, P.k1);
+                U4 w = philox(pix_global, (uint32_t)s, ev, 0u);
                 asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w));
                 kind = (int)mC.y;
                 param = mA.y;
@@ -1191,19 +1261,19 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                   if (kind != RT_KIND_DIALECTRIC) {
                     // vec3.rs:37-45 with 53-bit draws: a try is SIX consecutive words -- two tries per three blocks -- and the
                     // test is the reference's own f64 expression x*x + y*y + z*z < 1.0 (vec3.rs:87-89)
-                    U4 b1 = philox4x32_10(pix_global, (uint32_t)s, ev + 1u, 0u, P.k0, P.k1);
+                    U4 b1 = philox(pix_global, (uint32_t)s, ev + 1u, 0u);
                     uint32_t nblk = 2u, c0 = b1.z, c1 = b1.w;
                     double sx = u11_53(w.x, w.y), sy = u11_53(w.z, w.w), sz = u11_53(b1.x, b1.y);
                     bool ok = sx * sx + sy * sy + sz * sz < 1.0;
                     while (!ok) {
                         RT_COUNT_MAIN(6);
-                        U4 b = philox4x32_10(pix_global, (uint32_t)s, ev + nblk, 0u, P.k0, P.k1);
+                        U4 b = philox(pix_global, (uint32_t)s, ev + nblk, 0u);
                         nblk++;
                         sx = u11_53(c0, c1); sy = u11_53(b.x, b.y); sz = u11_53(b.z, b.w);       // try 2m+1: ends its block
                         ok = sx * sx + sy * sy + sz * sz < 1.0;
                         if (!ok) {
-                            b = philox4x32_10(pix_global, (uint32_t)s, ev + nblk, 0u, P.k0, P.k1);
-                            b1 = philox4x32_10(pix_global, (uint32_t)s, ev + nblk + 1u, 0u, P.k0, P.k1);
+                            b = philox(pix_global, (uint32_t)s, ev + nblk, 0u);
+                            b1 = philox(pix_global, (uint32_t)s, ev + nblk + 1u, 0u);
                             nblk += 2u;
                             sx = u11_53(b.x, b.y); sy = u11_53(b.z, b.w); sz = u11_53(b1.x, b1.y); // try 2m+2 = try 0 of the next three blocks
                             c0 = b1.z; c1 = b1.w;
@@ -1224,14 +1294,14 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     RT_COUNT_REDRAW_LANES(ok);
                     if (!ok) {
                         RT_COUNT_MAIN(6);
-                        U4 b = philox4x32_10(pix_global, (uint32_t)s, ev + 1u, 0u, P.k0, P.k1);
+                        U4 b = philox(pix_global, (uint32_t)s, ev + 1u, 0u);
                         nblk = 2u;
                         tx = w.w; ty = b.x; tz = b.y;                            // try 1
                         ok = unit_sphere_accepts(tx, ty, tz);
                         if (!ok) {
                             RT_COUNT_MAIN(6);
                             const uint32_t c1 = b.z, c2 = b.w;
-                            b = philox4x32_10(pix_global, (uint32_t)s, ev + 2u, 0u, P.k0, P.k1);
+                            b = philox(pix_global, (uint32_t)s, ev + 2u, 0u);
                             nblk = 3u;
                             tx = c1; ty = c2; tz = b.x;                          // try 2
                             ok = unit_sphere_accepts(tx, ty, tz);
@@ -1260,13 +1330,13 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                         uint32_t c0 = w.w;                                       // the word left over from the block before
                         do {
                             RT_COUNT_MAIN(6);
-                            U4 b = philox4x32_10(pix_global, (uint32_t)s, ev + nblk, 0u, P.k0, P.k1);
+                            U4 b = philox(pix_global, (uint32_t)s, ev + nblk, 0u);
                             nblk++;
                             tx = c0; ty = b.x; tz = b.y;                         // try 4m+1
                             ok = unit_sphere_accepts(tx, ty, tz);
                             if (!ok) {
                                 const uint32_t c1 = b.z, c2 = b.w;
-                                b = philox4x32_10(pix_global, (uint32_t)s, ev + nblk, 0u, P.k0, P.k1);
+                                b = philox(pix_global, (uint32_t)s, ev + nblk, 0u);
                                 nblk++;
                                 tx = c1; ty = c2; tz = b.x;                      // try 4m+2
                                 ok = unit_sphere_accepts(tx, ty, tz);
@@ -1274,7 +1344,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                                     tx = b.y; ty = b.z; tz = b.w;                // try 4m+3: no new block
                                     ok = unit_sphere_accepts(tx, ty, tz);
                                     if (!ok) {
-                                        b = philox4x32_10(pix_global, (uint32_t)s, ev + nblk, 0u, P.k0, P.k1);
+                                        b = philox(pix_global, (uint32_t)s, ev + nblk, 0u);
                                         nblk++;
                                         tx = b.x; ty = b.y; tz = b.z; c0 = b.w;  // try 4m+4 = try 0 of the next three blocks
                                         ok = unit_sphere_accepts(tx, ty, tz);

@@ -179,6 +179,14 @@ def phases_table(lines, counts):
     fin_s0 = L("// ---- (f) finished samples -> their block's sums", unit0)
     flush0 = L("auto flush_ring = [&]")
     end0 = L("// every block of this wave has finished its last sample", fin_s0)
+    # do_tile's two bodies: the group-by-group one (a tile some 16-ray group cannot reach) and the pipelined one (all four groups).  A tile runs
+    # ONE of them: weighting both with every tile charged the scalar stream of both (the census printed 1 212 scalar instructions per
+    # wave-bounce against 822 counted); c["full_share"] is the measured share of tiles whose group mask is 0xF (tools/block_counts.py on a
+    # -DRT_BLOCK_COUNTS -DRT_COUNT_MASKS build: profiles/scalar_trim_block_counts.txt)
+    skip0 = L("if (groups != 0xFu) {", dotile0)
+    skip_end = L("return;", skip0) + 1
+    full0 = L("f32x16 acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], b, zero16, 0, 0, 0);", skip_end)
+    full_end = pipe0 - 1
     return [
         ("tile loop: keep path, per half (4 x or/cmp/ds_or)", half0, look_end, c["halves"], "2mfma"),     # two static halves per look copy
         ("tile loop: keep path, per look with a candidate", keep0, half0 - 1, c["keeps"], "mfma"),
@@ -189,6 +197,8 @@ def phases_table(lines, counts):
         ("finish pool / take the minimum", fin0, fin_end, 1.0, 1),
         ("ground sphere exact test (always-exact list)", exact0, exact_end, 1.0, 3),      # three inlined copies (first always-exact sphere, the loop over
                                                                                       # further ones, the in-order form for out-of-range rays): the first runs
+        ("tile loop: per tile, group by group (a group skips)", skip0, skip_end, c["tiles"] * (1.0 - c["full_share"]), 3),
+        ("tile loop: per tile, all four groups (pipelined)", full0, full_end, c["tiles"] * c["full_share"], 3),
         ("tile loop: per tile (B operand, list entry, dispatch)", dotile0, loop_end, c["tiles"], 3),
         ("tile loop: per segment (zero the words, list read)", loop0, dotile0 - 1, 1.0, 1),
         ("footprints + tile list", which0, loop0 - 1, 1.0, 1),
@@ -206,6 +216,10 @@ def phases_table(lines, counts):
         ("pass prologue (alive ballot, a = d.d)", hit0, exact0 - 1, 1.0, 1),
     ]
 
+
+# share of the tile loop's tiles whose group mask is 0xF (every 16-ray group scans the tile), measured: profiles/scalar_trim_block_counts.txt
+FULL_BOOK, FULL_TENK = 0.543, 0.396
+SCALAR_PORT_CYCLES = 4.7        # SIMD cycles between two scalar instructions of one SIMD: the CU's one scalar unit serves four (profiles/r04_experiments.txt item 4)
 
 DEVICE_FUNCS = {  # functions of rt_device.hpp that get their own column in the per-phase split
     "philox4x32_10": "Philox block",
@@ -232,10 +246,10 @@ def main():
             want = "render_kernelILi5ELb0ELb1ELb0ELin1024"
     # measured trips per wave-bounce (profiles/r04_block_counts.txt: 1200x675x100; r04_block_counts_cfg4.txt: 10k spheres)
     counts = ({"looks": 20.0, "keeps": 14.03, "halves": 21.56, "pool_rounds": 1.90, "enum_trips": 5.6, "tiles": 8.43, "refills": 0.355,
-               "retry_blocks": 3.8, "flushes": 0.36 / 16.0, "always_extra": 0.3}
+               "retry_blocks": 3.8, "flushes": 0.36 / 16.0, "always_extra": 0.3, "full_share": FULL_TENK}
               if tenk else
               {"looks": 15.22, "keeps": 10.18, "halves": 16.24, "pool_rounds": 1.62, "enum_trips": 4.6, "tiles": 5.35, "refills": 0.377,
-               "retry_blocks": 3.72, "flushes": 0.377 / 4.0, "always_extra": 0.1})
+               "retry_blocks": 3.72, "flushes": 0.377 / 4.0, "always_extra": 0.1, "full_share": FULL_BOOK})
     elf, dis = build(extra, src)
     ins = kernel_instructions(dis, want)
     if not ins:
@@ -248,6 +262,7 @@ def main():
     cost = {}
     unplaced = collections.Counter()
     philox_in = collections.Counter()
+    last_ph = None
     for addr, op, ops in ins:
         cls, cyc = classify(op, ops)
         cost[cls] = cyc
@@ -258,6 +273,15 @@ def main():
             if any(lo <= ln <= hi for ln in klines):
                 ph = name
                 break
+        # an instruction WITHOUT a source line (the compiler's own control flow: exec save / restore, the branch around an empty mask; 190 of the
+        # dense kernel's scalar instructions) belongs to the code around it: it takes the phase of the instruction before it
+        if ph is None and not any(ln > 0 for fn, f, ln in stack):
+            ph = last_ph
+        # ... and so does the exec restore that closes a lane-level `if`: the compiler gives it the line of the CALL the `if` was inlined through (the
+        # recording path's eight restores per look carried do_tile's lines and were charged per tile, in both of its bodies)
+        if op == "s_or_b64" and ops.replace(" ", "").startswith("exec,exec,") and last_ph is not None:
+            ph = last_ph
+        last_ph = ph
         if ph is None:
             ph = "outside the bounce loop / unplaced"
             unplaced[tuple(klines[:2])] += 1
@@ -319,6 +343,23 @@ def main():
     for name, ex, cp, sv, dv, ds_, dl, cyc, phx in rows:
         print(f"{name:62s} {ex:6.2f} {cp:6.0f} {sv:6d} {sv / cp:6.1f} {dv:7.1f} {ds_:6.1f} {dl:5.1f} {cyc:7.0f} {100 * cyc / max(tot_c, 1):5.1f}%  {phx}")
     print(f"{'MODEL TOTAL per wave-bounce':62s} {'':6s} {'':6s} {tot_v:7.1f} {tot_s:6.1f} {tot_l:5.1f} {tot_c:7.0f}")
+    # ---- the scalar stream: what the SIMD's share of the CU's scalar unit has to get through per wave-bounce ----------------------------
+    print()
+    print(f"scalar stream per wave-bounce (dynamic, modelled); scalar-port cycles = (SALU + SMEM + branch) x {SCALAR_PORT_CYCLES} beside the phase's vector cycles:")
+    print(f"{'phase':62s} {'dSALU':>7s} {'dSMEM':>6s} {'dBRANCH':>7s} {'dWAIT':>6s} {'s-cycles':>8s} {'v-cycles':>8s}  {'s/v':>5s}")
+    tot = collections.Counter()
+    for name, ex, cp, sv, dv, ds_, dl, cyc, phx in rows:
+        st = static.get(name, {})
+        f = freq[name]
+        sa, sm, br, wt = st.get("salu", 0) * f, st.get("smem", 0) * f, st.get("branch", 0) * f, st.get("wait/nop", 0) * f
+        scyc = (sa + sm + br) * SCALAR_PORT_CYCLES
+        tot.update({"salu": sa, "smem": sm, "branch": br, "wait": wt, "scyc": scyc})
+        if sa + sm + br + wt > 0:
+            print(f"{name:62s} {sa:7.1f} {sm:6.1f} {br:7.1f} {wt:6.1f} {scyc:8.0f} {cyc:8.0f}  {scyc / cyc if cyc else 0:5.2f}")
+    print(f"{'MODEL TOTAL per wave-bounce':62s} {tot['salu']:7.1f} {tot['smem']:6.1f} {tot['branch']:7.1f} {tot['wait']:6.1f} {tot['scyc']:8.0f} {tot_c:8.0f}  "
+          f"{tot['scyc'] / max(tot_c, 1):5.2f}")
+    print(f"   SALU + branch = {tot['salu'] + tot['branch']:.1f} (what SQ_INSTS_SALU + SQ_INSTS_BRANCH count); vector : (SALU + branch) = "
+          f"{tot_v / max(tot['salu'] + tot['branch'], 1):.2f} : 1")
     print()
     print("dynamic vector instructions by encoding class (modelled), cycles each (measured, 4 waves/SIMD), cycles per wave-bounce:")
     dyn = collections.Counter()
