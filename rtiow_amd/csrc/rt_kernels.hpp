@@ -232,6 +232,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     constexpr bool kWideRing = SMALLGRID || (MODE == 5 && !DIAG && (ITEMS == kItemBlock || ITEMS == kItemBlockList || ITEMS == kItemBlockFrames || ITEMS == kItemBlockDense));
     constexpr int kRingDepth = kWideRing ? 2 : 4;
     constexpr int kRingSlots = kWideRing ? 16 : 8;
+    constexpr bool kMaskVotes = CAPPED && kRingDepth == 2;      // PHASE 5 on wave masks (the capped kernels with the ring of two)
     static_assert(kRingDepth * kRingSlots == rt::kRingDepth * rt::kRingSlots, "same LDS either way");
     __shared__ uint16_t cand[MODE == 1 ? kCandCap : 1][MODE == 1 ? kBlock : 1];     // MODE 1: per-lane candidate lists
     constexpr bool MATRIX = (MODE >= 2);
@@ -753,6 +754,20 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 if constexpr (TUBE) {
                     // which of the segment's words hold a candidate of this ray (the recording side sets bits only)
                     // (min(word, 1) << w | summary: a v_min_u32 and a v_lshl_or_b32 per word where `word != 0 ? 1 << w : 0` is a compare, a select and an or)
+                    if constexpr (CAPPED) {
+                        // (the capped dense kernels: the constant is opaque, or min(word, 1) is canonicalised into a compare and a select.  Small grid: two
+                        //  rows per trip and no remainder loop -- every row of the segment is zeroed, so the row behind an odd count reads as no candidate;
+                        //  the large-grid pair spills four more scalars with any paired or fixed-trip form, 67 against 63, and keeps one row per trip)
+                        uint32_t one = 1u;
+                        asm volatile("" : "+v"(one));
+                        if constexpr (SMALLGRID) {
+                            for (int w = 0; w < nwords_tube; w += 2) {
+                                summary |= min(bits_w[w * 64 + lane], one) << w;
+                                summary |= min(bits_w[(w + 1) * 64 + lane], one) << (w + 1);
+                            }
+                        } else
+                        for (int w = 0; w < nwords_tube; ++w) summary |= min(bits_w[w * 64 + lane], one) << w;
+                    } else
                     for (int w = 0; w < nwords_tube; ++w) summary |= min(bits_w[w * 64 + lane], 1u) << w;
                     if (!alive) summary = 0u;
                 } else {
@@ -1081,6 +1096,13 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 for (int t0 = 0; t0 < n_list; t0 += kSeg / 2) {
                     __builtin_amdgcn_s_setprio(3);
                     const int nwords = min(kSeg / 2, n_list - t0);          // one bitmap word per 32-sphere tile
+                    if constexpr (CAPPED) {
+                        // (the capped dense kernels: every row of the bitmap, seven paired stores and no loop around them -- the rows are exactly the area in
+                        //  front of the tile list, and a row the segment does not use stays zero for the summary above)
+                        static_assert(TUBE, "the rows in front of the tile list");
+#pragma unroll
+                        for (int w = 0; w < kSeg / 2; ++w) bits_w[w * 64 + lane] = 0u;
+                    } else
                     for (int w = 0; w < nwords; ++w) bits_w[w * 64 + lane] = 0u;
                     // the segment's tiles (and two more for the look-ahead), one per lane
                     const int listv = !SMALLGRID && list_all ? (min(t0 + lane, ntt) | (RT_GROUP_SKIP ? (int)0xF0000000u : 0))
@@ -1450,6 +1472,10 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
             const uint32_t age = (blk_seq - (my_blk >> 4)) & 0x0FFFFFFFu;
             const bool direct = finished && !(P.use_ring && age < (uint32_t)kRingDepth);
             const bool ringed = finished && !direct;
+            // (the capped dense kernels: `finished` comes out of the shading's joins as a bool, and every vote on it or on a bool made from it costs a
+            //  select and a compare to rebuild the lane mask.  One vote on it; the others are votes on compares, combined as wave masks.)
+            const unsigned long long fin_m = kMaskVotes ? __ballot(finished) : 0ull;
+            const unsigned long long ring_m = kMaskVotes && P.use_ring ? __ballot(age < (uint32_t)kRingDepth) : 0ull;
             RT_LDS_RING_ADDS(ringed, my_blk);
             if (finished) {
                 const unsigned long long q0 = quantize(radiance.x), q1 = quantize(radiance.y), q2 = quantize(radiance.z);
@@ -1461,8 +1487,25 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     atomicAdd(px + 0, q0); atomicAdd(px + 1, q1); atomicAdd(px + 2, q2);
                 }
             }
-            n_direct += (uint32_t)__popcll(__ballot(direct));
-            unsigned long long fm = __ballot(ringed);
+            n_direct += (uint32_t)__popcll(kMaskVotes ? fin_m & ~ring_m : __ballot(direct));
+            unsigned long long fm = kMaskVotes ? fin_m & ring_m : __ballot(ringed);
+            if constexpr (kMaskVotes) n_samples += (uint32_t)__popcll(fin_m);
+            if constexpr (kMaskVotes) {
+                if (fm != 0ull) {
+                    // (as below for a ring of two; a block's count changes only where its mask is not empty, so each test is one scalar compare and branch)
+                    __builtin_amdgcn_wave_barrier();
+                    const unsigned long long m0 = fm & __ballot(age == 0u);
+                    if (m0 != 0ull) {
+                        rem0 -= (uint32_t)__popcll(m0);
+                        if (rem0 == 0u) flush_ring(blk_seq & 1u);
+                    }
+                    fm &= ~m0;
+                    if (fm != 0ull) {
+                        rem1 -= (uint32_t)__popcll(fm);
+                        if (rem1 == 0u) flush_ring((blk_seq - 1u) & 1u);
+                    }
+                }
+            } else
             if (fm != 0ull) {
                 // count the finished samples per block (nearly always the current and the previous one), and write
                 // out the blocks that have just received their last sample (LDS operations of a wave execute in
@@ -1496,7 +1539,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 }
             }
         }
-        n_samples += (uint32_t)__popcll(__ballot(finished));
+        if constexpr (!kMaskVotes) n_samples += (uint32_t)__popcll(__ballot(finished));
         RT_STAMP(4);
     }
     // every block of this wave has finished its last sample and has been written out; a ring entry that
