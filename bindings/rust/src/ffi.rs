@@ -171,6 +171,34 @@ const _: () = assert!(offset_of!(rt_temporal, alpha_min) == 8);
 const _: () = assert!(offset_of!(rt_temporal, clamp_scale) == 32);
 const _: () = assert!(40 == size_of::<rt_temporal>());
 
+/// A batch of rays for `rt_trace_rays` / `rt_occluded`, structure-of-arrays: `origin` and `dir` are `[n][3]` (the direction is not
+/// normalised), `t_max` is `[n]` or null (+inf for every ray).  Host pointers for the host forms, device pointers for the device forms.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_rays {
+    pub origin: *const f64,
+    pub dir: *const f64,
+    pub t_max: *const f64,
+    pub n: i64,
+}
+
+/// Where `rt_trace_rays` writes: `index` (`[n]`, required: the winner's place in the uploaded list, -1 a miss) and, each optional (null),
+/// `t` `[n]`, `point` `[n][3]`, `normal` `[n][3]`, `front_face` `[n]`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_hits {
+    pub index: *mut i32,
+    pub t: *mut f64,
+    pub point: *mut f64,
+    pub normal: *mut f64,
+    pub front_face: *mut u8,
+}
+
+const _: () = assert!(offset_of!(rt_rays, n) == 24);
+const _: () = assert!(32 == size_of::<rt_rays>());
+const _: () = assert!(offset_of!(rt_hits, front_face) == 32);
+const _: () = assert!(40 == size_of::<rt_hits>());
+
 #[link(name = "rtiow_hip")]
 extern "C" {
     pub fn rt_create(device_id: i32, out: *mut *mut rt_context) -> i32;
@@ -259,6 +287,12 @@ extern "C" {
                             prev_fix: *const u64, prev_len: *const u32, prev_feat: *const u64, prev_feat_spp: i64,
                             prev_cam: *const rt_camera, width: i32, height: i32, tp: *const rt_temporal, out_fix: *mut u64,
                             out_len: *mut u32) -> i32;
+    /// Ray queries: `HittableList::hit(ray, t_min, t_max[k])` of every ray of the batch against the uploaded list (closest hit), and
+    /// whether it would hit at all (occlusion, `[n]` u8).  The device forms are asynchronous on `stream`; the structs are host pointers.
+    pub fn rt_trace_rays_device(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, hits: *const rt_hits, stream: *mut c_void) -> i32;
+    pub fn rt_trace_rays(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, hits: *const rt_hits, kernel_ms: *mut f32) -> i32;
+    pub fn rt_occluded_device(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, d_occluded: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_occluded(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, occluded: *mut u8, kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -9,6 +9,7 @@
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
+//                [--pick I,J]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -39,6 +40,9 @@
 // --temporal-sigma-normal 0.5; --temporal-sigma-depth 0.1; --temporal-clamp X: the scale of the neighbourhood clamp, default 1, a negative X switches
 // it off), with --denoise also rt_denoise on each accumulated frame (spp = 1, the frame's own features), then the one-sample resolve; the
 // frames are written as the batch writes them.  --denoise goes with a batch only together with --temporal.
+// --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
+// centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
+// in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
 // --devices: the frame's rows are dealt round-robin to one rt_context per listed device, each driven by
 // its own host thread, and gathered with ONE RCCL ncclGather to the first device (host/rtiow_multi.hpp).
 // A device may be listed more than once (two contexts on one GPU from two threads: the threading rule of
@@ -95,6 +99,8 @@ int main(int argc, char **argv)
     int feature_spp = 8;
     struct rt_denoise dn{};
     dn.levels = 4; dn.flags = RT_DENOISE_DEMODULATE; dn.sigma_color = 0.35; dn.sigma_normal = 1.0; dn.sigma_depth = 0.2;
+    bool pick = false;
+    int pick_i = 0, pick_j = 0;
     bool temporal = false;
     struct rt_temporal tp{};
     tp.flags = RT_TEMPORAL_CLAMP; tp.alpha_min = 0.1; tp.sigma_normal = 0.5; tp.sigma_depth = 0.1; tp.clamp_scale = 1.0;
@@ -157,6 +163,10 @@ int main(int argc, char **argv)
             if (tp.clamp_scale < 0.0) { tp.flags = 0u; tp.clamp_scale = 1.0; }
         }
         else if (arg("--scene")) scene_file = argv[++i];
+        else if (arg("--pick")) {
+            if (std::sscanf(argv[++i], "%d,%d", &pick_i, &pick_j) != 2) { std::fprintf(stderr, "--pick I,J\n"); return 2; }
+            pick = true;
+        }
         else if (!std::strcmp(argv[i], "--grid") && i + 2 < argc) { lo = std::atoi(argv[++i]); hi = std::atoi(argv[++i]); }
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
@@ -182,6 +192,37 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool batch = !cameras_file.empty() || orbit != 0;
+    if (pick) {
+        if (batch || !devices.empty() || width < 2 || height < 2 || pick_i < 0 || pick_i >= width || pick_j < 0 || pick_j >= height) {
+            std::fprintf(stderr, "--pick I,J: a pixel of the --width x --height frame (both >= 2) of the book camera, on one device\n");
+            return 2;
+        }
+        const rt_camera c = rtiow::Camera(rtiow::Point3(13, 2, 3), rtiow::Point3(0, 0, 0), rtiow::Vec3(0, 1, 0), 20.0,
+                                          (double)width / (double)height, 0.1, 10.0).flat();      // main.rs:108-118
+        const double u = ((double)pick_i + 0.5) / (double)(width - 1), v = ((double)pick_j + 0.5) / (double)(height - 1);
+        double o[3], d[3], t = 0.0, point[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < 3; ++k) {
+            o[k] = c.origin[k];
+            d[k] = ((c.lower_left_corner[k] + u * c.horizontal[k]) + v * c.vertical[k]) - c.origin[k];
+        }
+        int32_t index = -1;
+        rt_rays rays{};
+        rays.origin = o; rays.dir = d; rays.t_max = nullptr; rays.n = 1;
+        rt_hits hits{};
+        hits.index = &index; hits.t = &t; hits.point = point;
+        rt_context *ctx = nullptr;
+        int rc = rt_create(device, &ctx);
+        if (rc) return die("rt_create", rc);
+        rc = rt_upload_scene(ctx, flat.data(), (int32_t)flat.size());
+        if (!rc) rc = rt_trace_rays(ctx, &rays, 0.0001, &hits, nullptr);
+        if (rc) { die("rt_trace_rays", rc); rt_destroy(ctx); return 1; }
+        rt_destroy(ctx);
+        static const char *const kinds[] = {"lambertian", "metal", "dialectric"};
+        const int kind = index >= 0 ? flat[(size_t)index].kind : -1;
+        std::printf("pick %d %d: index %d kind %s t %.17g point %.17g %.17g %.17g\n", pick_i, pick_j, index,
+                    kind >= 0 && kind < 3 ? kinds[kind] : "none", t, point[0], point[1], point[2]);
+        return 0;
+    }
     if (!features_file.empty() && (!devices.empty() || !cameras_file.empty() || orbit != 0 || uniform53 || adaptive)) {
         std::fprintf(stderr, "--features renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --adaptive\n");
         return 2;

@@ -562,6 +562,62 @@ int rt_temporal_host(const uint64_t *fix, const uint32_t *count, int64_t spp, co
                      const rt_camera *prev_cam, int32_t width, int32_t height, const struct rt_temporal *tp, uint64_t *out_fix,
                      uint32_t *out_len);
 
+/* ---- ray queries: closest hit and occlusion for rays the caller supplies ---- */
+
+/* HittableList::hit (mod.rs:54-70) for rays that do not come from an rt_camera: picking, visibility between two points, ambient
+ * occlusion, collision probes, a wavefront integrator of the caller's own over the uploaded scene.  What other libraries call
+ * intersect / occluded.  DESIGN.md section 17.  Structure-of-arrays, so that a tensor passes as it is.
+ *
+ * The contract.  The closest hit of ray k is HittableList::hit(Ray { origin[k], dir[k] }, t_min, t_max[k]) over the uploaded list:
+ * closest_so_far starts at t_max[k] (mod.rs:56); Sphere::hit (sphere.rs:15-41) as written, in IEEE binary64, in the reference's operation
+ * order, no fused multiply-add; a root EQUAL to closest_so_far is accepted (sphere.rs:29, 31 reject only t_max < root), so the later
+ * sphere wins on equal t and a root equal to t_max is a hit.  The direction is not normalised (ray.rs: Ray as it stands): t is in units
+ * of |dir|.
+ *   Rays inside the filter's analysed range are answered in the order-independent form the render and feature kernels use, which
+ *   gives the same answer: a sphere's root is the near one if it is >= t_min, else the far one; the smallest root <= t_max wins, on
+ *   ties the later index.
+ *   Rays outside it take the list in list order exactly as written, NaN roots included (a NaN fails neither comparison of
+ *   sphere.rs:29, 31 and is accepted): a zero, NaN or infinite direction (precisely: |dir|^2, rounded to f32, not inside
+ *   (1e-20, 1e20)), |origin|_1 >= 1e15, a NaN t_max.
+ *   t_min is per call, > 0 and finite, as rt_params.t_min.  t_max is per ray and any double is legal: negative, zero and below t_min
+ *   simply miss.
+ *   A hit writes index (the place in the uploaded list), t, point = origin + dir * t (Ray::at, ray.rs:15-17), normal (HitRecord::new,
+ *   mod.rs:20-30: outward = (point - center) * (1/radius), flipped against the ray; a negative radius flips it as the reference does)
+ *   and front_face.  A miss writes index = -1, t = +inf, point = normal = 0, front_face = 0.  A NaN in t, point or normal is written as
+ *   the quiet NaN 0x7FF8000000000000 (IEEE 754 leaves the sign and payload of a generated NaN open, and processors differ).
+ *   occluded[k] = 1 iff the closest-hit query of ray k would return an index >= 0, else 0 (the kernel stops a ray at its first
+ *   accepted root; the answer does not depend on which root that is).
+ * The result is a pure function of scene, rays and t_min: the same bits from the device and the host forms, under RTIOW_NO_GRID /
+ * RTIOW_GRID_DIM, from either candidate scheme (RTIOW_TRACE_CANDIDATES=wave|ray, a diagnostic knob read per call), whatever the
+ * launch's size (RTIOW_TRACE_GRID_BLOCKS=k, likewise: at most k workgroups) and whichever position in the batch a ray has. */
+typedef struct {
+    const double *origin;   /* [n][3]                                              */
+    const double *dir;      /* [n][3], not normalised: Ray as ray.rs has it        */
+    const double *t_max;    /* [n], or NULL: +inf for every ray                    */
+    int64_t n;
+} rt_rays;
+typedef struct {
+    int32_t *index;         /* [n]  required: list index of the winner, -1 a miss  */
+    double  *t;             /* [n]     or NULL */
+    double  *point;         /* [n][3]  or NULL: Ray::at(t), ray.rs:15-17           */
+    double  *normal;        /* [n][3]  or NULL: HitRecord::new, mod.rs:20-30       */
+    uint8_t *front_face;    /* [n]     or NULL */
+} rt_hits;
+/* RT_ERR_INVALID_ARGUMENT from every form, found before anything is touched, the checks that need no context first: NULL rays or
+ * hits; n < 0 or n > 2^31; t_min not > 0 or not finite; with n > 0 a NULL origin, dir, index or occluded; then a NULL context or one
+ * created under RTIOW_SCAN_MODE=1.  RT_ERR_NO_SCENE before an upload.  n == 0 then succeeds and touches nothing.  Outputs must not
+ * overlap inputs or each other. */
+
+/* Device forms, asynchronous on `stream`.  The two structs are HOST pointers read during the call; the arrays they name are device
+ * pointers, 8-byte aligned (4 for index).  A query takes NONE of the context's launch slots and rt_last_stats does not report on it. */
+int rt_trace_rays_device(rt_context *ctx, const rt_rays *rays, double t_min, const rt_hits *hits, void *stream);
+/* Host-buffer form (copies in, traces on the device, copies out); synchronous.  kernel_ms (may be NULL): the kernel's time, from a pair
+ * of events the call creates and destroys itself. */
+int rt_trace_rays(rt_context *ctx, const rt_rays *rays, double t_min, const rt_hits *hits, float *kernel_ms);
+/* Occlusion: d_occluded / occluded is [n] u8. */
+int rt_occluded_device(rt_context *ctx, const rt_rays *rays, double t_min, void *d_occluded, void *stream);
+int rt_occluded(rt_context *ctx, const rt_rays *rays, double t_min, uint8_t *occluded, float *kernel_ms);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

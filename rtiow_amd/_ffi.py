@@ -52,6 +52,14 @@ class rt_temporal(C.Structure):
                 ("sigma_depth", C.c_double), ("clamp_scale", C.c_double)]
 
 
+class rt_rays(C.Structure):
+    _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("t_max", C.c_void_p), ("n", C.c_int64)]
+
+
+class rt_hits(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("front_face", C.c_void_p)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -104,6 +112,10 @@ SYMBOLS = [
                               C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, C.POINTER(C.c_float)]),
     ("rt_temporal_host", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
                                    C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP]),
+    ("rt_trace_rays_device", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, C.POINTER(rt_hits), _VP]),
+    ("rt_trace_rays", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, C.POINTER(rt_hits), C.POINTER(C.c_float)]),
+    ("rt_occluded_device", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, _VP, _VP]),
+    ("rt_occluded", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, _VP, C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -177,6 +177,57 @@ def tube_tile_host(spheres32):
     return words, bound, float(rho.value)
 
 
+_TRACE_OUTPUTS = ("t", "point", "normal", "front_face")
+
+
+def _check_want(want):
+    unknown = set(want) - set(_TRACE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+
+
+def _torch_rays(torch, renderer, origins, dirs, t_max):
+    n = origins.shape[0] if origins.dim() == 2 else -1
+    if not origins.is_cuda or origins.device.index != renderer.device_id:
+        raise ValueError(f"origins must be on the renderer's device cuda:{renderer.device_id} (is on {origins.device})")
+    tensors = [("origins", origins, (n, 3)), ("dirs", dirs, (n, 3))] + ([("t_max", t_max, (n,))] if t_max is not None else [])
+    for name, x, shape in tensors:
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous() or tuple(x.shape) != shape or x.device != origins.device:
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on the renderer's device")
+    return n
+
+
+def trace_rays_torch(renderer, origins, dirs, t_max=None, t_min=1e-4, want=("t", "point", "normal", "front_face")):
+    """Renderer.trace_rays on torch tensors: contiguous float64 tensors on the context's device, launched on torch.cuda.current_stream();
+    returns a dict of torch tensors ("index" int32, and what `want` names)."""
+    import torch
+    _check_want(want)
+    n = _torch_rays(torch, renderer, origins, dirs, t_max)
+    dev = origins.device
+    out = {"index": torch.empty(n, dtype=torch.int32, device=dev)}
+    shapes = {"t": ((n,), torch.float64), "point": ((n, 3), torch.float64), "normal": ((n, 3), torch.float64), "front_face": ((n,), torch.uint8)}
+    for name in ("t", "point", "normal", "front_face"):
+        if name in want:
+            out[name] = torch.empty(shapes[name][0], dtype=shapes[name][1], device=dev)
+    ptr = lambda name: out[name].data_ptr() if name in out else 0
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        renderer.trace_rays_device(n, origins.data_ptr(), dirs.data_ptr(), ptr("index"), t_max.data_ptr() if t_max is not None else 0, t_min,
+                                   ptr("t"), ptr("point"), ptr("normal"), ptr("front_face"), stream)
+    return out
+
+
+def occluded_torch(renderer, origins, dirs, t_max=None, t_min=1e-4):
+    """Renderer.occluded on torch tensors, on torch.cuda.current_stream(): a dict with "occluded", a uint8 tensor [n]."""
+    import torch
+    n = _torch_rays(torch, renderer, origins, dirs, t_max)
+    occ = torch.empty(n, dtype=torch.uint8, device=origins.device)
+    with torch.cuda.device(origins.device):
+        renderer.occluded_device(n, origins.data_ptr(), dirs.data_ptr(), occ.data_ptr(), t_max.data_ptr() if t_max is not None else 0, t_min,
+                                 torch.cuda.current_stream().cuda_stream)
+    return {"occluded": occ}
+
+
 class Renderer:
     """One rt_context (one GPU)."""
 
@@ -185,6 +236,7 @@ class Renderer:
         h = C.c_void_p()
         _ffi.check(self._lib.rt_create(int(device_id), C.byref(h)), "rt_create")
         self._h = h
+        self.device_id = int(device_id)
         self.n_spheres = None
 
     def close(self):
@@ -397,6 +449,60 @@ class Renderer:
     def features_to_f32_device(self, d_feat_ptr, width, rows, spp, d_out_ptr, stream=0):
         _ffi.check(self._lib.rt_features_to_f32_device(self._h, C.c_void_p(d_feat_ptr), int(width), int(rows), int(spp),
                                                        C.c_void_p(d_out_ptr), C.c_void_p(stream)), "rt_features_to_f32_device")
+
+    # -- ray queries: closest hit and occlusion for the caller's rays -----------------
+    @staticmethod
+    def _ray_arrays(origins, dirs, t_max):
+        origins = np.ascontiguousarray(origins, dtype=np.float64)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+        n = origins.shape[0] if origins.ndim == 2 else -1
+        if origins.shape != (n, 3) or dirs.shape != (n, 3):
+            raise ValueError(f"origins and dirs must both be [n, 3] (are {origins.shape}, {dirs.shape})")
+        if t_max is not None:
+            t_max = np.ascontiguousarray(t_max, dtype=np.float64)
+            if t_max.shape != (n,):
+                raise ValueError(f"t_max must be [n] (is {t_max.shape})")
+        rays = _ffi.rt_rays(origins.ctypes.data, dirs.ctypes.data, t_max.ctypes.data if t_max is not None else None, n)
+        return rays, (origins, dirs, t_max)
+
+    def trace_rays(self, origins, dirs, t_max=None, t_min=1e-4, want=("t", "point", "normal", "front_face")):
+        """rt_trace_rays: HittableList::hit(ray, t_min, t_max[k]) of every ray against the uploaded scene.  origins, dirs f64 [n, 3] (dirs
+        not normalised), t_max f64 [n] or None (+inf).  Returns a dict: "index" i32 [n] (-1: a miss) and whichever of "t" f64 [n] (+inf),
+        "point" f64 [n, 3], "normal" f64 [n, 3], "front_face" u8 [n] `want` names, and "kernel_ms"."""
+        _check_want(want)
+        rays, keep = self._ray_arrays(origins, dirs, t_max)
+        n = int(rays.n)
+        out = {"index": np.zeros(n, dtype=np.int32)}
+        shapes = {"t": ((n,), np.float64), "point": ((n, 3), np.float64), "normal": ((n, 3), np.float64), "front_face": ((n,), np.uint8)}
+        for name in ("t", "point", "normal", "front_face"):
+            if name in want:
+                out[name] = np.zeros(*shapes[name])
+        hits = _ffi.rt_hits(*[out[name].ctypes.data if name in out else None for name in ("index", "t", "point", "normal", "front_face")])
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_trace_rays(self._h, C.byref(rays), float(t_min), C.byref(hits), C.byref(ms)), "rt_trace_rays")
+        out["kernel_ms"] = float(ms.value)
+        return out
+
+    def occluded(self, origins, dirs, t_max=None, t_min=1e-4):
+        """rt_occluded.  Returns a dict, as trace_rays does: "occluded" u8 [n], 1 where trace_rays would return an index >= 0, and "kernel_ms"."""
+        rays, keep = self._ray_arrays(origins, dirs, t_max)
+        occ = np.zeros(int(rays.n), dtype=np.uint8)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_occluded(self._h, C.byref(rays), float(t_min), occ.ctypes.data_as(C.c_void_p), C.byref(ms)), "rt_occluded")
+        return {"occluded": occ, "kernel_ms": float(ms.value)}
+
+    def trace_rays_device(self, n, d_origin_ptr, d_dir_ptr, d_index_ptr, d_t_max_ptr=0, t_min=1e-4, d_t_ptr=0, d_point_ptr=0, d_normal_ptr=0,
+                          d_front_ptr=0, stream=0):
+        """rt_trace_rays_device on raw device pointers (0: left out); asynchronous on `stream`."""
+        rays = _ffi.rt_rays(d_origin_ptr or None, d_dir_ptr or None, d_t_max_ptr or None, int(n))
+        hits = _ffi.rt_hits(d_index_ptr or None, d_t_ptr or None, d_point_ptr or None, d_normal_ptr or None, d_front_ptr or None)
+        _ffi.check(self._lib.rt_trace_rays_device(self._h, C.byref(rays), float(t_min), C.byref(hits), C.c_void_p(stream)), "rt_trace_rays_device")
+
+    def occluded_device(self, n, d_origin_ptr, d_dir_ptr, d_occluded_ptr, d_t_max_ptr=0, t_min=1e-4, stream=0):
+        """rt_occluded_device on raw device pointers; d_occluded_ptr: device [n] u8; asynchronous on `stream`."""
+        rays = _ffi.rt_rays(d_origin_ptr or None, d_dir_ptr or None, d_t_max_ptr or None, int(n))
+        _ffi.check(self._lib.rt_occluded_device(self._h, C.byref(rays), float(t_min), C.c_void_p(d_occluded_ptr) if d_occluded_ptr else None,
+                                                C.c_void_p(stream)), "rt_occluded_device")
 
     # -- denoiser: an edge-avoiding a-trous filter driven by the feature buffers -------
     def denoise(self, fix, spp, feat, feat_spp, denoise=None, count=None):
