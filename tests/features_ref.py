@@ -1,8 +1,8 @@
 """CPU reference of the first-hit feature buffers (include/rtiow_hip.h "feature buffers") -- a test helper.
 
 Composed only from what oracle/ already exports: oracle.philox for the words, the camera run of oracle/oracle_f64.c's sample_ray
-restated in Python floats (IEEE binary64, no fused multiply-add), oracle_get_ray for the ray, oracle_world_hit for (index, t),
-oracle_sphere_hit on the winner for the normal, and Python integers for quantize / qs (oracle_b_quantize pins quantize).
+restated in Python floats (IEEE binary64, no fused multiply-add), oracle_get_ray for the ray, trace_ref.fast_hit (oracle_world_hit for
+(index, t), oracle_sphere_hit on the winner for the normal), and Python integers for quantize / qs (oracle_b_quantize pins quantize).
 """
 import ctypes as C
 import math
@@ -10,6 +10,7 @@ import math
 import numpy as np
 
 import oracle
+from trace_ref import Scene, fast_hit
 
 FEATURE_WORDS = 8
 MASK64 = (1 << 64) - 1
@@ -57,28 +58,10 @@ def camera_ray(ocam, width, height, seed, i, j, s):
     return o, d
 
 
-def first_hit(flat, ptr, n, o, d, t_min):
-    """(list index or -1, t, normal): HittableList::hit(ray, t_min, +inf) and the winner's HitRecord."""
-    lib = oracle.load()
-    t = C.c_double(0.0)
-    idx = lib.oracle_world_hit(ptr, n, o, d, t_min, C.byref(t))
-    if idx < 0:
-        return -1, 0.0, (0.0, 0.0, 0.0)
-    t2, front = C.c_double(0.0), C.c_int(0)
-    p, nrm = (C.c_double * 3)(), (C.c_double * 3)()
-    c = (C.c_double * 3)(*[float(x) for x in flat[idx]["center"]])
-    got = lib.oracle_sphere_hit(c, float(flat[idx]["radius"]), o, d, t_min, math.inf, C.byref(t2), p, nrm, C.byref(front))
-    assert got == 1
-    assert t2.value == t.value or (t2.value != t2.value and t.value != t.value)      # the same root, NaN included
-    return idx, t.value, (nrm[0], nrm[1], nrm[2])
-
-
 def render_features(ocam, flat, width, height, spp, *, sample_begin=0, seed=1, t_min=1e-4):
     """-> (feat u64 [H,W,8], ids i32 [H,W]): the eight exact sums of every pixel over the samples [sample_begin, sample_begin + spp)
     and the list index the first of them hits (-1: a miss)."""
-    flat = np.ascontiguousarray(flat)
-    assert flat.dtype.itemsize == 72
-    ptr, n = flat.ctypes.data_as(C.POINTER(oracle.sphere)), int(flat.shape[0])
+    scene = Scene(flat)
     feat = np.zeros((height, width, FEATURE_WORDS), dtype=np.uint64)
     ids = np.full((height, width), -1, dtype=np.int32)
     for j in range(height):
@@ -86,12 +69,12 @@ def render_features(ocam, flat, width, height, spp, *, sample_begin=0, seed=1, t
             sums = [0] * FEATURE_WORDS
             for s in range(sample_begin, sample_begin + spp):
                 o, d = camera_ray(ocam, width, height, seed, i, j, s)
-                idx, t, nrm = first_hit(flat, ptr, n, o, d, t_min)
+                idx, t, _, nrm, _ = fast_hit(scene, o, d, t_min)
                 if s == sample_begin:
                     ids[j, i] = idx
                 if idx < 0:
                     continue
-                rec = flat[idx]
+                rec = scene.flat[idx]
                 albedo = (1.0, 1.0, 1.0) if int(rec["kind"]) == KIND_DIALECTRIC else tuple(float(x) for x in rec["albedo"])
                 for c in range(3):
                     sums[c] += quantize(albedo[c])

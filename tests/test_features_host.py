@@ -23,7 +23,8 @@ def central_ray(ocam):
 
 def hit_of(flat, ocam):
     o, d = central_ray(ocam)
-    return fr.first_hit(flat, flat.ctypes.data_as(C.POINTER(fr.oracle.sphere)), len(flat), o, d, 1e-4)
+    idx, t, _, n, _ = fr.fast_hit(fr.Scene(flat), o, d, 1e-4)
+    return idx, t, n
 
 
 @pytest.fixture(scope="module")

@@ -5,10 +5,8 @@ cd "$(dirname "$0")/.."
 REV=$1; NAME=$2
 TMP=$(mktemp -d)
 git archive $REV rtiow_amd/csrc include | tar -x -C $TMP
-SRCS=$TMP/rtiow_amd/csrc/rt_api.hip
-[ -f $TMP/rtiow_amd/csrc/rt_frames.hip ] && SRCS="$SRCS $TMP/rtiow_amd/csrc/rt_frames.hip"      # (the second translation unit, from the frame batches on)
-[ -f $TMP/rtiow_amd/csrc/rt_features.hip ] && SRCS="$SRCS $TMP/rtiow_amd/csrc/rt_features.hip"  # (... the feature kernel's)
-[ -f $TMP/rtiow_amd/csrc/rt_dense.hip ] && SRCS="$SRCS $TMP/rtiow_amd/csrc/rt_dense.hip"        # (... the capped dense kernels')
+# every translation unit the revision has: the loader refuses a library that lacks a symbol it declares
+SRCS=$(ls $TMP/rtiow_amd/csrc/rt_*.hip)
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -mllvm -amdgpu-mfma-vgpr-form \
   -fPIC -shared -I $TMP/include -I $TMP/rtiow_amd/csrc -o tools/var_$NAME.so $SRCS
 rm -rf $TMP
