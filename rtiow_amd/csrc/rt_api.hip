@@ -3,6 +3,10 @@
 // Owns the device-side scene, the work counter, the statistics words and the
 // HIP events of one context; validates parameters; launches the persistent
 // render kernel.  No CPU fallback: every entry point needs a gfx950 device.
+//
+// This file holds the context's life cycle, the scene upload and the host forms of the scene's tables, the shard helpers, the dense and the
+// pixel-list launches with their statistics, and the conversions of the exact sums (rt_fix_to_f32_device, the two resolves) with their
+// kernels.  It defines what rt_host.hpp and rt_launch.hpp declare.  The other kernel families are translation units of their own beside it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,7 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "rt_host.hpp"          // rtiow_hip.h, rt_kernels.hpp, rt_context, launch_render: what rt_frames.hip shares with this file
+#include "rt_launch.hpp"        // rt_host.hpp (rtiow_hip.h, rt_context), rt_kernels.hpp, launch_render: what rt_frames.hip and rt_dense.hip share with this file
 
 namespace {
 
@@ -94,7 +98,7 @@ static_assert(rt_scene::kTablesVersion == 1, "the scene tables changed: bump kTa
               "this file -- a hashed kernel source (bench.py, kernel_source_sha) -- changes with them");
 static_assert(rt_scene::kTubeBasisErr == rt::kTubeBasisErr && rt_scene::kTubeCenterErr == rt::kTubeCenterErr && rt_scene::kFilterKU == rt::kFilterKU,
               "rt_scene_core.hpp and rt_device.hpp disagree on a filter constant");
-static_assert(rt_scene::kMatStride == rt::kMatStride, "rt_scene_core.hpp and rt_kernels.hpp disagree on the material record");
+static_assert(rt_scene::kMatStride == rt::kMatStride, "rt_scene_core.hpp and rt_params.hpp disagree on the material record");
 static_assert(sizeof(rt_scene::Word4) == sizeof(uint4) && offsetof(rt_scene::Word4, x) == offsetof(uint4, x) && offsetof(rt_scene::Word4, y) == offsetof(uint4, y) &&
               offsetof(rt_scene::Word4, z) == offsetof(uint4, z) && offsetof(rt_scene::Word4, w) == offsetof(uint4, w), "Word4 must have uint4's layout");
 
@@ -197,11 +201,9 @@ int rt_host::begin_launch(rt_context *ctx, hipStream_t stream, rt::KParams &kp, 
     return RT_OK;
 }
 
-namespace {
-
 // what a pixel-list render accepts beyond validate_params: checked before anything is touched.  The checks that need no context come
 // first (so a caller -- and a test -- without a device still gets the precise message), then the context's own.
-int validate_pixel_list(const rt_context *ctx, const rt_camera *cam, const rt_params *p, int64_t n_pixels)
+int rt_host::validate_pixel_list(const rt_context *ctx, const rt_camera *cam, const rt_params *p, int64_t n_pixels)
 {
     int rc = validate_params(p);
     if (rc) return rc;
@@ -218,38 +220,18 @@ int validate_pixel_list(const rt_context *ctx, const rt_camera *cam, const rt_pa
     return RT_OK;
 }
 
-int validate_adaptive(const rt_adaptive *a)
-{
-    if (!a) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive is NULL");
-    if (a->step < 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.step must be >= 1 (is %d)", a->step);
-    if (a->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.reserved must be 0");
-    if (!(a->threshold >= 0.0)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.threshold must be >= 0 (and not a NaN)");
-    if (!(a->dark_floor > 0.0) || !(a->dark_floor < INFINITY))
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.dark_floor must be > 0 and finite (with a zero floor a black pixel's error is 0/0)");
-    return RT_OK;
-}
-
-constexpr int kAdaptiveMaxSpp = 32766;     // n * 2^48 < 2^63: the half-buffer differences fit a signed 64-bit integer whatever the scene
-
-int validate_select(const void *fix, const void *half, const void *count, int32_t width, int32_t height, int32_t n, const rt_adaptive *a,
-                    const void *list_out, const void *n_out)
-{
-    if (!fix || !half || !count || !list_out || !n_out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_select_pixels: a buffer is NULL");
-    if (width < 1 || height < 1 || (long long)width * height > 0x7fffffffLL)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_select_pixels: bad width/height");
-    if (n < 2 || n > kAdaptiveMaxSpp || (n & 1))
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_select_pixels: n = %d samples must be even (two halves) and in [2, %d]", n, kAdaptiveMaxSpp);
-    return validate_adaptive(a);
-}
-
 #ifdef RTIOW_CROSSCHECK_MODES
+namespace rt_host {
 #include "xcheck/rt_xcheck_host.inc"       // B operands of scan modes 2-4
+}
 #endif
+
+namespace {
 
 // The dense launch's kernel: the one place that maps (mode, diag, u53, small grid, blocks of 1 024) to an instantiation, and says
 // which one ran (rt_stats::kernel_variant: 1 small grid, 2 U53, 4 blocks of 1 024; rt_last_dense_body).  The shipped kernel has a leaner
 // instantiation for scenes whose tile grid has <= 64 cells, and a second body with the capped unit-sphere redraw (rt_dense.hip;
-// RTIOW_DENSE_BODY=classic: the kernels below): kernel_variant says the same for both.
+// RTIOW_DENSE_BODY=classic: the instantiations below): kernel_variant says the same for both.
 int launch_dense(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, int mode, bool diag, bool u53, bool small_grid, bool large_blocks, int *grid)
 {
     const bool shipped = mode == 5 && !diag;
@@ -287,6 +269,115 @@ int launch_dense(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, int
 }
 
 } // namespace
+
+// ---- the exact sums' conversions: the kernels of rt_fix_to_f32_device, rt_resolve_rgba8_device and rt_resolve_rgba8_counts_device ----
+namespace rt {
+
+// exact sum -> f64 value (one rounding above 2^53)
+__device__ __forceinline__ double fix_to_f64(unsigned long long q)
+{
+    return ((double)(uint32_t)(q >> 32) * 4294967296.0 + (double)(uint32_t)q) * (1.0 / 4294967296.0);
+}
+
+__global__ void fix_to_f32_kernel(const unsigned long long *__restrict__ fix, float *__restrict__ out, long long count)
+{
+    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; k < count; k += stride) out[k] = (float)fix_to_f64(fix[k]);
+}
+
+// Color::to_rgba, vec3.rs:403-421, in f64, + the row flip of main.rs:141-145.
+__device__ __forceinline__ uint8_t as_u8(double x)
+{   // Rust `as u8`: saturating, NaN -> 0
+    if (!(x == x)) return 0;
+    if (x <= 0.0) return 0;
+    if (x >= 255.0) return 255;
+    return (uint8_t)x;
+}
+__device__ __forceinline__ double clamp_r(double x, double lo, double hi)
+{   // f64::clamp: NaN stays NaN
+    if (x < lo) return lo;
+    if (x > hi) return hi;
+    return x;
+}
+__global__ void resolve_rgba8_kernel(const unsigned long long *__restrict__ fix, uint8_t *__restrict__ out,
+                                     int width, int rows, double scale, int flip)
+{
+    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long npix = (long long)width * rows;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; k < npix; k += stride) {
+        const int r = (int)(k / width);
+        const int i = (int)(k - (long long)r * width);
+        const int dst = flip ? rows - 1 - r : r;
+        const unsigned long long *q = fix + k * 3;
+        uchar4 px;
+        px.x = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[0])), 0.0, 0.999));
+        px.y = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[1])), 0.0, 0.999));
+        px.z = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[2])), 0.0, 0.999));
+        px.w = 255;
+        reinterpret_cast<uchar4 *>(out)[(long long)dst * width + i] = px;
+    }
+}
+
+// Color::to_rgba with each pixel's OWN sample count (vec3.rs:403-421 with samples_per_pixel = count[p]) + the row flip: the resolve of
+// an adaptive frame.  A pixel without samples (count 0) divides by zero as the reference would: 0 * inf = NaN -> byte 0.
+__global__ void resolve_rgba8_counts_kernel(const unsigned long long *__restrict__ fix, const uint32_t *__restrict__ count,
+                                            uint8_t *__restrict__ out, int width, int rows, int flip)
+{
+    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long npix = (long long)width * rows;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; k < npix; k += stride) {
+        const int r = (int)(k / width);
+        const int i = (int)(k - (long long)r * width);
+        const int dst = flip ? rows - 1 - r : r;
+        const unsigned long long *q = fix + k * 3;
+        const double scale = 1.0 / (double)count[k];            // vec3.rs:409
+        uchar4 px;
+        px.x = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[0])), 0.0, 0.999));
+        px.y = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[1])), 0.0, 0.999));
+        px.z = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[2])), 0.0, 0.999));
+        px.w = 255;
+        reinterpret_cast<uchar4 *>(out)[(long long)dst * width + i] = px;
+    }
+}
+
+// ---- the tube filter's known-answer kernel (rt_filter_tube_device, beside rt_tube_tile_host below) ----
+// The one known-answer kernel that is NOT in rt_selftest.hip: it stages its operands in LDS through the very helpers the render kernel
+// calls, and compiled in a translation unit without a render kernel its address arithmetic comes out in another order (304 instructions
+// instead of 308, tools/isa_fingerprint.py --all).  It is there to run the kernel's own code, so it stays in the kernel's unit.
+// One tile of the MODE 5 (tube) filter exactly as the render kernel evaluates it: 64 rays against
+// the 32 columns of `tile`.  h_out[ray][column][k] = lambda u_k.(c - o) as the matrix pipe returns it;
+// rows_out[ray] = (lambda u_1, lambda u_2, t_1, t_2, sane).
+__global__ __launch_bounds__(64) void tube_products_kernel(const double *o, const double *d, const uint4 *tile, float rho,
+                                                         float *h_out, float *rows_out)
+{
+    typedef float f32x16 __attribute__((ext_vector_type(16)));
+    __shared__ uint4 stage[64 * 4];
+    const int lane = threadIdx.x, col = lane & 31, hh = lane >> 5;
+    const TubeRay T = make_tube(mk(o[3 * lane], o[3 * lane + 1], o[3 * lane + 2]),
+                                mk(d[3 * lane], d[3 * lane + 1], d[3 * lane + 2]), rho);
+    for (int k = 0; k < 2; ++k) for (int i = 0; i < 3; ++i) rows_out[lane * 9 + 3 * k + i] = T.u[k][i];
+    rows_out[lane * 9 + 6] = T.t[0]; rows_out[lane * 9 + 7] = T.t[1]; rows_out[lane * 9 + 8] = T.sane ? 1.0f : 0.0f;
+    bf16x8 A[4];
+    uint32_t w[2][8];
+    tube_a_words(T, w);
+    tube_stage_operands(stage, lane, w, A);
+    const bf16x8 b = __builtin_bit_cast(bf16x8, tile[lane]);
+    const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int G = 0; G < 4; ++G) {
+        const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[G], b, zero16, 0, 0, 0);
+        for (int bb = 0; bb < 2; ++bb)
+            for (int j = 0; j < 4; ++j) {
+                const int ray = 16 * G + 8 * bb + 4 * hh + j;
+                h_out[(ray * 32 + col) * 2 + 0] = acc[8 * bb + j];
+                h_out[(ray * 32 + col) * 2 + 1] = acc[8 * bb + 4 + j];
+            }
+    }
+}
+
+} // namespace rt
 
 extern "C" {
 
@@ -444,7 +535,7 @@ int rt_render_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
 
     const long long npix = (long long)rows * p->width;
     // Work items are single pixel-samples in pixel-major order (item w = pixel * spp + sample), handed out in
-    // blocks of consecutive items (plan_launch, rt_host.hpp); the work counter counts blocks.
+    // blocks of consecutive items (plan_launch, rt_launch.hpp); the work counter counts blocks.
     const unsigned long long total_items = (unsigned long long)npix * (unsigned long long)p->spp;
     const int mode = (p->flags & RT_FLAG_NO_FILTER) ? 0 : ctx->scan_mode;
     const bool diag = (p->flags & RT_FLAG_DIAG_STATS) != 0, u53 = (p->flags & RT_FLAG_UNIFORM53) != 0;
@@ -683,166 +774,6 @@ int rt_render_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
     return RT_OK;
 }
 
-// ---- adaptive sampling -------------------------------------------------------------------------------------------------------
-int rt_select_pixels_host(const uint64_t *fix, const uint64_t *half, const uint32_t *count, int32_t width, int32_t height,
-                          int32_t n, const rt_adaptive *a, uint32_t *list_out, int64_t *n_out)
-{
-    int rc = validate_select(fix, half, count, width, height, n, a, list_out, n_out);
-    if (rc) return rc;
-    const size_t npix = (size_t)width * height;
-    std::vector<char> noisy(npix);
-    const double sc = 1.0 / ((double)n * 4294967296.0);
-    for (size_t p = 0; p < npix; ++p)
-        noisy[p] = count[p] == (uint32_t)n &&
-                   rt::select_noisy((const unsigned long long *)fix + p * 3, (const unsigned long long *)half + p * 3, sc, a->threshold, a->dark_floor);
-    int64_t m = 0;
-    for (int j = 0; j < height; ++j)
-        for (int i = 0; i < width; ++i) {
-            const size_t p = (size_t)j * width + i;
-            if (count[p] != (uint32_t)n) continue;
-            bool act = false;
-            for (int jj = std::max(j - 1, 0); jj <= std::min(j + 1, height - 1); ++jj)
-                for (int ii = std::max(i - 1, 0); ii <= std::min(i + 1, width - 1); ++ii) act = act || noisy[(size_t)jj * width + ii];
-            if (act) list_out[m++] = (uint32_t)p;
-        }
-    *n_out = m;
-    return RT_OK;
-}
-
-int rt_select_pixels_device(rt_context *ctx, const void *d_fix, const void *d_half, const void *d_count, int32_t width,
-                            int32_t height, int32_t n, const rt_adaptive *a, void *d_list_out, void *d_n_out, void *stream_v)
-{
-    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    int rc = validate_select(d_fix, d_half, d_count, width, height, n, a, d_list_out, d_n_out);
-    if (rc) return rc;
-    RT_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const uint32_t npix = (uint32_t)((long long)width * height);
-    const uint32_t blocks = (npix + rt::kSelBlock - 1) / rt::kSelBlock;
-    // scratch: noisy[npix], active[npix] (bytes, each rounded up to 256), the workgroups' counts [blocks]
-    const size_t flags_bytes = ((size_t)npix + 255) / 256 * 256;
-    rc = ensure(&ctx->d_sel, &ctx->sel_bytes, 2 * flags_bytes + (size_t)blocks * sizeof(uint32_t));
-    if (rc) return rc;
-    uint8_t *noisy = (uint8_t *)ctx->d_sel, *active = noisy + flags_bytes;
-    uint32_t *block_count = (uint32_t *)(active + flags_bytes);
-    const double sc = 1.0 / ((double)n * 4294967296.0);
-    hipLaunchKernelGGL(rt::select_noisy_kernel, dim3(blocks), dim3(rt::kSelBlock), 0, stream, (const unsigned long long *)d_fix,
-                       (const unsigned long long *)d_half, (const uint32_t *)d_count, npix, (uint32_t)n, sc, a->threshold, a->dark_floor, noisy);
-    hipLaunchKernelGGL(rt::select_active_kernel, dim3(blocks), dim3(rt::kSelBlock), 0, stream, (const uint8_t *)noisy,
-                       (const uint32_t *)d_count, (int)width, (int)height, (uint32_t)n, active, block_count);
-    hipLaunchKernelGGL(rt::select_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, blocks, (uint32_t *)d_n_out);
-    hipLaunchKernelGGL(rt::select_write_kernel, dim3(blocks), dim3(rt::kSelBlock), 0, stream, (const uint8_t *)active,
-                       (const uint32_t *)block_count, npix, (uint32_t *)d_list_out);
-    RT_HIP(hipGetLastError());
-    return RT_OK;
-}
-
-int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_adaptive *a,
-                       uint64_t *out_fix, uint64_t *out_half, uint32_t *out_count, rt_stats *stats)
-{
-    int rc = validate_params(p);
-    if (rc) return rc;
-    rc = validate_adaptive(a);
-    if (rc) return rc;
-    if (p->sample_begin != 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive numbers its own passes: sample_begin must be 0 (is %d)", p->sample_begin);
-    if (p->spp < 2 * (long long)a->step || p->spp % (2 * (long long)a->step) != 0 || p->spp > kAdaptiveMaxSpp)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive: spp = %d (the most samples a pixel may get) must be a multiple of 2 * step = %lld "
-                    "and <= %d", p->spp, 2 * (long long)a->step, kAdaptiveMaxSpp);
-    rc = validate_pixel_list(ctx, cam, p, 0);
-    if (rc) return rc;
-    if (!out_fix || !out_count) return fail(RT_ERR_INVALID_ARGUMENT, "out_fix/out_count is NULL");
-    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
-    RT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->own_stream;
-    const size_t npix = (size_t)p->width * p->height;
-    const size_t sums = npix * 3 * sizeof(uint64_t);
-    // the frame's state, all on the device: fix | half | one pass's compact sums | count | list | running counters (5 x u64), list length
-    Stage stage(ctx);
-    const size_t b_fix = stage.add(sums), b_half = stage.add(sums), b_pass = stage.add(sums);
-    const size_t b_count = stage.add(npix * sizeof(uint32_t)), b_list = stage.add(npix * sizeof(uint32_t)), b_total = stage.add(64);
-    if ((rc = stage.commit())) return rc;
-    void *d_fix = stage.at(b_fix), *d_half = stage.at(b_half), *d_pass = stage.at(b_pass);
-    uint32_t *d_count = stage.at<uint32_t>(b_count), *d_list = stage.at<uint32_t>(b_list);
-    unsigned long long *d_total = stage.at<unsigned long long>(b_total);
-    uint32_t *d_n = (uint32_t *)(d_total + 5);
-    RT_HIP(hipMemsetAsync(d_total, 0, 64, st));
-
-    const uint32_t step = (uint32_t)a->step;
-    float kernel_ms = 0.0f;
-    unsigned long long zero_depth = 0;
-    rt_stats shape{};                                                    // grid, variant ... of the latest launch
-    int round_slots[2] = {0, 0};
-    auto after_pass = [&](int k) -> int {                                // the launch's counters -> the running total; remember its events
-        hipLaunchKernelGGL(rt::stats_accumulate_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)ctx->d_stats, d_total);
-        RT_HIP(hipGetLastError());
-        zero_depth += ctx->zero_depth_samples;
-        round_slots[k] = ctx->cur;
-        shape = ctx->last;
-        return RT_OK;
-    };
-    auto round_time = [&]() -> int {                                     // (after the round's synchronise: both passes have finished)
-        for (int k = 0; k < 2; ++k) {
-            float ms = 0.0f;
-            RT_HIP(hipEventElapsedTime(&ms, ctx->e0_slots[round_slots[k]], ctx->e1_slots[round_slots[k]]));
-            kernel_ms += ms;
-        }
-        return RT_OK;
-    };
-    rt_params q = *p;
-    q.spp = (int32_t)step;
-    // round 1: every pixel, through the dense kernel.  Pass 0 -> fix, a copy of it is `half`, pass 1 is added to fix.
-    q.sample_begin = 0; q.flags = p->flags & ~RT_FLAG_ACCUMULATE;
-    rc = rt_render_device(ctx, cam, &q, d_fix, st);
-    if (rc) return rc;
-    if ((rc = after_pass(0))) return rc;
-    RT_HIP(hipMemcpyAsync(d_half, d_fix, sums, hipMemcpyDeviceToDevice, st));
-    q.sample_begin = (int32_t)step; q.flags = p->flags | RT_FLAG_ACCUMULATE;
-    rc = rt_render_device(ctx, cam, &q, d_fix, st);
-    if (rc) return rc;
-    if ((rc = after_pass(1))) return rc;
-    hipLaunchKernelGGL(rt::fill_u32_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, d_count, 2u * step, (uint32_t)npix);
-    RT_HIP(hipGetLastError());
-    q.flags = p->flags & ~RT_FLAG_ACCUMULATE;
-    for (uint32_t n = 2u * step; ; n += 2u * step) {
-        uint32_t n_list = 0;
-        if (n < (uint32_t)p->spp) {
-            rc = rt_select_pixels_device(ctx, d_fix, d_half, d_count, p->width, p->height, (int32_t)n, a, d_list, d_n, st);
-            if (rc) return rc;
-            RT_HIP(hipMemcpyAsync(&n_list, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));    // the round's ONE word
-        }
-        RT_HIP(hipStreamSynchronize(st));
-        if ((rc = round_time())) return rc;
-        if (n_list == 0u) break;
-        for (int k = 0; k < 2; ++k) {                                    // passes n / step (even: also into half) and n / step + 1
-            q.sample_begin = (int32_t)(n + (uint32_t)k * step);
-            rc = rt_render_pixels_device(ctx, cam, &q, d_list, (int64_t)n_list, d_pass, st);
-            if (rc) return rc;
-            if ((rc = after_pass(k))) return rc;
-            hipLaunchKernelGGL(rt::add_back_kernel, dim3((n_list + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)d_list, n_list,
-                               (const unsigned long long *)d_pass, (unsigned long long *)d_fix,
-                               k == 0 ? (unsigned long long *)d_half : (unsigned long long *)nullptr, d_count, step);
-            RT_HIP(hipGetLastError());
-        }
-    }
-    unsigned long long total[5];
-    RT_HIP(hipMemcpyAsync(out_fix, d_fix, sums, hipMemcpyDeviceToHost, st));
-    if (out_half) RT_HIP(hipMemcpyAsync(out_half, d_half, sums, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipMemcpyAsync(out_count, d_count, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    RT_HIP(hipMemcpyAsync(total, d_total, sizeof(total), hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    if (stats) {
-        memset(stats, 0, sizeof(*stats));
-        stats->n_spheres = shape.n_spheres; stats->grid_blocks = shape.grid_blocks; stats->block_threads = shape.block_threads;
-        stats->scan_mode = shape.scan_mode; stats->kernel_variant = shape.kernel_variant;
-        stats->rays_traced = total[0];
-        stats->samples = total[1] + zero_depth;
-        stats->direct_samples = total[4];
-        stats->sphere_tests = total[0] * (unsigned long long)(shape.n_spheres > 0 ? shape.n_spheres : 0);
-        stats->kernel_ms = kernel_ms;
-    }
-    return RT_OK;
-}
-
 int rt_resolve_rgba8_counts_device(rt_context *ctx, const void *d_fix, const void *d_count, int32_t width, int32_t rows,
                                    int32_t flip, void *d_rgba, void *stream_v)
 {
@@ -878,71 +809,6 @@ int rt_resolve_rgba8_counts(rt_context *ctx, const uint64_t *fix, const uint32_t
     RT_HIP(st.sync());
     return RT_OK;
 }
-
-int rt_f64_div_sqrt_device(rt_context *ctx, const double *a, const double *b, int32_t n,
-                           double *out_div, double *out_sqrt)
-{
-    if (!ctx || !a || !b || !out_div || !out_sqrt || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (n == 0) return RT_OK;
-    RT_HIP(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * sizeof(double);
-    Stage st(ctx);
-    const size_t b_a = st.add(bytes), b_b = st.add(bytes), b_q = st.add(bytes), b_r = st.add(bytes);
-    int rc = st.commit();
-    if (rc) return rc;
-    RT_HIP(st.up(b_a, a, bytes));
-    RT_HIP(st.up(b_b, b, bytes));
-    hipLaunchKernelGGL(rt::f64_div_sqrt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream,
-                       st.at<const double>(b_a), st.at<const double>(b_b), (int)n, st.at<double>(b_q), st.at<double>(b_r));
-    RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out_div, b_q, bytes));
-    RT_HIP(st.down(out_sqrt, b_r, bytes));
-    RT_HIP(st.sync());
-    return RT_OK;
-}
-
-int rt_quantize_device(rt_context *ctx, const double *x, int32_t n, uint64_t *out)
-{
-    if (!ctx || !x || !out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (n == 0) return RT_OK;
-    RT_HIP(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * sizeof(double);
-    Stage st(ctx);
-    const size_t b_x = st.add(bytes), b_q = st.add(bytes);
-    int rc = st.commit();
-    if (rc) return rc;
-    RT_HIP(st.up(b_x, x, bytes));
-    hipLaunchKernelGGL(rt::quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.at<const double>(b_x), (int)n,
-                       st.at<unsigned long long>(b_q));
-    RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out, b_q, bytes));
-    RT_HIP(st.sync());
-    return RT_OK;
-}
-
-int rt_unit_accept_device(rt_context *ctx, const uint32_t *words, int32_t n, uint32_t *out_accept, double *out_uniforms)
-{
-    if (!ctx || !words || !out_accept || !out_uniforms || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    if (n == 0) return RT_OK;
-    RT_HIP(hipSetDevice(ctx->device));
-    const size_t wb = (size_t)n * 3 * sizeof(uint32_t), ab = (size_t)n * sizeof(uint32_t), ub = (size_t)n * 4 * sizeof(double);
-    Stage st(ctx);
-    const size_t b_u = st.add(ub), b_w = st.add(wb), b_a = st.add(ab);
-    int rc = st.commit();
-    if (rc) return rc;
-    RT_HIP(st.up(b_w, words, wb));
-    hipLaunchKernelGGL(rt::unit_accept_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.at<const uint32_t>(b_w), (int)n,
-                       st.at<uint32_t>(b_a), st.at<double>(b_u));
-    RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out_accept, b_a, ab));
-    RT_HIP(st.down(out_uniforms, b_u, ub));
-    RT_HIP(st.sync());
-    return RT_OK;
-}
-
-#ifdef RTIOW_CROSSCHECK_MODES
-#include "xcheck/rt_xcheck_hooks.inc"      // rt_filter_products_device, rt_filter_lifted_device
-#endif
 
 int rt_tube_tile_host(const rt_sphere *spheres32, uint32_t *out_words, float *out_bound, float *out_rho)
 {
@@ -987,22 +853,6 @@ int rt_tile_layout_host(const rt_sphere *spheres, int32_t n, int32_t out_dims[2]
     if ((size_t)cap < L.slot_of.size()) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tile_layout_host: out_slot_of too small");
     for (size_t k = 0; k < L.slot_of.size(); ++k) out_slot_of[k] = L.slot_of[k];
     return (int)L.slot_of.size();
-}
-
-int rt_philox_device(rt_context *ctx, const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
-{
-    if (!ctx || !ctr || !key || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    RT_HIP(hipSetDevice(ctx->device));
-    Stage st(ctx);
-    const size_t b_out = st.add(16);
-    int rc = st.commit();
-    if (rc) return rc;
-    hipLaunchKernelGGL(rt::philox_kat_kernel, dim3(1), dim3(1), 0, ctx->own_stream,
-                       ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], st.at<uint32_t>(b_out));
-    RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out, b_out, 16));
-    RT_HIP(st.sync());
-    return RT_OK;
 }
 
 } // extern "C"

@@ -20,7 +20,6 @@
 #include <cstring>
 #include <vector>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: no kernel of rt_api.hip is instantiated here
 #include "rt_host.hpp"
 #include "rt_denoise_core.hpp"
 

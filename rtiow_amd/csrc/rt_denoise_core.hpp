@@ -43,7 +43,7 @@ RT_DN_FN LevelConst level_const(double sigma_color, double sigma_normal, double 
     return k;
 }
 
-// exact sum -> f64 value, hi/lo form (rt_kernels.hpp, fix_to_f64)
+// exact sum -> f64 value, hi/lo form (rt_api.hip, fix_to_f64)
 RT_DN_FN double value(uint64_t q)
 {
     return ((double)(uint32_t)(q >> 32) * 4294967296.0 + (double)(uint32_t)q) * (1.0 / 4294967296.0);

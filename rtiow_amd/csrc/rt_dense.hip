@@ -4,7 +4,7 @@
 // The fourth translation unit of librtiow_hip.so.  It owns four instantiations of the render kernel,
 // rt::render_kernel<5, false, SMALLGRID, false, rt::kItemBlockDense | rt::kItemBlockDenseLarge>, the function the dense launch's one dispatch
 // (launch_dense, rt_api.hip) reaches them through, and the diagnostic that says which body the last dense launch ran (rtiow_hip_diag.h).  The
-// launch itself -- plan, KParams, slot, clears, tail -- is the shared path of rt_host.hpp: nothing of it is here.  Every other kernel of the library stays
+// launch itself -- plan, KParams, slot, clears, tail -- is the shared path of rt_launch.hpp: nothing of it is here.  Every other kernel of the library stays
 // where it was: rt_api.hip's and rt_frames.hip's device code is untouched, and the classic dense kernels remain in the library
 // (RTIOW_DENSE_BODY=classic runs them for the same launch: the same frame, the A/B baseline).
 #include <hip/hip_runtime.h>
@@ -12,15 +12,14 @@
 #include <cstdlib>
 #include <cstring>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: render_kernel and what it needs; the resolve / selection / known-answer kernels are rt_api.hip's
-#include "rt_host.hpp"
+#include "rt_launch.hpp"
 #include "rtiow_hip_diag.h"
 
 namespace rt_host {
 
 // Which launches take the capped body when RTIOW_DENSE_BODY is not set: decided per instantiation by the interleaved A/B of
 // profiles/capped_redraw_ab.txt (tools/dense_body_ab.py) -- a default only where the capped body is faster by at least three times the
-// rebuild-to-rebuild band of +-0.3 % in both orders: the headline shape (small grid, blocks of 1 024) alone (rt_host.hpp, kDenseCappedDefault).
+// rebuild-to-rebuild band of +-0.3 % in both orders: the headline shape (small grid, blocks of 1 024) alone (rt_launch.hpp, kDenseCappedDefault).
 static bool capped_by_default(bool small_grid, bool large_blocks)
 {
     return kDenseCappedDefault[small_grid ? 1 : 0][large_blocks ? 1 : 0];

@@ -21,6 +21,7 @@ namespace rt {
 struct D3 { double x, y, z; };
 
 __device__ __forceinline__ D3 mk(double x, double y, double z) { D3 r; r.x = x; r.y = y; r.z = z; return r; }
+__device__ __forceinline__ D3 ld3(const double *p) { return mk(p[0], p[1], p[2]); }
 // vec3.rs:137-147, :243-253, :330-356, :358-367
 __device__ __forceinline__ D3 operator+(D3 a, D3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ D3 operator-(D3 a, D3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }

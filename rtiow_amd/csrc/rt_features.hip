@@ -15,7 +15,6 @@
 
 #include <cstring>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: KParams and the constants; rt_api.hip owns the kernels defined there
 #include "rt_host.hpp"
 #ifdef RT_FEATURES_COUNT
 #define RT_SCAN_COUNT               // rt_first_hit.hpp: the scan's diagnostic counters (tools/features_bench.py --counts)
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(kFeatBlock) void features_kernel(const KParams P, c
     }
 }
 
-// exact sum -> f64 value, hi/lo form (rt_kernels.hpp, fix_to_f64)
+// exact sum -> f64 value, hi/lo form (rt_api.hip, fix_to_f64)
 __device__ __forceinline__ double feat_fix_to_f64(unsigned long long q)
 {
     return ((double)(uint32_t)(q >> 32) * 4294967296.0 + (double)(uint32_t)q) * (1.0 / 4294967296.0);

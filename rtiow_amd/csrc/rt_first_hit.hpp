@@ -1,6 +1,6 @@
 // rt_first_hit.hpp -- HittableList::hit (mod.rs:54-70) of the 64 rays of one wave against the uploaded list: the scan that
 // rt::features_kernel (rt_features.hip, camera rays, t_max = +inf) and rt::trace_kernel (rt_trace.hip, the caller's rays, a t_max per ray)
-// share.  Both include it after rt_host.hpp; it uses the building blocks of rt_device.hpp and the tables rt_upload_scene built.
+// share.  Both include it after rt_host.hpp (KParams and the constants: rt_params.hpp); it uses the building blocks of rt_device.hpp and the tables rt_upload_scene built.
 //
 // Per wave: the rays' filter rows (filter_rows), the spheres that skip the filter or, for a ray outside the filter's analysed range, the
 // whole list as written (exact_prologue), which tiles of 32 columns the rays can reach (wave_footprint), the tube filter on a tile (four
@@ -13,6 +13,8 @@
 // The tie rule (among equal roots the LATER sphere of the list), the strict t_min and the NaN behaviour of the two exact tests are stated
 // HERE and nowhere else outside the render kernel (rt_kernels.hpp, exact_test).
 #pragma once
+#include "rt_params.hpp"
+#include "rt_device.hpp"
 
 namespace rt {
 

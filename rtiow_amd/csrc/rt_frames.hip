@@ -3,14 +3,13 @@
 // The second translation unit of librtiow_hip.so.  It owns the frame-batch instantiations of the render kernel,
 // rt::render_kernel<5, false, SMALLGRID, false, rt::kItemBlockFrames> (rt_kernels.hpp), and the three entry points that launch
 // them: their validation, the frame fields of KParams and the kernel choice.  The context, validate_params and the launch path that
-// the dense and the pixel-list renders take as well (plan_launch, fill_common_params, run_launch) are shared through rt_host.hpp.
-// Every other kernel of the library stays in rt_api.hip, whose device code this file leaves untouched.
+// the dense and the pixel-list renders take as well (plan_launch, fill_common_params, run_launch) are shared through rt_host.hpp and
+// rt_launch.hpp.  This file defines no other kernel (the resolve of its rgba8 form is rt_api.hip's).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: render_kernel and what it needs; the resolve / selection / known-answer kernels are rt_api.hip's
-#include "rt_host.hpp"
+#include "rt_launch.hpp"
 
 using namespace rt_host;
 

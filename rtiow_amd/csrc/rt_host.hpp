@@ -1,18 +1,15 @@
-// rt_host.hpp -- what the translation units of librtiow_hip.so share: the context, the error path, parameter validation and the ONE
-// launch path of the render kernel, which the dense, the pixel-list and the frame-batch entry points all take: plan_launch (work-block
-// size, ring, blocks of 1 024: a pure function of a few integers), magic_for, fill_common_params, run_launch (slot, clears, the
-// "nothing to trace" exit, the kernel, the tail) and launch_render (one instantiation).  An entry point keeps its own validation, its
-// own few KParams fields and its kernel choice.  rt_api.hip defines the functions declared here (and every kernel but the frame-batch
-// instantiations of render_kernel, which rt_frames.hip owns, and the capped dense ones, which rt_dense.hip owns).
-// The host-buffer entry points share their plumbing here as well: StageLayout / Stage (one device arena per context, laid out per call),
-// timed_section (a pair of events of the call's own around its kernels) and grid_256.
+// rt_host.hpp -- what EVERY translation unit of librtiow_hip.so shares: the context, the error path, parameter validation, the scene's
+// fields of the kernel-argument block (set_scene_params) and the plumbing of the host-buffer entry points: StageLayout / Stage (one device
+// arena per context, laid out per call), timed_section (a pair of events of the call's own around its kernels) and grid_256.
+// rt_api.hip defines the functions declared here.  The render kernel is not among what is shared: this header takes its argument block
+// from rt_params.hpp, and the units that launch it -- rt_api.hip, rt_frames.hip, rt_dense.hip -- add rt_launch.hpp.
 // rt_scene_core.hpp (included here for rt_context's Header) builds the scene's tables on the host, pure and HIP-free; a change to what a
 // table holds bumps its kTablesVersion and the static_assert on it in rt_api.hip, so that the hashed sources change with it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "rtiow_hip.h"
-#include "rt_kernels.hpp"
+#include "rt_params.hpp"
 #include "rt_scene_core.hpp"
 #include "rt_round_keys.hpp"
 #ifdef RTIOW_CROSSCHECK_MODES
@@ -77,6 +74,8 @@ struct rt_context {
 namespace rt_host {
 
 int validate_params(const rt_params *p);
+// what a pixel-list render accepts beyond validate_params (rt_api.hip; the adaptive driver of rt_adaptive.hip asks it too)
+int validate_pixel_list(const rt_context *ctx, const rt_camera *cam, const rt_params *p, int64_t n_pixels);
 int ensure(void **ptr, size_t *have, size_t need);
 void set_scene_params(const rt_context *ctx, rt::KParams &kp);
 
@@ -144,104 +143,5 @@ int timed_section(rt_context *ctx, const char *name, float *kernel_ms, Body body
     if (he != hipSuccess) return fail(RT_ERR_HIP, "%s: %s", name, hipGetErrorString(he));
     return RT_OK;
 }
-
-// the shipped kernel has a leaner instantiation for scenes whose tile grid (with the tiles every ray scans) has <= 64 cells
-inline bool small_grid_scene(const rt_context *ctx) { return ctx->scene.grid_dim > 0 && ctx->scene.n_global + ctx->scene.grid_dim * ctx->scene.grid_dim <= 64; }
-
-// udiv_small (rt_kernels.hpp): numerators are < d + kItemBlockLarge (spp, width) or < 65536 (rows / tile_rows), so for
-// d < 2^15 the product x * d stays below 2^32 and floor(x * M / 2^32) is the exact quotient
-inline uint32_t magic_for(long long d)
-{
-    return (d <= 1 || d >= 32768) ? 0u : (uint32_t)(0x100000000ULL / (unsigned long long)d + 1ULL);
-}
-
-// How a launch is cut into work blocks.  Block sums in LDS (use_ring): a block's consecutive samples must touch no more pixels than
-// its sums have slots -- ceil((items - 1) / spp) + 1 <= 8, or 16 on the shipped kernels (scan mode 5 without the diagnostic counters)
-// --: blocks of 256 from 37 (17) samples per pixel on, and below that the largest multiple of 64 (a block is started 64 samples at a
-// time) that fits: 192, 128 or 64 pixel-samples, down to 9 (5) samples per pixel.  Fewer, or fewer than ring_min_spp
-// (RTIOW_RING_MIN_SPP, tests): every sample is added to the frame buffer with three 64-bit atomics of its own -- a quarter of the frame
-// time at 20-32 samples per pixel (1200x675x32: 5.46 ms that way, 4.04 ms with block sums) -- in blocks of 256.
-// Blocks of kItemBlockLarge (large_blocks) for launches that are long enough for their last blocks not to matter (rt_kernels.hpp): the
-// shipped kernel, block sums in LDS, >= 147 samples per pixel (69 for scenes on the small-grid kernel), >= large_min_items
-// pixel-samples; never on pixel lists and frame batches (large_allowed).  The large-grid kernel's instantiation for blocks of 1 024
-// keeps a ring of 4 x 8: a launch that will take it is sized for 8 slots.
-struct LaunchPlan {
-    bool use_ring;
-    unsigned block_items;      // KParams::block_items: kItemBlockLarge with large_blocks, else the ring's block, else kItemBlock
-    bool large_blocks;
-};
-inline LaunchPlan plan_launch(int spp, int ring_min_spp, bool shipped_kernel, bool small_grid, bool large_allowed,
-                              unsigned long long total_items, unsigned long long large_min_items)
-{
-    const bool large_fits = shipped_kernel && large_allowed && spp >= ring_min_spp && total_items >= large_min_items &&
-                            spp >= (small_grid ? rt::kLargeMinSppSmallGrid : rt::kLargeMinSpp);
-    const unsigned slots = (shipped_kernel && (small_grid || !large_fits) ? 2u : 1u) * (unsigned)rt::kRingSlots;
-    unsigned ring_block = 0;
-    for (unsigned items = rt::kItemBlock; items >= 64u && spp >= 1; items -= 64u)
-        if ((items - 1u + (unsigned)spp - 1u) / (unsigned)spp + 1u <= slots) { ring_block = items; break; }
-    LaunchPlan plan;
-    plan.use_ring = ring_block != 0u && spp >= ring_min_spp;
-    plan.large_blocks = large_fits && plan.use_ring && ring_block == (unsigned)rt::kItemBlock;
-    plan.block_items = plan.large_blocks ? rt::kItemBlockLarge : plan.use_ring ? ring_block : (unsigned)rt::kItemBlock;
-    return plan;
-}
-
-// The KParams fields every launch path fills the same way (the rest is zero): image size, samples, depth, key, the plan, the item and
-// block counts, the scene's tables and the sums.  The sharding fields say "one shard" (rt_render_device overwrites them); rows,
-// magic_width, magic_tile, the camera(s), pix_list and the frame fields are the caller's.
-void fill_common_params(const rt_context *ctx, const rt_params *p, const LaunchPlan &plan, unsigned long long npix,
-                        unsigned long long total_items, unsigned long long n_blocks, void *d_fix, rt::KParams &kp);
-// What every launch does before its kernel: takes the other slot of per-launch state (if the launch that used it last is still running
-// on another stream, `stream` waits for it -- the host does not; a call is validated BEFORE it takes a slot), clears clear_bytes of
-// d_fix (0: RT_FLAG_ACCUMULATE) and the slot's counters, resets what rt_last_stats reports.  *trace: there is something
-// to trace; else (max_depth 0 or no items: ray_color(depth <= 0) is black without tracing, main.rs:40-42) both events are
-// recorded, the launch counts as made and reports untraced_scan_mode.
-int begin_launch(rt_context *ctx, hipStream_t stream, rt::KParams &kp, int max_depth, size_t clear_bytes, int untraced_scan_mode, bool *trace);
-
-// One launch from slot to tail; launch(&grid) picks and starts the kernel (launch_render) and sets ctx->last.scan_mode / kernel_variant.
-template <class Launch>
-int run_launch(rt_context *ctx, hipStream_t stream, rt::KParams &kp, int max_depth, size_t clear_bytes, int untraced_scan_mode, Launch launch)
-{
-    bool trace = false;
-    int grid = 0;
-    int rc = begin_launch(ctx, stream, kp, max_depth, clear_bytes, untraced_scan_mode, &trace);
-    if (rc || !trace) return rc;
-    rc = launch(&grid);
-    if (rc) return rc;
-    ctx->launched = true;
-    ctx->last.grid_blocks = grid;
-    return RT_OK;
-}
-
-template <int MODE, bool DIAG, bool SMALLGRID = false, bool U53 = false, int ITEMS = rt::kItemBlock>
-int launch_render(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, int *grid_out)
-{
-    int per_cu = ctx->blocks_per_cu;
-    if (per_cu <= 0) {
-        int occ = 0;
-        RT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, rt::render_kernel<MODE, DIAG, SMALLGRID, U53, ITEMS>, rt::kBlock, 0));
-        per_cu = occ < 1 ? 1 : (occ > 8 ? 8 : occ);
-    }
-    // persistent grid, but never more lanes than there are work items
-    long long grid = (long long)ctx->cu_count * per_cu;
-    const long long need = (long long)((kp.total_items + rt::kBlock - 1) / rt::kBlock);
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    *grid_out = (int)grid;
-    RT_HIP(hipEventRecord(ctx->ev0, stream));
-    hipLaunchKernelGGL((rt::render_kernel<MODE, DIAG, SMALLGRID, U53, ITEMS>), dim3((unsigned)grid), dim3(rt::kBlock), 0, stream, kp);
-    RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(ctx->ev1, stream));
-    return RT_OK;
-}
-
-// rt_dense.hip: the dense launch's instantiations with the capped unit-sphere redraw (ITEMS = kItemBlockDense / kItemBlockDenseLarge).
-// kDenseCappedDefault[small grid][blocks of 1 024]: the launches that take them when RTIOW_DENSE_BODY is not set.  Measured, interleaved with the
-// classic body in both orders (profiles/capped_redraw_ab.txt): small grid on blocks of 1 024 (1200x675x500) -1.1 .. -1.3 %: the default; small grid on
-// blocks of 256 -0.8 .. -0.9 % at 1200x675x100 but +0.4 .. +1.5 % on the 0.65 ms launch 400x225x10, large grid +0.3 % (blocks of 1 024) and +0.6 %
-// (blocks of 256): those three stay on the classic body and keep the capped one behind RTIOW_DENSE_BODY=capped.
-constexpr bool kDenseCappedDefault[2][2] = {{false, false}, {false, true}};
-bool dense_body_is_capped(bool small_grid, bool large_blocks);
-int launch_dense_capped(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, bool small_grid, bool large_blocks, int *grid_out);
 
 } // namespace rt_host

@@ -1,4 +1,4 @@
-// rt_kernels.hpp -- the render megakernel and the resolve kernels (gfx950).
+// rt_kernels.hpp -- the render megakernel (gfx950).
 //
 // One launch renders a shard of the image: main.rs:122-139 without to_rgba.
 //
@@ -29,12 +29,14 @@
 //     per-pixel sums in the wave's LDS, and a block goes to the frame buffer ONCE, when its last
 //     sample has finished (one 64-bit atomic per pixel and channel per block: the frame buffer sees
 //     ~3 x 64-byte memory-side requests per 256 samples).
+//
+// This file holds the kernel and nothing after it.  Its argument block and the launch constants are rt_params.hpp, the host code that
+// launches it is rt_launch.hpp; the translation units that instantiate it are rt_api.hip (the dense and the pixel-list launches),
+// rt_frames.hip and rt_dense.hip.  Every other kernel of the library lives beside its entry points, in the .hip file that launches it.
 #pragma once
+#include "rt_params.hpp"
 #include "rt_device.hpp"
 #include "rt_diag.hpp"
-#ifdef RTIOW_CROSSCHECK_MODES
-#include "xcheck/rt_xcheck_params.hpp"
-#endif
 #include <type_traits>
 #include <cstddef>
 
@@ -44,101 +46,10 @@
 
 namespace rt {
 
-struct KCamera {
-    double origin[3], llc[3], horizontal[3], vertical[3], u[3], v[3];
-    double lens_radius;
-};
-
-struct KParams {
-    KCamera cam;
-    double t_min;
-    int32_t width, height;
-    int32_t spp, sample_begin, max_depth;
-    uint32_t k0, k1;
-    int32_t tile_rows, shard_index, shard_count;
-    int32_t rows;              // compact rows of this shard
-    int32_t n_spheres;
-    int32_t use_ring;          // 1: per-wave LDS block sums (whenever a block's pixels fit the ring's pixel slots: rt_api.hip picks block_items for that); 0: every sample goes to the frame buffer directly
-    uint32_t npix;             // rows * width
-    uint32_t n_blocks;         // work blocks of block_items consecutive pixel-samples, pixel-major: item w = pixel * spp + sample
-    unsigned long long total_items;   // npix * spp
-    double inv_spp;            // 1.0 / spp (block -> first pixel)
-    double inv_width;          // 1.0 / width (first pixel -> row, column)
-    // per-lane divisions of small numerators by launch constants, as multiply-high (udiv_small below):
-    // floor(2^32 / d) + 1 for d = spp, width, tile_rows (unused where d == 1 or d >= 2^16)
-    uint32_t magic_spp, magic_width, magic_tile;
-    uint32_t block_items;      // pixel-samples per work block: ITEMS, or -- launches of few samples per pixel -- the multiple of 64 below it whose pixels
-                               // still fit the ring's pixel slots (rt_api.hip)
-    const float *filt;         // [n][4]  f32 filter record (cx, cy, cz, K')
-#ifdef RTIOW_CROSSCHECK_MODES
-    KXcheckTables x;           // the B operands of scan modes 2-4 (xcheck/rt_xcheck_params.hpp)
-#endif
-    const uint4 *btube;        // [tiles/2 + 1][64] MODE 5 B operands: 32 spheres x 16 K-slots, each column scaled by 2 / its bound (rt_device.hpp)
-    float tube_rho;            // MODE 5 radius floor
-    float scene_scale;         // MODE 5: sum over axes of the largest |coordinate| a scanned sphere reaches (error margins of grid_cells)
-    // MODE 5: the table's columns are ordered by position (rt_api.hip): tiles [0, n_global) hold the spheres every
-    // ray scans, tile n_global + iz * grid_dim + ix those whose centre lies in cell (ix, iz) of a square xz grid.
-    const double *geo_slot;    // [columns][4] exact (cx, cy, cz, r*r) in column order
-    const uint32_t *slot_orig; // [columns] place in the caller's list of the sphere in each column
-    float grid[8];             // x0, z0, 1/cell, x1, z1, y lo, y hi, largest radius of a sphere that lives in a cell
-    int32_t grid_dim;          // cells per side; 0: no grid (every tile is scanned, columns in list order)
-    unsigned long long grid_rows;      // bit k * grid_dim for every k with (k + 1) * grid_dim <= 64 (grids of <= 64 cells)
-    int32_t n_global;
-    int32_t n_tiles;
-    int32_t n_always;          // spheres that skip the filter and are always tested exactly
-    int32_t always_idx[8];
-    const double *geo;         // [n][4]  exact (cx, cy, cz, r*r)
-    const double *mat;         // [n][10] exact (1/r, param, albedo rgb, kind, 1/param, r0(1/ir), r0(ir), -)
-    unsigned long long *fix;   // [rows][width][3] exact sums
-    unsigned int *queue;       // work counter
-    unsigned long long *stats; // [0] rays [1] samples [2] candidates [3] exact roots [4] samples sent to the frame buffer one by one [8..15] diagnostic builds [16..79] rays per bounce index (DIAG)
-    const uint32_t *pix_list;  // pixel-list launches (ITEMS = kItemBlockList): [npix] global pixel numbers g = j * width + i; `fix` is then [npix][3], entry k for pix_list[k] (last member: the
-                               // offsets of everything render_kernel reads stay where they were)
-    // frame-batch launches (ITEMS = kItemBlockFrames; after pix_list for the same reason).  n_blocks = n_frames * frame_blocks and
-    // total_items = n_frames * frame_items; `fix` is [n_frames][height][width][3]
-    const KCamera *cams;       // [n_frames] cameras, DEVICE memory
-    unsigned long long frame_items;    // width * height * spp: pixel-samples of one frame
-    double inv_frame_blocks;   // 1.0 / frame_blocks (block -> frame)
-    uint32_t frame_blocks;     // work blocks per frame = ceil(frame_items / block_items): no block straddles two frames
-    uint32_t frame_pix;        // width * height: virtual pixel f * frame_pix + g is pixel g of frame f
-    int32_t sample_stride;     // frame f renders the samples [sample_begin + f * sample_stride, ... + spp)
-    // the capped dense kernels (ITEMS = kItemBlockDense / kItemBlockDenseLarge): the ten round-key pairs of (k0, k1), filled by the host (rt_round_keys.hpp)
-    // and read where they lie, in the kernel-argument block, with scalar loads (rt_device.hpp, philox4x32_10_table).  The last member, like pix_list and
-    // cams before it: the offsets of everything else stay where they were.  No other kernel reads it.
-    uint32_t round_keys[20];
-};
-
-constexpr int RT_KIND_LAMBERTIAN = 0, RT_KIND_METAL = 1, RT_KIND_DIALECTRIC = 2;
-constexpr int kBlock = 256;
-constexpr int kCandCap = 24;        // MODE 1: per-lane candidate slots
-constexpr int kScanUnroll = 8;      // MODE 1: spheres per scalar-load batch / overflow check
-constexpr int kItemBlock = 256;     // pixel-samples a wave reserves per atomic on the work counter
-// ... and 1 024 for launches of at least 2 x 10^8 pixel-samples at >= 147 samples per pixel (ceil(1023 / 147) + 1 = 8 pixels: still kRingSlots; the
-// small-grid kernel: >= 69 samples per pixel, ceil(1023 / 69) + 1 = 16 pixels, its large blocks' ring has 2 x 16 pixel slots, render_kernel below):
-// reserving a block is a returning atomic the whole wave waits for, and a block's sums are one frame-buffer request per pixel and channel:
-// a quarter of both (1200x675x500: 52.7 -> 51.3 ms; 10k spheres 1920x1080x256: 93.7 -> 91.5 ms).  Smaller launches keep 256: their last
-// blocks are the end-of-launch tail (1200x675x147 is 5 % slower with 1 024).
-constexpr int kItemBlockLarge = 1024;
-constexpr int kItemBlockList = -kItemBlock;   // as the ITEMS of render_kernel: work blocks of kItemBlock pixel-samples over a pixel list (render_kernel below)
-constexpr int kItemBlockFrames = -2 * kItemBlock;   // ... and over a BATCH OF FRAMES, one camera each (rt_render_frames_device; instantiated from rt_frames.hip only)
-// ... and the dense launch once more, with the CAPPED unit-sphere redraw (render_kernel below, PHASE 4): blocks of kItemBlock /
-// of kItemBlockLarge pixel-samples, decoded, queued and summed exactly as ITEMS = kItemBlock / kItemBlockLarge (instantiated from rt_dense.hip only)
-constexpr int kItemBlockDense = -3 * kItemBlock;
-constexpr int kItemBlockDenseLarge = -4 * kItemBlock;
-static_assert(kItemBlockLarge + 32768 < 65536, "udiv_small: numerators x < d + kItemBlockLarge with d < 2^15 keep x * d < 2^32");
-constexpr int kLargeMinSpp = 147;
-constexpr int kLargeMinSppSmallGrid = 69;
-constexpr unsigned long long kLargeMinItems = 200000000ull;   // (1200x675: blocks of 1 024 against 256 at 150 / 200 / 250 / 300 / 350 spp: +3.5 / -0.5 / -1.9 / -2.2 / -2.5 %)
-constexpr int kRingSlots = 8;       // pixels a block may touch when its sums are kept in LDS: ceil((block_items - 1) / spp) + 1 <= 8 -- blocks of 256 from
-                                    //   37 spp per launch on, of 192 / 128 / 64 down to 9 spp (rt_api.hip); below that samples go to the frame buffer one by one
-constexpr int kRingDepth = 4;       // blocks of one wave that may be unfinished at the same time (older ones: see `orphan`)
-                                    //   (the shipped scan mode's kernels: 2 blocks x 16 pixels, render_kernel below: blocks of 256 from 17 spp on, sums down to 5 spp)
-constexpr int kMatStride = 10;      // doubles per material record
-constexpr int kListCap = 126;       // MODE 5: longest list of tiles a wave scans by list; beyond, it scans the whole table
-constexpr int kSegTilesTube = 28;   // MODE 5: 14 bitmap words of 32 columns per segment (a wave's list is 5-13 tiles long)
-constexpr int kSegTiles = 36;       // matrix filter: tiles (of 16 spheres) per candidate-bitmap segment
-
-__device__ __forceinline__ D3 ld3(const double *p) { return mk(p[0], p[1], p[2]); }
+// What rt_params.hpp states of the argument block, pinned here: this file is a hashed kernel source (bench.py, kernel_source_sha)
+// and rt_params.hpp is not.
+static_assert(kParamsVersion == 1, "KParams or a launch constant changed: bump kParamsVersion in rt_params.hpp AND this assert, so that "
+              "this file -- a hashed kernel source -- changes with them");
 
 // x / d for a launch constant d >= 1 and a numerator with x < d + 65536 and x < 2^31, without a division (a `/`
 // would have the compiler keep one reciprocal per divisor in a VGPR for the whole bounce loop):
@@ -184,7 +95,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // U53 (RT_FLAG_UNIFORM53): every uniform takes two consecutive Philox words (53 random bits, as rand's gen::<f64>()) instead
 // of one word's 32 bits: same draw order, same runs; the rejection tests run in f64 as the reference writes them (the
 // integer form needs the 2^-31 lattice of single words).  An optional mode: ~2x the Philox work of the retry loops.
-// ITEMS: pixel-samples per work block (kItemBlock, or kItemBlockLarge for launches with enough samples: see rt_api.hip).
+// ITEMS: pixel-samples per work block (kItemBlock, or kItemBlockLarge for launches with enough samples: see plan_launch, rt_launch.hpp).
 // ... or kItemBlockList = -kItemBlock: blocks of kItemBlock pixel-samples over a PIXEL LIST (rt_render_pixels_device).  The launch is then a "virtual
 // image" of P.npix pixels in the order of P.pix_list; local pixel k is pixel g = P.pix_list[k] of the frame.  Only the start of a sample
 // differs (local pixel -> g -> (i, j)); the work blocks, the queue, the block sums and their write-out address pixels by their local number, so
@@ -1570,270 +1481,4 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     }
 }
 
-#ifndef RT_RENDER_KERNEL_ONLY       // (a further translation unit that instantiates render_kernel -- rt_frames.hip, rt_dense.hip -- leaves the other kernels to rt_api.hip)
-// exact sum -> f64 value (one rounding above 2^53)
-__device__ __forceinline__ double fix_to_f64(unsigned long long q)
-{
-    return ((double)(uint32_t)(q >> 32) * 4294967296.0 + (double)(uint32_t)q) * (1.0 / 4294967296.0);
-}
-
-__global__ void fix_to_f32_kernel(const unsigned long long *__restrict__ fix, float *__restrict__ out, long long count)
-{
-    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; k < count; k += stride) out[k] = (float)fix_to_f64(fix[k]);
-}
-
-// Color::to_rgba, vec3.rs:403-421, in f64, + the row flip of main.rs:141-145.
-__device__ __forceinline__ uint8_t as_u8(double x)
-{   // Rust `as u8`: saturating, NaN -> 0
-    if (!(x == x)) return 0;
-    if (x <= 0.0) return 0;
-    if (x >= 255.0) return 255;
-    return (uint8_t)x;
-}
-__device__ __forceinline__ double clamp_r(double x, double lo, double hi)
-{   // f64::clamp: NaN stays NaN
-    if (x < lo) return lo;
-    if (x > hi) return hi;
-    return x;
-}
-__global__ void resolve_rgba8_kernel(const unsigned long long *__restrict__ fix, uint8_t *__restrict__ out,
-                                     int width, int rows, double scale, int flip)
-{
-    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long npix = (long long)width * rows;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; k < npix; k += stride) {
-        const int r = (int)(k / width);
-        const int i = (int)(k - (long long)r * width);
-        const int dst = flip ? rows - 1 - r : r;
-        const unsigned long long *q = fix + k * 3;
-        uchar4 px;
-        px.x = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[0])), 0.0, 0.999));
-        px.y = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[1])), 0.0, 0.999));
-        px.z = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[2])), 0.0, 0.999));
-        px.w = 255;
-        reinterpret_cast<uchar4 *>(out)[(long long)dst * width + i] = px;
-    }
-}
-
-// Color::to_rgba with each pixel's OWN sample count (vec3.rs:403-421 with samples_per_pixel = count[p]) + the row flip: the resolve of
-// an adaptive frame.  A pixel without samples (count 0) divides by zero as the reference would: 0 * inf = NaN -> byte 0.
-__global__ void resolve_rgba8_counts_kernel(const unsigned long long *__restrict__ fix, const uint32_t *__restrict__ count,
-                                            uint8_t *__restrict__ out, int width, int rows, int flip)
-{
-    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long npix = (long long)width * rows;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (; k < npix; k += stride) {
-        const int r = (int)(k / width);
-        const int i = (int)(k - (long long)r * width);
-        const int dst = flip ? rows - 1 - r : r;
-        const unsigned long long *q = fix + k * 3;
-        const double scale = 1.0 / (double)count[k];            // vec3.rs:409
-        uchar4 px;
-        px.x = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[0])), 0.0, 0.999));
-        px.y = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[1])), 0.0, 0.999));
-        px.z = as_u8(256.0 * clamp_r(__builtin_sqrt(scale * fix_to_f64(q[2])), 0.0, 0.999));
-        px.w = 255;
-        reinterpret_cast<uchar4 *>(out)[(long long)dst * width + i] = px;
-    }
-}
-
-// ---- adaptive sampling: error estimate, selection, add-back (rtiow_hip.h, rt_select_pixels_device) ----
-// The rule, stated once for the device and the host (rt_select_pixels_host compiles this very function): is pixel p, whose sums hold n
-// samples of which `half` holds n / 2, still noisy?  Integers for the differences, then binary64 in the written order (-ffp-contract=off).
-__host__ __device__ inline bool select_noisy(const unsigned long long *fix, const unsigned long long *half, double sc, double threshold,
-                                             double dark_floor)
-{
-    double D = 0.0, S = 0.0;
-    for (int c = 0; c < 3; ++c) {
-        const long long t = (long long)(2ull * half[c] - fix[c]);          // fits: n <= 32766 samples of <= 2^48 each
-        const unsigned long long d = t < 0 ? (unsigned long long)(-t) : (unsigned long long)t;
-        D = c == 0 ? (double)d : D + (double)d;                             // ((d_r + d_g) + d_b)
-        S = c == 0 ? (double)fix[c] : S + (double)fix[c];
-    }
-    const double m = S * sc;
-    const double err = (D * sc) / __builtin_sqrt(m > dark_floor ? m : dark_floor);
-    return !(err <= threshold);
-}
-
-constexpr int kSelBlock = 256;      // pixels per workgroup of the selection kernels (consecutive pixel numbers)
-
-// (1) noisy[p] = candidate && !(err <= threshold)
-__global__ __launch_bounds__(kSelBlock) void select_noisy_kernel(const unsigned long long *__restrict__ fix, const unsigned long long *__restrict__ half,
-                                                                 const uint32_t *__restrict__ count, uint32_t npix, uint32_t n, double sc,
-                                                                 double threshold, double dark_floor, uint8_t *__restrict__ noisy)
-{
-    const uint32_t p = blockIdx.x * (uint32_t)kSelBlock + threadIdx.x;
-    if (p >= npix) return;
-    noisy[p] = (count[p] == n && select_noisy(fix + (size_t)p * 3u, half + (size_t)p * 3u, sc, threshold, dark_floor)) ? 1 : 0;
-}
-
-// (2) active[p] = candidate && (a pixel of the 3x3 neighbourhood, clipped at the frame's edges, is noisy); block_count[b] = how many in workgroup b
-__global__ __launch_bounds__(kSelBlock) void select_active_kernel(const uint8_t *__restrict__ noisy, const uint32_t *__restrict__ count,
-                                                                  int width, int height, uint32_t n, uint8_t *__restrict__ active,
-                                                                  uint32_t *__restrict__ block_count)
-{
-    __shared__ uint32_t s_cnt[kSelBlock / 64];
-    const uint32_t npix = (uint32_t)width * (uint32_t)height;
-    const uint32_t p = blockIdx.x * (uint32_t)kSelBlock + threadIdx.x;
-    bool act = false;
-    if (p < npix && count[p] == n) {
-        const int j = (int)(p / (uint32_t)width), i = (int)(p - (uint32_t)j * (uint32_t)width);
-        const int j0 = j > 0 ? j - 1 : 0, j1 = j < height - 1 ? j + 1 : height - 1;
-        const int i0 = i > 0 ? i - 1 : 0, i1 = i < width - 1 ? i + 1 : width - 1;
-        for (int jj = j0; jj <= j1; ++jj)
-            for (int ii = i0; ii <= i1; ++ii) act = act || noisy[(size_t)jj * (size_t)width + (size_t)ii] != 0;
-    }
-    if (p < npix) active[p] = act ? 1 : 0;
-    const unsigned long long m = __ballot(act);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-}
-
-// (3) exclusive scan of the workgroups' counts, in place, by ONE workgroup (chunks of 1 024 with a running carry); the total -> *n_out
-__global__ __launch_bounds__(1024) void select_scan_kernel(uint32_t *__restrict__ block_count, uint32_t n_blocks, uint32_t *__restrict__ n_out)
-{
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid == 0) s_carry = 0u;
-    __syncthreads();
-    for (uint32_t base = 0; base < n_blocks; base += 1024u) {
-        const uint32_t k = base + tid;
-        const uint32_t v = k < n_blocks ? block_count[k] : 0u;
-        uint32_t x = v;                                                     // inclusive scan within the wave
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63u) s_wave[wave] = x;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-        if (k < n_blocks) block_count[k] = before + x - v;
-        __syncthreads();
-        if (tid == 1023u) s_carry = before + x;
-        __syncthreads();
-    }
-    if (tid == 0) *n_out = s_carry;
-}
-
-// (4) the active pixels' numbers, ascending: workgroup offset + the waves before this one + the rank within the wave (ballot + v_mbcnt)
-__global__ __launch_bounds__(kSelBlock) void select_write_kernel(const uint8_t *__restrict__ active, const uint32_t *__restrict__ block_offset,
-                                                                 uint32_t npix, uint32_t *__restrict__ list)
-{
-    __shared__ uint32_t s_cnt[kSelBlock / 64];
-    const uint32_t p = blockIdx.x * (uint32_t)kSelBlock + threadIdx.x;
-    const bool act = p < npix && active[p] != 0;
-    const unsigned long long m = __ballot(act);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t at = block_offset[blockIdx.x];
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) at += s_cnt[w];
-    at += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (act) list[at] = p;                                                  // (at < the total <= npix = the list's capacity)
-}
-
-// One pass's compact sums back into the frame's state at the listed pixels (no duplicates in a selection's list): fix += pass,
-// half += pass on the even-numbered passes (half != nullptr), count += step.
-__global__ void add_back_kernel(const uint32_t *__restrict__ list, uint32_t n_list, const unsigned long long *__restrict__ pass,
-                                unsigned long long *__restrict__ fix, unsigned long long *__restrict__ half, uint32_t *__restrict__ count,
-                                uint32_t step)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_list) return;
-    const size_t g = list[k];
-    for (int c = 0; c < 3; ++c) {
-        const unsigned long long v = pass[(size_t)k * 3u + c];
-        fix[g * 3u + c] += v;
-        if (half) half[g * 3u + c] += v;
-    }
-    count[g] += step;
-}
-
-__global__ void fill_u32_kernel(uint32_t *__restrict__ dst, uint32_t value, uint32_t n)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) dst[k] = value;
-}
-
-// a launch's counters (KParams::stats [0..4]) added to a running total: rt_render_adaptive reads the total once, at the end
-__global__ void stats_accumulate_kernel(const unsigned long long *__restrict__ stats, unsigned long long *__restrict__ total)
-{
-    if (threadIdx.x < 5) total[threadIdx.x] += stats[threadIdx.x];
-}
-
-__global__ void philox_kat_kernel(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                  uint32_t k0, uint32_t k1, uint32_t *out)
-{
-    const U4 r = philox4x32_10(c0, c1, c2, c3, k0, k1);
-    out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
-}
-
-
-// One tile of the MODE 5 (tube) filter exactly as the render kernel evaluates it: 64 rays against
-// the 32 columns of `tile`.  h_out[ray][column][k] = lambda u_k.(c - o) as the matrix pipe returns it;
-// rows_out[ray] = (lambda u_1, lambda u_2, t_1, t_2, sane).
-__global__ __launch_bounds__(64) void tube_products_kernel(const double *o, const double *d, const uint4 *tile, float rho,
-                                                         float *h_out, float *rows_out)
-{
-    typedef float f32x16 __attribute__((ext_vector_type(16)));
-    __shared__ uint4 stage[64 * 4];
-    const int lane = threadIdx.x, col = lane & 31, hh = lane >> 5;
-    const TubeRay T = make_tube(mk(o[3 * lane], o[3 * lane + 1], o[3 * lane + 2]),
-                                mk(d[3 * lane], d[3 * lane + 1], d[3 * lane + 2]), rho);
-    for (int k = 0; k < 2; ++k) for (int i = 0; i < 3; ++i) rows_out[lane * 9 + 3 * k + i] = T.u[k][i];
-    rows_out[lane * 9 + 6] = T.t[0]; rows_out[lane * 9 + 7] = T.t[1]; rows_out[lane * 9 + 8] = T.sane ? 1.0f : 0.0f;
-    bf16x8 A[4];
-    uint32_t w[2][8];
-    tube_a_words(T, w);
-    tube_stage_operands(stage, lane, w, A);
-    const bf16x8 b = __builtin_bit_cast(bf16x8, tile[lane]);
-    const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int G = 0; G < 4; ++G) {
-        const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[G], b, zero16, 0, 0, 0);
-        for (int bb = 0; bb < 2; ++bb)
-            for (int j = 0; j < 4; ++j) {
-                const int ray = 16 * G + 8 * bb + 4 * hh + j;
-                h_out[(ray * 32 + col) * 2 + 0] = acc[8 * bb + j];
-                h_out[(ray * 32 + col) * 2 + 1] = acc[8 * bb + 4 + j];
-            }
-    }
-}
-
-__global__ void f64_div_sqrt_kernel(const double *a, const double *b, int n, double *q, double *r)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) { q[k] = a[k] / b[k]; r[k] = __builtin_sqrt(a[k]); }
-}
-
-// known-answer hook: the kernel's own quantize() (contract C5) on n radiance values
-__global__ void quantize_kernel(const double *x, int n, unsigned long long *q)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) q[k] = quantize(x[k]);
-}
-
-// known-answer hook: the kernel's own rejection tests and word -> uniform conversions on n triples of Philox words.
-// acc[k] = unit_sphere_accepts(w) | unit_disk_accepts(w.x, w.y) << 1; uni[k] = (u01(w.x), u11(w.x), u11(w.y), u11(w.z))
-__global__ void unit_accept_kernel(const uint32_t *w, int n, uint32_t *acc, double *uni)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) {
-        const uint32_t x = w[3 * k], y = w[3 * k + 1], z = w[3 * k + 2];
-        acc[k] = (unit_sphere_accepts(x, y, z) ? 1u : 0u) | (unit_disk_accepts(x, y) ? 2u : 0u);
-        uni[4 * k] = u01(x); uni[4 * k + 1] = u11(x); uni[4 * k + 2] = u11(y); uni[4 * k + 3] = u11(z);
-    }
-}
-
-#endif // RT_RENDER_KERNEL_ONLY
-
 } // namespace rt
-
-#if defined(RTIOW_CROSSCHECK_MODES) && !defined(RT_RENDER_KERNEL_ONLY)
-#include "xcheck/rt_xcheck_kernels.hpp"    // known-answer kernels of modes 2-4
-#endif

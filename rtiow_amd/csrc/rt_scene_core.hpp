@@ -21,7 +21,7 @@ namespace rt_scene {
 // is what moves kernel_source_sha and keeps recorded counters from being replayed against other tables.
 constexpr int kTablesVersion = 1;
 
-// What the build shares with the device code, stated here and pinned against rt:: (rt_device.hpp, rt_kernels.hpp) by static_asserts in
+// What the build shares with the device code, stated here and pinned against rt:: (rt_device.hpp, rt_params.hpp) by static_asserts in
 // rt_api.hip, the one place that sees both sides.
 constexpr float kUnitRoundoff = 5.9604644775390625e-08f;                // 2^-24
 constexpr float kFilterKU = 128.0f * kUnitRoundoff;                     // 2^-17
@@ -154,7 +154,7 @@ struct Knobs {
 // Where MODE 5 puts each sphere in its table of columns (tiles of 32), and the grid the kernel finds tiles with.
 struct TileLayout {
     int grid_dim = 0, n_global = 0;
-    float grid[8] = {};             // rt_kernels.hpp, KParams::grid
+    float grid[8] = {};             // rt_params.hpp, KParams::grid
     float scale = 0.0f;             // sum over axes of the largest |coordinate| of the grid's box
     std::vector<int> slot_of;       // column -> place in the caller's list, -1 = padding; a multiple of 32 long
 };

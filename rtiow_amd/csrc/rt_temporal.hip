@@ -17,7 +17,6 @@
 #include <cmath>
 #include <vector>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: no kernel of rt_api.hip is instantiated here
 #include "rt_host.hpp"
 #include "rt_temporal_core.hpp"
 

@@ -21,7 +21,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: KParams and the constants; rt_api.hip owns the kernels defined there
 #include "rt_host.hpp"
 #ifdef RT_TRACE_COUNT
 #define RT_SCAN_COUNT               // rt_first_hit.hpp: the scan's diagnostic counters (tools/trace_bench.py --counts)

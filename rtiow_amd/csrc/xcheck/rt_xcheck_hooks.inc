@@ -1,6 +1,6 @@
 // rt_xcheck_hooks.inc -- part of the CROSS-CHECK build only (-DRTIOW_CROSSCHECK_MODES: tools/librtiow_hip_xcheck.so, a test artefact).
 // Host side of scan modes 2-4, the earlier matrix-pipe forms of the sphere-scan filter (DESIGN.md section 5.2); the product library carries
-// modes 0, 1 and 5 and never includes this file.  Included inside rt_api.hip's extern "C" block: the known-answer hooks the header declares under RTIOW_CROSSCHECK_MODES
+// modes 0, 1 and 5 and never includes this file.  Included inside rt_selftest.hip's extern "C" block: the known-answer hooks the header declares under RTIOW_CROSSCHECK_MODES
 // (those of modes 2-4, and rt_grid_cells_device: the shipped mode's grid footprint, kept out of the product ABI).
 int rt_filter_products_device(rt_context *ctx, const float *r1, const float *r2, const float *s,
                                int32_t bf16x3, float *out_hb, float *out_q)

@@ -1,6 +1,7 @@
 // rt_xcheck_host.inc -- part of the CROSS-CHECK build only (-DRTIOW_CROSSCHECK_MODES: tools/librtiow_hip_xcheck.so, a test artefact).
 // Host side of scan modes 2-4, the earlier matrix-pipe forms of the sphere-scan filter (DESIGN.md section 5.2); the product library carries
-// modes 0, 1 and 5 and never includes this file.  Included inside rt_api.hip's anonymous namespace (after upload_table; filter_kprime and host_split_bf16x3 are rt_scene_core.hpp's): the B operands of modes 2-4.
+// modes 0, 1 and 5 and never includes this file.  Included inside namespace rt_host in rt_api.hip (after upload_table; filter_kprime and host_split_bf16x3 are rt_scene_core.hpp's): the B operands of modes 2-4.
+// lifted_column and lifted_tile are declared in rt_xcheck_host_ctx.hpp: rt_filter_lifted_device (rt_xcheck_hooks.inc, rt_selftest.hip) calls them too.
 // ---- MODE 4 (lifted form, rt_device.hpp): the per-sphere column C_0..C_10 and its 64 K-slots ----
 // `s == nullptr` (padding) or `never` (a sphere on the always-exact list): a column no ray keeps.
 // Every C_k is computed in f64 from the exact centre/radius and rounded once; C_10 = -K' is
@@ -19,7 +20,7 @@ void lifted_column(const rt_sphere *s, bool never, float C[rt::kLiftTerms])
     C[10] = -kp;
 }
 // B-side dwords of the slot layout documented at lifted_a_words()
-void lifted_b_words(const float C[rt::kLiftTerms], uint32_t w[32])
+static void lifted_b_words(const float C[rt::kLiftTerms], uint32_t w[32])
 {
     for (int p = 0; p < 9; ++p) {
         uint32_t y[3]; rt_scene::host_split_bf16x3(C[1 + p], y);
@@ -48,7 +49,7 @@ void lifted_tile(const float C[16][rt::kLiftTerms], uint4 out[128])
 
 
 // the device tables of the scan mode the context runs (2: f32 B operand + K'; 3: three-piece bf16 B operand + K' at the larger KU; 4: lifted form)
-int xcheck_upload_tables(rt_context *ctx, const rt_sphere *spheres, int n, const rt_scene::Tables &T)
+static int xcheck_upload_tables(rt_context *ctx, const rt_sphere *spheres, int n, const rt_scene::Tables &T)
 {
     int rc = RT_OK;
     const std::vector<float> &filt = T.filt;

@@ -4,6 +4,7 @@
 // the shipped mode's grid footprint (rt_grid_cells_device).
 #pragma once
 namespace rt {
+typedef float f32x4 __attribute__((ext_vector_type(4)));    // (rt_kernels.hpp has the same typedef; rt_selftest.hip, which includes this file, does not see that one)
 // Known-answer hook for the matrix forms of the filter: one wave, 64 ray rows x 16 sphere
 // columns; returns HB and Q exactly as the render kernel's tiles compute them
 // (bf16x3 != 0: v_mfma_f32_16x16x32_bf16 on three-piece operands; else v_mfma_f32_16x16x4_f32).

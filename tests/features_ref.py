@@ -94,7 +94,7 @@ def same(got, want):
 
 
 def fix_to_f64(q):
-    """rt_kernels.hpp fix_to_f64 on a u64 array: ((f64)(q >> 32) * 2^32 + (f64)(u32)q) * 2^-32."""
+    """rt_api.hip fix_to_f64 on a u64 array: ((f64)(q >> 32) * 2^32 + (f64)(u32)q) * 2^-32."""
     q = np.asarray(q, dtype=np.uint64)
     return ((q >> np.uint64(32)).astype(np.float64) * 4294967296.0 + (q & np.uint64(0xFFFFFFFF)).astype(np.float64)) * (1.0 / 4294967296.0)
 

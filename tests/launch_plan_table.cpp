@@ -2,8 +2,7 @@
 // only and compares every line with its own restatement of the rule).  No device, no HIP call.
 #include <cstdio>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: no kernel is defined, none is instantiated here
-#include "rt_host.hpp"
+#include "rt_launch.hpp"
 
 int main()
 {

@@ -4,7 +4,6 @@
 #include <cstdio>
 #include <vector>
 
-#define RT_RENDER_KERNEL_ONLY       // rt_kernels.hpp: no kernel is defined, none is instantiated here
 #include "rt_host.hpp"
 
 static void row(const char *name, const std::vector<size_t> &sizes)

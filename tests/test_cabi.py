@@ -112,6 +112,6 @@ def test_product_library_carries_no_crosscheck_kernels():
         xmodes = set(int(m) for m in re.findall(rb"_ZN2rt13render_kernelILi(\d)E", open(x, "rb").read()))
         assert xmodes == {0, 1, 2, 3, 4, 5}, xmodes
     # ... and the product sources hold none of their definitions (only the include stubs under RTIOW_CROSSCHECK_MODES)
-    for rel in ("rt_kernels.hpp", "rt_device.hpp", "rt_api.hip"):
+    for rel in ("rt_kernels.hpp", "rt_device.hpp", "rt_api.hip", "rt_params.hpp", "rt_launch.hpp", "rt_host.hpp", "rt_adaptive.hip", "rt_selftest.hip"):
         src = open(os.path.join(ROOT, "rtiow_amd", "csrc", rel)).read()
         assert "LiftedRay make_lifted" not in src and "a_operand_bf16x3(float" not in src and "auto check_sign_half" not in src, rel

@@ -1,5 +1,5 @@
 """The three launch paths of the render kernel -- dense (rt_render_device), pixel list (rt_render_pixels_device) and frame batch
-(rt_render_frames_device) -- share one plan, one parameter fill, one prologue and one tail (rt_host.hpp).  Through the public API
+(rt_render_frames_device) -- share one plan, one parameter fill, one prologue and one tail (rt_launch.hpp).  Through the public API
 only: the same frame through all three, launched back to back on one context and one stream, is the same bits (and Oracle B's), and
 rt_last_stats reports per path what it always did -- the kernel variant, the scan mode (after a max_depth 0 call too: 0, 0 and 5),
 the samples and the grid.  A rejected RT_FLAG_UNIFORM53 combination touches nothing."""

@@ -15,7 +15,7 @@ import rtiow_amd as rt
 from rtiow_amd import _ffi
 from grid_model import minimal_scale, model_grid_cells
 
-K_LIST_CAP = 126           # rt_kernels.hpp kListCap: the longest tile list a wave scans by list
+K_LIST_CAP = 126           # rt_params.hpp kListCap: the longest tile list a wave scans by list
 K_SEG_TILES = 14           # tiles per segment of the tile loop (kSegTilesTube / 2)
 
 

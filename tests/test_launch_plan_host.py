@@ -1,4 +1,4 @@
-"""The launch plan without a GPU: rt_host::plan_launch (rt_host.hpp) decides the work-block size, whether block sums are kept in
+"""The launch plan without a GPU: rt_host::plan_launch (rt_launch.hpp) decides the work-block size, whether block sums are kept in
 the LDS ring, and whether a launch takes blocks of 1 024 -- for the dense, the pixel-list and the frame-batch launches alike.  It is
 a pure function of a few integers, so tests/launch_plan_table.cpp (host code only, its own main) prints it for a table of inputs and
 every line is compared with a restatement that does not copy the formula: the pixels a block of `items` consecutive pixel-samples
