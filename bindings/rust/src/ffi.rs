@@ -199,6 +199,62 @@ const _: () = assert!(32 == size_of::<rt_rays>());
 const _: () = assert!(offset_of!(rt_hits, front_face) == 32);
 const _: () = assert!(40 == size_of::<rt_hits>());
 
+/// `RT_SCATTER_*`: what `rt_scatter` writes to `status`.
+pub const RT_SCATTER_ABSORBED: u8 = 0;
+pub const RT_SCATTER_SCATTERED: u8 = 1;
+pub const RT_SCATTER_MISS: u8 = 2;
+pub const RT_SCATTER_BAD_INDEX: u8 = 3;
+
+/// The paths of `rt_camera_rays`, structure-of-arrays: `pixel` and `sample` `[n]` in; `origin`, `dir` `[n][3]` and `event` `[n]` out.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_camera_batch {
+    pub pixel: *const u32,
+    pub sample: *const u32,
+    pub origin: *mut f64,
+    pub dir: *mut f64,
+    pub event: *mut u32,
+    pub n: i64,
+}
+
+/// The paths of `rt_scatter`: the incoming `dir`, the hit as `rt_trace_rays` wrote it, the path's `(pixel, sample)` and its `event`
+/// (in and out); `out_origin`, `out_dir` (may be `dir`), `attenuation` `[n][3]` and `status` `[n]` out.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_scatter_batch {
+    pub dir: *const f64,
+    pub index: *const i32,
+    pub point: *const f64,
+    pub normal: *const f64,
+    pub front_face: *const u8,
+    pub pixel: *const u32,
+    pub sample: *const u32,
+    pub event: *mut u32,
+    pub out_origin: *mut f64,
+    pub out_dir: *mut f64,
+    pub attenuation: *mut f64,
+    pub status: *mut u8,
+    pub n: i64,
+}
+
+/// The samples of `rt_accumulate`: `pixel` `[n]`, `weight` `[n][3]`, `sky_dir` `[n][3]` or null, `select` `[n]` or null.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_accumulate_batch {
+    pub pixel: *const u32,
+    pub weight: *const f64,
+    pub sky_dir: *const f64,
+    pub select: *const u8,
+    pub n: i64,
+}
+
+const _: () = assert!(offset_of!(rt_camera_batch, n) == 40);
+const _: () = assert!(48 == size_of::<rt_camera_batch>());
+const _: () = assert!(offset_of!(rt_scatter_batch, n) == 96);
+const _: () = assert!(104 == size_of::<rt_scatter_batch>());
+const _: () = assert!(offset_of!(rt_accumulate_batch, n) == 32);
+const _: () = assert!(40 == size_of::<rt_accumulate_batch>());
+
 #[link(name = "rtiow_hip")]
 extern "C" {
     pub fn rt_create(device_id: i32, out: *mut *mut rt_context) -> i32;
@@ -293,6 +349,15 @@ extern "C" {
     pub fn rt_trace_rays(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, hits: *const rt_hits, kernel_ms: *mut f32) -> i32;
     pub fn rt_occluded_device(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, d_occluded: *mut c_void, stream: *mut c_void) -> i32;
     pub fn rt_occluded(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, occluded: *mut u8, kernel_ms: *mut f32) -> i32;
+    pub fn rt_camera_rays_device(ctx: *mut rt_context, cam: *const rt_camera, width: i32, height: i32, seed: u64, flags: u32,
+                                 batch: *const rt_camera_batch, stream: *mut c_void) -> i32;
+    pub fn rt_camera_rays(ctx: *mut rt_context, cam: *const rt_camera, width: i32, height: i32, seed: u64, flags: u32,
+                          batch: *const rt_camera_batch, kernel_ms: *mut f32) -> i32;
+    pub fn rt_scatter_device(ctx: *mut rt_context, seed: u64, flags: u32, batch: *const rt_scatter_batch, stream: *mut c_void) -> i32;
+    pub fn rt_scatter(ctx: *mut rt_context, seed: u64, flags: u32, batch: *const rt_scatter_batch, kernel_ms: *mut f32) -> i32;
+    pub fn rt_accumulate_device(ctx: *mut rt_context, batch: *const rt_accumulate_batch, d_fix: *mut c_void, npix: i64,
+                                stream: *mut c_void) -> i32;
+    pub fn rt_accumulate(ctx: *mut rt_context, batch: *const rt_accumulate_batch, fix: *mut u64, npix: i64, kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -618,6 +618,95 @@ int rt_trace_rays(rt_context *ctx, const rt_rays *rays, double t_min, const rt_h
 int rt_occluded_device(rt_context *ctx, const rt_rays *rays, double t_min, void *d_occluded, void *stream);
 int rt_occluded(rt_context *ctx, const rt_rays *rays, double t_min, uint8_t *occluded, float *kernel_ms);
 
+/* ---- wavefront path steps: camera rays, material scatter, accumulate ---------- */
+
+/* The three things a path needs besides its closest hit, as calls of their own, so that a wavefront integrator driven from outside --
+ * camera rays -> loop { rt_trace_rays; accumulate the misses; scatter; throughput *= attenuation } -- reproduces the exact sums of
+ * rt_render bit for bit, and whatever the megakernel does not do (AOVs per bounce, a direct-only pass, the caller's own termination
+ * rule, extra radiance terms) is a few lines of caller code on top.  DESIGN.md section 18.  Structure-of-arrays like the ray queries:
+ * the arrays of one step are named by one struct, inputs and outputs alike.
+ *
+ * The random stream of a path: Philox key `seed`, counter (pixel, sample, event, 0) with pixel the global number
+ * g = j * width + i (j = 0 the BOTTOM row) and event the index of the NEXT UNUSED block of that (pixel, sample).  event is the only
+ * random state a path carries between steps: the camera step gives it, every scatter advances it.  Draws are the default stream's:
+ * u01(w) = w * 2^-32, u11(w) = (int32_t)w * 2^-31.  flags: 0; RT_FLAG_UNIFORM53 (not built for these steps) and every other bit is
+ * RT_ERR_INVALID_ARGUMENT.
+ * IEEE binary64, the reference's operation order, no fused multiply-add; a NaN in a double output is written as the quiet NaN
+ * 0x7FF8000000000000, as the ray queries write it.  A result is a pure function of its inputs: the same bits from the device and the
+ * host forms, whatever the launch's size (RTIOW_SHADE_GRID_BLOCKS=k, a diagnostic knob read per call: at most k workgroups) and
+ * wherever in the batch a path stands. */
+
+/* sample_ray: main.rs:131-134 + Camera::get_ray, camera.rs:47-54.  Block 0 of (pixel[k], sample[k]) = (u jitter, v jitter, lens x,
+ * lens y); every further random_in_unit_disk try (vec3.rs:59-68) takes the next two words, on into blocks 1, 2, ...; i = pixel % width,
+ * j = pixel / width, u = (i + e0) / (width - 1), v = (j + e1) / (height - 1).  event[k] = 1 + ceil((tries - 1) / 2).  Exactly the camera
+ * ray rt_render traces for that pixel and sample index.  Needs no uploaded scene. */
+typedef struct {
+    const uint32_t *pixel;   /* [n]    in                                            */
+    const uint32_t *sample;  /* [n]    in                                            */
+    double   *origin;        /* [n][3] out                                           */
+    double   *dir;           /* [n][3] out, not normalised                           */
+    uint32_t *event;         /* [n]    out: the next unused block                    */
+    int64_t n;
+} rt_camera_batch;
+
+/* Scatter::scatter of materials.rs (:21-31 Lambertian, :48-62 Metal, :76-105 Dialectric) in the order Oracle B states it, for the hit
+ * (index, point, normal, front_face) exactly as rt_trace_rays writes it and the incoming direction dir.  The material is the uploaded
+ * sphere index[k].  Lambertian and Metal take one run of unit-sphere tries (vec3.rs:37-45) of three consecutive words each, starting at
+ * block event[k], to acceptance: event += ceil(3 tries / 4); Metal draws whatever its fuzz, as the reference does.  The Dialectric draws
+ * one word of one block, only when it can refract: event += 1 then, unchanged otherwise (total internal reflection).  A Lambertian
+ * whose normal + unit vector is near zero (vec3.rs:111-114) scatters along the normal. */
+enum { RT_SCATTER_ABSORBED = 0,    /* Metal with dot(scattered, normal) <= 0: attenuation written as zeros, out_origin / out_dir NOT written, event advanced */
+       RT_SCATTER_SCATTERED = 1,   /* out_origin = point, out_dir, attenuation and event written                                                          */
+       RT_SCATTER_MISS = 2,        /* index == -1: nothing but the status written, event unchanged                                                        */
+       RT_SCATTER_BAD_INDEX = 3 }; /* index < -1 or >= the sphere count: nothing read from the scene, nothing but the status written                      */
+typedef struct {
+    const double  *dir;         /* [n][3] in: the direction of the ray that hit                  */
+    const int32_t *index;       /* [n]    in: rt_hits.index                                      */
+    const double  *point;       /* [n][3] in: rt_hits.point                                      */
+    const double  *normal;      /* [n][3] in: rt_hits.normal                                     */
+    const uint8_t *front_face;  /* [n]    in: rt_hits.front_face                                 */
+    const uint32_t *pixel;      /* [n]    in                                                     */
+    const uint32_t *sample;     /* [n]    in                                                     */
+    uint32_t *event;            /* [n]    in and out                                             */
+    double   *out_origin;       /* [n][3] out: may be the very array the next trace reads        */
+    double   *out_dir;          /* [n][3] out: may be `dir` itself (a path reads its own elements before it writes them); no other overlap */
+    double   *attenuation;      /* [n][3] out                                                    */
+    uint8_t  *status;           /* [n]    out: RT_SCATTER_*                                      */
+    int64_t n;
+} rt_scatter_batch;
+
+/* Contract C5 for samples the caller finishes: per channel, quantize(weight * sky(sky_dir)) is added to d_fix[pixel[k]] -- the very
+ * buffer rt_render_device fills and rt_resolve_rgba8 reads -- with one 64-bit atomic add.  sky: main.rs:54-56 (unit_direction = unit_vector(dir),
+ * t = 0.5 * (unit_direction.y + 1.0), (1, 1, 1) * (1.0 - t) + (0.5, 0.7, 1.0) * t), multiplied as Oracle B's mulv(throughput, sky).  With
+ * sky_dir NULL the value is weight itself.  Paths with select[k] == 0 (select given) or pixel[k] >= npix add nothing and touch no memory:
+ * documented, not an error.  Integer sums: the result does not depend on order, on how a batch is split, or on the streams the calls run
+ * on (the caller orders zeroing before and reading after, as for rt_render_device's passes).  Needs no uploaded scene. */
+typedef struct {
+    const uint32_t *pixel;      /* [n]    in: entry of d_fix                                     */
+    const double   *weight;     /* [n][3] in                                                     */
+    const double   *sky_dir;    /* [n][3] in, or NULL                                            */
+    const uint8_t  *select;     /* [n]    in, or NULL: every path                                */
+    int64_t n;
+} rt_accumulate_batch;
+
+/* RT_ERR_INVALID_ARGUMENT from every form, found before anything is touched, the checks that need no context first: a NULL camera or
+ * batch struct, a NULL fix buffer; n < 0 or n > 2^31; with n > 0 a NULL array other than sky_dir and select; width or height < 2;
+ * npix <= 0 or > 2^32; flags != 0; then a NULL context.  RT_ERR_NO_SCENE from the scatter step before an upload.  n == 0 then succeeds and
+ * touches nothing.
+ * Device forms: asynchronous on `stream`; the structs (and the camera) are HOST pointers read during the call, the arrays they name device
+ * pointers, 8-byte aligned (4 for the 32-bit ones).  A step takes NONE of the context's launch slots and rt_last_stats does not report on it.
+ * Host-buffer forms: copy in, run on the device, copy out; synchronous; what a step does not write keeps the caller's bytes; kernel_ms
+ * (may be NULL): the kernel's time, from a pair of events the call creates and destroys itself. */
+int rt_camera_rays_device(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, uint32_t flags,
+                          const rt_camera_batch *batch, void *stream);
+int rt_camera_rays(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, uint32_t flags,
+                   const rt_camera_batch *batch, float *kernel_ms);
+int rt_scatter_device(rt_context *ctx, uint64_t seed, uint32_t flags, const rt_scatter_batch *batch, void *stream);
+int rt_scatter(rt_context *ctx, uint64_t seed, uint32_t flags, const rt_scatter_batch *batch, float *kernel_ms);
+/* d_fix / fix: [npix][3] u64 exact sums, added to. */
+int rt_accumulate_device(rt_context *ctx, const rt_accumulate_batch *batch, void *d_fix, int64_t npix, void *stream);
+int rt_accumulate(rt_context *ctx, const rt_accumulate_batch *batch, uint64_t *fix, int64_t npix, float *kernel_ms);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

@@ -60,6 +60,20 @@ class rt_hits(C.Structure):
     _fields_ = [("index", C.c_void_p), ("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("front_face", C.c_void_p)]
 
 
+class rt_camera_batch(C.Structure):
+    _fields_ = [("pixel", C.c_void_p), ("sample", C.c_void_p), ("origin", C.c_void_p), ("dir", C.c_void_p), ("event", C.c_void_p), ("n", C.c_int64)]
+
+
+class rt_scatter_batch(C.Structure):
+    _fields_ = [("dir", C.c_void_p), ("index", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("front_face", C.c_void_p),
+                ("pixel", C.c_void_p), ("sample", C.c_void_p), ("event", C.c_void_p), ("out_origin", C.c_void_p), ("out_dir", C.c_void_p),
+                ("attenuation", C.c_void_p), ("status", C.c_void_p), ("n", C.c_int64)]
+
+
+class rt_accumulate_batch(C.Structure):
+    _fields_ = [("pixel", C.c_void_p), ("weight", C.c_void_p), ("sky_dir", C.c_void_p), ("select", C.c_void_p), ("n", C.c_int64)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -72,6 +86,7 @@ RT_DENOISE_MAX_LEVELS = 8
 RT_DENOISE_ALBEDO_FLOOR = 0.015625
 RT_TEMPORAL_CLAMP = 0x1
 RT_TEMPORAL_MAX_LEN = 65535
+RT_SCATTER_ABSORBED, RT_SCATTER_SCATTERED, RT_SCATTER_MISS, RT_SCATTER_BAD_INDEX = 0, 1, 2, 3
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
@@ -116,6 +131,13 @@ SYMBOLS = [
     ("rt_trace_rays", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, C.POINTER(rt_hits), C.POINTER(C.c_float)]),
     ("rt_occluded_device", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, _VP, _VP]),
     ("rt_occluded", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, _VP, C.POINTER(C.c_float)]),
+    ("rt_camera_rays_device", C.c_int, [_VP, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(rt_camera_batch), _VP]),
+    ("rt_camera_rays", C.c_int, [_VP, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.POINTER(rt_camera_batch),
+                        C.POINTER(C.c_float)]),
+    ("rt_scatter_device", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.POINTER(rt_scatter_batch), _VP]),
+    ("rt_scatter", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.POINTER(rt_scatter_batch), C.POINTER(C.c_float)]),
+    ("rt_accumulate_device", C.c_int, [_VP, C.POINTER(rt_accumulate_batch), _VP, C.c_int64, _VP]),
+    ("rt_accumulate", C.c_int, [_VP, C.POINTER(rt_accumulate_batch), _VP, C.c_int64, C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

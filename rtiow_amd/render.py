@@ -227,6 +227,114 @@ def occluded_torch(renderer, origins, dirs, t_max=None, t_min=1e-4):
                                  torch.cuda.current_stream().cuda_stream)
     return {"occluded": occ}
 
+# -- wavefront path steps on torch tensors (rt_camera_rays / rt_scatter / rt_accumulate) ------------------------
+# The 32-bit unsigned arrays of the C ABI (pixel, sample, event) travel as int32 tensors and the u64 sums as an int64 tensor, each
+# holding the same bits.
+
+def _torch_check(torch, renderer, items):
+    """items: (name, tensor, dtype, shape); every tensor contiguous, on the renderer's device."""
+    for name, x, dtype, shape in items:
+        if not x.is_cuda or x.device.index != renderer.device_id:
+            raise ValueError(f"{name} must be on the renderer's device cuda:{renderer.device_id} (is on {x.device})")
+        if x.dtype != dtype or not x.is_contiguous() or tuple(x.shape) != shape:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} (is {x.dtype} {tuple(x.shape)})")
+
+
+def camera_rays_torch(renderer, cam, width, height, seed, pixel, sample):
+    """Renderer.camera_rays on torch tensors, on torch.cuda.current_stream(): pixel, sample int32 [n] -> a dict of "origin", "dir"
+    float64 [n, 3] and "event" int32 [n]."""
+    import torch
+    n = pixel.shape[0] if pixel.dim() == 1 else -1
+    _torch_check(torch, renderer, [("pixel", pixel, torch.int32, (n,)), ("sample", sample, torch.int32, (n,))])
+    dev = pixel.device
+    out = {"origin": torch.empty((n, 3), dtype=torch.float64, device=dev), "dir": torch.empty((n, 3), dtype=torch.float64, device=dev),
+           "event": torch.empty(n, dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        renderer.camera_rays_device(cam, width, height, seed, n, pixel.data_ptr(), sample.data_ptr(), out["origin"].data_ptr(),
+                                    out["dir"].data_ptr(), out["event"].data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def scatter_torch(renderer, seed, dirs, index, point, normal, front_face, pixel, sample, event, out=None):
+    """Renderer.scatter on torch tensors, on torch.cuda.current_stream().  dirs, point, normal float64 [n, 3]; index, pixel, sample, event
+    int32 [n]; front_face uint8 [n] -- the hit exactly as trace_rays_torch returns it.  `event` is advanced in place.  out (optional): a
+    dict of tensors to write to, any of "out_origin", "out_dir" (may be `dirs` itself), "attenuation" float64 [n, 3], "status" uint8 [n];
+    what it does not name is allocated (uninitialised where the step does not write).  Returns the dict of the four outputs."""
+    import torch
+    n = index.shape[0] if index.dim() == 1 else -1
+    dev = index.device
+    res = dict(out or {})
+    for name in ("out_origin", "out_dir", "attenuation"):
+        if name not in res:
+            res[name] = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    if "status" not in res:
+        res["status"] = torch.empty(n, dtype=torch.uint8, device=dev)
+    _torch_check(torch, renderer, [("dirs", dirs, torch.float64, (n, 3)), ("index", index, torch.int32, (n,)), ("point", point, torch.float64, (n, 3)),
+                                   ("normal", normal, torch.float64, (n, 3)), ("front_face", front_face, torch.uint8, (n,)),
+                                   ("pixel", pixel, torch.int32, (n,)), ("sample", sample, torch.int32, (n,)), ("event", event, torch.int32, (n,)),
+                                   ("out_origin", res["out_origin"], torch.float64, (n, 3)), ("out_dir", res["out_dir"], torch.float64, (n, 3)),
+                                   ("attenuation", res["attenuation"], torch.float64, (n, 3)), ("status", res["status"], torch.uint8, (n,))])
+    with torch.cuda.device(dev):
+        renderer.scatter_device(seed, n, dirs.data_ptr(), index.data_ptr(), point.data_ptr(), normal.data_ptr(), front_face.data_ptr(),
+                                pixel.data_ptr(), sample.data_ptr(), event.data_ptr(), res["out_origin"].data_ptr(), res["out_dir"].data_ptr(),
+                                res["attenuation"].data_ptr(), res["status"].data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return res
+
+
+def accumulate_torch(renderer, fix, pixel, weight, sky_dir=None, select=None):
+    """Renderer.accumulate on torch tensors, on torch.cuda.current_stream(): adds to `fix`, an int64 tensor [..., 3] holding the u64 sums'
+    bits (entry pixel[k] of its flattened [npix, 3]).  pixel int32 [n], weight float64 [n, 3], sky_dir float64 [n, 3] or None, select
+    uint8 [n] or None."""
+    import torch
+    n = pixel.shape[0] if pixel.dim() == 1 else -1
+    items = [("fix", fix, torch.int64, tuple(fix.shape)), ("pixel", pixel, torch.int32, (n,)), ("weight", weight, torch.float64, (n, 3))]
+    if sky_dir is not None:
+        items.append(("sky_dir", sky_dir, torch.float64, (n, 3)))
+    if select is not None:
+        items.append(("select", select, torch.uint8, (n,)))
+    _torch_check(torch, renderer, items)
+    if fix.dim() < 1 or fix.shape[-1] != 3:
+        raise ValueError(f"fix must be [..., 3] (is {tuple(fix.shape)})")
+    with torch.cuda.device(fix.device):
+        renderer.accumulate_device(n, pixel.data_ptr(), weight.data_ptr(), fix.data_ptr(), fix.numel() // 3,
+                                   sky_dir.data_ptr() if sky_dir is not None else 0, select.data_ptr() if select is not None else 0,
+                                   torch.cuda.current_stream().cuda_stream)
+
+
+def render_wavefront_torch(renderer, cam, params, batch=1 << 20):
+    """The reference wavefront integrator: rt_render's frame from nothing but the path steps, the ray query and torch indexing, on
+    torch.cuda.current_stream().  Batches of `batch` (pixel, sample) pairs, pixel-major; each batch: camera rays, then up to max_depth
+    times { closest hit; the misses add throughput * sky to the sums; scatter; throughput *= attenuation; ended paths are dropped }.
+    Honours width, height, spp, sample_begin, max_depth, t_min and seed of `params` (flags 0, shard_count 1).  Returns (the sums as an
+    int64 tensor [H, W, 3] holding the u64 bits rt_render_device writes, the number of rays traced)."""
+    import torch
+    if params.flags != 0 or params.shard_count != 1:
+        raise ValueError("render_wavefront_torch takes flags == 0 and shard_count == 1")
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    W, H, spp, seed = int(params.width), int(params.height), int(params.spp), int(params.seed)
+    dev = torch.device("cuda", renderer.device_id)
+    fix = torch.zeros((H, W, 3), dtype=torch.int64, device=dev)
+    total, rays = W * H * spp, 0
+    for begin in range(0, total, int(batch)):
+        item = torch.arange(begin, min(begin + int(batch), total), dtype=torch.int64, device=dev)
+        pixel = torch.div(item, spp, rounding_mode="floor").to(torch.int32)
+        sample = (item % spp + int(params.sample_begin)).to(torch.int32)
+        cr = camera_rays_torch(renderer, cam, W, H, seed, pixel, sample)
+        origin, dirs, event = cr["origin"], cr["dir"], cr["event"]
+        thr = torch.ones((pixel.shape[0], 3), dtype=torch.float64, device=dev)
+        for _ in range(int(params.max_depth)):
+            if pixel.shape[0] == 0:
+                break
+            rays += int(pixel.shape[0])
+            hit = trace_rays_torch(renderer, origin, dirs, t_min=float(params.t_min), want=("point", "normal", "front_face"))
+            accumulate_torch(renderer, fix, pixel, thr, sky_dir=dirs, select=(hit["index"] < 0).to(torch.uint8))
+            sc = scatter_torch(renderer, seed, dirs, hit["index"], hit["point"], hit["normal"], hit["front_face"], pixel, sample, event)
+            keep = torch.nonzero(sc["status"] == _ffi.RT_SCATTER_SCATTERED).squeeze(1)      # (the one host wait of a bounce: its length)
+            thr = thr[keep] * sc["attenuation"][keep]
+            pixel, sample, event, origin, dirs = pixel[keep], sample[keep], event[keep], sc["out_origin"][keep], sc["out_dir"][keep]
+    return fix, rays
+
 
 class Renderer:
     """One rt_context (one GPU)."""
@@ -503,6 +611,99 @@ class Renderer:
         rays = _ffi.rt_rays(d_origin_ptr or None, d_dir_ptr or None, d_t_max_ptr or None, int(n))
         _ffi.check(self._lib.rt_occluded_device(self._h, C.byref(rays), float(t_min), C.c_void_p(d_occluded_ptr) if d_occluded_ptr else None,
                                                 C.c_void_p(stream)), "rt_occluded_device")
+
+    # -- wavefront path steps: camera rays, material scatter, accumulate ---------------
+    @staticmethod
+    def _u32(x, name, n=None):
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        if x.ndim != 1 or (n is not None and x.shape[0] != n):
+            raise ValueError(f"{name} must be [n] (is {x.shape})")
+        return x
+
+    @staticmethod
+    def _v3(x, name, n):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (n, 3):
+            raise ValueError(f"{name} must be [{n}, 3] (is {x.shape})")
+        return x
+
+    def camera_rays(self, cam, width, height, seed, pixel, sample, flags=0):
+        """rt_camera_rays: the camera ray rt_render traces for (pixel[k], sample[k]) of a width x height frame.  pixel, sample u32 [n].
+        Returns a dict: "origin", "dir" f64 [n, 3], "event" u32 [n] (the next unused Philox block) and "kernel_ms"."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        pixel = self._u32(pixel, "pixel")
+        n = int(pixel.shape[0])
+        sample = self._u32(sample, "sample", n)
+        out = {"origin": np.zeros((n, 3)), "dir": np.zeros((n, 3)), "event": np.zeros(n, dtype=np.uint32)}
+        b = _ffi.rt_camera_batch(pixel.ctypes.data, sample.ctypes.data, out["origin"].ctypes.data, out["dir"].ctypes.data, out["event"].ctypes.data, n)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_camera_rays(self._h, C.byref(rc), int(width), int(height), int(seed), int(flags), C.byref(b), C.byref(ms)),
+                   "rt_camera_rays")
+        out["kernel_ms"] = float(ms.value)
+        return out
+
+    def scatter(self, seed, dirs, index, point, normal, front_face, pixel, sample, event, out=None, flags=0):
+        """rt_scatter: Scatter::scatter of the uploaded sphere index[k] for the hit as trace_rays returns it.  `event` (u32 [n]) is not
+        modified: the advanced values come back as "event".  out (optional): a dict of C-contiguous arrays to write to, any of "out_origin",
+        "out_dir" (may be `dirs` itself), "attenuation" f64 [n, 3]; what the step does not write keeps its bytes.  Returns a dict:
+        "out_origin", "out_dir", "attenuation", "status" u8 [n] (RT_SCATTER_*), "event" and "kernel_ms"."""
+        index = np.ascontiguousarray(index, dtype=np.int32)
+        n = int(index.shape[0])
+        dirs, point, normal = self._v3(dirs, "dirs", n), self._v3(point, "point", n), self._v3(normal, "normal", n)
+        front_face = np.ascontiguousarray(front_face, dtype=np.uint8)
+        pixel, sample = self._u32(pixel, "pixel", n), self._u32(sample, "sample", n)
+        res = dict(out or {})
+        for name in ("out_origin", "out_dir", "attenuation"):
+            if name not in res:
+                res[name] = np.zeros((n, 3))
+            a = res[name]
+            if a.dtype != np.float64 or a.shape != (n, 3) or not a.flags.c_contiguous:
+                raise ValueError(f"{name} must be a C-contiguous float64 array [{n}, 3]")
+        res["status"] = np.zeros(n, dtype=np.uint8)
+        res["event"] = np.array(self._u32(event, "event", n), copy=True)
+        b = _ffi.rt_scatter_batch(dirs.ctypes.data, index.ctypes.data, point.ctypes.data, normal.ctypes.data, front_face.ctypes.data,
+                                  pixel.ctypes.data, sample.ctypes.data, res["event"].ctypes.data, res["out_origin"].ctypes.data,
+                                  res["out_dir"].ctypes.data, res["attenuation"].ctypes.data, res["status"].ctypes.data, n)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_scatter(self._h, int(seed), int(flags), C.byref(b), C.byref(ms)), "rt_scatter")
+        res["kernel_ms"] = float(ms.value)
+        return res
+
+    def accumulate(self, fix, pixel, weight, sky_dir=None, select=None):
+        """rt_accumulate: adds quantize(weight * sky(sky_dir)) -- weight itself without sky_dir -- to entry pixel[k] of `fix`, a C-contiguous
+        u64 array [..., 3], IN PLACE.  select u8 [n] or None.  Returns the kernel's time in ms."""
+        if fix.dtype != np.uint64 or not fix.flags.c_contiguous or fix.ndim < 1 or fix.shape[-1] != 3:
+            raise ValueError("fix must be a C-contiguous uint64 array [..., 3]")
+        pixel = self._u32(pixel, "pixel")
+        n = int(pixel.shape[0])
+        weight = self._v3(weight, "weight", n)
+        sky_dir = self._v3(sky_dir, "sky_dir", n) if sky_dir is not None else None
+        select = np.ascontiguousarray(select, dtype=np.uint8) if select is not None else None
+        b = _ffi.rt_accumulate_batch(pixel.ctypes.data, weight.ctypes.data, sky_dir.ctypes.data if sky_dir is not None else None,
+                                     select.ctypes.data if select is not None else None, n)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_accumulate(self._h, C.byref(b), fix.ctypes.data_as(C.c_void_p), fix.size // 3, C.byref(ms)), "rt_accumulate")
+        return float(ms.value)
+
+    def camera_rays_device(self, cam, width, height, seed, n, d_pixel_ptr, d_sample_ptr, d_origin_ptr, d_dir_ptr, d_event_ptr, stream=0, flags=0):
+        """rt_camera_rays_device on raw device pointers; asynchronous on `stream`."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        b = _ffi.rt_camera_batch(d_pixel_ptr or None, d_sample_ptr or None, d_origin_ptr or None, d_dir_ptr or None, d_event_ptr or None, int(n))
+        _ffi.check(self._lib.rt_camera_rays_device(self._h, C.byref(rc), int(width), int(height), int(seed), int(flags), C.byref(b),
+                                                   C.c_void_p(stream)), "rt_camera_rays_device")
+
+    def scatter_device(self, seed, n, d_dir_ptr, d_index_ptr, d_point_ptr, d_normal_ptr, d_front_ptr, d_pixel_ptr, d_sample_ptr, d_event_ptr,
+                       d_out_origin_ptr, d_out_dir_ptr, d_attenuation_ptr, d_status_ptr, stream=0, flags=0):
+        """rt_scatter_device on raw device pointers; d_event_ptr is read and written; asynchronous on `stream`."""
+        b = _ffi.rt_scatter_batch(*[p or None for p in (d_dir_ptr, d_index_ptr, d_point_ptr, d_normal_ptr, d_front_ptr, d_pixel_ptr, d_sample_ptr,
+                                                        d_event_ptr, d_out_origin_ptr, d_out_dir_ptr, d_attenuation_ptr, d_status_ptr)], int(n))
+        _ffi.check(self._lib.rt_scatter_device(self._h, int(seed), int(flags), C.byref(b), C.c_void_p(stream)), "rt_scatter_device")
+
+    def accumulate_device(self, n, d_pixel_ptr, d_weight_ptr, d_fix_ptr, npix, d_sky_dir_ptr=0, d_select_ptr=0, stream=0):
+        """rt_accumulate_device on raw device pointers; d_fix_ptr: device [npix][3] u64, added to; asynchronous on `stream`."""
+        b = _ffi.rt_accumulate_batch(d_pixel_ptr or None, d_weight_ptr or None, d_sky_dir_ptr or None, d_select_ptr or None, int(n))
+        _ffi.check(self._lib.rt_accumulate_device(self._h, C.byref(b), C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
+                                                  C.c_void_p(stream)), "rt_accumulate_device")
 
     # -- denoiser: an edge-avoiding a-trous filter driven by the feature buffers -------
     def denoise(self, fix, spp, feat, feat_spp, denoise=None, count=None):

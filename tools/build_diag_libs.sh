@@ -5,7 +5,7 @@
 # wave exit times (RT_EXIT_TIMES).  -> tools/lib_{stamps,counts,exit}.so
 cd "$(dirname "$0")/.."
 # (every translation unit of the library: the diagnostic macros live in the kernel they all instantiate)
-SRCS=$(ls rtiow_amd/csrc/rt_*.hip)
+SRCS=$(ls rtiow_amd/csrc/rt_*.hip rtiow_amd/csrc/wavefront/*.hip)
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -mllvm -amdgpu-mfma-vgpr-form -fPIC -shared -I include -I rtiow_amd/csrc"
 hipcc $FLAGS -DRT_PHASE_STAMPS -o tools/lib_stamps.so $SRCS &
 hipcc $FLAGS -DRT_BLOCK_COUNTS -o tools/lib_counts.so $SRCS &
