@@ -248,6 +248,25 @@ pub struct rt_accumulate_batch {
     pub n: i64,
 }
 
+/// A path queue (`rt_paths_begin_device`, `rt_paths_step_device`): structure-of-arrays in DEVICE memory, caller-owned.  The live paths are
+/// slots `[0, *count)`; `count` is one device word the kernels read and the host never does.  `scratch`: `rt_path_scratch_words(capacity)` words.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_path_queue {
+    pub capacity: i64,
+    pub count: *mut u32,
+    pub pixel: *mut u32,
+    pub sample: *mut u32,
+    pub event: *mut u32,
+    pub origin: *mut f64,
+    pub dir: *mut f64,
+    pub throughput: *mut f64,
+    pub scratch: *mut u32,
+}
+
+const _: () = assert!(offset_of!(rt_path_queue, count) == 8);
+const _: () = assert!(offset_of!(rt_path_queue, scratch) == 64);
+const _: () = assert!(72 == size_of::<rt_path_queue>());
 const _: () = assert!(offset_of!(rt_camera_batch, n) == 40);
 const _: () = assert!(48 == size_of::<rt_camera_batch>());
 const _: () = assert!(offset_of!(rt_scatter_batch, n) == 96);
@@ -358,6 +377,20 @@ extern "C" {
     pub fn rt_accumulate_device(ctx: *mut rt_context, batch: *const rt_accumulate_batch, d_fix: *mut c_void, npix: i64,
                                 stream: *mut c_void) -> i32;
     pub fn rt_accumulate(ctx: *mut rt_context, batch: *const rt_accumulate_batch, fix: *mut u64, npix: i64, kernel_ms: *mut f32) -> i32;
+    /// The device path queue: `rt_paths_begin_device` fills slots `[0, n)` with the camera rays of the items `first_item ..` (pixel-major);
+    /// `rt_paths_step_device` is one bounce of every live path of `input` -- closest hit, the sky term of a miss added to `d_fix`, scatter,
+    /// throughput -- with the survivors written to `output` in order; `rt_render_wavefront*` render the whole frame from the two,
+    /// `rt_render_device`'s sums bit for bit.  The device forms are asynchronous on `stream` and take no host wait.
+    pub fn rt_path_scratch_words(capacity: i64) -> i64;
+    pub fn rt_paths_begin_device(ctx: *mut rt_context, cam: *const rt_camera, width: i32, height: i32, seed: u64, flags: u32, spp: i32,
+                                 sample_begin: i32, first_item: i64, n: i64, q: *const rt_path_queue, stream: *mut c_void) -> i32;
+    pub fn rt_paths_step_device(ctx: *mut rt_context, seed: u64, flags: u32, t_min: f64, input: *const rt_path_queue,
+                                output: *const rt_path_queue, d_fix: *mut c_void, npix: i64, d_rays: *mut c_void,
+                                stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_device(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, d_fix: *mut c_void,
+                                      d_rays: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, fix: *mut u64, rays_traced: *mut u64,
+                               kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

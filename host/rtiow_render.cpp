@@ -9,7 +9,7 @@
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
-//                [--pick I,J]
+//                [--pick I,J] [--wavefront]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -40,6 +40,8 @@
 // --temporal-sigma-normal 0.5; --temporal-sigma-depth 0.1; --temporal-clamp X: the scale of the neighbourhood clamp, default 1, a negative X switches
 // it off), with --denoise also rt_denoise on each accumulated frame (spp = 1, the frame's own features), then the one-sample resolve; the
 // frames are written as the batch writes them.  --denoise goes with a batch only together with --temporal.
+// --wavefront: the same frame through the device path queue (rt_render_wavefront: per batch one begin and --depth fused bounce steps, DESIGN.md
+// section 19), then rt_resolve_rgba8: the bytes of the default run.  Single device; with none of the other modes.
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -87,7 +89,7 @@ int main(int argc, char **argv)
     unsigned long long seed = 1, scene_seed = 1;
     std::string out = "image.ppm", dump, scene_file;
     std::vector<int> devices;                    // --devices 0,1,...: one context + host thread per entry
-    bool force_rccl = false, uniform53 = false, two_calls = false;
+    bool force_rccl = false, uniform53 = false, two_calls = false, wavefront = false;
     int passes = 1;
     int tile_rows = 1;
     bool adaptive = false;
@@ -139,6 +141,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--force-rccl")) force_rccl = true;
         else if (!std::strcmp(argv[i], "--uniform53")) uniform53 = true;
         else if (!std::strcmp(argv[i], "--two-calls")) two_calls = true;
+        else if (!std::strcmp(argv[i], "--wavefront")) wavefront = true;
         else if (arg("--passes")) passes = std::atoi(argv[++i]);
         else if (arg("--adaptive")) { adaptive = true; threshold = std::atof(argv[++i]); }
         else if (arg("--step")) step = std::atoi(argv[++i]);
@@ -235,8 +238,8 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--denoise renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --passes, --two-calls, --features\n");
         return 2;
     }
-    if (batch && (!devices.empty() || passes > 1 || adaptive || uniform53 || two_calls)) {
-        std::fprintf(stderr, "--cameras / --orbit render a frame batch on one device and go with none of --devices, --passes, --adaptive, --uniform53, --two-calls\n");
+    if (batch && (!devices.empty() || passes > 1 || adaptive || uniform53 || two_calls || wavefront)) {
+        std::fprintf(stderr, "--cameras / --orbit render a frame batch on one device and go with none of --devices, --passes, --adaptive, --uniform53, --two-calls, --wavefront\n");
         return 2;
     }
     if (!cameras_file.empty() && orbit != 0) { std::fprintf(stderr, "--cameras and --orbit: one or the other\n"); return 2; }
@@ -346,6 +349,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--adaptive runs on one device and goes with none of --devices, --passes, --two-calls, --uniform53\n");
         return 2;
     }
+    if (wavefront && (!devices.empty() || adaptive || denoise || passes > 1 || two_calls || uniform53 || !features_file.empty())) {
+        std::fprintf(stderr, "--wavefront runs on one device and goes with none of --devices, --adaptive, --denoise, --passes, --two-calls, --uniform53, --features\n");
+        return 2;
+    }
     if (!devices.empty()) {
         // one rt_context per listed device, each driven by its own host thread; rows dealt round-robin;
         // one RCCL gather of the exact sums to the first device (main.rs:122-123 + the ordered collect() :139)
@@ -421,6 +428,14 @@ int main(int argc, char **argv)
             if ((e = hipStreamSynchronize(st2[0])) != hipSuccess) return hip_die(e, "hipStreamSynchronize");
             (void)hipFree(d_fix); (void)hipFree(d_rgba);
             for (int k = 0; k < 2; ++k) (void)hipStreamDestroy(st2[k]);
+        } else if (wavefront) {                  // the device path queue: the same sums, then the same resolve
+            std::vector<uint64_t> fix(npix * 3);
+            uint64_t rays = 0;
+            rc = rt_render_wavefront(ctx, &rc_cam, &p, fix.data(), &rays, &st.kernel_ms);
+            if (rc) return die("rt_render_wavefront", rc);
+            st.rays_traced = rays; st.samples = (uint64_t)npix * (uint64_t)spp;
+            rc = rt_resolve_rgba8(ctx, fix.data(), width, height, spp, 1, rgba.data());
+            if (rc) return die("rt_resolve_rgba8", rc);
         } else if (two_calls) {                  // the sums through host memory: rt_render, then rt_resolve_rgba8 (same bytes)
             std::vector<uint64_t> fix(npix * 3);
             rc = rt_render(ctx, &rc_cam, &p, nullptr, fix.data(), &st);                  // main.rs:122-136

@@ -707,6 +707,63 @@ int rt_scatter(rt_context *ctx, uint64_t seed, uint32_t flags, const rt_scatter_
 int rt_accumulate_device(rt_context *ctx, const rt_accumulate_batch *batch, void *d_fix, int64_t npix, void *stream);
 int rt_accumulate(rt_context *ctx, const rt_accumulate_batch *batch, uint64_t *fix, int64_t npix, float *kernel_ms);
 
+/* ---- path queue: a fused bounce step on device-resident paths, and the frame rendered from it ---------- */
+
+/* The wavefront integrator of the steps above with the paths, and their NUMBER, kept on the device: one call per bounce, no host wait
+ * between bounces.  DESIGN.md section 19.  A queue is structure-of-arrays and caller-owned (torch tensors pass as they are): the live
+ * paths are slots [0, *count), in order; `count` is ONE word of device memory that the kernels read and the host never does.  The
+ * random stream, the arithmetic and the NaN rule are those of the wavefront path steps; flags: 0 only.  RTIOW_PATHS_GRID_BLOCKS=k (a
+ * diagnostic knob read per call): at most k workgroups per launch; a result does not depend on it. */
+typedef struct rt_path_queue {
+    int64_t   capacity;        /* 1 .. 2^24 slots                                                                    */
+    uint32_t *count;           /* device, ONE word: the live paths; a value above capacity is read as capacity       */
+    uint32_t *pixel;           /* [capacity]                                                                         */
+    uint32_t *sample;          /* [capacity]                                                                         */
+    uint32_t *event;           /* [capacity]    the next unused Philox block, as in the wavefront steps              */
+    double   *origin;          /* [capacity][3]                                                                      */
+    double   *dir;             /* [capacity][3] not normalised                                                       */
+    double   *throughput;      /* [capacity][3]                                                                      */
+    uint32_t *scratch;         /* [rt_path_scratch_words(capacity)]: the compaction's counts, offsets and alive marks */
+} rt_path_queue;
+/* 3 words per 64 slots: 3 * ceil(capacity / 64); 0 for a capacity outside [1, 2^24] */
+int64_t rt_path_scratch_words(int64_t capacity);
+
+/* Slot k in [0, n) becomes item first_item + k of a frame of width x height pixels with spp samples each, pixel-major:
+ * pixel = item / spp, sample = sample_begin + item % spp; origin, dir and event are rt_camera_rays' for that pair; throughput (1, 1, 1);
+ * *q->count = n.  Slots at or past n keep their bytes.  Needs 0 <= n <= capacity, spp >= 1, sample_begin >= 0, first_item >= 0 and
+ * first_item + n <= width * height * spp.  Needs no uploaded scene. */
+int rt_paths_begin_device(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, uint32_t flags, int32_t spp,
+                          int32_t sample_begin, int64_t first_item, int64_t n, const rt_path_queue *q, void *stream);
+
+/* One bounce of every live path of `in`.  Closest hit: HittableList::hit(ray, t_min, +inf), as rt_trace_rays answers it.  A miss adds
+ * quantize(throughput * sky(dir)) to d_fix[pixel] exactly as rt_accumulate does with sky_dir (pixel >= npix adds nothing) and the path
+ * ends.  A hit scatters exactly as rt_scatter: RT_SCATTER_ABSORBED ends the path; RT_SCATTER_SCATTERED survives with origin = the hit
+ * point, dir = the scattered direction, throughput = throughput * attenuation (one f64 multiply per channel) and the advanced event.
+ * The survivors are written to `out` IN THE ORDER THEY HAD IN `in`, into slots [0, m), and *out->count = m; slots of `out` at or past m
+ * keep the caller's bytes.  `in` and `out` are distinct queues that share no array, out->capacity >= in->capacity.  After the call the
+ * arrays of `in` (its scratch included) hold intermediate values and *in->count is unchanged.  d_rays (may be NULL): one device u64 that
+ * gains the number of live paths of `in` (a plain add: calls that share it are ordered by their streams).  A count of 0 does nothing but
+ * *out->count = 0.  d_fix: [npix][3] u64 exact sums, added to. */
+int rt_paths_step_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                         void *d_fix, int64_t npix, void *d_rays, void *stream);
+
+/* The whole frame from the two calls above: rt_render_device's exact sums bit for bit, and in *d_rays / *rays_traced (may be NULL) the
+ * rt_stats.rays_traced of that render.  Honours width, height, spp, sample_begin, max_depth, t_min and seed of `p`; flags must be 0 and
+ * shard_count 1.  d_fix ([height][width][3] u64) and d_rays are zeroed first.  The frame's width * height * spp items go in batches of
+ * RTIOW_WAVEFRONT_BATCH (read per call; default 2^20, at most 2^24): per batch one begin, then max_depth steps between two queues the
+ * context owns (allocated on first use, regrown when a batch is larger, freed by rt_destroy); a path still alive after max_depth steps
+ * adds nothing.  No host wait inside the call: the device form is asynchronous on `stream` (calls on one context must be ordered by the
+ * caller: they share its queues).  The host-buffer form copies out and synchronises; kernel_ms (may be NULL): the kernels' time.
+ *
+ * RT_ERR_INVALID_ARGUMENT from every form of this block, found before anything is touched, the checks that need no context first: a
+ * NULL camera, params or queue struct, a NULL array of a queue, a NULL d_fix / fix; capacity outside [1, 2^24]; n outside [0, capacity];
+ * `in` == `out` or a shared array; out->capacity < in->capacity; width or height < 2 (and spp, sample_begin, first_item as above); npix
+ * outside [1, 2^32]; flags != 0 (RT_FLAG_UNIFORM53 named); t_min not finite or not > 0; then a NULL context; then a context created under
+ * another scan mode than the shipped one (RTIOW_SCAN_MODE); then RT_ERR_NO_SCENE (not for rt_paths_begin_device).  These calls take NONE
+ * of the context's launch slots and rt_last_stats does not report on them. */
+int rt_render_wavefront_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, void *d_fix, void *d_rays, void *stream);
+int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *fix, uint64_t *rays_traced, float *kernel_ms);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

@@ -74,6 +74,11 @@ class rt_accumulate_batch(C.Structure):
     _fields_ = [("pixel", C.c_void_p), ("weight", C.c_void_p), ("sky_dir", C.c_void_p), ("select", C.c_void_p), ("n", C.c_int64)]
 
 
+class rt_path_queue(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("count", C.c_void_p), ("pixel", C.c_void_p), ("sample", C.c_void_p), ("event", C.c_void_p),
+                ("origin", C.c_void_p), ("dir", C.c_void_p), ("throughput", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -138,6 +143,13 @@ SYMBOLS = [
     ("rt_scatter", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.POINTER(rt_scatter_batch), C.POINTER(C.c_float)]),
     ("rt_accumulate_device", C.c_int, [_VP, C.POINTER(rt_accumulate_batch), _VP, C.c_int64, _VP]),
     ("rt_accumulate", C.c_int, [_VP, C.POINTER(rt_accumulate_batch), _VP, C.c_int64, C.POINTER(C.c_float)]),
+    ("rt_path_scratch_words", C.c_int64, [C.c_int64]),
+    ("rt_paths_begin_device", C.c_int, [_VP, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_int64,
+                                        C.c_int64, C.POINTER(rt_path_queue), _VP]),
+    ("rt_paths_step_device", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(rt_path_queue), C.POINTER(rt_path_queue), _VP, C.c_int64,
+                                       _VP, _VP]),
+    ("rt_render_wavefront_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, _VP, _VP]),
+    ("rt_render_wavefront", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

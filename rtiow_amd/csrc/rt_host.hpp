@@ -20,6 +20,17 @@ namespace rt_host {
 int fail(int code, const char *fmt, ...);          // records the thread's rt_last_error message, returns `code`
 }
 
+namespace rt_host {
+// a device allocation a context owns and releases with itself
+struct DeviceBlock {
+    void *ptr = nullptr; size_t bytes = 0;
+    DeviceBlock() = default;
+    DeviceBlock(const DeviceBlock &) = delete;
+    DeviceBlock &operator=(const DeviceBlock &) = delete;
+    ~DeviceBlock() { if (ptr) (void)hipFree(ptr); }
+};
+}
+
 #define RT_HIP(call)                                                                          \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
@@ -69,6 +80,9 @@ struct rt_context {
     void *d_sel = nullptr; size_t sel_bytes = 0;
     int last_dense_body = 0;              // rt_last_dense_body (rtiow_hip_diag.h): 1 when the latest rt_render_device launch ran a capped-redraw kernel of rt_dense.hip, else 0
     int ring_min_spp = 0;                 // RTIOW_RING_MIN_SPP (diagnostic): spp per launch from which block sums are kept in LDS (0: the kernel's own minimum)
+    // rt_render_wavefront_device's two path queues (wavefront/rt_paths.hip): a device form's, so not in the arena; allocated on first use,
+    // regrown when a batch is larger, freed by rt_destroy (which selects the device, then deletes the context: the member's destructor)
+    rt_host::DeviceBlock paths;
 };
 
 namespace rt_host {

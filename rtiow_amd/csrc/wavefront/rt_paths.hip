@@ -1,0 +1,438 @@
+// rt_paths.hip -- the device path queue: a fused bounce step on device-resident paths and the frame rendered from it (rtiow_hip.h, "path
+// queue").
+//
+// The eleventh translation unit of librtiow_hip.so.  Four kernels of its own:
+//   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
+//   bounce_kernel         one wave per 64 consecutive slots, grid-stride over the live slots: closest hit (first_hit_wave<false> whole, the
+//                         record in registers), then the sky add of a miss or Scatter::scatter -- both from rt_shade_core.hpp --; the new
+//                         state is written IN PLACE, and per wave the number of survivors and their ballot go to the queue's scratch.
+//   queue_scan_kernel     ONE workgroup: the exclusive scan of the waves' counts, in place; *out->count; d_rays.
+//   queue_compact_kernel  one wave per 64 slots: the survivors move to `out` at offset + rank, so their order is kept.
+// The live count is a word of device memory every kernel reads for itself; the host sizes the grids from the capacity and never waits.
+// NO kernel waits for another workgroup (no look-back chain, no flag, no grid-wide barrier): a wave that waits for a workgroup that has not
+// been scheduled would hang, so the scan is a launch of its own, ordered by the stream.  No atomics except the three 64-bit adds of a miss.
+// It composes rt_first_hit.hpp and rt_shade_core.hpp and restates none of their arithmetic; rt_kernels.hpp and rt_launch.hpp are not read.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "rt_host.hpp"
+#include "rt_first_hit.hpp"
+#include "rt_shade_core.hpp"
+
+using namespace rt_host;
+
+namespace rt {
+
+constexpr int kPathBlock = 256;                     // four waves, each on 64 consecutive slots
+constexpr int kPathWaves = kPathBlock / 64;
+constexpr int kScanBlock = 1024;                    // the one workgroup of the scan
+constexpr int kScratchPerWave = 3;                  // scratch words per 64 slots: [0] survivors, then their exclusive offset; [1], [2] the alive ballot
+
+struct QueueArrays {
+    uint32_t *count, *pixel, *sample, *event;
+    double *origin, *dir, *thr;
+    uint32_t *scratch;
+    uint32_t capacity;
+};
+
+struct BeginArgs {
+    long long n, first_item;
+    uint32_t spp, sample_begin;
+    int32_t width, height;
+    uint32_t k0, k1;
+};
+
+// the live count as every kernel of a step reads it: the word in device memory, clamped to the capacity
+__device__ __forceinline__ uint32_t live_count(const QueueArrays &Q)
+{
+    const uint32_t n = *Q.count;
+    return n < Q.capacity ? n : Q.capacity;
+}
+
+__global__ __launch_bounds__(kPathBlock) void path_begin_kernel(const KCamera cam, const QueueArrays Q, const BeginArgs A)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *Q.count = (uint32_t)A.n;
+    const double wm1 = (double)(A.width - 1), hm1 = (double)(A.height - 1);
+    const long long stride = (long long)gridDim.x * kPathBlock;
+    for (long long k = (long long)blockIdx.x * kPathBlock + threadIdx.x; k < A.n; k += stride) {
+        const unsigned long long item = (unsigned long long)(A.first_item + k);
+        const unsigned long long pix = item / A.spp;                    // pixel-major: item = pixel * spp + sample
+        const uint32_t g_pix = (uint32_t)pix, g_s = A.sample_begin + (uint32_t)(item - pix * A.spp);
+        D3 origin, dir;
+        const uint32_t ev = sample_ray(cam, (uint32_t)A.width, wm1, hm1, g_pix, g_s, A.k0, A.k1, origin, dir);
+        Q.pixel[k] = g_pix; Q.sample[k] = g_s; Q.event[k] = ev;
+        store3(Q.origin, k, origin);
+        store3(Q.dir, k, dir);
+        Q.thr[3 * k] = 1.0; Q.thr[3 * k + 1] = 1.0; Q.thr[3 * k + 2] = 1.0;
+    }
+}
+
+// One bounce of the live paths.  P: the scene's tables, t_min, the key (k0, k1) and the sums (fix); npix: entries of P.fix.
+__global__ __launch_bounds__(kPathBlock) void bounce_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix)
+{
+    __shared__ uint4 s_stage[kPathWaves][64 * 4];
+    const int lane = (int)threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    uint4 *stage = s_stage[wave];
+    const long long n = (long long)live_count(Q);
+    const long long n_trips = (n + 63) >> 6;
+    const long long n_waves = (long long)gridDim.x * kPathWaves;
+
+    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) {
+        const long long k = wv * 64 + lane;
+        // lanes past the live count stay in the wave: rows that keep nothing, nothing written
+        const bool valid = k < n;
+        D3 o = mk(0.0, 0.0, 0.0), d = mk(0.0, 0.0, 0.0), thr = mk(0.0, 0.0, 0.0);
+        uint32_t g_pix = 0u, g_s = 0u, ev = 0u;
+        if (valid) {
+            o = ld3(Q.origin + 3 * k); d = ld3(Q.dir + 3 * k); thr = ld3(Q.thr + 3 * k);
+            g_pix = Q.pixel[k]; g_s = Q.sample[k]; ev = Q.event[k];
+        }
+        FirstHit fh = {__builtin_inf(), -1};            // mod.rs:56: closest_so_far = t_max = +inf
+        ScanCounts cnt = {true};
+        first_hit_wave<false>(P, stage, lane, o, d, valid, fh, cnt);
+
+        bool alive = false;
+        if (valid) {
+            if (fh.hit < 0) {
+                // contract C5, as rt_accumulate with sky_dir: the path ends in the sky
+                if ((unsigned long long)g_pix < npix) {
+                    const D3 v = sky_sample(thr, d);
+                    unsigned long long *px = P.fix + (size_t)g_pix * 3u;
+                    atomicAdd(px + 0, quantize(v.x)); atomicAdd(px + 1, quantize(v.y)); atomicAdd(px + 2, quantize(v.z));
+                }
+            } else {
+                const HitRecord rec = hit_record(P, o, d, fh);          // (in registers: never written to memory)
+                D3 ndir, albedo;
+                alive = !scatter_path(rec.mrec, d, rec.normal, rec.front, g_pix, g_s, ev, P.k0, P.k1, ndir, albedo);
+                if (alive) {
+                    store3(Q.origin, k, rec.p);
+                    store3(Q.dir, k, ndir);
+                    store3(Q.thr, k, thr * albedo);
+                    Q.event[k] = ev;
+                }
+            }
+        }
+        const unsigned long long live = __ballot(alive);
+        if (lane == 0) {
+            uint32_t *s = Q.scratch + kScratchPerWave * wv;
+            s[0] = (uint32_t)__popcll(live); s[1] = (uint32_t)live; s[2] = (uint32_t)(live >> 32);
+        }
+    }
+}
+
+// ONE workgroup: thread t owns a run of consecutive waves' counts; the threads' sums are scanned in LDS; the run is rewritten as offsets.
+__global__ __launch_bounds__(kScanBlock) void queue_scan_kernel(const QueueArrays Q, uint32_t *out_count, unsigned long long *rays)
+{
+    __shared__ uint32_t s_sum[kScanBlock];
+    const uint32_t t = threadIdx.x;
+    const uint32_t n = live_count(Q);
+    const uint32_t n_trips = (n + 63u) >> 6;
+    const uint32_t per = (n_trips + kScanBlock - 1u) / kScanBlock;
+    const uint32_t lo = min(t * per, n_trips), hi = min(lo + per, n_trips);
+    uint32_t sum = 0u;
+    for (uint32_t w = lo; w < hi; ++w) sum += Q.scratch[kScratchPerWave * (size_t)w];
+    s_sum[t] = sum;
+    __syncthreads();
+    for (uint32_t off = 1u; off < (uint32_t)kScanBlock; off <<= 1) {
+        const uint32_t below = t >= off ? s_sum[t - off] : 0u;
+        __syncthreads();
+        s_sum[t] += below;
+        __syncthreads();
+    }
+    uint32_t run = s_sum[t] - sum;
+    for (uint32_t w = lo; w < hi; ++w) {
+        const uint32_t c = Q.scratch[kScratchPerWave * (size_t)w];
+        Q.scratch[kScratchPerWave * (size_t)w] = run;
+        run += c;
+    }
+    if (t == 0u) {
+        *out_count = s_sum[kScanBlock - 1];
+        if (rays) *rays += (unsigned long long)n;
+    }
+}
+
+// The survivors of `in` to `out` at offset + rank: stable.  offset + rank < the survivors' total <= the live count <= in.capacity <=
+// out.capacity (checked on the host), so every store lies inside `out`.
+__global__ __launch_bounds__(kPathBlock) void queue_compact_kernel(const QueueArrays In, const QueueArrays Out)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const long long wave = (long long)((int)threadIdx.x >> 6);
+    const long long n_trips = ((long long)live_count(In) + 63) >> 6;
+    const long long n_waves = (long long)gridDim.x * kPathWaves;
+    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) {
+        const uint32_t *s = In.scratch + kScratchPerWave * wv;
+        const unsigned long long live = ((unsigned long long)s[2] << 32) | (unsigned long long)s[1];
+        if (((live >> lane) & 1ull) == 0ull) continue;
+        const long long k = wv * 64 + lane;
+        const long long to = (long long)s[0] + __popcll(live & ((1ull << lane) - 1ull));
+        if (to >= (long long)Out.capacity) continue;    // (cannot happen; a store never leaves `out` whatever the scratch holds)
+        Out.pixel[to] = In.pixel[k]; Out.sample[to] = In.sample[k]; Out.event[to] = In.event[k];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            Out.origin[3 * to + c] = In.origin[3 * k + c]; Out.dir[3 * to + c] = In.dir[3 * k + c]; Out.thr[3 * to + c] = In.thr[3 * k + c];
+        }
+    }
+}
+
+} // namespace rt
+
+namespace {
+
+constexpr int64_t kMaxCapacity = (int64_t)1 << 24;
+constexpr long long kDefaultBatch = 1ll << 20;
+
+// RTIOW_PATHS_GRID_BLOCKS=k (diagnostic, read per call): at most k workgroups, so that the kernels' grid-stride trip runs at a test's size
+unsigned capped_grid(long long grid)
+{
+    const char *e = getenv("RTIOW_PATHS_GRID_BLOCKS");
+    const long long cap = e && *e ? atoll(e) : 0;
+    if (cap > 0 && grid > cap) grid = cap;
+    return (unsigned)(grid < 1 ? 1 : grid);
+}
+
+// RTIOW_PATHS_STEP_PARTS=mask (diagnostic, read per call; tools/paths_bench.py times the kernels of a step one by one with it): which of
+// a step's launches are issued -- 1 the bounce, 2 the scan, 4 the compaction; not set: all three
+int step_parts()
+{
+    const char *e = getenv("RTIOW_PATHS_STEP_PARTS");
+    const int v = e && *e ? atoi(e) : 0;
+    return v > 0 ? v & 7 : 7;
+}
+
+int check_flags(const char *what, uint32_t flags)
+{
+    if (flags & RT_FLAG_UNIFORM53)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: RT_FLAG_UNIFORM53 is not built for the path queue (flags 0x%x; only 0 is legal)", what, flags);
+    if (flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x (only 0 is legal)", what, flags);
+    return RT_OK;
+}
+#define RT_NEED(ptr, what, name) \
+    do { if (!(ptr)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s is NULL", what, name); } while (0)
+
+int check_queue(const char *what, const char *name, const rt_path_queue *q)
+{
+    if (!q) return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s is NULL", what, name);
+    const void *arrays[8] = {q->count, q->pixel, q->sample, q->event, q->origin, q->dir, q->throughput, q->scratch};
+    static const char *const field[8] = {"count", "pixel", "sample", "event", "origin", "dir", "throughput", "scratch"};
+    for (int k = 0; k < 8; ++k)
+        if (!arrays[k]) return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s->%s is NULL", what, name, field[k]);
+    if (q->capacity < 1 || q->capacity > kMaxCapacity)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s->capacity must be in [1, 2^24] (is %lld)", what, name, (long long)q->capacity);
+    return RT_OK;
+}
+
+// the context's part of every check, after the context-free ones
+int check_context(const rt_context *ctx, const char *what, bool needs_scene)
+{
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (ctx->scan_mode != 5)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s needs the shipped scan mode 5; this context was created under RTIOW_SCAN_MODE=%d", what, ctx->scan_mode);
+    if (needs_scene && ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    return RT_OK;
+}
+
+int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint32_t flags, int32_t spp, int32_t sample_begin,
+                int64_t first_item, int64_t n, const rt_path_queue *q)
+{
+    const char *what = "rt_paths_begin";
+    RT_NEED(cam, what, "cam");
+    if (int rc = check_queue(what, "queue", q)) return rc;
+    if (n < 0 || n > q->capacity)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: n must be in [0, capacity = %lld] (is %lld)", what, (long long)q->capacity, (long long)n);
+    if (width < 2 || height < 2) return fail(RT_ERR_INVALID_ARGUMENT, "%s: width and height must be >= 2 (are %d, %d)", what, width, height);
+    if ((long long)width * height > 0x7fffffffLL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: width * height does not fit the 32-bit Philox pixel counter", what);
+    if (spp < 1 || sample_begin < 0 || (long long)spp + sample_begin > 0x7fffffffLL)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: spp must be >= 1, sample_begin >= 0 and spp + sample_begin <= 2^31 - 1 (are %d, %d)", what, spp, sample_begin);
+    if (first_item < 0 || first_item + n > (long long)width * height * spp)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: the items [first_item, first_item + n) must lie in [0, width * height * spp) (first_item %lld, n %lld)",
+                    what, (long long)first_item, (long long)n);
+    if (int rc = check_flags(what, flags)) return rc;
+    return check_context(ctx, what, false);
+}
+
+int check_step(const rt_context *ctx, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out, const void *d_fix, int64_t npix)
+{
+    const char *what = "rt_paths_step";
+    if (int rc = check_queue(what, "in", in)) return rc;
+    if (int rc = check_queue(what, "out", out)) return rc;
+    RT_NEED(d_fix, what, "d_fix");
+    if (in == out) return fail(RT_ERR_INVALID_ARGUMENT, "%s: in and out must be distinct queues", what);
+    const void *a[8] = {in->count, in->pixel, in->sample, in->event, in->origin, in->dir, in->throughput, in->scratch};
+    const void *b[8] = {out->count, out->pixel, out->sample, out->event, out->origin, out->dir, out->throughput, out->scratch};
+    for (const void *x : a)
+        for (const void *y : b)
+            if (x == y) return fail(RT_ERR_INVALID_ARGUMENT, "%s: in and out share an array", what);
+    if (out->capacity < in->capacity)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: out->capacity (%lld) must be >= in->capacity (%lld)", what, (long long)out->capacity, (long long)in->capacity);
+    if (npix <= 0 || npix > (int64_t)1 << 32) return fail(RT_ERR_INVALID_ARGUMENT, "%s: npix must be in [1, 2^32] (is %lld)", what, (long long)npix);
+    if (int rc = check_flags(what, flags)) return rc;
+    if (!(t_min > 0.0) || !std::isfinite(t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, t_min);
+    return check_context(ctx, what, true);
+}
+
+rt::QueueArrays arrays_of(const rt_path_queue *q)
+{
+    rt::QueueArrays a;
+    a.count = q->count; a.pixel = q->pixel; a.sample = q->sample; a.event = q->event;
+    a.origin = q->origin; a.dir = q->dir; a.thr = q->throughput; a.scratch = q->scratch; a.capacity = (uint32_t)q->capacity;
+    return a;
+}
+
+// (validated arguments from here on)
+int launch_begin(const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, int32_t spp, int32_t sample_begin, int64_t first_item, int64_t n,
+                 const rt_path_queue *q, hipStream_t stream)
+{
+    rt::KCamera kc;
+    static_assert(sizeof(rt::KCamera) == sizeof(rt_camera), "camera layouts must match");
+    memcpy(&kc, cam, sizeof(rt_camera));
+    rt::BeginArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = (long long)n; a.first_item = (long long)first_item; a.spp = (uint32_t)spp; a.sample_begin = (uint32_t)sample_begin;
+    a.width = width; a.height = height; a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
+    // (at least one workgroup: an empty batch still writes the count)
+    hipLaunchKernelGGL(rt::path_begin_kernel, dim3(capped_grid(grid_256(a.n))), dim3(rt::kPathBlock), 0, stream, kc, arrays_of(q), a);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_path_queue *in, const rt_path_queue *out, void *d_fix, int64_t npix,
+                void *d_rays, hipStream_t stream)
+{
+    rt::KParams kp;
+    memset(&kp, 0, sizeof(kp));
+    kp.t_min = t_min;
+    kp.n_spheres = ctx->n_spheres;
+    kp.k0 = (uint32_t)seed; kp.k1 = (uint32_t)(seed >> 32);
+    kp.fix = (unsigned long long *)d_fix;
+    set_scene_params(ctx, kp);
+    const rt::QueueArrays qi = arrays_of(in), qo = arrays_of(out);
+    // the grids come from the CAPACITY: the live count is the device's to know.  One wave per 64 slots; waves past the count leave at once.
+    const dim3 grid(capped_grid(rt::wave_grid(((long long)in->capacity + 63) / 64, rt::kPathWaves))), block(rt::kPathBlock);
+    const int parts = step_parts();
+    if (parts & 1) hipLaunchKernelGGL(rt::bounce_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix);
+    if (parts & 2) hipLaunchKernelGGL(rt::queue_scan_kernel, dim3(1), dim3(rt::kScanBlock), 0, stream, qi, out->count, (unsigned long long *)d_rays);
+    if (parts & 4) hipLaunchKernelGGL(rt::queue_compact_kernel, grid, block, 0, stream, qi, qo);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// one context-owned queue of `capacity` slots laid out from `base` on (256-byte blocks, as the staging arena lays its own out)
+struct OwnedQueues {
+    StageLayout layout;
+    size_t at[2][8];
+    explicit OwnedQueues(int64_t capacity)
+    {
+        const size_t cap = (size_t)capacity, w32 = cap * sizeof(uint32_t), v3 = cap * 3 * sizeof(double);
+        for (int k = 0; k < 2; ++k) {
+            size_t *o = at[k];
+            o[0] = layout.add(sizeof(uint32_t)); o[1] = layout.add(w32); o[2] = layout.add(w32); o[3] = layout.add(w32);
+            o[4] = layout.add(v3); o[5] = layout.add(v3); o[6] = layout.add(v3);
+            o[7] = layout.add((size_t)rt_path_scratch_words(capacity) * sizeof(uint32_t));
+        }
+    }
+    rt_path_queue queue(void *base, int k, int64_t capacity) const
+    {
+        char *b = static_cast<char *>(base);
+        const size_t *o = at[k];
+        rt_path_queue q;
+        q.capacity = capacity;
+        q.count = (uint32_t *)(b + o[0]); q.pixel = (uint32_t *)(b + o[1]); q.sample = (uint32_t *)(b + o[2]); q.event = (uint32_t *)(b + o[3]);
+        q.origin = (double *)(b + o[4]); q.dir = (double *)(b + o[5]); q.throughput = (double *)(b + o[6]); q.scratch = (uint32_t *)(b + o[7]);
+        return q;
+    }
+};
+
+// RTIOW_WAVEFRONT_BATCH (read per call): items per batch, default 2^20, in [1, 2^24]
+long long batch_items()
+{
+    const char *e = getenv("RTIOW_WAVEFRONT_BATCH");
+    long long v = e && *e ? atoll(e) : 0;
+    if (v < 1) v = kDefaultBatch;
+    return v > kMaxCapacity ? (long long)kMaxCapacity : v;
+}
+
+int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const void *fix)
+{
+    RT_NEED(cam, what, "cam");
+    RT_NEED(p, what, "params");
+    RT_NEED(fix, what, "fix");
+    if (int rc = validate_params(p)) return rc;
+    if (int rc = check_flags(what, p->flags)) return rc;
+    if (p->shard_count != 1) return fail(RT_ERR_INVALID_ARGUMENT, "%s: shard_count must be 1 (is %d)", what, p->shard_count);
+    if (!std::isfinite(p->t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, p->t_min);
+    return check_context(ctx, what, true);
+}
+
+} // namespace
+
+extern "C" {
+
+int64_t rt_path_scratch_words(int64_t capacity)
+{
+    if (capacity < 1 || capacity > kMaxCapacity) return 0;
+    return rt::kScratchPerWave * ((capacity + 63) / 64);
+}
+
+int rt_paths_begin_device(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, uint32_t flags, int32_t spp,
+                          int32_t sample_begin, int64_t first_item, int64_t n, const rt_path_queue *q, void *stream_v)
+{
+    if (int rc = check_begin(ctx, cam, width, height, flags, spp, sample_begin, first_item, n, q)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return launch_begin(cam, width, height, seed, spp, sample_begin, first_item, n, q, (hipStream_t)stream_v);
+}
+
+int rt_paths_step_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                         void *d_fix, int64_t npix, void *d_rays, void *stream_v)
+{
+    if (int rc = check_step(ctx, flags, t_min, in, out, d_fix, npix)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, (hipStream_t)stream_v);
+}
+
+int rt_render_wavefront_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, void *d_fix, void *d_rays, void *stream_v)
+{
+    if (int rc = check_render(ctx, "rt_render_wavefront", cam, p, d_fix)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const long long npix = (long long)p->width * p->height, total = npix * p->spp;
+    RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(uint64_t), stream));
+    if (d_rays) RT_HIP(hipMemsetAsync(d_rays, 0, sizeof(uint64_t), stream));
+    if (total == 0) return RT_OK;
+    const long long batch = batch_items() < total ? batch_items() : total;
+    const OwnedQueues own(batch);
+    if (int rc = ensure(&ctx->paths.ptr, &ctx->paths.bytes, own.layout.total)) return rc;
+    const rt_path_queue q[2] = {own.queue(ctx->paths.ptr, 0, batch), own.queue(ctx->paths.ptr, 1, batch)};
+    // per batch: begin, then max_depth steps from one queue to the other; nothing here waits for the device.  (A step on an empty queue
+    // leaves at once; what the empty steps of a batch cost is in profiles/paths.txt.)
+    for (long long first = 0; first < total; first += batch) {
+        const long long n = total - first < batch ? total - first : batch;
+        if (int rc = launch_begin(cam, p->width, p->height, p->seed, p->spp, p->sample_begin, first, n, &q[0], stream)) return rc;
+        for (int depth = 0; depth < p->max_depth; ++depth)
+            if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, stream)) return rc;
+    }
+    return RT_OK;
+}
+
+int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *fix, uint64_t *rays_traced, float *kernel_ms)
+{
+    if (int rc = check_render(ctx, "rt_render_wavefront", cam, p, fix)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t fb = (size_t)p->width * p->height * 3 * sizeof(uint64_t);
+    Stage st(ctx);
+    const size_t b_fix = st.add(fb), b_rays = st.add(sizeof(uint64_t));
+    if (int rc = st.commit()) return rc;
+    return timed_section(ctx, "rt_render_wavefront", kernel_ms,
+        [&] { return rt_render_wavefront_device(ctx, cam, p, st.at(b_fix), st.at(b_rays), ctx->own_stream); },
+        [&] {
+            hipError_t he = st.down(fix, b_fix, fb);
+            if (he == hipSuccess && rays_traced) he = st.down(rays_traced, b_rays, sizeof(uint64_t));
+            return he;
+        });
+}
+
+} // extern "C"

@@ -2,8 +2,8 @@
 //
 // The tenth translation unit of librtiow_hip.so.  Three kernels of its own, one lane per path, grid-stride over the batch: what a path needs
 // besides its closest hit (rt_trace.hip) and what until now lived only inside render_kernel -- the camera ray of a (pixel, sample), Scatter::scatter
-// of the three materials on the keyed Philox stream, and the sky term quantised into the exact sums.  They COMPOSE rt_device.hpp (philox4x32_10,
-// u01, u11, unit_sphere_accepts, unit_disk_accepts, reflect, refract, reflectance, min_1, unit_vector, quantize) and state none of it again;
+// of the three materials on the keyed Philox stream, and the sky term quantised into the exact sums.  The per-path bodies are rt_shade_core.hpp,
+// which the fused bounce step of rt_paths.hip shares; the kernels here are load -> call -> store.  The bodies COMPOSE rt_device.hpp and state none of it again;
 // rt_kernels.hpp, rt_device.hpp, rt_params.hpp, rt_launch.hpp, rt_api.hip, rt_dense.hip and rt_first_hit.hpp are untouched, so every other kernel
 // keeps its machine code.  No LDS, no work queue, no scratch, no launch slot.  The sphere's material record is read through vector loads: the
 // index diverges over the wave.
@@ -13,7 +13,7 @@
 #include <cstring>
 
 #include "rt_host.hpp"
-#include "rt_device.hpp"
+#include "rt_shade_core.hpp"
 
 using namespace rt_host;
 
@@ -55,46 +55,21 @@ struct AccumulateArgs {
     unsigned long long npix;
 };
 
-// a NaN result leaves as THE quiet NaN 0x7FF8000000000000, as the ray queries write it (IEEE 754 leaves sign and payload of a generated NaN open)
-__device__ __forceinline__ double shade_canonical_nan(double x)
-{
-    return x != x ? __longlong_as_double(0x7FF8000000000000ll) : x;
-}
-__device__ __forceinline__ void store3(double *p, long long k, D3 v)
-{
-    p[3 * k] = shade_canonical_nan(v.x); p[3 * k + 1] = shade_canonical_nan(v.y); p[3 * k + 2] = shade_canonical_nan(v.z);
-}
-
-// ---- sample_ray: main.rs:131-134 + camera.rs:47-54, the render kernel's own start of a sample --------------------------------------
+// ---- sample_ray (rt_shade_core.hpp) -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kShadeBlock) void camera_rays_kernel(const KCamera cam, const CameraRayArgs A)
 {
     const double wm1 = (double)(A.width - 1), hm1 = (double)(A.height - 1);
     const long long stride = (long long)gridDim.x * kShadeBlock;
     for (long long k = (long long)blockIdx.x * kShadeBlock + threadIdx.x; k < A.n; k += stride) {
-        const uint32_t g_pix = A.pixel[k], g_s = A.sample[k];
-        const uint32_t j = g_pix / (uint32_t)A.width, i = g_pix - j * (uint32_t)A.width;
-        U4 w = philox4x32_10(g_pix, g_s, 0u, 0u, A.k0, A.k1);
-        uint32_t ev = 1u;
-        const double cu = ((double)i + u01(w.x)) / wm1;                 // main.rs:131
-        const double cv = ((double)j + u01(w.y)) / hm1;                 // main.rs:132
-        // vec3.rs:59-68: block 0 = (u jitter, v jitter, lens x, lens y); every further block holds two tries
-        uint32_t wx = w.z, wy = w.w;
-        while (!unit_disk_accepts(wx, wy)) {
-            w = philox4x32_10(g_pix, g_s, ev, 0u, A.k0, A.k1);
-            ev++;
-            wx = w.x; wy = w.y;
-            if (!unit_disk_accepts(wx, wy)) { wx = w.z; wy = w.w; }
-        }
-        const D3 cam_origin = ld3(cam.origin);
-        const D3 rd = mk(u11(wx), u11(wy), 0.0) * cam.lens_radius;
-        const D3 offset = ld3(cam.u) * rd.x + ld3(cam.v) * rd.y;
-        store3(A.origin, k, cam_origin + offset);
-        store3(A.dir, k, (((ld3(cam.llc) + ld3(cam.horizontal) * cu) + ld3(cam.vertical) * cv) - cam_origin) - offset);
+        D3 origin, dir;
+        const uint32_t ev = sample_ray(cam, (uint32_t)A.width, wm1, hm1, A.pixel[k], A.sample[k], A.k0, A.k1, origin, dir);
+        store3(A.origin, k, origin);
+        store3(A.dir, k, dir);
         A.event[k] = ev;
     }
 }
 
-// ---- Scatter::scatter, materials.rs:21-31, 48-62, 76-105 ----------------------------------------------------------------------------
+// ---- Scatter::scatter (rt_shade_core.hpp) -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kShadeBlock) void scatter_kernel(const ScatterArgs A)
 {
     const long long stride = (long long)gridDim.x * kShadeBlock;
@@ -107,69 +82,8 @@ __global__ __launch_bounds__(kShadeBlock) void scatter_kernel(const ScatterArgs 
         const bool front = A.front[k] != 0;
         const uint32_t g_pix = A.pixel[k], g_s = A.sample[k];
         uint32_t ev = A.event[k];
-        const double *mrec = A.mat + kMatStride * (size_t)hit;
-        const double2 mA = *reinterpret_cast<const double2 *>(mrec);          // 1/r, param
-        const double2 mB = *reinterpret_cast<const double2 *>(mrec + 2);      // albedo r, g
-        const double2 mC = *reinterpret_cast<const double2 *>(mrec + 4);      // albedo b, kind
-        const int kind = (int)mC.y;
-        const double param = mA.y;
-        const D3 albedo = mk(mB.x, mB.y, mC.x);                               // (a Dialectric's record holds (1, 1, 1), materials.rs:103)
-
-        D3 ndir;
-        bool absorbed = false;
-        if (kind != RT_KIND_DIALECTRIC) {
-            // vec3.rs:37-45: redraw until |p|^2 < 1, a plain loop to acceptance.  The tries of one scatter take consecutive words of consecutive
-            // blocks: four tries per three blocks.
-            U4 b = philox4x32_10(g_pix, g_s, ev, 0u, A.k0, A.k1);
-            uint32_t nblk = 1u;
-            uint32_t tx = b.x, ty = b.y, tz = b.z, c0 = b.w;
-            bool ok = unit_sphere_accepts(tx, ty, tz);                                       // try 4m
-            while (!ok) {
-                b = philox4x32_10(g_pix, g_s, ev + nblk, 0u, A.k0, A.k1);
-                nblk++;
-                tx = c0; ty = b.x; tz = b.y;                                                 // try 4m+1
-                ok = unit_sphere_accepts(tx, ty, tz);
-                if (!ok) {
-                    const uint32_t c1 = b.z, c2 = b.w;
-                    b = philox4x32_10(g_pix, g_s, ev + nblk, 0u, A.k0, A.k1);
-                    nblk++;
-                    tx = c1; ty = c2; tz = b.x;                                              // try 4m+2
-                    ok = unit_sphere_accepts(tx, ty, tz);
-                    if (!ok) {
-                        tx = b.y; ty = b.z; tz = b.w;                                        // try 4m+3: no new block
-                        ok = unit_sphere_accepts(tx, ty, tz);
-                        if (!ok) {
-                            b = philox4x32_10(g_pix, g_s, ev + nblk, 0u, A.k0, A.k1);
-                            nblk++;
-                            tx = b.x; ty = b.y; tz = b.z; c0 = b.w;                          // try 4m+4 = try 0 of the next three blocks
-                            ok = unit_sphere_accepts(tx, ty, tz);
-                        }
-                    }
-                }
-            }
-            ev += nblk;
-            const D3 sp = mk(u11(tx), u11(ty), u11(tz));
-            if (kind == RT_KIND_LAMBERTIAN) {                                                // materials.rs:21-31
-                ndir = nrm + unit_vector(sp);
-                const double eps = 1e-8;                                                     // vec3.rs:111-114
-                if (__builtin_fabs(ndir.x) < eps && __builtin_fabs(ndir.y) < eps && __builtin_fabs(ndir.z) < eps) ndir = nrm;
-            } else {                                                                         // materials.rs:48-62
-                ndir = unit_vector(reflect(d, nrm)) + sp * param;
-                absorbed = dot(ndir, nrm) <= 0.0;
-            }
-        } else {                                                                             // materials.rs:76-105
-            const double ratio = front ? mrec[6] : param;                                    // 1.0 / ir, hoisted by the upload: the same operation
-            const D3 ud = unit_vector(d);
-            const double cos_theta = min_1(-dot(ud, nrm));
-            const double sin_theta = __builtin_sqrt(1.0 - cos_theta * cos_theta);
-            bool do_refract = false;
-            if (ratio * sin_theta <= 1.0) {                                                  // && short-circuit: the draw only if it can refract
-                const U4 w = philox4x32_10(g_pix, g_s, ev, 0u, A.k0, A.k1);
-                ev++;
-                do_refract = reflectance(cos_theta, ratio) <= u01(w.x);
-            }
-            ndir = do_refract ? refract(ud, nrm, ratio) : reflect(ud, nrm);
-        }
+        D3 ndir, albedo;
+        const bool absorbed = scatter_path(A.mat + kMatStride * (size_t)hit, d, nrm, front, g_pix, g_s, ev, A.k0, A.k1, ndir, albedo);
 
         A.event[k] = ev;
         if (absorbed) {
@@ -193,12 +107,7 @@ __global__ __launch_bounds__(kShadeBlock) void accumulate_kernel(const Accumulat
         const unsigned long long pix = A.pixel[k];
         if (pix >= A.npix) continue;
         D3 v = ld3(A.weight + 3 * k);
-        if (A.sky_dir) {
-            const D3 ud = unit_vector(ld3(A.sky_dir + 3 * k));                               // main.rs:54-56
-            const double t = 0.5 * (ud.y + 1.0);
-            const D3 sky = mk(1.0, 1.0, 1.0) * (1.0 - t) + mk(0.5, 0.7, 1.0) * t;
-            v = v * sky;                                                                     // contract C3: mulv(throughput, sky)
-        }
+        if (A.sky_dir) v = sky_sample(v, ld3(A.sky_dir + 3 * k));
         unsigned long long *px = A.fix + (size_t)pix * 3u;
         atomicAdd(px + 0, quantize(v.x)); atomicAdd(px + 1, quantize(v.y)); atomicAdd(px + 2, quantize(v.z));
     }

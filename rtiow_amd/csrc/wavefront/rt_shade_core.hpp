@@ -1,0 +1,127 @@
+// rt_shade_core.hpp -- the per-path bodies of the wavefront steps: the camera ray of a (pixel, sample), Scatter::scatter of the three
+// materials on the keyed Philox stream, and the sky sample.  Values in, values out: no global load except the material record, no store.
+// wavefront/rt_shade.hip (one step per kernel: load -> call -> store) and wavefront/rt_paths.hip (the fused bounce step of the device path
+// queue) call the same functions, so the arithmetic is stated once.  They COMPOSE rt_device.hpp (philox4x32_10, u01, u11,
+// unit_sphere_accepts, unit_disk_accepts, reflect, refract, reflectance, min_1, unit_vector) and state none of it again.
+#pragma once
+#include "rt_params.hpp"
+#include "rt_device.hpp"
+
+namespace rt {
+
+// a NaN result leaves as THE quiet NaN 0x7FF8000000000000, as the ray queries write it (IEEE 754 leaves sign and payload of a generated NaN open)
+__device__ __forceinline__ double shade_canonical_nan(double x)
+{
+    return x != x ? __longlong_as_double(0x7FF8000000000000ll) : x;
+}
+__device__ __forceinline__ void store3(double *p, long long k, D3 v)
+{
+    p[3 * k] = shade_canonical_nan(v.x); p[3 * k + 1] = shade_canonical_nan(v.y); p[3 * k + 2] = shade_canonical_nan(v.z);
+}
+
+// ---- sample_ray: main.rs:131-134 + camera.rs:47-54, the render kernel's own start of a sample -----------------------------------------
+// wm1, hm1: (double)(width - 1), (double)(height - 1).  Returns the next unused Philox block of the path's stream.
+__device__ __forceinline__ uint32_t sample_ray(const KCamera &cam, uint32_t width, double wm1, double hm1, uint32_t g_pix, uint32_t g_s, uint32_t k0,
+                                               uint32_t k1, D3 &origin, D3 &dir)
+{
+    const uint32_t j = g_pix / width, i = g_pix - j * width;
+    U4 w = philox4x32_10(g_pix, g_s, 0u, 0u, k0, k1);
+    uint32_t ev = 1u;
+    const double cu = ((double)i + u01(w.x)) / wm1;                 // main.rs:131
+    const double cv = ((double)j + u01(w.y)) / hm1;                 // main.rs:132
+    // vec3.rs:59-68: block 0 = (u jitter, v jitter, lens x, lens y); every further block holds two tries
+    uint32_t wx = w.z, wy = w.w;
+    while (!unit_disk_accepts(wx, wy)) {
+        w = philox4x32_10(g_pix, g_s, ev, 0u, k0, k1);
+        ev++;
+        wx = w.x; wy = w.y;
+        if (!unit_disk_accepts(wx, wy)) { wx = w.z; wy = w.w; }
+    }
+    const D3 cam_origin = ld3(cam.origin);
+    const D3 rd = mk(u11(wx), u11(wy), 0.0) * cam.lens_radius;
+    const D3 offset = ld3(cam.u) * rd.x + ld3(cam.v) * rd.y;
+    origin = cam_origin + offset;
+    dir = (((ld3(cam.llc) + ld3(cam.horizontal) * cu) + ld3(cam.vertical) * cv) - cam_origin) - offset;
+    return ev;
+}
+
+// ---- Scatter::scatter, materials.rs:21-31, 48-62, 76-105 ------------------------------------------------------------------------------
+// The hit (d: the incoming direction; nrm, front: the record's normal and face) on the sphere whose material record is mrec.  ev: the
+// path's next unused block, advanced.  Returns `absorbed`; otherwise ndir is the scattered direction and albedo the attenuation.
+__device__ __forceinline__ bool scatter_path(const double *mrec, const D3 &d, const D3 &nrm, bool front, uint32_t g_pix, uint32_t g_s, uint32_t &ev,
+                                             uint32_t k0, uint32_t k1, D3 &ndir, D3 &albedo)
+{
+    const double2 mA = *reinterpret_cast<const double2 *>(mrec);          // 1/r, param
+    const double2 mB = *reinterpret_cast<const double2 *>(mrec + 2);      // albedo r, g
+    const double2 mC = *reinterpret_cast<const double2 *>(mrec + 4);      // albedo b, kind
+    const int kind = (int)mC.y;
+    const double param = mA.y;
+    albedo = mk(mB.x, mB.y, mC.x);                                        // (a Dialectric's record holds (1, 1, 1), materials.rs:103)
+
+    bool absorbed = false;
+    if (kind != RT_KIND_DIALECTRIC) {
+        // vec3.rs:37-45: redraw until |p|^2 < 1, a plain loop to acceptance.  The tries of one scatter take consecutive words of consecutive
+        // blocks: four tries per three blocks.
+        U4 b = philox4x32_10(g_pix, g_s, ev, 0u, k0, k1);
+        uint32_t nblk = 1u;
+        uint32_t tx = b.x, ty = b.y, tz = b.z, c0 = b.w;
+        bool ok = unit_sphere_accepts(tx, ty, tz);                                       // try 4m
+        while (!ok) {
+            b = philox4x32_10(g_pix, g_s, ev + nblk, 0u, k0, k1);
+            nblk++;
+            tx = c0; ty = b.x; tz = b.y;                                                 // try 4m+1
+            ok = unit_sphere_accepts(tx, ty, tz);
+            if (!ok) {
+                const uint32_t c1 = b.z, c2 = b.w;
+                b = philox4x32_10(g_pix, g_s, ev + nblk, 0u, k0, k1);
+                nblk++;
+                tx = c1; ty = c2; tz = b.x;                                              // try 4m+2
+                ok = unit_sphere_accepts(tx, ty, tz);
+                if (!ok) {
+                    tx = b.y; ty = b.z; tz = b.w;                                        // try 4m+3: no new block
+                    ok = unit_sphere_accepts(tx, ty, tz);
+                    if (!ok) {
+                        b = philox4x32_10(g_pix, g_s, ev + nblk, 0u, k0, k1);
+                        nblk++;
+                        tx = b.x; ty = b.y; tz = b.z; c0 = b.w;                          // try 4m+4 = try 0 of the next three blocks
+                        ok = unit_sphere_accepts(tx, ty, tz);
+                    }
+                }
+            }
+        }
+        ev += nblk;
+        const D3 sp = mk(u11(tx), u11(ty), u11(tz));
+        if (kind == RT_KIND_LAMBERTIAN) {                                                // materials.rs:21-31
+            ndir = nrm + unit_vector(sp);
+            const double eps = 1e-8;                                                     // vec3.rs:111-114
+            if (__builtin_fabs(ndir.x) < eps && __builtin_fabs(ndir.y) < eps && __builtin_fabs(ndir.z) < eps) ndir = nrm;
+        } else {                                                                         // materials.rs:48-62
+            ndir = unit_vector(reflect(d, nrm)) + sp * param;
+            absorbed = dot(ndir, nrm) <= 0.0;
+        }
+    } else {                                                                             // materials.rs:76-105
+        const double ratio = front ? mrec[6] : param;                                    // 1.0 / ir, hoisted by the upload: the same operation
+        const D3 ud = unit_vector(d);
+        const double cos_theta = min_1(-dot(ud, nrm));
+        const double sin_theta = __builtin_sqrt(1.0 - cos_theta * cos_theta);
+        bool do_refract = false;
+        if (ratio * sin_theta <= 1.0) {                                                  // && short-circuit: the draw only if it can refract
+            const U4 w = philox4x32_10(g_pix, g_s, ev, 0u, k0, k1);
+            ev++;
+            do_refract = reflectance(cos_theta, ratio) <= u01(w.x);
+        }
+        ndir = do_refract ? refract(ud, nrm, ratio) : reflect(ud, nrm);
+    }
+    return absorbed;
+}
+
+// ---- contract C3: mulv(throughput, sky(dir)), main.rs:54-56 ---------------------------------------------------------------------------
+__device__ __forceinline__ D3 sky_sample(const D3 &weight, const D3 &dir)
+{
+    const D3 ud = unit_vector(dir);                                                      // main.rs:54-56
+    const double t = 0.5 * (ud.y + 1.0);
+    const D3 sky = mk(1.0, 1.0, 1.0) * (1.0 - t) + mk(0.5, 0.7, 1.0) * t;
+    return weight * sky;                                                                 // contract C3: mulv(throughput, sky)
+}
+
+} // namespace rt

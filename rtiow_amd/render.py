@@ -336,6 +336,63 @@ def render_wavefront_torch(renderer, cam, params, batch=1 << 20):
     return fix, rays
 
 
+# -- the device path queue (rt_paths_begin_device / rt_paths_step_device) -----------------------------------------
+
+class PathQueue:
+    """An rt_path_queue of `capacity` slots as torch tensors on `device`: count int32 [1], pixel / sample / event int32 [capacity],
+    origin / dir / throughput float64 [capacity, 3], scratch int32 [rt_path_scratch_words(capacity)] (the 32-bit unsigned arrays travel
+    as int32 tensors holding the same bits).  The live paths are slots [0, count), and count lives on the device: reading it
+    (`int(q.count)`) is a host wait the integrator itself never takes."""
+    FIELDS = ("count", "pixel", "sample", "event", "origin", "dir", "throughput", "scratch")
+
+    def __init__(self, capacity, device):
+        import torch
+        capacity = int(capacity)
+        words = int(_ffi.load().rt_path_scratch_words(capacity))
+        if words == 0:
+            raise ValueError(f"capacity must be in [1, 2^24] (is {capacity})")
+        self.capacity, self.device = capacity, torch.device(device)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=self.device)
+        f64 = lambda: torch.zeros((capacity, 3), dtype=torch.float64, device=self.device)
+        self.count, self.pixel, self.sample, self.event = i32(1), i32(capacity), i32(capacity), i32(capacity)
+        self.origin, self.dir, self.throughput = f64(), f64(), f64()
+        self.scratch = i32(words)
+
+    def struct(self):
+        """The rt_path_queue naming the tensors' memory (valid while they live)."""
+        return _ffi.rt_path_queue(self.capacity, *[getattr(self, f).data_ptr() for f in self.FIELDS])
+
+
+def _check_queue(renderer, q, name):
+    if q.device.type != "cuda" or q.device.index != renderer.device_id:
+        raise ValueError(f"{name} must be on the renderer's device cuda:{renderer.device_id} (is on {q.device})")
+
+
+def paths_begin_torch(renderer, cam, width, height, seed, spp, sample_begin, first_item, n, queue):
+    """rt_paths_begin_device on a PathQueue, on torch.cuda.current_stream(): slots [0, n) become the items first_item .. first_item + n - 1
+    (pixel = item // spp, sample = sample_begin + item % spp) with their camera rays, throughput 1; count = n.  No host wait."""
+    import torch
+    _check_queue(renderer, queue, "queue")
+    with torch.cuda.device(queue.device):
+        renderer.paths_begin_device(cam, width, height, seed, spp, sample_begin, first_item, n, queue.struct(), torch.cuda.current_stream().cuda_stream)
+
+
+def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4):
+    """rt_paths_step_device on two PathQueues, on torch.cuda.current_stream(): one bounce of the live paths of `qin`; the survivors go to
+    `qout` in order.  fix: an int64 tensor [..., 3] holding the u64 sums' bits, added to; rays: an int64 tensor [1] that gains the live
+    count, or None.  No host wait."""
+    import torch
+    _check_queue(renderer, qin, "qin")
+    _check_queue(renderer, qout, "qout")
+    items = [("fix", fix, torch.int64, tuple(fix.shape))] + ([("rays", rays, torch.int64, (1,))] if rays is not None else [])
+    _torch_check(torch, renderer, items)
+    if fix.dim() < 1 or fix.shape[-1] != 3:
+        raise ValueError(f"fix must be [..., 3] (is {tuple(fix.shape)})")
+    with torch.cuda.device(qin.device):
+        renderer.paths_step_device(seed, qin.struct(), qout.struct(), fix.data_ptr(), fix.numel() // 3, rays.data_ptr() if rays is not None else 0,
+                                   t_min, torch.cuda.current_stream().cuda_stream)
+
+
 class Renderer:
     """One rt_context (one GPU)."""
 
@@ -704,6 +761,36 @@ class Renderer:
         b = _ffi.rt_accumulate_batch(d_pixel_ptr or None, d_weight_ptr or None, d_sky_dir_ptr or None, d_select_ptr or None, int(n))
         _ffi.check(self._lib.rt_accumulate_device(self._h, C.byref(b), C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
                                                   C.c_void_p(stream)), "rt_accumulate_device")
+
+    # -- the device path queue and the frame rendered from it ----------------------------
+    def paths_begin_device(self, cam, width, height, seed, spp, sample_begin, first_item, n, queue, stream=0, flags=0):
+        """rt_paths_begin_device; queue: an _ffi.rt_path_queue of device pointers (PathQueue.struct()); asynchronous on `stream`."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        _ffi.check(self._lib.rt_paths_begin_device(self._h, C.byref(rc), int(width), int(height), int(seed), int(flags), int(spp), int(sample_begin),
+                                                   int(first_item), int(n), C.byref(queue), C.c_void_p(stream)), "rt_paths_begin_device")
+
+    def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0):
+        """rt_paths_step_device; qin, qout: _ffi.rt_path_queue structs of device pointers; asynchronous on `stream`."""
+        _ffi.check(self._lib.rt_paths_step_device(self._h, int(seed), int(flags), float(t_min), C.byref(qin), C.byref(qout),
+                                                  C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
+                                                  C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)), "rt_paths_step_device")
+
+    def render_wavefront(self, cam, params):
+        """rt_render_wavefront: the frame through the device path queue -> (the exact sums u64 [H, W, 3], the rays traced): what
+        Renderer.render returns as `fix` and as stats["rays_traced"]."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        fix = np.zeros((params.height, params.width, 3), dtype=np.uint64)
+        rays = C.c_uint64(0)
+        _ffi.check(self._lib.rt_render_wavefront(self._h, C.byref(rc), C.byref(params), fix.ctypes.data_as(C.c_void_p), C.byref(rays), None),
+                   "rt_render_wavefront")
+        return fix, int(rays.value)
+
+    def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0):
+        """rt_render_wavefront_device on raw device pointers (d_fix [H][W][3] u64, d_rays one u64 or 0); asynchronous on `stream`."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        _ffi.check(self._lib.rt_render_wavefront_device(self._h, C.byref(rc), C.byref(params), C.c_void_p(d_fix_ptr) if d_fix_ptr else None,
+                                                        C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)),
+                   "rt_render_wavefront_device")
 
     # -- denoiser: an edge-avoiding a-trous filter driven by the feature buffers -------
     def denoise(self, fix, spp, feat, feat_spp, denoise=None, count=None):
