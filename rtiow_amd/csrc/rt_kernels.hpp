@@ -660,6 +660,11 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
             // owners push the candidates of segment seg0 (ascending sphere order); rounds run as the ring fills
             // MODE 5: the tiles this pass scans -- every tile of the table in turn, or the list behind the bitmap words
             bool list_all = true;
+#if defined(RT_LDS_CONFLICTS) || defined(RT_COUNT_ENUM)
+            constexpr bool kAsmWalk = false;                    // (the conflict model and the trip counters read each trip's masks and addresses)
+#else
+            constexpr bool kAsmWalk = CAPPED && TUBE && SMALLGRID;
+#endif
             auto enumerate = [&](int seg0, int nwords_tube = 0) {
                 unsigned summary = 0u, word = 0u;
                 if constexpr (TUBE) {
@@ -684,7 +689,77 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 } else {
                     summary = alive ? s_sum[tid] : 0u;
                 }
+                // (kAsmWalk, once per call: the walk's LDS addresses and the full lane mask its trips restore)
+                uint32_t row_at = 0u, tl_at = 0u, pool_at = 0u;
+                unsigned long long full_exec = 0ull;
+                if constexpr (kAsmWalk) {
+                    typedef __attribute__((address_space(3))) unsigned int *LdsWord;
+                    row_at = (uint32_t)(uintptr_t)(LdsWord)(bits_w + lane);                     // word w of this lane: + 256 w
+                    tl_at = (uint32_t)(uintptr_t)(LdsWord)(bits_w + seg0);                      // the tile of word w: + 4 (kSeg / 2) 64 + 4 w
+                    pool_at = (uint32_t)(uintptr_t)(LdsWord)pool_w;
+                    asm volatile("s_mov_b64 %[fx], exec" : [fx] "=s"(full_exec));
+                }
                 int wbase = 0;
+                if constexpr (kAsmWalk) {
+                    // The capped small-grid kernels: the trips of the loop below as ONE asm block that loops until the walk is over or 64 pairs wait
+                    // for a pooled round (pool_round stays C++ and runs between two entries) -- lane for lane the same refills and the same pushes
+                    // in the same trips, so the ring holds the same pairs in the same order.  v_cmpx narrows exec to the lanes that have a candidate
+                    // and leaves their mask in vcc: the rank (v_mbcnt) and the count (s_bcnt1) read it, and the empty-exec branch behind it is the
+                    // walk's exit.  A lane never gains a candidate during a call, so exec only narrows from trip to trip and the full mask, saved once
+                    // per call, comes back when the block is left, not after every trip.  The refill runs under a second v_cmpx (word == 0) and
+                    // exec comes back from vcc; a trip in which no lane refills branches round it: measured without that branch, the two LDS reads
+                    // of an empty refill and the wait for them cost more than the branch (profiles/scalar_trim3_ab.txt).  8 scalar instructions and
+                    // 3 exec writes per trip where the compiler's form has 15 and 4 (two s_and_saveexec regions with a branch each, two s_or restores,
+                    // three copies of pool_n / pool_done, beside two dead v_readfirstlane).  The block touches vector registers, scalar registers and
+                    // LDS -- nothing on the scalar unit writes memory -- and waits for its own two LDS reads.
+                    for (;;) {
+                        uint32_t cnt, av, t0, t1, t2;
+                        unsigned long long refill_m;
+                        asm volatile("0:\n\t"
+                                     "v_or_b32_e32 %[t0], %[sum], %[word]\n\t"
+                                     "v_cmpx_ne_u32_e32 vcc, 0, %[t0]\n\t"                     // exec = vcc = has (a lane never gains a candidate: exec only narrows from trip to trip)
+                                     "s_cbranch_execz 1f\n\t"
+                                     "s_bcnt1_i32_b64 %[cnt], vcc\n\t"
+                                     "v_mbcnt_lo_u32_b32 %[t2], vcc_lo, 0\n\t"
+                                     "v_mbcnt_hi_u32_b32 %[t2], vcc_hi, %[t2]\n\t"
+                                     "v_cmpx_eq_u32_e64 %[rm], 0, %[word]\n\t"                 // exec = has && word == 0: the refill
+                                     "s_cbranch_execz 2f\n\t"
+                                     "v_ffbl_b32_e32 %[t0], %[sum]\n\t"
+                                     "v_lshl_add_u32 %[t1], %[t0], 8, %[row]\n\t"
+                                     "v_lshl_add_u32 %[t0], %[t0], 2, %[tl]\n\t"
+                                     "ds_read_b32 %[t0], %[t0] offset:%[tlo]\n\t"
+                                     "ds_read_b32 %[word], %[t1]\n\t"
+                                     "v_add_u32_e32 %[t1], -1, %[sum]\n\t"
+                                     "v_and_b32_e32 %[sum], %[t1], %[sum]\n\t"
+                                     "s_waitcnt lgkmcnt(1)\n\t"
+                                     "v_lshlrev_b32_e32 %[wb], 5, %[t0]\n\t"                   // (32 * (entry & 0x0FFFFFFF): the shift drops the group bits)
+                                     "s_waitcnt lgkmcnt(0)\n"
+                                     "2:\n\t"
+                                     "s_mov_b64 exec, vcc\n\t"                                 // exec = has: the push
+                                     "v_ffbl_b32_e32 %[t0], %[word]\n\t"
+                                     "v_add_u32_e32 %[t1], -1, %[word]\n\t"
+                                     "v_and_b32_e32 %[word], %[t1], %[word]\n\t"
+                                     "v_add_u32_e32 %[t2], %[pn], %[t2]\n\t"
+                                     "v_add_u32_e32 %[t0], %[t0], %[wb]\n\t"
+                                     "v_and_b32_e32 %[t2], 0x7f, %[t2]\n\t"
+                                     "v_lshl_or_b32 %[t0], %[t0], 6, %[ln]\n\t"
+                                     "v_lshl_add_u32 %[t2], %[t2], 2, %[pool]\n\t"
+                                     "ds_write_b32 %[t2], %[t0]\n\t"
+                                     "s_add_i32 %[pn], %[pn], %[cnt]\n\t"
+                                     "s_sub_i32 %[av], %[pn], %[pd]\n\t"
+                                     "s_cmp_lt_u32 %[av], 64\n\t"
+                                     "s_cbranch_scc1 0b\n"                                     // (64 pairs wait: out, for a pooled round)
+                                     "1:\n\t"
+                                     "s_mov_b64 exec, %[fx]"
+                                     : [sum] "+v"(summary), [word] "+v"(word), [wb] "+v"(wbase), [pn] "+s"(pool_n), [cnt] "=&s"(cnt), [av] "=&s"(av), [rm] "=&s"(refill_m),
+                                       [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2)
+                                     : [row] "v"(row_at), [tl] "v"(tl_at), [pool] "v"(pool_at), [ln] "v"(lane), [fx] "s"(full_exec), [pd] "s"(pool_done),
+                                       [tlo] "i"(4 * (kSeg / 2) * 64)
+                                     : "vcc", "scc", "memory");
+                        if (pool_n - pool_done < 64u) break;
+                        pool_round();
+                    }
+                } else
                 for (;;) {
                     const bool has = (summary | word) != 0u;
                     const unsigned long long m = __ballot(has);
@@ -720,6 +795,15 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     //  mod.rs:61-67's later-sphere-wins; a ray outside the filter's range has no candidates, its seed, NaN roots
                     //  included, comes back bit for bit)
                     if (alive) { hit = (int)hb - 1; closest = key_f64(best_w[lane]); }
+                } else if constexpr (CAPPED) {
+                    // (the capped dense kernels: the same decision without a lane-level region -- every lane reads its own minimum, the four
+                    //  compares are combined as masks on the scalar unit and three selects take the hit: two nested exec regions with a branch
+                    //  and two restores less.  A lane without a ray or without a pooled root takes nothing, as below; a NaN root passes no compare.)
+                    const double root = key_f64(best_w[lane]);
+                    const int idx = (int)hb - 1;
+                    const bool take = alive & (hb != 0u) & ((root < closest) | ((root == closest) & (idx > hit)));
+                    closest = take ? root : closest;
+                    hit = take ? idx : hit;
                 } else
                 if (alive && hb != 0u) {
                     const double root = key_f64(best_w[lane]);

@@ -11,6 +11,8 @@ hardware's instruction counters (SQ_INSTS_VALU per wave-bounce).
 usage: tools/isa_census.py [--kernel SUBSTR] [--tenk] [--frames] [--dense] [-D...]   default kernel: render_kernelILi5ELb0ELb1ELb0ELi256 (shipped, small grid)
        --frames: the frame-batch instantiation of the small-grid kernel (render_kernelILi5ELb0ELb1ELb0ELin512, compiled from rt_frames.hip)
        --dense: the capped-redraw instantiation of the small-grid kernel on blocks of 1 024 (render_kernelILi5ELb0ELb1ELb0ELin1024, compiled from rt_dense.hip)
+       --call-site-lines: an inlined lambda's instructions without a source line go to the line of its call (how the records up to
+                          profiles/scalar_trim2_census_after.txt were taken), not to the lambda
 """
 import collections, json, os, re, subprocess, sys
 
@@ -263,11 +265,32 @@ def main():
     unplaced = collections.Counter()
     philox_in = collections.Counter()
     last_ph = None
+    # A frame WITHOUT a line inside an inlined helper (the exec restores that close pool_round's nested lane-level `if`s: nine scalar instructions that run
+    # once per pooled round) used to fall through to the line of the CALL, i.e. to the walk's trip or to finish_pool, and was charged per trip.  The
+    # line tables name every lambda "operator()", so the helper is found through the call: when the frame outside a line-less one sits on a line that calls
+    # exactly one of this file's lambdas (`auto NAME = [`), the line-less frame counts as that lambda's first line.  --call-site-lines: the old attribution.
+    lambda_at = {}
+    if "--call-site-lines" not in args:
+        for i, text in enumerate(lines):
+            m = re.search(r"\bauto (\w+) = \[", text)
+            if m:
+                lambda_at[m.group(1)] = i + 1
+
+    def helper_lines(stack):
+        out = []
+        for k, (fn, f, ln) in enumerate(stack[:-1]):
+            outer = stack[k + 1]
+            if f == "rt_kernels.hpp" and ln == 0 and outer[1] == "rt_kernels.hpp" and 0 < outer[2] <= len(lines):
+                called = {n for n in lambda_at if re.search(r"\b%s\(" % n, lines[outer[2] - 1]) and lambda_at[n] != outer[2]}
+                if len(called) == 1:
+                    out.append(lambda_at[called.pop()])
+        return out
+
     for addr, op, ops in ins:
         cls, cyc = classify(op, ops)
         cost[cls] = cyc
         stack = sym.get(addr, [])
-        klines = [ln for fn, f, ln in stack if f == "rt_kernels.hpp"]
+        klines = [ln for fn, f, ln in stack if f == "rt_kernels.hpp"] + helper_lines(stack)
         ph = None
         for name, lo, hi, _, _ in phases:
             if any(lo <= ln <= hi for ln in klines):
