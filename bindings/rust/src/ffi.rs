@@ -264,6 +264,24 @@ pub struct rt_path_queue {
     pub scratch: *mut u32,
 }
 
+/// What lights a frame of the path queue (`rt_paths_step_lit_device`, `rt_render_wavefront_lit*`): the two ends of the sky gradient and one
+/// radiance per uploaded sphere (`emission`: `[n_emission][3]`, a DEVICE pointer in the `_device` forms, a host pointer in
+/// `rt_render_wavefront_lit`; null: no lights).  A sphere is a light iff a channel of its entry is `> 0`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_lighting {
+    pub sky_bottom: [f64; 3],
+    pub sky_top: [f64; 3],
+    pub emission: *const f64,
+    pub n_emission: i32,
+    pub flags: u32,
+}
+
+const _: () = assert!(offset_of!(rt_lighting, sky_top) == 24);
+const _: () = assert!(offset_of!(rt_lighting, emission) == 48);
+const _: () = assert!(offset_of!(rt_lighting, n_emission) == 56);
+const _: () = assert!(offset_of!(rt_lighting, flags) == 60);
+const _: () = assert!(64 == size_of::<rt_lighting>());
 const _: () = assert!(offset_of!(rt_path_queue, count) == 8);
 const _: () = assert!(offset_of!(rt_path_queue, scratch) == 64);
 const _: () = assert!(72 == size_of::<rt_path_queue>());
@@ -391,6 +409,16 @@ extern "C" {
                                       d_rays: *mut c_void, stream: *mut c_void) -> i32;
     pub fn rt_render_wavefront(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, fix: *mut u64, rays_traced: *mut u64,
                                kernel_ms: *mut f32) -> i32;
+    /// The path queue with a settable sky and emissive spheres: a miss adds the sky of `light`, a hit on a sphere whose entry of
+    /// `light.emission` has a channel `> 0` adds `throughput * e` and ends the path.  With the reference's sky and no table these are the
+    /// unlit forms bit for bit.
+    pub fn rt_paths_step_lit_device(ctx: *mut rt_context, seed: u64, flags: u32, t_min: f64, input: *const rt_path_queue,
+                                    output: *const rt_path_queue, d_fix: *mut c_void, npix: i64, d_rays: *mut c_void,
+                                    light: *const rt_lighting, stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_lit_device(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                          d_fix: *mut c_void, d_rays: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_lit(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                   fix: *mut u64, rays_traced: *mut u64, kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -9,7 +9,7 @@
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
-//                [--pick I,J] [--wavefront]
+//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]...]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -42,6 +42,10 @@
 // frames are written as the batch writes them.  --denoise goes with a batch only together with --temporal.
 // --wavefront: the same frame through the device path queue (rt_render_wavefront: per batch one begin and --depth fused bounce steps, DESIGN.md
 // section 19), then rt_resolve_rgba8: the bytes of the default run.  Single device; with none of the other modes.
+// --sky B_r,B_g,B_b:T_r,T_g,T_b and --emit INDEX:r,g,b (repeatable), both only with --wavefront: the frame lit by a settable sky -- colour B
+// where the unit ray direction's y is -1, T where it is +1; the reference's is 1,1,1:0.5,0.7,1 -- and by emissive spheres -- sphere INDEX of
+// the scene's list radiates (r, g, b), a path that reaches it adds throughput * (r, g, b) and ends -- (rt_render_wavefront_lit, DESIGN.md
+// section 20).  --sky 0,0,0:0,0,0 --emit 0:4,3.2,2.4 is a night frame lit by one sphere.
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -103,6 +107,12 @@ int main(int argc, char **argv)
     dn.levels = 4; dn.flags = RT_DENOISE_DEMODULATE; dn.sigma_color = 0.35; dn.sigma_normal = 1.0; dn.sigma_depth = 0.2;
     bool pick = false;
     int pick_i = 0, pick_j = 0;
+    bool lit = false;                            // --sky / --emit: the lit wavefront frame
+    rt_lighting light{};
+    light.sky_bottom[0] = light.sky_bottom[1] = light.sky_bottom[2] = 1.0;
+    light.sky_top[0] = 0.5; light.sky_top[1] = 0.7; light.sky_top[2] = 1.0;
+    struct Emit { long index; double rgb[3]; };
+    std::vector<Emit> emits;
     bool temporal = false;
     struct rt_temporal tp{};
     tp.flags = RT_TEMPORAL_CLAMP; tp.alpha_min = 0.1; tp.sigma_normal = 0.5; tp.sigma_depth = 0.1; tp.clamp_scale = 1.0;
@@ -164,6 +174,25 @@ int main(int argc, char **argv)
         else if (arg("--temporal-clamp")) {
             tp.clamp_scale = std::atof(argv[++i]);
             if (tp.clamp_scale < 0.0) { tp.flags = 0u; tp.clamp_scale = 1.0; }
+        }
+        else if (arg("--sky")) {
+            double *b = light.sky_bottom, *t = light.sky_top;
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%lf,%lf,%lf:%lf,%lf,%lf%c", &b[0], &b[1], &b[2], &t[0], &t[1], &t[2], &tail) != 6) {
+                std::fprintf(stderr, "--sky B_r,B_g,B_b:T_r,T_g,T_b\n");
+                return 2;
+            }
+            lit = true;
+        }
+        else if (arg("--emit")) {
+            Emit e{};
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%ld:%lf,%lf,%lf%c", &e.index, &e.rgb[0], &e.rgb[1], &e.rgb[2], &tail) != 4) {
+                std::fprintf(stderr, "--emit INDEX:r,g,b\n");
+                return 2;
+            }
+            emits.push_back(e);
+            lit = true;
         }
         else if (arg("--scene")) scene_file = argv[++i];
         else if (arg("--pick")) {
@@ -353,6 +382,22 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--wavefront runs on one device and goes with none of --devices, --adaptive, --denoise, --passes, --two-calls, --uniform53, --features\n");
         return 2;
     }
+    if (lit && !wavefront) {
+        std::fprintf(stderr, "--sky and --emit light the frame of the device path queue only: they need --wavefront\n");
+        return 2;
+    }
+    std::vector<double> emission;                // --emit: one (r, g, b) per sphere of the list
+    if (!emits.empty()) {
+        emission.assign(flat.size() * 3, 0.0);
+        for (const Emit &e : emits) {
+            if (e.index < 0 || (size_t)e.index >= flat.size()) {
+                std::fprintf(stderr, "--emit %ld: the scene has %zu spheres\n", e.index, flat.size());
+                return 2;
+            }
+            for (int c = 0; c < 3; ++c) emission[(size_t)e.index * 3 + c] = e.rgb[c];
+        }
+        light.emission = emission.data(); light.n_emission = (int32_t)flat.size();
+    }
     if (!devices.empty()) {
         // one rt_context per listed device, each driven by its own host thread; rows dealt round-robin;
         // one RCCL gather of the exact sums to the first device (main.rs:122-123 + the ordered collect() :139)
@@ -431,8 +476,13 @@ int main(int argc, char **argv)
         } else if (wavefront) {                  // the device path queue: the same sums, then the same resolve
             std::vector<uint64_t> fix(npix * 3);
             uint64_t rays = 0;
-            rc = rt_render_wavefront(ctx, &rc_cam, &p, fix.data(), &rays, &st.kernel_ms);
-            if (rc) return die("rt_render_wavefront", rc);
+            if (lit) {
+                rc = rt_render_wavefront_lit(ctx, &rc_cam, &p, &light, fix.data(), &rays, &st.kernel_ms);
+                if (rc) return die("rt_render_wavefront_lit", rc);
+            } else {
+                rc = rt_render_wavefront(ctx, &rc_cam, &p, fix.data(), &rays, &st.kernel_ms);
+                if (rc) return die("rt_render_wavefront", rc);
+            }
             st.rays_traced = rays; st.samples = (uint64_t)npix * (uint64_t)spp;
             rc = rt_resolve_rgba8(ctx, fix.data(), width, height, spp, 1, rgba.data());
             if (rc) return die("rt_resolve_rgba8", rc);

@@ -764,6 +764,45 @@ int rt_paths_step_device(rt_context *ctx, uint64_t seed, uint32_t flags, double 
 int rt_render_wavefront_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, void *d_fix, void *d_rays, void *stream);
 int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *fix, uint64_t *rays_traced, float *kernel_ms);
 
+/* ---- lighting: a settable sky and emissive spheres for the path queue ---------------------------------- */
+
+/* What lights a frame of the path queue.  rt_render* and the unlit forms above know nothing of it: their sky is
+ * the reference's gradient and no sphere emits.  The struct is a HOST pointer read during the call.  `emission` is a DEVICE pointer in
+ * the two _device forms and a HOST pointer in rt_render_wavefront_lit, which stages it like every host-buffer form. */
+typedef struct {
+    double sky_bottom[3];    /* sky colour where unit_vector(dir).y = -1;  the reference: (1, 1, 1)        */
+    double sky_top[3];       /* ... where it is +1;                        the reference: (0.5, 0.7, 1.0)  */
+    const double *emission;  /* [n_emission][3] radiance per uploaded sphere, list order; NULL: no lights  */
+    int32_t n_emission;      /* the uploaded sphere count when emission != NULL, else 0                    */
+    uint32_t flags;          /* 0                                                                          */
+} rt_lighting;               /* 64 bytes */
+
+/* One lit bounce.  Everything rt_paths_step_device promises holds (stable order, *out->count, d_rays, the count clamp, what `in` holds
+ * afterwards, no launch slot, the NaN rule).  Two things differ:
+ *  - a MISS adds quantize(throughput * sky) with ud = unit_vector(dir), t = 0.5 * (ud.y + 1.0), sky = sky_bottom * (1.0 - t) + sky_top * t:
+ *    the operations and their order are those of the unlit step with the two constants replaced, so with the reference's two colours
+ *    the result is that step's bit for bit;
+ *  - a HIT on sphere s (its list index) reads e = emission[s] when emission is given.  s is a light iff e.x > 0 || e.y > 0 || e.z > 0 (a
+ *    NaN or a non-positive channel compares false: every bit pattern has a meaning, the device forms validate no table).  On a light the
+ *    path adds quantize(throughput * e) per channel to d_fix[pixel] (nothing when pixel >= npix; a negative or NaN channel of the product
+ *    adds 0, one above RT_SAMPLE_CLAMP adds the clamp) and ENDS: it draws nothing from its stream, its material is not read, both faces
+ *    emit.  A sphere that is not a light scatters exactly as in the unlit step.  Tie rule, t_min and NaN roots are the closest-hit
+ *    scan's: a light is an ordinary sphere until the hit is known.
+ * The frame forms are rt_render_wavefront*'s loop with the lit step: the same batches, the same context-owned queues, the same
+ * RTIOW_WAVEFRONT_BATCH, no host wait; a path alive after max_depth steps adds nothing, one that reaches a light at step max_depth or
+ * earlier adds.  With the reference's sky and no light the frame is rt_render_device's sums and ray count bit for bit.
+ *
+ * RT_ERR_INVALID_ARGUMENT, found before anything is touched: first every context-free check of the unlit form, in its order; then a NULL
+ * light; light->flags != 0; a sky component that is not finite or is negative; emission == NULL with n_emission != 0; n_emission < 0;
+ * in rt_render_wavefront_lit, which can see them, an emission entry that is NaN, infinite or negative; then the context checks of the
+ * unlit form (NULL, scan mode, RT_ERR_NO_SCENE); then emission != NULL with n_emission different from the uploaded sphere count. */
+int rt_paths_step_lit_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                             void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, void *stream);
+int rt_render_wavefront_lit_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, void *d_fix, void *d_rays,
+                                   void *stream);
+int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix,
+                            uint64_t *rays_traced, float *kernel_ms);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

@@ -79,6 +79,11 @@ class rt_path_queue(C.Structure):
                 ("origin", C.c_void_p), ("dir", C.c_void_p), ("throughput", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class rt_lighting(C.Structure):
+    _fields_ = [("sky_bottom", C.c_double * 3), ("sky_top", C.c_double * 3), ("emission", C.c_void_p), ("n_emission", C.c_int32),
+                ("flags", C.c_uint32)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -150,6 +155,11 @@ SYMBOLS = [
                                        _VP, _VP]),
     ("rt_render_wavefront_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, _VP, _VP]),
     ("rt_render_wavefront", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), _VP, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("rt_paths_step_lit_device", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(rt_path_queue), C.POINTER(rt_path_queue), _VP,
+                                           C.c_int64, _VP, C.POINTER(rt_lighting), _VP]),
+    ("rt_render_wavefront_lit_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), _VP, _VP, _VP]),
+    ("rt_render_wavefront_lit", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), _VP, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -1,16 +1,19 @@
 // rt_paths.hip -- the device path queue: a fused bounce step on device-resident paths and the frame rendered from it (rtiow_hip.h, "path
 // queue").
 //
-// The eleventh translation unit of librtiow_hip.so.  Four kernels of its own:
+// The eleventh translation unit of librtiow_hip.so.  Five kernels of its own:
 //   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
 //   bounce_kernel         one wave per 64 consecutive slots, grid-stride over the live slots: closest hit (first_hit_wave<false> whole, the
 //                         record in registers), then the sky add of a miss or Scatter::scatter -- both from rt_shade_core.hpp --; the new
 //                         state is written IN PLACE, and per wave the number of survivors and their ballot go to the queue's scratch.
+//   bounce_lit_kernel     the same trip (bounce_trip<LIT>, stated once) with the sky's two colours from its argument and emissive spheres: a hit
+//                         on a sphere whose entry of the emission table has a channel > 0 adds throughput * e and ends the path (rtiow_hip.h,
+//                         "lighting").
 //   queue_scan_kernel     ONE workgroup: the exclusive scan of the waves' counts, in place; *out->count; d_rays.
 //   queue_compact_kernel  one wave per 64 slots: the survivors move to `out` at offset + rank, so their order is kept.
 // The live count is a word of device memory every kernel reads for itself; the host sizes the grids from the capacity and never waits.
 // NO kernel waits for another workgroup (no look-back chain, no flag, no grid-wide barrier): a wave that waits for a workgroup that has not
-// been scheduled would hang, so the scan is a launch of its own, ordered by the stream.  No atomics except the three 64-bit adds of a miss.
+// been scheduled would hang, so the scan is a launch of its own, ordered by the stream.  No atomics except the three 64-bit adds of a miss or of a light hit.
 // It composes rt_first_hit.hpp and rt_shade_core.hpp and restates none of their arithmetic; rt_kernels.hpp and rt_launch.hpp are not read.
 #include <hip/hip_runtime.h>
 
@@ -70,42 +73,61 @@ __global__ __launch_bounds__(kPathBlock) void path_begin_kernel(const KCamera ca
     }
 }
 
-// One bounce of the live paths.  P: the scene's tables, t_min, the key (k0, k1) and the sums (fix); npix: entries of P.fix.
-__global__ __launch_bounds__(kPathBlock) void bounce_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix)
+// What a lit step knows beyond P (rtiow_hip.h, "lighting"): the two ends of the sky gradient and the per-sphere radiance
+// table.  By value: the colours are wave-uniform and stay in scalar registers.  emission: [n_emission][3] device doubles or NULL.
+struct LitArgs {
+    double sky_bottom[3], sky_top[3];
+    const double *emission;
+    int32_t n_emission;
+};
+
+// the three 64-bit adds of a path that ends with radiance v (contract C5); g_pix: inside the frame
+__device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, const D3 &v)
 {
-    __shared__ uint4 s_stage[kPathWaves][64 * 4];
-    const int lane = (int)threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    uint4 *stage = s_stage[wave];
-    const long long n = (long long)live_count(Q);
-    const long long n_trips = (n + 63) >> 6;
-    const long long n_waves = (long long)gridDim.x * kPathWaves;
+    unsigned long long *px = P.fix + (size_t)g_pix * 3u;
+    atomicAdd(px + 0, quantize(v.x)); atomicAdd(px + 1, quantize(v.y)); atomicAdd(px + 2, quantize(v.z));
+}
 
-    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) {
-        const long long k = wv * 64 + lane;
-        // lanes past the live count stay in the wave: rows that keep nothing, nothing written
-        const bool valid = k < n;
-        D3 o = mk(0.0, 0.0, 0.0), d = mk(0.0, 0.0, 0.0), thr = mk(0.0, 0.0, 0.0);
-        uint32_t g_pix = 0u, g_s = 0u, ev = 0u;
-        if (valid) {
-            o = ld3(Q.origin + 3 * k); d = ld3(Q.dir + 3 * k); thr = ld3(Q.thr + 3 * k);
-            g_pix = Q.pixel[k]; g_s = Q.sample[k]; ev = Q.event[k];
-        }
-        FirstHit fh = {__builtin_inf(), -1};            // mod.rs:56: closest_so_far = t_max = +inf
-        ScanCounts cnt = {true};
-        first_hit_wave<false>(P, stage, lane, o, d, valid, fh, cnt);
+// One trip of a wave over the 64 slots from 64 wv on: the body of both bounce kernels.  LIT: the sky's two colours come from L, and a hit
+// on a sphere whose entry of L.emission has a channel > 0 adds throughput * e and ends the path before its material is read.
+template <bool LIT>
+__device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays &Q, const unsigned long long npix, const LitArgs &L, uint4 *stage,
+                                            const int lane, const long long wv, const long long n)
+{
+    const long long k = wv * 64 + lane;
+    // lanes past the live count stay in the wave: rows that keep nothing, nothing written
+    const bool valid = k < n;
+    D3 o = mk(0.0, 0.0, 0.0), d = mk(0.0, 0.0, 0.0), thr = mk(0.0, 0.0, 0.0);
+    uint32_t g_pix = 0u, g_s = 0u, ev = 0u;
+    if (valid) {
+        o = ld3(Q.origin + 3 * k); d = ld3(Q.dir + 3 * k); thr = ld3(Q.thr + 3 * k);
+        g_pix = Q.pixel[k]; g_s = Q.sample[k]; ev = Q.event[k];
+    }
+    FirstHit fh = {__builtin_inf(), -1};                // mod.rs:56: closest_so_far = t_max = +inf
+    ScanCounts cnt = {true};
+    first_hit_wave<false>(P, stage, lane, o, d, valid, fh, cnt);
 
-        bool alive = false;
-        if (valid) {
-            if (fh.hit < 0) {
-                // contract C5, as rt_accumulate with sky_dir: the path ends in the sky
-                if ((unsigned long long)g_pix < npix) {
-                    const D3 v = sky_sample(thr, d);
-                    unsigned long long *px = P.fix + (size_t)g_pix * 3u;
-                    atomicAdd(px + 0, quantize(v.x)); atomicAdd(px + 1, quantize(v.y)); atomicAdd(px + 2, quantize(v.z));
+    bool alive = false;
+    if (valid) {
+        if (fh.hit < 0) {
+            // contract C5, as rt_accumulate with sky_dir: the path ends in the sky
+            if ((unsigned long long)g_pix < npix) {
+                if constexpr (LIT) add_sample(P, g_pix, sky_blend(thr, d, ld3(L.sky_bottom), ld3(L.sky_top)));
+                else add_sample(P, g_pix, sky_sample(thr, d));
+            }
+        } else {
+            bool light = false;
+            if constexpr (LIT) {
+                // (fh.hit < n_emission: no table content or count makes this read leave the table)
+                if (L.emission && fh.hit < L.n_emission) {
+                    const D3 e = ld3(L.emission + 3 * (size_t)fh.hit);
+                    light = e.x > 0.0 || e.y > 0.0 || e.z > 0.0;    // a NaN or a non-positive channel compares false
+                    // both faces emit; no draw; the path ends; a pixel outside the frame adds nothing
+                    if (light && (unsigned long long)g_pix < npix) add_sample(P, g_pix, thr * e);
                 }
-            } else {
-                const HitRecord rec = hit_record(P, o, d, fh);          // (in registers: never written to memory)
+            }
+            if (!light) {
+                const HitRecord rec = hit_record(P, o, d, fh);      // (in registers: never written to memory)
                 D3 ndir, albedo;
                 alive = !scatter_path(rec.mrec, d, rec.normal, rec.front, g_pix, g_s, ev, P.k0, P.k1, ndir, albedo);
                 if (alive) {
@@ -116,13 +138,38 @@ __global__ __launch_bounds__(kPathBlock) void bounce_kernel(const KParams P, con
                 }
             }
         }
-        const unsigned long long live = __ballot(alive);
-        if (lane == 0) {
-            uint32_t *s = Q.scratch + kScratchPerWave * wv;
-            s[0] = (uint32_t)__popcll(live); s[1] = (uint32_t)live; s[2] = (uint32_t)(live >> 32);
-        }
+    }
+    const unsigned long long live = __ballot(alive);
+    if (lane == 0) {
+        uint32_t *s = Q.scratch + kScratchPerWave * wv;
+        s[0] = (uint32_t)__popcll(live); s[1] = (uint32_t)live; s[2] = (uint32_t)(live >> 32);
     }
 }
+
+// the waves' grid-stride loop over the live slots, one trip per 64 of them: the same text in both kernels, with the LDS stage a kernel's own
+#define RT_BOUNCE_LOOP(LIT, L) \
+    __shared__ uint4 s_stage[kPathWaves][64 * 4]; \
+    const int lane = (int)threadIdx.x & 63; \
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); \
+    uint4 *stage = s_stage[wave]; \
+    const long long n = (long long)live_count(Q); \
+    const long long n_trips = (n + 63) >> 6; \
+    const long long n_waves = (long long)gridDim.x * kPathWaves; \
+    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) bounce_trip<LIT>(P, Q, npix, L, stage, lane, wv, n)
+
+// One bounce of the live paths.  P: the scene's tables, t_min, the key (k0, k1) and the sums (fix); npix: entries of P.fix.
+__global__ __launch_bounds__(kPathBlock) void bounce_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix)
+{
+    const LitArgs none = {};
+    RT_BOUNCE_LOOP(false, none);
+}
+
+// ... with a settable sky and emissive spheres (rt_paths_step_lit_device)
+__global__ __launch_bounds__(kPathBlock) void bounce_lit_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L)
+{
+    RT_BOUNCE_LOOP(true, L);
+}
+#undef RT_BOUNCE_LOOP
 
 // ONE workgroup: thread t owns a run of consecutive waves' counts; the threads' sums are scanned in LDS; the run is rewritten as offsets.
 __global__ __launch_bounds__(kScanBlock) void queue_scan_kernel(const QueueArrays Q, uint32_t *out_count, unsigned long long *rays)
@@ -235,6 +282,36 @@ int check_context(const rt_context *ctx, const char *what, bool needs_scene)
     return RT_OK;
 }
 
+// the context-free part of the lighting checks, after the entry point's own; host_table: the emission is a host pointer the call may read
+int check_light(const char *what, const rt_lighting *light, bool host_table)
+{
+    RT_NEED(light, what, "light");
+    if (light->flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown light->flags 0x%x (only 0 is legal)", what, light->flags);
+    for (int c = 0; c < 3; ++c) {
+        if (!(light->sky_bottom[c] >= 0.0) || !std::isfinite(light->sky_bottom[c]))
+            return fail(RT_ERR_INVALID_ARGUMENT, "%s: light->sky_bottom[%d] must be finite and >= 0 (is %g)", what, c, light->sky_bottom[c]);
+        if (!(light->sky_top[c] >= 0.0) || !std::isfinite(light->sky_top[c]))
+            return fail(RT_ERR_INVALID_ARGUMENT, "%s: light->sky_top[%d] must be finite and >= 0 (is %g)", what, c, light->sky_top[c]);
+    }
+    if (!light->emission && light->n_emission != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: light->n_emission must be 0 when light->emission is NULL (is %d)", what, light->n_emission);
+    if (light->n_emission < 0) return fail(RT_ERR_INVALID_ARGUMENT, "%s: light->n_emission must be >= 0 (is %d)", what, light->n_emission);
+    if (host_table && light->emission)
+        for (long long k = 0; k < 3ll * light->n_emission; ++k)
+            if (!(light->emission[k] >= 0.0) || !std::isfinite(light->emission[k]))
+                return fail(RT_ERR_INVALID_ARGUMENT, "%s: light->emission[%lld][%d] must be finite and >= 0 (is %g)", what, k / 3, (int)(k % 3),
+                            light->emission[k]);
+    return RT_OK;
+}
+
+// ... and the part that needs the uploaded scene: a table has one entry per sphere
+int check_light_count(const rt_context *ctx, const char *what, const rt_lighting *light)
+{
+    if (light->emission && light->n_emission != ctx->n_spheres)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: light->n_emission (%d) must be the uploaded sphere count (%d)", what, light->n_emission, ctx->n_spheres);
+    return RT_OK;
+}
+
 int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint32_t flags, int32_t spp, int32_t sample_begin,
                 int64_t first_item, int64_t n, const rt_path_queue *q)
 {
@@ -255,9 +332,10 @@ int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int3
     return check_context(ctx, what, false);
 }
 
-int check_step(const rt_context *ctx, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out, const void *d_fix, int64_t npix)
+// light: NULL for the unlit step (lit: whether the call is a lit one)
+int check_step(const rt_context *ctx, const char *what, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out, const void *d_fix,
+               int64_t npix, bool lit, const rt_lighting *light)
 {
-    const char *what = "rt_paths_step";
     if (int rc = check_queue(what, "in", in)) return rc;
     if (int rc = check_queue(what, "out", out)) return rc;
     RT_NEED(d_fix, what, "d_fix");
@@ -272,7 +350,10 @@ int check_step(const rt_context *ctx, uint32_t flags, double t_min, const rt_pat
     if (npix <= 0 || npix > (int64_t)1 << 32) return fail(RT_ERR_INVALID_ARGUMENT, "%s: npix must be in [1, 2^32] (is %lld)", what, (long long)npix);
     if (int rc = check_flags(what, flags)) return rc;
     if (!(t_min > 0.0) || !std::isfinite(t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, t_min);
-    return check_context(ctx, what, true);
+    if (lit)
+        if (int rc = check_light(what, light, false)) return rc;
+    if (int rc = check_context(ctx, what, true)) return rc;
+    return lit ? check_light_count(ctx, what, light) : RT_OK;
 }
 
 rt::QueueArrays arrays_of(const rt_path_queue *q)
@@ -300,8 +381,9 @@ int launch_begin(const rt_camera *cam, int32_t width, int32_t height, uint64_t s
     return RT_OK;
 }
 
+// light: NULL launches bounce_kernel, else bounce_lit_kernel with the struct's values (light->emission: a device pointer)
 int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_path_queue *in, const rt_path_queue *out, void *d_fix, int64_t npix,
-                void *d_rays, hipStream_t stream)
+                void *d_rays, const rt_lighting *light, hipStream_t stream)
 {
     rt::KParams kp;
     memset(&kp, 0, sizeof(kp));
@@ -314,7 +396,15 @@ int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_pat
     // the grids come from the CAPACITY: the live count is the device's to know.  One wave per 64 slots; waves past the count leave at once.
     const dim3 grid(capped_grid(rt::wave_grid(((long long)in->capacity + 63) / 64, rt::kPathWaves))), block(rt::kPathBlock);
     const int parts = step_parts();
-    if (parts & 1) hipLaunchKernelGGL(rt::bounce_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix);
+    if ((parts & 1) && !light) hipLaunchKernelGGL(rt::bounce_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix);
+    if ((parts & 1) && light) {
+        rt::LitArgs la;
+        memset(&la, 0, sizeof(la));
+        memcpy(la.sky_bottom, light->sky_bottom, sizeof(la.sky_bottom));
+        memcpy(la.sky_top, light->sky_top, sizeof(la.sky_top));
+        la.emission = light->emission; la.n_emission = light->emission ? light->n_emission : 0;
+        hipLaunchKernelGGL(rt::bounce_lit_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la);
+    }
     if (parts & 2) hipLaunchKernelGGL(rt::queue_scan_kernel, dim3(1), dim3(rt::kScanBlock), 0, stream, qi, out->count, (unsigned long long *)d_rays);
     if (parts & 4) hipLaunchKernelGGL(rt::queue_compact_kernel, grid, block, 0, stream, qi, qo);
     RT_HIP(hipGetLastError());
@@ -356,7 +446,9 @@ long long batch_items()
     return v > kMaxCapacity ? (long long)kMaxCapacity : v;
 }
 
-int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const void *fix)
+// lit / light / host_table as in check_step and check_light
+int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const void *fix, bool lit = false,
+                 const rt_lighting *light = nullptr, bool host_table = false)
 {
     RT_NEED(cam, what, "cam");
     RT_NEED(p, what, "params");
@@ -365,7 +457,31 @@ int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, 
     if (int rc = check_flags(what, p->flags)) return rc;
     if (p->shard_count != 1) return fail(RT_ERR_INVALID_ARGUMENT, "%s: shard_count must be 1 (is %d)", what, p->shard_count);
     if (!std::isfinite(p->t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, p->t_min);
-    return check_context(ctx, what, true);
+    if (lit)
+        if (int rc = check_light(what, light, host_table)) return rc;
+    if (int rc = check_context(ctx, what, true)) return rc;
+    return lit ? check_light_count(ctx, what, light) : RT_OK;
+}
+
+// The frame of both device forms (validated arguments): per batch one begin, then max_depth steps from one queue to the other; nothing
+// here waits for the device.  (A step on an empty queue leaves at once; what the empty steps of a batch cost is in profiles/paths.txt.)
+int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, void *d_fix, void *d_rays, hipStream_t stream)
+{
+    const long long npix = (long long)p->width * p->height, total = npix * p->spp;
+    RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(uint64_t), stream));
+    if (d_rays) RT_HIP(hipMemsetAsync(d_rays, 0, sizeof(uint64_t), stream));
+    if (total == 0) return RT_OK;
+    const long long batch = batch_items() < total ? batch_items() : total;
+    const OwnedQueues own(batch);
+    if (int rc = ensure(&ctx->paths.ptr, &ctx->paths.bytes, own.layout.total)) return rc;
+    const rt_path_queue q[2] = {own.queue(ctx->paths.ptr, 0, batch), own.queue(ctx->paths.ptr, 1, batch)};
+    for (long long first = 0; first < total; first += batch) {
+        const long long n = total - first < batch ? total - first : batch;
+        if (int rc = launch_begin(cam, p->width, p->height, p->seed, p->spp, p->sample_begin, first, n, &q[0], stream)) return rc;
+        for (int depth = 0; depth < p->max_depth; ++depth)
+            if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, light, stream)) return rc;
+    }
+    return RT_OK;
 }
 
 } // namespace
@@ -389,33 +505,32 @@ int rt_paths_begin_device(rt_context *ctx, const rt_camera *cam, int32_t width, 
 int rt_paths_step_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
                          void *d_fix, int64_t npix, void *d_rays, void *stream_v)
 {
-    if (int rc = check_step(ctx, flags, t_min, in, out, d_fix, npix)) return rc;
+    if (int rc = check_step(ctx, "rt_paths_step", flags, t_min, in, out, d_fix, npix, false, nullptr)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, (hipStream_t)stream_v);
+    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, nullptr, (hipStream_t)stream_v);
+}
+
+int rt_paths_step_lit_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                             void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, void *stream_v)
+{
+    if (int rc = check_step(ctx, "rt_paths_step_lit", flags, t_min, in, out, d_fix, npix, true, light)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, light, (hipStream_t)stream_v);
 }
 
 int rt_render_wavefront_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, void *d_fix, void *d_rays, void *stream_v)
 {
     if (int rc = check_render(ctx, "rt_render_wavefront", cam, p, d_fix)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    hipStream_t stream = (hipStream_t)stream_v;
-    const long long npix = (long long)p->width * p->height, total = npix * p->spp;
-    RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(uint64_t), stream));
-    if (d_rays) RT_HIP(hipMemsetAsync(d_rays, 0, sizeof(uint64_t), stream));
-    if (total == 0) return RT_OK;
-    const long long batch = batch_items() < total ? batch_items() : total;
-    const OwnedQueues own(batch);
-    if (int rc = ensure(&ctx->paths.ptr, &ctx->paths.bytes, own.layout.total)) return rc;
-    const rt_path_queue q[2] = {own.queue(ctx->paths.ptr, 0, batch), own.queue(ctx->paths.ptr, 1, batch)};
-    // per batch: begin, then max_depth steps from one queue to the other; nothing here waits for the device.  (A step on an empty queue
-    // leaves at once; what the empty steps of a batch cost is in profiles/paths.txt.)
-    for (long long first = 0; first < total; first += batch) {
-        const long long n = total - first < batch ? total - first : batch;
-        if (int rc = launch_begin(cam, p->width, p->height, p->seed, p->spp, p->sample_begin, first, n, &q[0], stream)) return rc;
-        for (int depth = 0; depth < p->max_depth; ++depth)
-            if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, stream)) return rc;
-    }
-    return RT_OK;
+    return render_frame(ctx, cam, p, nullptr, d_fix, d_rays, (hipStream_t)stream_v);
+}
+
+int rt_render_wavefront_lit_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, void *d_fix, void *d_rays,
+                                   void *stream_v)
+{
+    if (int rc = check_render(ctx, "rt_render_wavefront_lit", cam, p, d_fix, true, light, false)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return render_frame(ctx, cam, p, light, d_fix, d_rays, (hipStream_t)stream_v);
 }
 
 int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *fix, uint64_t *rays_traced, float *kernel_ms)
@@ -428,6 +543,32 @@ int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *
     if (int rc = st.commit()) return rc;
     return timed_section(ctx, "rt_render_wavefront", kernel_ms,
         [&] { return rt_render_wavefront_device(ctx, cam, p, st.at(b_fix), st.at(b_rays), ctx->own_stream); },
+        [&] {
+            hipError_t he = st.down(fix, b_fix, fb);
+            if (he == hipSuccess && rays_traced) he = st.down(rays_traced, b_rays, sizeof(uint64_t));
+            return he;
+        });
+}
+
+int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix, uint64_t *rays_traced,
+                            float *kernel_ms)
+{
+    if (int rc = check_render(ctx, "rt_render_wavefront_lit", cam, p, fix, true, light, true)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t fb = (size_t)p->width * p->height * 3 * sizeof(uint64_t);
+    const size_t eb = light->emission ? (size_t)light->n_emission * 3 * sizeof(double) : 0;
+    Stage st(ctx);
+    const size_t b_fix = st.add(fb), b_rays = st.add(sizeof(uint64_t)), b_em = st.add(eb);
+    if (int rc = st.commit()) return rc;
+    rt_lighting dev = *light;                           // the same lighting with the table on the device
+    if (eb) {
+        RT_HIP(st.up(b_em, light->emission, eb));
+        dev.emission = st.at<double>(b_em);
+    } else {
+        dev.emission = nullptr; dev.n_emission = 0;     // (a table of no entries lights nothing)
+    }
+    return timed_section(ctx, "rt_render_wavefront_lit", kernel_ms,
+        [&] { return render_frame(ctx, cam, p, &dev, st.at(b_fix), st.at(b_rays), ctx->own_stream); },
         [&] {
             hipError_t he = st.down(fix, b_fix, fb);
             if (he == hipSuccess && rays_traced) he = st.down(rays_traced, b_rays, sizeof(uint64_t));

@@ -116,12 +116,17 @@ __device__ __forceinline__ bool scatter_path(const double *mrec, const D3 &d, co
 }
 
 // ---- contract C3: mulv(throughput, sky(dir)), main.rs:54-56 ---------------------------------------------------------------------------
-__device__ __forceinline__ D3 sky_sample(const D3 &weight, const D3 &dir)
+// ... for a sky whose colour is `bottom` where unit_vector(dir).y = -1 and `top` where it is +1
+__device__ __forceinline__ D3 sky_blend(const D3 &weight, const D3 &dir, const D3 &bottom, const D3 &top)
 {
     const D3 ud = unit_vector(dir);                                                      // main.rs:54-56
     const double t = 0.5 * (ud.y + 1.0);
-    const D3 sky = mk(1.0, 1.0, 1.0) * (1.0 - t) + mk(0.5, 0.7, 1.0) * t;
+    const D3 sky = bottom * (1.0 - t) + top * t;
     return weight * sky;                                                                 // contract C3: mulv(throughput, sky)
+}
+__device__ __forceinline__ D3 sky_sample(const D3 &weight, const D3 &dir)
+{
+    return sky_blend(weight, dir, mk(1.0, 1.0, 1.0), mk(0.5, 0.7, 1.0));
 }
 
 } // namespace rt

@@ -377,10 +377,66 @@ def paths_begin_torch(renderer, cam, width, height, seed, spp, sample_begin, fir
         renderer.paths_begin_device(cam, width, height, seed, spp, sample_begin, first_item, n, queue.struct(), torch.cuda.current_stream().cuda_stream)
 
 
-def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4):
+class Lighting:
+    """What lights a frame of the path queue (rt_lighting): the sky's colour where the unit direction's y is -1
+    (sky_bottom) and +1 (sky_top), and the radiance of emissive spheres.  emission: None (no lights), an [n, 3] array with one row per
+    sphere of the scene in list order, a {sphere index: (r, g, b)} dict (every other sphere emits nothing), or -- for the device forms --
+    a float64 torch tensor [n, 3] on the renderer's device.  A sphere is a light iff a channel of its row is > 0; a path that hits a
+    light adds throughput * e and ends.  The defaults are the reference's sky and no light: the unlit frame bit for bit."""
+
+    def __init__(self, sky_bottom=(1.0, 1.0, 1.0), sky_top=(0.5, 0.7, 1.0), emission=None):
+        self.sky_bottom, self.sky_top = tuple(float(x) for x in sky_bottom), tuple(float(x) for x in sky_top)
+        if len(self.sky_bottom) != 3 or len(self.sky_top) != 3:
+            raise ValueError("sky_bottom and sky_top are (r, g, b)")
+        self.emission = emission
+        self._device_table = None
+
+    def _is_tensor(self):
+        return hasattr(self.emission, "data_ptr")
+
+    def table(self, n_spheres):
+        """The emission as a contiguous float64 array [n_spheres, 3] on the host, or None."""
+        e = self.emission
+        if e is None:
+            return None
+        if self._is_tensor():
+            e = e.detach().cpu().numpy()
+        if isinstance(e, dict):
+            out = np.zeros((int(n_spheres), 3), dtype=np.float64)
+            for index, rgb in e.items():
+                if not 0 <= int(index) < int(n_spheres):
+                    raise ValueError(f"emission names sphere {index}; the scene has {n_spheres}")
+                out[int(index)] = rgb
+            return out
+        out = np.ascontiguousarray(e, dtype=np.float64)
+        if out.ndim != 2 or out.shape[1] != 3:
+            raise ValueError(f"emission must be [n, 3] (is {out.shape})")
+        return out
+
+    def device_table(self, renderer):
+        """The emission as a float64 tensor [n, 3] on the renderer's device (kept alive by this object), or None."""
+        if self.emission is None:
+            return None
+        import torch
+        t = self.emission
+        if not self._is_tensor():
+            key = (renderer.n_spheres or 0, renderer.device_id)
+            if self._device_table is None or self._device_table[0] != key:          # (built once per scene length: the object is a value)
+                self._device_table = (key, torch.from_numpy(np.array(self.table(key[0]))).to(torch.device("cuda", renderer.device_id)))
+            t = self._device_table[1]
+        _torch_check(torch, renderer, [("emission", t, torch.float64, (t.shape[0] if t.dim() else 0, 3))])
+        return t
+
+    def struct(self, emission_ptr=None, n_emission=0):
+        """The rt_lighting naming `emission_ptr` (host or device, as the entry point wants it)."""
+        return _ffi.rt_lighting((C.c_double * 3)(*self.sky_bottom), (C.c_double * 3)(*self.sky_top), emission_ptr or None, int(n_emission), 0)
+
+
+def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, lighting=None):
     """rt_paths_step_device on two PathQueues, on torch.cuda.current_stream(): one bounce of the live paths of `qin`; the survivors go to
     `qout` in order.  fix: an int64 tensor [..., 3] holding the u64 sums' bits, added to; rays: an int64 tensor [1] that gains the live
-    count, or None.  No host wait."""
+    count, or None.  lighting: a Lighting (rt_paths_step_lit_device; its emission a float64 tensor [n, 3] on the device, or what
+    Lighting.device_table makes of it), None: the unlit step.  No host wait."""
     import torch
     _check_queue(renderer, qin, "qin")
     _check_queue(renderer, qout, "qout")
@@ -390,7 +446,7 @@ def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4):
         raise ValueError(f"fix must be [..., 3] (is {tuple(fix.shape)})")
     with torch.cuda.device(qin.device):
         renderer.paths_step_device(seed, qin.struct(), qout.struct(), fix.data_ptr(), fix.numel() // 3, rays.data_ptr() if rays is not None else 0,
-                                   t_min, torch.cuda.current_stream().cuda_stream)
+                                   t_min, torch.cuda.current_stream().cuda_stream, lighting=lighting)
 
 
 class Renderer:
@@ -769,28 +825,50 @@ class Renderer:
         _ffi.check(self._lib.rt_paths_begin_device(self._h, C.byref(rc), int(width), int(height), int(seed), int(flags), int(spp), int(sample_begin),
                                                    int(first_item), int(n), C.byref(queue), C.c_void_p(stream)), "rt_paths_begin_device")
 
-    def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0):
-        """rt_paths_step_device; qin, qout: _ffi.rt_path_queue structs of device pointers; asynchronous on `stream`."""
-        _ffi.check(self._lib.rt_paths_step_device(self._h, int(seed), int(flags), float(t_min), C.byref(qin), C.byref(qout),
-                                                  C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
-                                                  C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)), "rt_paths_step_device")
+    def _device_lighting(self, lighting):
+        """(the rt_lighting of a device form, the tensor it names -- to be kept until the call has been made)."""
+        table = lighting.device_table(self)
+        return lighting.struct(table.data_ptr() if table is not None else None, table.shape[0] if table is not None else 0), table
 
-    def render_wavefront(self, cam, params):
+    def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0, lighting=None):
+        """rt_paths_step_device, or with a Lighting rt_paths_step_lit_device; qin, qout: _ffi.rt_path_queue structs of device pointers;
+        asynchronous on `stream`."""
+        head = (self._h, int(seed), int(flags), float(t_min), C.byref(qin), C.byref(qout), C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
+                C.c_void_p(d_rays_ptr) if d_rays_ptr else None)
+        if lighting is None:
+            _ffi.check(self._lib.rt_paths_step_device(*head, C.c_void_p(stream)), "rt_paths_step_device")
+            return
+        light, _keep = self._device_lighting(lighting)
+        _ffi.check(self._lib.rt_paths_step_lit_device(*head, C.byref(light), C.c_void_p(stream)), "rt_paths_step_lit_device")
+
+    def render_wavefront(self, cam, params, lighting=None):
         """rt_render_wavefront: the frame through the device path queue -> (the exact sums u64 [H, W, 3], the rays traced): what
-        Renderer.render returns as `fix` and as stats["rays_traced"]."""
+        Renderer.render returns as `fix` and as stats["rays_traced"].  lighting: a Lighting (rt_render_wavefront_lit: a settable sky and
+        emissive spheres), None: the unlit frame."""
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         fix = np.zeros((params.height, params.width, 3), dtype=np.uint64)
         rays = C.c_uint64(0)
-        _ffi.check(self._lib.rt_render_wavefront(self._h, C.byref(rc), C.byref(params), fix.ctypes.data_as(C.c_void_p), C.byref(rays), None),
-                   "rt_render_wavefront")
+        if lighting is None:
+            _ffi.check(self._lib.rt_render_wavefront(self._h, C.byref(rc), C.byref(params), fix.ctypes.data_as(C.c_void_p), C.byref(rays), None),
+                       "rt_render_wavefront")
+            return fix, int(rays.value)
+        table = lighting.table(self.n_spheres or 0)
+        light = lighting.struct(table.ctypes.data if table is not None else None, table.shape[0] if table is not None else 0)
+        _ffi.check(self._lib.rt_render_wavefront_lit(self._h, C.byref(rc), C.byref(params), C.byref(light), fix.ctypes.data_as(C.c_void_p),
+                                                     C.byref(rays), None), "rt_render_wavefront_lit")
         return fix, int(rays.value)
 
-    def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0):
-        """rt_render_wavefront_device on raw device pointers (d_fix [H][W][3] u64, d_rays one u64 or 0); asynchronous on `stream`."""
+    def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0, lighting=None):
+        """rt_render_wavefront_device on raw device pointers (d_fix [H][W][3] u64, d_rays one u64 or 0); asynchronous on `stream`.
+        lighting: a Lighting (rt_render_wavefront_lit_device; its emission as in paths_step_torch), None: the unlit frame."""
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
-        _ffi.check(self._lib.rt_render_wavefront_device(self._h, C.byref(rc), C.byref(params), C.c_void_p(d_fix_ptr) if d_fix_ptr else None,
-                                                        C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)),
-                   "rt_render_wavefront_device")
+        tail = (C.c_void_p(d_fix_ptr) if d_fix_ptr else None, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream))
+        if lighting is None:
+            _ffi.check(self._lib.rt_render_wavefront_device(self._h, C.byref(rc), C.byref(params), *tail), "rt_render_wavefront_device")
+            return
+        light, _keep = self._device_lighting(lighting)
+        _ffi.check(self._lib.rt_render_wavefront_lit_device(self._h, C.byref(rc), C.byref(params), C.byref(light), *tail),
+                   "rt_render_wavefront_lit_device")
 
     # -- denoiser: an edge-avoiding a-trous filter driven by the feature buffers -------
     def denoise(self, fix, spp, feat, feat_spp, denoise=None, count=None):
