@@ -22,6 +22,11 @@ struct D3 { double x, y, z; };
 
 __device__ __forceinline__ D3 mk(double x, double y, double z) { D3 r; r.x = x; r.y = y; r.z = z; return r; }
 __device__ __forceinline__ D3 ld3(const double *p) { return mk(p[0], p[1], p[2]); }
+// A value nobody reads on the path that takes it (the capped dense kernels' shading, rt_kernels.hpp): some vector register, no instruction.  Where
+// a variable has a real definition on one side of a join and this on the other, the join costs no copy; a constant there costs a v_mov for every lane.
+__device__ __forceinline__ double unread_f64() { double x; asm volatile("" : "=v"(x)); return x; }
+__device__ __forceinline__ uint32_t unread_u32() { uint32_t x; asm volatile("" : "=v"(x)); return x; }
+__device__ __forceinline__ D3 unread_d3() { return mk(unread_f64(), unread_f64(), unread_f64()); }
 // vec3.rs:137-147, :243-253, :330-356, :358-367
 __device__ __forceinline__ D3 operator+(D3 a, D3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ D3 operator-(D3 a, D3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }

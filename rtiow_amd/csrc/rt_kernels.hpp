@@ -616,6 +616,9 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 const D3 rd = mk(from_lane_f64(src, d.x), from_lane_f64(src, d.y), from_lane_f64(src, d.z));
                 bool has_root = false;
                 unsigned long long key = 0ull;
+                // (the capped dense kernels: key and, below, old are read only where has_root holds, and there both are defined -- `has_root && old > key`
+                //  may be evaluated for every lane, and its value is used under has_root alone: no constant for the lanes without a root)
+                if constexpr (CAPPED) key = (unsigned long long)__double_as_longlong(unread_f64());
                 if (act) {
                     if (DIAG) n_cand++;
                     // sphere.rs:16-34, exactly as exact_test() computes it
@@ -643,6 +646,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 // old minimum; (3) the roots EQUAL to the final minimum record the largest sphere index among them --
                 // the order-independent form of mod.rs:61-67 (smallest root, ties -> the later sphere of the list).
                 unsigned long long old = 0ull;
+                if constexpr (CAPPED) old = (unsigned long long)__double_as_longlong(unread_f64());
                 RT_LDS_N(4, 12, 4, false, false, src, true);                            // the twelve ds_bpermute of (o, d)
                 RT_LDS(2, 8, true, false, &best_w[r], has_root);
                 if (has_root) old = atomicMin(&best_w[r], key);
@@ -895,9 +899,17 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     const unsigned long long kh[2] = {__ballot(keeps(X[0])), __ballot(keeps(X[1]))};
                     if (__builtin_expect((kh[0] | kh[1]) != 0ull, 0)) {
                         RT_COUNT(3);
+                        unsigned bit;
+                        if constexpr (CAPPED) {
+                            // (the capped dense kernels: 1 << (lane & 31) as ONE instruction on the register that holds the lane id -- the shift reads
+                            //  the low five bits of its count -- where the pinned copy of col32 cost a v_mov beside the shift per look with a candidate;
+                            //  the asm is what keeps the address arithmetic on this side of the branch, as the pin did)
+                            asm volatile("v_lshlrev_b32_e64 %0, %1, 1" : "=v"(bit) : "v"(lane));
+                        } else {
                         int colv = col32;
                         asm volatile("" : "+v"(colv));              // keep the address arithmetic on this side of the branch
-                        const unsigned bit = 1u << colv;
+                        bit = 1u << colv;
+                        }
                         int rbase = wrel * 64 + 4 * hh;             // (4 hh folded into the row's base, not into each word's index: -0.3 %)
                         unsigned int *row = bits_w + rbase;
 #pragma unroll
@@ -1241,13 +1253,30 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
         D3 radiance = mk(0.0, 0.0, 0.0);
         if (alive) {
             bool done = false;
-            D3 L = mk(0.0, 0.0, 0.0);
+            // (the capped dense kernels: L IS radiance -- zero from the top of the pass, the sky's colour written in place -- where a second triple
+            //  cost three v_mov for its zeros and three for `radiance = L`; a lane that does not finish leaves with zeros nobody reads)
+            D3 L_ = mk(0.0, 0.0, 0.0);
+            D3 &L = CAPPED ? radiance : L_;
             const bool is_hit = hit >= 0;
             int kind = -1;
             bool front = false;
             D3 p = o, nrm = mk(0.0, 0.0, 0.0), sp = mk(0.0, 0.0, 0.0), albedo = mk(1.0, 1.0, 1.0);
             double param = 0.0, inv_param = 0.0, r0_front = 0.0, r0_back = 0.0;
             uint32_t w_first = 0u, w_second = 0u;
+            if constexpr (CAPPED) {
+                // The capped dense kernels: a lane without a hit (sky) takes none of these from a constant -- sixteen v_mov for every alive lane of every
+                // pass.  What reads them below, and why a lane without a hit (kind == -1) never uses what it read:
+                //   p          nobody: these kernels compute the hit point in o's registers (below)
+                //   nrm        reflect(d, nrm) for V: computed, then discarded unless kind == METAL; every other read is inside `else` of `!is_hit`
+                //   sp         `V = sp`: selected only where kind == LAMBERTIAN; `uV + sp * param`: kind == METAL
+                //   albedo     the throughput's product: inside `else` of `!is_hit`, kind != DIALECTRIC and not parked (a hit lane has the record's)
+                //   param, inv_param, r0_front, r0_back, w_first (w_second: the 53-bit stream only)   the Dialectric branch, the Metal branch: kind >= 0
+                // kind (-1) and front keep their definitions: they decide the paths.  A hit lane defines every one of them from the sphere's records,
+                // but for sp (Lambertian, Metal: the draw) which a Dialectric lane never reads.
+                p = unread_d3(); nrm = unread_d3(); sp = unread_d3(); albedo = unread_d3();
+                param = unread_f64(); inv_param = unread_f64(); r0_front = unread_f64(); r0_back = unread_f64();
+                w_first = unread_u32();
+            }
             if (is_hit) {
                 const double *mrec = mat + kMatStride * (size_t)hit;
                 const double4 g = *reinterpret_cast<const double4 *>(geo + 4 * (size_t)hit);
@@ -1267,10 +1296,15 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 param = mA.y;
                 albedo = mk(mB.x, mB.y, mC.x);
                 // sphere.rs:36-37 + mod.rs:20-30
+                // (the capped dense kernels: the hit point is computed AFTER the tries, under the mask of the lanes that scatter, into o's own registers --
+                //  it is the next ray's origin, and `o = p` at the end of the pass cost three v_mov_b64.  A parked lane keeps o and computes a hit record
+                //  from it that nobody reads: it is neither shaded nor moved in this pass.)
+                if constexpr (!CAPPED) {
                 p = o + d * closest;                                             // ray.rs:15-17
                 const D3 outward = (p - mk(g.x, g.y, g.z)) * mA.x;               // / radius = * (1/radius)
                 front = dot(d, outward) < 0.0;
                 nrm = front ? outward : (mk(0.0, 0.0, 0.0) - outward);
+                }
                 w_first = w.x;
                 if constexpr (U53) w_second = w.y;
                 RT_STAMP(11);
@@ -1303,6 +1337,9 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     inv_param = mD_.x; r0_front = mD_.y; r0_back = mE_.x;
                   }
                 } else if constexpr (CAPPED) {
+                  // (the Dialectric's constants are read by Dialectric lanes only, and every hit lane has loaded them: taken as loaded, not selected by kind --
+                  //  six v_cndmask at the join below)
+                  inv_param = mD_.x; r0_front = mD_.y; r0_back = mE_.x;
                   if (kind != RT_KIND_DIALECTRIC) {
                     // vec3.rs:37-45 with a budget of one period of the stream contract per pass: tries 0-3 use every word of the blocks
                     // ev, ev + 1, ev + 2 and leave none over.  No loop, no carried word; the two wave-level branches stay (nearly always taken).
@@ -1331,9 +1368,16 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     parked = !ok;                                                // (then nblk == 3: the next pass starts at "try 0 of the next three blocks")
                     ev += nblk;
                     sp = mk(u11(tx), u11(ty), u11(tz));
-                  } else {
-                    inv_param = mD_.x; r0_front = mD_.y; r0_back = mE_.x;
                   }
+                  if (!parked) o = o + d * closest;                              // ray.rs:15-17: p, in place
+                  // (a lambda on purpose: the same three statements written in line compile to 50 spilled scalar registers on the small-grid pair, through the
+                  //  lambda to 37 -- the parent has 39; tools/kernel_resources.py is the gate for any edit here, profiles/vector_trim_ab.txt)
+                  auto hit_record = [&]() {
+                      const D3 outward = (o - mk(g.x, g.y, g.z)) * mA.x;         // / radius = * (1/radius)
+                      front = dot(d, outward) < 0.0;
+                      nrm = front ? outward : (mk(0.0, 0.0, 0.0) - outward);
+                  };
+                  hit_record();
                 } else
                 if (kind != RT_KIND_DIALECTRIC) {
                     // vec3.rs:37-45: redraw until |p|^2 < 1 -- on the integers behind the three uniforms, where the
@@ -1390,7 +1434,13 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 L = mk(s_thr[0][tid], s_thr[1][tid], s_thr[2][tid]) * sky;       // contract C3
                 done = true;
             } else {
-                D3 ndir;
+                // (the capped dense kernels: the materials run for the lanes that scatter only, and write the new direction into d's own registers --
+                //  none of them reads d, they read uV -- where `d = ndir` cost three v_mov_b64.  A parked lane keeps d.)
+                constexpr bool kDirInPlace = CAPPED;
+                D3 ndir_;
+                D3 &ndir = kDirInPlace ? d : ndir_;
+                if (kDirInPlace && parked) {
+                } else
                 if (kind == RT_KIND_LAMBERTIAN) {                                // materials.rs:21-31
                     ndir = nrm + uV;
                     const double eps = 1e-8;
@@ -1428,8 +1478,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                             s_thr[1][tid] = s_thr[1][tid] * albedo.y;
                             s_thr[2][tid] = s_thr[2][tid] * albedo.z;
                         }
-                        o = p;
-                        d = ndir;
+                        // (o and d hold the next ray already: the hit point and the materials above)
                         depth -= 1;
                         if (depth <= 0) done = true;
                     }

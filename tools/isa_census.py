@@ -13,6 +13,8 @@ usage: tools/isa_census.py [--kernel SUBSTR] [--tenk] [--frames] [--dense] [-D..
        --dense: the capped-redraw instantiation of the small-grid kernel on blocks of 1 024 (render_kernelILi5ELb0ELb1ELb0ELin1024, compiled from rt_dense.hip)
        --call-site-lines: an inlined lambda's instructions without a source line go to the line of its call (how the records up to
                           profiles/scalar_trim2_census_after.txt were taken), not to the lambda
+       --copies: after the tables, per phase and source line, the static count and the count per wave-bounce of v_mov*, v_cndmask*, v_cmp* and
+                 v_accvgpr* -- the instructions a phase's joins cost beside its arithmetic (profiles/vector_trim_census_{before,after}.txt)
 """
 import collections, json, os, re, subprocess, sys
 
@@ -223,6 +225,8 @@ def phases_table(lines, counts):
 FULL_BOOK, FULL_TENK = 0.543, 0.396
 SCALAR_PORT_CYCLES = 4.7        # SIMD cycles between two scalar instructions of one SIMD: the CU's one scalar unit serves four (profiles/r04_experiments.txt item 4)
 
+COPY_FAMILIES = ("v_mov", "v_cndmask", "v_cmp", "v_accvgpr")      # --copies: the per-phase table of these (v_cmp* includes v_cmpx*)
+
 DEVICE_FUNCS = {  # functions of rt_device.hpp that get their own column in the per-phase split
     "philox4x32_10": "Philox block",
 }
@@ -265,6 +269,7 @@ def main():
     unplaced = collections.Counter()
     philox_in = collections.Counter()
     last_ph = None
+    copies_at = collections.defaultdict(collections.Counter)    # phase -> (opcode family, source line) -> static count   (--copies)
     # A frame WITHOUT a line inside an inlined helper (the exec restores that close pool_round's nested lane-level `if`s: nine scalar instructions that run
     # once per pooled round) used to fall through to the line of the CALL, i.e. to the walk's trip or to finish_pool, and was charged per trip.  The
     # line tables name every lambda "operator()", so the helper is found through the call: when the frame outside a line-less one sits on a line that calls
@@ -309,6 +314,17 @@ def main():
             ph = "outside the bounce loop / unplaced"
             unplaced[tuple(klines[:2])] += 1
         static[ph][cls] += 1
+        fam = next((f for f in COPY_FAMILIES if op.startswith(f)), None)
+        if fam:
+            # the source line: the innermost frame of rt_kernels.hpp that has one; a line-less frame of an inlined helper is the helper's (as above);
+            # failing both, the innermost frame with a line in any file (rt_device.hpp's helpers)
+            at = next((f"rt_kernels.hpp:{ln}" for fn, f, ln in stack if f == "rt_kernels.hpp" and ln > 0), None)
+            hl = helper_lines(stack)
+            if hl and (at is None or (stack[0][1] == "rt_kernels.hpp" and stack[0][2] == 0)):
+                at = f"rt_kernels.hpp:{hl[0]} (helper)"
+            if at is None:
+                at = next((f"{f}:{ln}" for fn, f, ln in stack if ln > 0), "no line")
+            copies_at[ph][(fam, at)] += 1
         if dump and dump in ph:
             print(f"{addr:08x} {cls:18s} {op} {ops}   ; {' < '.join(f'{f.split(chr(46))[0][-8:]}:{ln}' for fn, f, ln in stack[:3])}")
         if any(fn.startswith("rt::philox4x32_10") or "philox4x32_10" in fn for fn, f, ln in stack):
@@ -398,6 +414,23 @@ def main():
             items = [(c, st.get(c, 0) * freq[name]) for c in vcls if st.get(c, 0) * freq[name] >= 3.0]
             if items:
                 print(f"   {name[:50]:50s} " + "  ".join(f"{c[5:]}={n:.0f}" for c, n in sorted(items, key=lambda kv: -kv[1])))
+    if "--copies" in args:
+        # what the compiler emits for a phase's joins rather than for its arithmetic: register copies, selects, the compares that feed them, AGPR traffic
+        print("\ncopies, selects and compares by phase and source line: static count, count per wave-bounce (static x the phase's executions / copies)")
+        grand = collections.Counter()
+        for name, lo, hi, ex, rule in phases + [("outside the bounce loop / unplaced", 0, 0, 0.0, 1)]:
+            got = copies_at.get(name)
+            if not got:
+                continue
+            per = collections.Counter()
+            for (fam, at), n in got.items():
+                per[fam] += n
+                grand[fam] += n * freq[name]
+            print(f"\n{name}  (x {freq[name]:.3f} per static instruction)")
+            print("   " + "  ".join(f"{fam}* {per[fam]:3d} static {per[fam] * freq[name]:6.1f} dyn" for fam in COPY_FAMILIES))
+            for (fam, at), n in sorted(got.items(), key=lambda kv: (COPY_FAMILIES.index(kv[0][0]), -kv[1], kv[0][1])):
+                print(f"      {fam + '*':14s} {n:4d} {n * freq[name]:7.2f}   {at}")
+        print("\nTOTAL per wave-bounce: " + "  ".join(f"{fam}* {grand[fam]:.1f}" for fam in COPY_FAMILIES))
     if unplaced:
         print("\nunplaced (kernel lines of the stack):", unplaced.most_common(12))
 
