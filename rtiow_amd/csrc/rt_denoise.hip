@@ -288,21 +288,17 @@ int rt_denoise(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int6
     if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)width * height;
-    const size_t fix_bytes = npix * 3 * sizeof(uint64_t), feat_bytes = npix * RT_FEATURE_WORDS * sizeof(uint64_t);
-    const size_t count_bytes = count ? npix * sizeof(uint32_t) : 0;
-    Stage st(ctx);
-    const size_t b_fix = st.add(fix_bytes), b_feat = st.add(feat_bytes), b_out = st.add(fix_bytes);
-    const size_t b_work = st.add(npix * rt::kDnWorkDoubles * sizeof(double)), b_count = st.add(count_bytes);
+    Stage st(ctx);                                      // (the order of the blocks: tests/stage_layout_table.cpp, denoise_blocks)
+    const auto sums = st.in(fix, npix * 3), guides = st.in(feat, npix * RT_FEATURE_WORDS);
+    const auto out = st.out(out_fix, npix * 3);
+    const auto work = st.scratch<double>(npix * rt::kDnWorkDoubles);
+    const auto counts = st.in(count, npix);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_fix, fix, fix_bytes));
-    RT_HIP(st.up(b_feat, feat, feat_bytes));
-    if (count) RT_HIP(st.up(b_count, count, count_bytes));
-    return timed_section(ctx, "rt_denoise", kernel_ms,
-        [&] {
-            return rt_denoise_device(ctx, st.at(b_fix), count ? st.at(b_count) : nullptr, spp, st.at(b_feat), feat_spp, width, height, dn,
-                                     st.at(b_work), st.at(b_out), ctx->own_stream);
-        },
-        [&] { return st.down(out_fix, b_out, fix_bytes); });
+    RT_HIP(st.upload());
+    return timed_section(ctx, "rt_denoise", kernel_ms, st, [&] {
+        return rt_denoise_device(ctx, st.ptr(sums), st.ptr(counts), spp, st.ptr(guides), feat_spp, width, height, dn, st.ptr(work), st.ptr(out),
+                                 ctx->own_stream);
+    });
 }
 
 // the library's own CPU statement of the filter: the very functions the kernels compile, one pixel after the other

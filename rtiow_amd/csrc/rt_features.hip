@@ -218,18 +218,14 @@ int rt_render_features(rt_context *ctx, const rt_camera *cam, const rt_params *p
     int rc = begin_features(ctx, cam, p, out_feat);
     if (rc) return rc;
     const size_t npix = (size_t)p->width * p->height;
-    const size_t feat_bytes = npix * RT_FEATURE_WORDS * sizeof(uint64_t), ids_bytes = out_ids ? npix * sizeof(int32_t) : 0;
     Stage st(ctx);
-    const size_t b_feat = st.add(feat_bytes), b_ids = st.add(ids_bytes);
+    const auto feat = st.out(out_feat, npix * RT_FEATURE_WORDS);
+    const auto ids = st.out(out_ids, npix);
     if ((rc = st.commit())) return rc;
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    return timed_section(ctx, "rt_render_features", kernel_ms,
-        [&] { return rt_render_features_device(ctx, cam, &q, st.at(b_feat), out_ids ? st.at(b_ids) : nullptr, ctx->own_stream); },
-        [&] {
-            const hipError_t he = st.down(out_feat, b_feat, feat_bytes);
-            return he == hipSuccess && out_ids ? st.down(out_ids, b_ids, ids_bytes) : he;
-        });
+    return timed_section(ctx, "rt_render_features", kernel_ms, st,
+        [&] { return rt_render_features_device(ctx, cam, &q, st.ptr(feat), st.ptr(ids), ctx->own_stream); });
 }
 
 #ifdef RT_FEATURES_COUNT
@@ -257,12 +253,13 @@ int rt_features_to_f32(rt_context *ctx, const uint64_t *feat, int32_t width, int
     RT_HIP(hipSetDevice(ctx->device));
     const size_t count = (size_t)width * rows * RT_FEATURE_WORDS;
     Stage st(ctx);
-    const size_t b_feat = st.add(count * sizeof(uint64_t)), b_out = st.add(count * sizeof(float));
+    const auto words = st.in(feat, count);
+    const auto f32 = st.out(out, count);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_feat, feat, count * sizeof(uint64_t)));
-    rc = rt_features_to_f32_device(ctx, st.at(b_feat), width, rows, spp, st.at(b_out), ctx->own_stream);
+    RT_HIP(st.upload());
+    rc = rt_features_to_f32_device(ctx, st.ptr(words), width, rows, spp, st.ptr(f32), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(st.down(out, b_out, count * sizeof(float)));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     return RT_OK;
 }

@@ -105,14 +105,15 @@ int rt_render_frames(rt_context *ctx, const rt_camera *cams, int32_t n_frames, i
     RT_HIP(hipSetDevice(ctx->device));
     const size_t count = (size_t)n_frames * p->width * p->height * 3;
     Stage st(ctx);
-    const size_t b_fix = st.add(count * sizeof(uint64_t)), b_cams = st.add((size_t)n_frames * sizeof(rt_camera));
+    const auto sums = st.out(out_fix, count);
+    const auto d_cams = st.in(cams, (size_t)n_frames);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_cams, cams, (size_t)n_frames * sizeof(rt_camera)));
+    RT_HIP(st.upload());
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_frames_device(ctx, st.at<const rt_camera>(b_cams), n_frames, sample_stride, &q, st.at(b_fix), ctx->own_stream);
+    rc = rt_render_frames_device(ctx, st.ptr(d_cams), n_frames, sample_stride, &q, st.ptr(sums), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(st.down(out_fix, b_fix, count * sizeof(uint64_t)));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
@@ -132,26 +133,28 @@ int rt_render_frames_rgba8(rt_context *ctx, const rt_camera *cams, int32_t n_fra
     const size_t frame_pix = (size_t)p->width * p->height;
     const size_t npix = frame_pix * (size_t)n_frames;
     Stage st(ctx);
-    const size_t b_fix = st.add(npix * 3 * sizeof(uint64_t)), b_rgba = st.add(npix * 4), b_cams = st.add((size_t)n_frames * sizeof(rt_camera));
+    const auto sums = st.scratch<uint64_t>(npix * 3);
+    const auto rgba = st.out(out_rgba, npix * 4);
+    const auto d_cams = st.in(cams, (size_t)n_frames);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_cams, cams, (size_t)n_frames * sizeof(rt_camera)));
+    RT_HIP(st.upload());
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_frames_device(ctx, st.at<const rt_camera>(b_cams), n_frames, sample_stride, &q, st.at(b_fix), ctx->own_stream);
+    rc = rt_render_frames_device(ctx, st.ptr(d_cams), n_frames, sample_stride, &q, st.ptr(sums), ctx->own_stream);
     if (rc) return rc;
     // Color::to_rgba is per pixel; only the flip knows about frames.  Unflipped, the batch is one image of n_frames * height rows;
     // flipped, every frame is resolved on its own (the resolve kernel is rt_api.hip's: this file adds none)
     if (!flip && (long long)n_frames * p->height <= 0x7fffffffLL) {
-        rc = rt_resolve_rgba8_device(ctx, st.at(b_fix), p->width, n_frames * p->height, (int64_t)p->spp, 0, st.at(b_rgba), ctx->own_stream);
+        rc = rt_resolve_rgba8_device(ctx, st.ptr(sums), p->width, n_frames * p->height, (int64_t)p->spp, 0, st.ptr(rgba), ctx->own_stream);
         if (rc) return rc;
     } else {
         for (int32_t f = 0; f < n_frames; ++f) {
-            rc = rt_resolve_rgba8_device(ctx, st.at<const uint64_t>(b_fix) + (size_t)f * frame_pix * 3, p->width, p->height, (int64_t)p->spp,
-                                         flip, st.at<uint8_t>(b_rgba) + (size_t)f * frame_pix * 4, ctx->own_stream);
+            rc = rt_resolve_rgba8_device(ctx, st.ptr(sums) + (size_t)f * frame_pix * 3, p->width, p->height, (int64_t)p->spp, flip,
+                                         st.ptr(rgba) + (size_t)f * frame_pix * 4, ctx->own_stream);
             if (rc) return rc;
         }
     }
-    RT_HIP(st.down(out_rgba, b_rgba, npix * 4));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;

@@ -1,12 +1,19 @@
 // rt_host.hpp -- what EVERY translation unit of librtiow_hip.so shares: the context, the error path, parameter validation, the scene's
-// fields of the kernel-argument block (set_scene_params) and the plumbing of the host-buffer entry points: StageLayout / Stage (one device
-// arena per context, laid out per call), timed_section (a pair of events of the call's own around its kernels) and grid_256.
+// fields of the kernel-argument block (set_scene_params) and the plumbing of the host-buffer entry points: StageLayout / StagePlan / Stage
+// (one device arena per context, laid out per call: a buffer is DECLARED once -- host pointer, element count, direction -- and its offset,
+// its copies and its device pointer follow from that), timed_section (a pair of events of the call's own around its kernels) and grid_256.
+// Also the argument checks the ray and path families share (rt_trace.hip, wavefront/rt_shade.hip, wavefront/rt_paths.hip): RT_NEED,
+// check_no_flags / check_count / check_t_min / check_npix / check_frame_dims / check_context, and capped_grid and to_kcamera.
 // rt_api.hip defines the functions declared here.  The render kernel is not among what is shared: this header takes its argument block
 // from rt_params.hpp, and the units that launch it -- rt_api.hip, rt_frames.hip, rt_dense.hip -- add rt_launch.hpp.
 // rt_scene_core.hpp (included here for rt_context's Header) builds the scene's tables on the host, pure and HIP-free; a change to what a
 // table holds bumps its kTablesVersion and the static_assert on it in rt_api.hip, so that the hashed sources change with it.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
 
 #include "rtiow_hip.h"
 #include "rt_params.hpp"
@@ -113,22 +120,81 @@ struct StageLayout {
     }
 };
 
+// What one host-form call declared, in declaration order: per buffer its block's offset (StageLayout::add, so a call that declares its
+// buffers in a given order has the layout add() gives that order), its bytes, the caller's pointer and the direction.  A caller's pointer
+// that is NULL declares a block of 0 bytes that is ABSENT: this is the one place where "optional buffer left out" is decided.  Fixed
+// capacity, no heap: a declaration past kCapacity is remembered (overflow) and writes nothing.  Pure, no HIP call
+// (tests/stage_layout_table.cpp tabulates it).
+enum class StageDir : unsigned char { in, out, inout, scratch };
+struct StagePlan {
+    static constexpr int kCapacity = 16;
+    struct Block { size_t offset, bytes; void *host; StageDir dir; };
+    StageLayout layout;
+    Block blocks[kCapacity];
+    int n = 0;
+    bool overflow = false;
+    // the block's number, -1 past the capacity
+    int declare(StageDir dir, const void *host, size_t bytes)
+    {
+        if (n == kCapacity) { overflow = true; return -1; }
+        if (dir != StageDir::scratch && !host) bytes = 0;
+        blocks[n] = {layout.add(bytes), bytes, const_cast<void *>(host), dir};
+        return n++;
+    }
+    // the block has a device pointer: a scratch block, or a buffer the caller gave
+    bool present(int k) const { return k >= 0 && k < n && (blocks[k].dir == StageDir::scratch || blocks[k].host); }
+    // the block is copied before / after the call's kernels: upload() and download() take them in declaration order
+    bool goes_up(int k) const { return present(k) && (blocks[k].dir == StageDir::in || blocks[k].dir == StageDir::inout); }
+    bool comes_down(int k) const { return present(k) && (blocks[k].dir == StageDir::out || blocks[k].dir == StageDir::inout); }
+};
+
+// a declared buffer of elements T: only a name for the block -- its device pointer is Stage::ptr's to give, after commit()
+template <class T> struct Staged { int block = -1; };
+
 // One host-form call's use of the arena.  THE RULE: device-form entry points never touch the arena; a host-form entry point lays its
-// blocks out once (add ... commit), before its first copy, and from then on calls only device forms -- so nothing can move or reuse a
-// block while the call's work is in flight on own_stream.  commit() grows the arena to this call's total with ensure(): never shrunk,
-// contents not preserved.  up / down / sync are hipMemcpyAsync / hipStreamSynchronize on ctx->own_stream.
+// blocks out once (declare or add ... commit), before its first copy, and from then on calls only device forms -- so nothing can move or
+// reuse a block while the call's work is in flight on own_stream.  commit() grows the arena to this call's total with ensure(): never
+// shrunk, contents not preserved; the arena may MOVE when it grows, which is why a declaration returns a Staged and not a pointer.
+// The declared layer: in / out / inout(host, count) and scratch<T>(count) declare a buffer once; upload() copies every in and inout
+// buffer the caller gave, download() every out and inout one, in declaration order; ptr(handle) is the device copy, nullptr for a buffer
+// the caller left out.  The primitive layer below it -- add / at / up / down on byte offsets -- is what rt_api.hip and rt_adaptive.hip
+// use; both share one layout.  The copies and sync are hipMemcpyAsync / hipStreamSynchronize on ctx->own_stream.
 class Stage {
 public:
     explicit Stage(rt_context *ctx) : ctx_(ctx) {}
-    size_t add(size_t bytes) { return layout_.add(bytes); }
-    int commit() { return ensure(&ctx_->d_arena, &ctx_->arena_bytes, layout_.total); }
+    size_t add(size_t bytes) { return plan_.layout.add(bytes); }
+    int commit()
+    {
+        if (plan_.overflow) return fail(RT_ERR_INVALID_ARGUMENT, "Stage: a call declared more than %d buffers", StagePlan::kCapacity);
+        return ensure(&ctx_->d_arena, &ctx_->arena_bytes, plan_.layout.total);
+    }
     template <class T = void> T *at(size_t block) const { return reinterpret_cast<T *>(static_cast<char *>(ctx_->d_arena) + block); }
     hipError_t up(size_t block, const void *src, size_t bytes) const { return hipMemcpyAsync(at(block), src, bytes, hipMemcpyHostToDevice, ctx_->own_stream); }
     hipError_t down(void *dst, size_t block, size_t bytes) const { return hipMemcpyAsync(dst, at(block), bytes, hipMemcpyDeviceToHost, ctx_->own_stream); }
     hipError_t sync() const { return hipStreamSynchronize(ctx_->own_stream); }
+
+    template <class T> Staged<const T> in(const T *host, size_t count) { return {plan_.declare(StageDir::in, host, count * sizeof(T))}; }
+    template <class T> Staged<T> out(T *host, size_t count) { return {plan_.declare(StageDir::out, host, count * sizeof(T))}; }
+    template <class T> Staged<T> inout(T *host, size_t count) { return {plan_.declare(StageDir::inout, host, count * sizeof(T))}; }
+    template <class T> Staged<T> scratch(size_t count) { return {plan_.declare(StageDir::scratch, nullptr, count * sizeof(T))}; }
+    template <class T> T *ptr(Staged<T> h) const { return plan_.present(h.block) ? at<T>(plan_.blocks[h.block].offset) : nullptr; }
+    hipError_t upload() const
+    {
+        hipError_t he = hipSuccess;
+        for (int k = 0; k < plan_.n && he == hipSuccess; ++k)
+            if (plan_.goes_up(k)) he = up(plan_.blocks[k].offset, plan_.blocks[k].host, plan_.blocks[k].bytes);
+        return he;
+    }
+    hipError_t download() const
+    {
+        hipError_t he = hipSuccess;
+        for (int k = 0; k < plan_.n && he == hipSuccess; ++k)
+            if (plan_.comes_down(k)) he = down(plan_.blocks[k].host, plan_.blocks[k].offset, plan_.blocks[k].bytes);
+        return he;
+    }
 private:
     rt_context *ctx_;
-    StageLayout layout_;
+    StagePlan plan_;
 };
 
 // Times what body() enqueues on ctx->own_stream with a pair of events of this call's own (the context's belong to its launch slots),
@@ -156,6 +222,72 @@ int timed_section(rt_context *ctx, const char *name, float *kernel_ms, Body body
     if (rc) return rc;
     if (he != hipSuccess) return fail(RT_ERR_HIP, "%s: %s", name, hipGetErrorString(he));
     return RT_OK;
+}
+
+// ... of a host form on the declared layer: its downloads are st.download()
+template <class Body>
+int timed_section(rt_context *ctx, const char *name, float *kernel_ms, const Stage &st, Body body)
+{
+    return timed_section(ctx, name, kernel_ms, body, [&st] { return st.download(); });
+}
+
+// ---- the argument checks the ray and path families share (rt_trace.hip, wavefront/rt_shade.hip, wavefront/rt_paths.hip).  An entry point
+// runs the context-free ones first, then check_context, then selects the device.
+#define RT_NEED(ptr, what, name) \
+    do { if (!(ptr)) return rt_host::fail(RT_ERR_INVALID_ARGUMENT, "%s: %s is NULL", what, name); } while (0)
+
+// noun: what the family calls itself ("the wavefront steps", "the path queue")
+inline int check_no_flags(const char *what, uint32_t flags, const char *noun)
+{
+    if (flags & RT_FLAG_UNIFORM53)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: RT_FLAG_UNIFORM53 is not built for %s (flags 0x%x; only 0 is legal)", what, noun, flags);
+    if (flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x (only 0 is legal)", what, flags);
+    return RT_OK;
+}
+inline int check_count(const char *what, int64_t n)
+{
+    if (n < 0 || n > (int64_t)1 << 31) return fail(RT_ERR_INVALID_ARGUMENT, "%s: n must be in [0, 2^31] (is %lld)", what, (long long)n);
+    return RT_OK;
+}
+inline int check_t_min(const char *what, double t_min)
+{
+    if (!(t_min > 0.0) || !std::isfinite(t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, t_min);
+    return RT_OK;
+}
+inline int check_npix(const char *what, int64_t npix)
+{
+    if (npix <= 0 || npix > (int64_t)1 << 32) return fail(RT_ERR_INVALID_ARGUMENT, "%s: npix must be in [1, 2^32] (is %lld)", what, (long long)npix);
+    return RT_OK;
+}
+inline int check_frame_dims(const char *what, int32_t width, int32_t height)
+{
+    if (width < 2 || height < 2) return fail(RT_ERR_INVALID_ARGUMENT, "%s: width and height must be >= 2 (are %d, %d)", what, width, height);
+    return RT_OK;
+}
+// the context's part of every check, after the context-free ones
+inline int check_context(const rt_context *ctx, const char *what, bool needs_mode5, bool needs_scene)
+{
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (needs_mode5 && ctx->scan_mode != 5)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s needs the shipped scan mode 5; this context was created under RTIOW_SCAN_MODE=%d", what, ctx->scan_mode);
+    if (needs_scene && ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    return RT_OK;
+}
+
+// a family's diagnostic knob <env_name>=k (read per call): at most k workgroups, so that a kernel's grid-stride trip runs at a test's size
+inline long long capped_grid(const char *env_name, long long grid)
+{
+    const char *e = getenv(env_name);
+    const long long cap = e && *e ? atoll(e) : 0;
+    return cap > 0 && grid > cap ? cap : grid;
+}
+
+inline rt::KCamera to_kcamera(const rt_camera *cam)
+{
+    rt::KCamera kc;
+    static_assert(sizeof(rt::KCamera) == sizeof(rt_camera), "camera layouts must match");
+    memcpy(&kc, cam, sizeof(rt_camera));
+    return kc;
 }
 
 } // namespace rt_host

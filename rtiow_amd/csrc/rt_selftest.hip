@@ -62,18 +62,16 @@ int rt_f64_div_sqrt_device(rt_context *ctx, const double *a, const double *b, in
     if (!ctx || !a || !b || !out_div || !out_sqrt || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * sizeof(double);
     Stage st(ctx);
-    const size_t b_a = st.add(bytes), b_b = st.add(bytes), b_q = st.add(bytes), b_r = st.add(bytes);
+    const auto d_a = st.in(a, (size_t)n), d_b = st.in(b, (size_t)n);
+    const auto d_q = st.out(out_div, (size_t)n), d_r = st.out(out_sqrt, (size_t)n);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_a, a, bytes));
-    RT_HIP(st.up(b_b, b, bytes));
+    RT_HIP(st.upload());
     hipLaunchKernelGGL(rt::f64_div_sqrt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream,
-                       st.at<const double>(b_a), st.at<const double>(b_b), (int)n, st.at<double>(b_q), st.at<double>(b_r));
+                       st.ptr(d_a), st.ptr(d_b), (int)n, st.ptr(d_q), st.ptr(d_r));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out_div, b_q, bytes));
-    RT_HIP(st.down(out_sqrt, b_r, bytes));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     return RT_OK;
 }
@@ -83,16 +81,15 @@ int rt_quantize_device(rt_context *ctx, const double *x, int32_t n, uint64_t *ou
     if (!ctx || !x || !out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n * sizeof(double);
     Stage st(ctx);
-    const size_t b_x = st.add(bytes), b_q = st.add(bytes);
+    const auto d_x = st.in(x, (size_t)n);
+    const auto d_q = st.out(reinterpret_cast<unsigned long long *>(out), (size_t)n);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_x, x, bytes));
-    hipLaunchKernelGGL(rt::quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.at<const double>(b_x), (int)n,
-                       st.at<unsigned long long>(b_q));
+    RT_HIP(st.upload());
+    hipLaunchKernelGGL(rt::quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.ptr(d_x), (int)n, st.ptr(d_q));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out, b_q, bytes));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     return RT_OK;
 }
@@ -102,17 +99,17 @@ int rt_unit_accept_device(rt_context *ctx, const uint32_t *words, int32_t n, uin
     if (!ctx || !words || !out_accept || !out_uniforms || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t wb = (size_t)n * 3 * sizeof(uint32_t), ab = (size_t)n * sizeof(uint32_t), ub = (size_t)n * 4 * sizeof(double);
     Stage st(ctx);
-    const size_t b_u = st.add(ub), b_w = st.add(wb), b_a = st.add(ab);
+    const auto d_u = st.out(out_uniforms, (size_t)n * 4);
+    const auto d_w = st.in(words, (size_t)n * 3);
+    const auto d_a = st.out(out_accept, (size_t)n);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_w, words, wb));
-    hipLaunchKernelGGL(rt::unit_accept_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.at<const uint32_t>(b_w), (int)n,
-                       st.at<uint32_t>(b_a), st.at<double>(b_u));
+    RT_HIP(st.upload());
+    hipLaunchKernelGGL(rt::unit_accept_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.ptr(d_w), (int)n, st.ptr(d_a),
+                       st.ptr(d_u));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out_accept, b_a, ab));
-    RT_HIP(st.down(out_uniforms, b_u, ub));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     return RT_OK;
 }
@@ -126,13 +123,12 @@ int rt_philox_device(rt_context *ctx, const uint32_t ctr[4], const uint32_t key[
     if (!ctx || !ctr || !key || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     RT_HIP(hipSetDevice(ctx->device));
     Stage st(ctx);
-    const size_t b_out = st.add(16);
+    const auto d_out = st.out(out, 4);
     int rc = st.commit();
     if (rc) return rc;
-    hipLaunchKernelGGL(rt::philox_kat_kernel, dim3(1), dim3(1), 0, ctx->own_stream,
-                       ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], st.at<uint32_t>(b_out));
+    hipLaunchKernelGGL(rt::philox_kat_kernel, dim3(1), dim3(1), 0, ctx->own_stream, ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], st.ptr(d_out));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out, b_out, 16));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     return RT_OK;
 }

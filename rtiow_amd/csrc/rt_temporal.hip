@@ -145,32 +145,21 @@ int rt_temporal(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int
     if (rc) return rc;
     if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
     RT_HIP(hipSetDevice(ctx->device));
-    const bool hist = prev_cam != nullptr;
+    const bool hist = prev_cam != nullptr;              // no history: its three buffers are left out whatever the caller passed
     const size_t npix = (size_t)width * height;
-    const size_t fix_bytes = npix * 3 * sizeof(uint64_t), feat_bytes = npix * RT_FEATURE_WORDS * sizeof(uint64_t), len_bytes = npix * sizeof(uint32_t);
-    Stage st(ctx);
-    const size_t b_fix = st.add(fix_bytes), b_feat = st.add(feat_bytes), b_count = st.add(count ? len_bytes : 0);
-    const size_t b_pfix = st.add(hist ? fix_bytes : 0), b_pfeat = st.add(hist ? feat_bytes : 0), b_plen = st.add(hist ? len_bytes : 0);
-    const size_t b_out = st.add(fix_bytes), b_olen = st.add(len_bytes);
+    Stage st(ctx);                                      // (the order of the blocks: tests/stage_layout_table.cpp, temporal_blocks)
+    const auto sums = st.in(fix, npix * 3), guides = st.in(feat, npix * RT_FEATURE_WORDS);
+    const auto counts = st.in(count, npix);
+    const auto psums = st.in(hist ? prev_fix : nullptr, npix * 3), pguides = st.in(hist ? prev_feat : nullptr, npix * RT_FEATURE_WORDS);
+    const auto plen = st.in(hist ? prev_len : nullptr, npix);
+    const auto out = st.out(out_fix, npix * 3);
+    const auto olen = st.out(out_len, npix);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_fix, fix, fix_bytes));
-    RT_HIP(st.up(b_feat, feat, feat_bytes));
-    if (count) RT_HIP(st.up(b_count, count, len_bytes));
-    if (hist) {
-        RT_HIP(st.up(b_pfix, prev_fix, fix_bytes));
-        RT_HIP(st.up(b_pfeat, prev_feat, feat_bytes));
-        RT_HIP(st.up(b_plen, prev_len, len_bytes));
-    }
-    return timed_section(ctx, "rt_temporal", kernel_ms,
-        [&] {
-            return rt_temporal_device(ctx, st.at(b_fix), count ? st.at(b_count) : nullptr, spp, st.at(b_feat), feat_spp, cam,
-                                      hist ? st.at(b_pfix) : nullptr, hist ? st.at(b_plen) : nullptr, hist ? st.at(b_pfeat) : nullptr, prev_feat_spp,
-                                      prev_cam, width, height, tp, st.at(b_out), st.at(b_olen), ctx->own_stream);
-        },
-        [&] {
-            const hipError_t he = st.down(out_fix, b_out, fix_bytes);
-            return he == hipSuccess ? st.down(out_len, b_olen, len_bytes) : he;
-        });
+    RT_HIP(st.upload());
+    return timed_section(ctx, "rt_temporal", kernel_ms, st, [&] {
+        return rt_temporal_device(ctx, st.ptr(sums), st.ptr(counts), spp, st.ptr(guides), feat_spp, cam, st.ptr(psums), st.ptr(plen), st.ptr(pguides),
+                                  prev_feat_spp, prev_cam, width, height, tp, st.ptr(out), st.ptr(olen), ctx->own_stream);
+    });
 }
 
 // the library's own CPU statement: the very functions the kernel compiles, one pixel after the other

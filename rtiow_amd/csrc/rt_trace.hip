@@ -17,7 +17,6 @@
 // goes idle and the wave leaves the tile loop when no lane is left.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -237,15 +236,6 @@ bool candidates_knob_ray()
     return kTraceDefaultRay;
 }
 
-// RTIOW_TRACE_GRID_BLOCKS=k (diagnostic, read per call): at most k workgroups, so that the kernel's grid-stride trip runs at a test's size
-long long grid_blocks_knob()
-{
-    const char *e = getenv("RTIOW_TRACE_GRID_BLOCKS");
-    if (!e || !*e) return 0;
-    const long long v = atoll(e);
-    return v > 0 ? v : 0;
-}
-
 // The start of every ray query.  What it accepts is checked before anything is touched: the checks that need no context come first (a
 // caller without a device still gets the precise message), then the context's own; then the device.  `out`: hits->index or d_occluded.
 // *go: there are rays to trace (an empty batch is RT_OK with nothing done).
@@ -254,18 +244,14 @@ int begin_trace(const rt_context *ctx, const char *what, const rt_rays *rays, do
     *go = false;
     if (!rays) return fail(RT_ERR_INVALID_ARGUMENT, "%s: rays is NULL", what);
     if (!has_out_struct) return fail(RT_ERR_INVALID_ARGUMENT, "%s: hits is NULL", what);
-    if (rays->n < 0 || rays->n > (int64_t)1 << 31)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s: n must be in [0, 2^31] (is %lld)", what, (long long)rays->n);
-    if (!(t_min > 0.0) || !std::isfinite(t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, t_min);
+    if (int rc = check_count(what, rays->n)) return rc;
+    if (int rc = check_t_min(what, t_min)) return rc;
     if (rays->n > 0) {
         if (!rays->origin) return fail(RT_ERR_INVALID_ARGUMENT, "%s: rays->origin is NULL", what);
         if (!rays->dir) return fail(RT_ERR_INVALID_ARGUMENT, "%s: rays->dir is NULL", what);
         if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "%s: the required output (hits->index / occluded) is NULL", what);
     }
-    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (ctx->scan_mode != 5)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s needs the shipped scan mode 5; this context was created under RTIOW_SCAN_MODE=%d", what, ctx->scan_mode);
-    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (int rc = check_context(ctx, what, true, true)) return rc;
     if (rays->n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     *go = true;
@@ -285,10 +271,8 @@ int launch_trace(rt_context *ctx, const rt_rays *rays, double t_min, const rt_hi
     ta.origin = rays->origin; ta.dir = rays->dir; ta.t_max = rays->t_max; ta.n = (long long)rays->n;
     if (hits) { ta.index = hits->index; ta.t = hits->t; ta.point = hits->point; ta.normal = hits->normal; ta.front = hits->front_face; }
     ta.occluded = (uint8_t *)d_occluded;
-    // one wave per 64 rays
-    long long grid = rt::wave_grid(((long long)rays->n + 63) / 64, rt::kTraceWaves);
-    const long long cap = grid_blocks_knob();
-    if (cap > 0 && grid > cap) grid = cap;
+    // one wave per 64 rays; RTIOW_TRACE_GRID_BLOCKS: the diagnostic cap
+    const long long grid = capped_grid("RTIOW_TRACE_GRID_BLOCKS", rt::wave_grid(((long long)rays->n + 63) / 64, rt::kTraceWaves));
     const bool ray = candidates_knob_ray(), any = hits == nullptr;
     const dim3 g((unsigned)grid), b(rt::kTraceBlock);
     if (ray && any) hipLaunchKernelGGL((rt::trace_kernel<true, true>), g, b, 0, stream, kp, ta);
@@ -299,29 +283,14 @@ int launch_trace(rt_context *ctx, const rt_rays *rays, double t_min, const rt_hi
     return RT_OK;
 }
 
-// the host forms' common part: rays up, `device` on own_stream between the events, `downloads` after them
+// the host forms' common part: the three ray buffers, declared
 struct StagedRays {
-    size_t b_o, b_d, b_tmax;
-    rt_rays dev;
+    Staged<const double> origin, dir, t_max;
 };
-void stage_rays(Stage &st, const rt_rays *rays, StagedRays &s)
+StagedRays stage_rays(Stage &st, const rt_rays *rays)
 {
     const size_t n = (size_t)rays->n;
-    s.b_o = st.add(n * 3 * sizeof(double));
-    s.b_d = st.add(n * 3 * sizeof(double));
-    s.b_tmax = st.add(rays->t_max ? n * sizeof(double) : 0);
-}
-hipError_t upload_rays(const Stage &st, const rt_rays *rays, StagedRays &s)
-{
-    const size_t n = (size_t)rays->n;
-    hipError_t he = st.up(s.b_o, rays->origin, n * 3 * sizeof(double));
-    if (he == hipSuccess) he = st.up(s.b_d, rays->dir, n * 3 * sizeof(double));
-    if (he == hipSuccess && rays->t_max) he = st.up(s.b_tmax, rays->t_max, n * sizeof(double));
-    s.dev.origin = st.at<double>(s.b_o);
-    s.dev.dir = st.at<double>(s.b_d);
-    s.dev.t_max = rays->t_max ? st.at<double>(s.b_tmax) : nullptr;
-    s.dev.n = rays->n;
-    return he;
+    return {st.in(rays->origin, 3 * n), st.in(rays->dir, 3 * n), st.in(rays->t_max, n)};
 }
 
 } // namespace
@@ -344,29 +313,15 @@ int rt_trace_rays(rt_context *ctx, const rt_rays *rays, double t_min, const rt_h
     if (rc || !go) return rc;
     const size_t n = (size_t)rays->n;
     Stage st(ctx);
-    StagedRays sr;
-    stage_rays(st, rays, sr);
-    const size_t b_index = st.add(n * sizeof(int32_t)), b_t = st.add(hits->t ? n * sizeof(double) : 0);
-    const size_t b_point = st.add(hits->point ? n * 3 * sizeof(double) : 0), b_normal = st.add(hits->normal ? n * 3 * sizeof(double) : 0);
-    const size_t b_front = st.add(hits->front_face ? n : 0);
+    const StagedRays sr = stage_rays(st, rays);
+    const auto index = st.out(hits->index, n);
+    const auto t = st.out(hits->t, n), point = st.out(hits->point, 3 * n), normal = st.out(hits->normal, 3 * n);
+    const auto front = st.out(hits->front_face, n);
     if ((rc = st.commit())) return rc;
-    RT_HIP(upload_rays(st, rays, sr));
-    rt_hits dh;
-    dh.index = st.at<int32_t>(b_index);
-    dh.t = hits->t ? st.at<double>(b_t) : nullptr;
-    dh.point = hits->point ? st.at<double>(b_point) : nullptr;
-    dh.normal = hits->normal ? st.at<double>(b_normal) : nullptr;
-    dh.front_face = hits->front_face ? st.at<uint8_t>(b_front) : nullptr;
-    return timed_section(ctx, "rt_trace_rays", kernel_ms,
-        [&] { return rt_trace_rays_device(ctx, &sr.dev, t_min, &dh, ctx->own_stream); },
-        [&] {
-            hipError_t he = st.down(hits->index, b_index, n * sizeof(int32_t));
-            if (he == hipSuccess && hits->t) he = st.down(hits->t, b_t, n * sizeof(double));
-            if (he == hipSuccess && hits->point) he = st.down(hits->point, b_point, n * 3 * sizeof(double));
-            if (he == hipSuccess && hits->normal) he = st.down(hits->normal, b_normal, n * 3 * sizeof(double));
-            if (he == hipSuccess && hits->front_face) he = st.down(hits->front_face, b_front, n);
-            return he;
-        });
+    RT_HIP(st.upload());
+    const rt_rays dr = {st.ptr(sr.origin), st.ptr(sr.dir), st.ptr(sr.t_max), rays->n};
+    const rt_hits dh = {st.ptr(index), st.ptr(t), st.ptr(point), st.ptr(normal), st.ptr(front)};
+    return timed_section(ctx, "rt_trace_rays", kernel_ms, st, [&] { return rt_trace_rays_device(ctx, &dr, t_min, &dh, ctx->own_stream); });
 }
 
 int rt_occluded_device(rt_context *ctx, const rt_rays *rays, double t_min, void *d_occluded, void *stream_v)
@@ -382,16 +337,13 @@ int rt_occluded(rt_context *ctx, const rt_rays *rays, double t_min, uint8_t *occ
     bool go;
     int rc = begin_trace(ctx, "rt_occluded", rays, t_min, true, occluded, &go);
     if (rc || !go) return rc;
-    const size_t n = (size_t)rays->n;
     Stage st(ctx);
-    StagedRays sr;
-    stage_rays(st, rays, sr);
-    const size_t b_occ = st.add(n);
+    const StagedRays sr = stage_rays(st, rays);
+    const auto occ = st.out(occluded, (size_t)rays->n);
     if ((rc = st.commit())) return rc;
-    RT_HIP(upload_rays(st, rays, sr));
-    return timed_section(ctx, "rt_occluded", kernel_ms,
-        [&] { return rt_occluded_device(ctx, &sr.dev, t_min, st.at(b_occ), ctx->own_stream); },
-        [&] { return st.down(occluded, b_occ, n); });
+    RT_HIP(st.upload());
+    const rt_rays dr = {st.ptr(sr.origin), st.ptr(sr.dir), st.ptr(sr.t_max), rays->n};
+    return timed_section(ctx, "rt_occluded", kernel_ms, st, [&] { return rt_occluded_device(ctx, &dr, t_min, st.ptr(occ), ctx->own_stream); });
 }
 
 #ifdef RT_TRACE_COUNT

@@ -232,12 +232,10 @@ namespace {
 constexpr int64_t kMaxCapacity = (int64_t)1 << 24;
 constexpr long long kDefaultBatch = 1ll << 20;
 
-// RTIOW_PATHS_GRID_BLOCKS=k (diagnostic, read per call): at most k workgroups, so that the kernels' grid-stride trip runs at a test's size
-unsigned capped_grid(long long grid)
+// RTIOW_PATHS_GRID_BLOCKS: the diagnostic cap on the kernels' grids; at least one workgroup
+unsigned paths_grid(long long grid)
 {
-    const char *e = getenv("RTIOW_PATHS_GRID_BLOCKS");
-    const long long cap = e && *e ? atoll(e) : 0;
-    if (cap > 0 && grid > cap) grid = cap;
+    grid = capped_grid("RTIOW_PATHS_GRID_BLOCKS", grid);
     return (unsigned)(grid < 1 ? 1 : grid);
 }
 
@@ -250,15 +248,7 @@ int step_parts()
     return v > 0 ? v & 7 : 7;
 }
 
-int check_flags(const char *what, uint32_t flags)
-{
-    if (flags & RT_FLAG_UNIFORM53)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s: RT_FLAG_UNIFORM53 is not built for the path queue (flags 0x%x; only 0 is legal)", what, flags);
-    if (flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x (only 0 is legal)", what, flags);
-    return RT_OK;
-}
-#define RT_NEED(ptr, what, name) \
-    do { if (!(ptr)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s is NULL", what, name); } while (0)
+const char *const kNoun = "the path queue";
 
 int check_queue(const char *what, const char *name, const rt_path_queue *q)
 {
@@ -269,16 +259,6 @@ int check_queue(const char *what, const char *name, const rt_path_queue *q)
         if (!arrays[k]) return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s->%s is NULL", what, name, field[k]);
     if (q->capacity < 1 || q->capacity > kMaxCapacity)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s->capacity must be in [1, 2^24] (is %lld)", what, name, (long long)q->capacity);
-    return RT_OK;
-}
-
-// the context's part of every check, after the context-free ones
-int check_context(const rt_context *ctx, const char *what, bool needs_scene)
-{
-    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (ctx->scan_mode != 5)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s needs the shipped scan mode 5; this context was created under RTIOW_SCAN_MODE=%d", what, ctx->scan_mode);
-    if (needs_scene && ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
     return RT_OK;
 }
 
@@ -320,7 +300,7 @@ int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int3
     if (int rc = check_queue(what, "queue", q)) return rc;
     if (n < 0 || n > q->capacity)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: n must be in [0, capacity = %lld] (is %lld)", what, (long long)q->capacity, (long long)n);
-    if (width < 2 || height < 2) return fail(RT_ERR_INVALID_ARGUMENT, "%s: width and height must be >= 2 (are %d, %d)", what, width, height);
+    if (int rc = check_frame_dims(what, width, height)) return rc;
     if ((long long)width * height > 0x7fffffffLL)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: width * height does not fit the 32-bit Philox pixel counter", what);
     if (spp < 1 || sample_begin < 0 || (long long)spp + sample_begin > 0x7fffffffLL)
@@ -328,8 +308,8 @@ int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int3
     if (first_item < 0 || first_item + n > (long long)width * height * spp)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: the items [first_item, first_item + n) must lie in [0, width * height * spp) (first_item %lld, n %lld)",
                     what, (long long)first_item, (long long)n);
-    if (int rc = check_flags(what, flags)) return rc;
-    return check_context(ctx, what, false);
+    if (int rc = check_no_flags(what, flags, kNoun)) return rc;
+    return check_context(ctx, what, true, false);
 }
 
 // light: NULL for the unlit step (lit: whether the call is a lit one)
@@ -347,12 +327,12 @@ int check_step(const rt_context *ctx, const char *what, uint32_t flags, double t
             if (x == y) return fail(RT_ERR_INVALID_ARGUMENT, "%s: in and out share an array", what);
     if (out->capacity < in->capacity)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: out->capacity (%lld) must be >= in->capacity (%lld)", what, (long long)out->capacity, (long long)in->capacity);
-    if (npix <= 0 || npix > (int64_t)1 << 32) return fail(RT_ERR_INVALID_ARGUMENT, "%s: npix must be in [1, 2^32] (is %lld)", what, (long long)npix);
-    if (int rc = check_flags(what, flags)) return rc;
-    if (!(t_min > 0.0) || !std::isfinite(t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, t_min);
+    if (int rc = check_npix(what, npix)) return rc;
+    if (int rc = check_no_flags(what, flags, kNoun)) return rc;
+    if (int rc = check_t_min(what, t_min)) return rc;
     if (lit)
         if (int rc = check_light(what, light, false)) return rc;
-    if (int rc = check_context(ctx, what, true)) return rc;
+    if (int rc = check_context(ctx, what, true, true)) return rc;
     return lit ? check_light_count(ctx, what, light) : RT_OK;
 }
 
@@ -368,15 +348,12 @@ rt::QueueArrays arrays_of(const rt_path_queue *q)
 int launch_begin(const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, int32_t spp, int32_t sample_begin, int64_t first_item, int64_t n,
                  const rt_path_queue *q, hipStream_t stream)
 {
-    rt::KCamera kc;
-    static_assert(sizeof(rt::KCamera) == sizeof(rt_camera), "camera layouts must match");
-    memcpy(&kc, cam, sizeof(rt_camera));
     rt::BeginArgs a;
     memset(&a, 0, sizeof(a));
     a.n = (long long)n; a.first_item = (long long)first_item; a.spp = (uint32_t)spp; a.sample_begin = (uint32_t)sample_begin;
     a.width = width; a.height = height; a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
     // (at least one workgroup: an empty batch still writes the count)
-    hipLaunchKernelGGL(rt::path_begin_kernel, dim3(capped_grid(grid_256(a.n))), dim3(rt::kPathBlock), 0, stream, kc, arrays_of(q), a);
+    hipLaunchKernelGGL(rt::path_begin_kernel, dim3(paths_grid(grid_256(a.n))), dim3(rt::kPathBlock), 0, stream, to_kcamera(cam), arrays_of(q), a);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
@@ -394,7 +371,7 @@ int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_pat
     set_scene_params(ctx, kp);
     const rt::QueueArrays qi = arrays_of(in), qo = arrays_of(out);
     // the grids come from the CAPACITY: the live count is the device's to know.  One wave per 64 slots; waves past the count leave at once.
-    const dim3 grid(capped_grid(rt::wave_grid(((long long)in->capacity + 63) / 64, rt::kPathWaves))), block(rt::kPathBlock);
+    const dim3 grid(paths_grid(rt::wave_grid(((long long)in->capacity + 63) / 64, rt::kPathWaves))), block(rt::kPathBlock);
     const int parts = step_parts();
     if ((parts & 1) && !light) hipLaunchKernelGGL(rt::bounce_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix);
     if ((parts & 1) && light) {
@@ -454,12 +431,12 @@ int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, 
     RT_NEED(p, what, "params");
     RT_NEED(fix, what, "fix");
     if (int rc = validate_params(p)) return rc;
-    if (int rc = check_flags(what, p->flags)) return rc;
+    if (int rc = check_no_flags(what, p->flags, kNoun)) return rc;
     if (p->shard_count != 1) return fail(RT_ERR_INVALID_ARGUMENT, "%s: shard_count must be 1 (is %d)", what, p->shard_count);
     if (!std::isfinite(p->t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, p->t_min);
     if (lit)
         if (int rc = check_light(what, light, host_table)) return rc;
-    if (int rc = check_context(ctx, what, true)) return rc;
+    if (int rc = check_context(ctx, what, true, true)) return rc;
     return lit ? check_light_count(ctx, what, light) : RT_OK;
 }
 
@@ -537,17 +514,12 @@ int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *
 {
     if (int rc = check_render(ctx, "rt_render_wavefront", cam, p, fix)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t fb = (size_t)p->width * p->height * 3 * sizeof(uint64_t);
     Stage st(ctx);
-    const size_t b_fix = st.add(fb), b_rays = st.add(sizeof(uint64_t));
+    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
+    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);     // (counted whether or not the caller asks)
     if (int rc = st.commit()) return rc;
-    return timed_section(ctx, "rt_render_wavefront", kernel_ms,
-        [&] { return rt_render_wavefront_device(ctx, cam, p, st.at(b_fix), st.at(b_rays), ctx->own_stream); },
-        [&] {
-            hipError_t he = st.down(fix, b_fix, fb);
-            if (he == hipSuccess && rays_traced) he = st.down(rays_traced, b_rays, sizeof(uint64_t));
-            return he;
-        });
+    return timed_section(ctx, "rt_render_wavefront", kernel_ms, st,
+        [&] { return rt_render_wavefront_device(ctx, cam, p, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
 }
 
 int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix, uint64_t *rays_traced,
@@ -555,25 +527,17 @@ int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_para
 {
     if (int rc = check_render(ctx, "rt_render_wavefront_lit", cam, p, fix, true, light, true)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t fb = (size_t)p->width * p->height * 3 * sizeof(uint64_t);
-    const size_t eb = light->emission ? (size_t)light->n_emission * 3 * sizeof(double) : 0;
     Stage st(ctx);
-    const size_t b_fix = st.add(fb), b_rays = st.add(sizeof(uint64_t)), b_em = st.add(eb);
+    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
+    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);     // (counted whether or not the caller asks)
+    const auto emission = st.in(light->emission, (size_t)light->n_emission * 3);
     if (int rc = st.commit()) return rc;
+    RT_HIP(st.upload());
     rt_lighting dev = *light;                           // the same lighting with the table on the device
-    if (eb) {
-        RT_HIP(st.up(b_em, light->emission, eb));
-        dev.emission = st.at<double>(b_em);
-    } else {
-        dev.emission = nullptr; dev.n_emission = 0;     // (a table of no entries lights nothing)
-    }
-    return timed_section(ctx, "rt_render_wavefront_lit", kernel_ms,
-        [&] { return render_frame(ctx, cam, p, &dev, st.at(b_fix), st.at(b_rays), ctx->own_stream); },
-        [&] {
-            hipError_t he = st.down(fix, b_fix, fb);
-            if (he == hipSuccess && rays_traced) he = st.down(rays_traced, b_rays, sizeof(uint64_t));
-            return he;
-        });
+    dev.emission = st.ptr(emission);
+    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
+    return timed_section(ctx, "rt_render_wavefront_lit", kernel_ms, st,
+        [&] { return render_frame(ctx, cam, p, &dev, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
 }
 
 } // extern "C"

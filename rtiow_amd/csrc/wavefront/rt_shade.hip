@@ -9,7 +9,6 @@
 // index diverges over the wave.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 
 #include "rt_host.hpp"
@@ -117,30 +116,10 @@ __global__ __launch_bounds__(kShadeBlock) void accumulate_kernel(const Accumulat
 
 namespace {
 
-// RTIOW_SHADE_GRID_BLOCKS=k (diagnostic, read per call): at most k workgroups, so that the kernels' grid-stride trip runs at a test's size
-unsigned shade_grid(long long n)
-{
-    unsigned grid = grid_256(n);
-    const char *e = getenv("RTIOW_SHADE_GRID_BLOCKS");
-    const long long cap = e && *e ? atoll(e) : 0;
-    if (cap > 0 && (long long)grid > cap) grid = (unsigned)cap;
-    return grid;
-}
+// RTIOW_SHADE_GRID_BLOCKS: the diagnostic cap on the kernels' grids
+unsigned shade_grid(long long n) { return (unsigned)capped_grid("RTIOW_SHADE_GRID_BLOCKS", grid_256(n)); }
 
-int check_n(const char *what, int64_t n)
-{
-    if (n < 0 || n > (int64_t)1 << 31) return fail(RT_ERR_INVALID_ARGUMENT, "%s: n must be in [0, 2^31] (is %lld)", what, (long long)n);
-    return RT_OK;
-}
-int check_flags(const char *what, uint32_t flags)
-{
-    if (flags & RT_FLAG_UNIFORM53)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s: RT_FLAG_UNIFORM53 is not built for the wavefront steps (flags 0x%x; only 0 is legal)", what, flags);
-    if (flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x (only 0 is legal)", what, flags);
-    return RT_OK;
-}
-#define RT_NEED(ptr, what, name) \
-    do { if (!(ptr)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: %s is NULL", what, name); } while (0)
+const char *const kNoun = "the wavefront steps";
 
 // What each step accepts, checked before anything is touched: the checks that need no context first, then the context's own, then the
 // device.  *go: there are paths to run (an empty batch is RT_OK with nothing done).
@@ -150,14 +129,14 @@ int begin_camera_rays(const rt_context *ctx, const rt_camera *cam, int32_t width
     *go = false;
     RT_NEED(cam, what, "cam");
     RT_NEED(b, what, "batch");
-    if (int rc = check_n(what, b->n)) return rc;
+    if (int rc = check_count(what, b->n)) return rc;
     if (b->n > 0) {
         RT_NEED(b->pixel, what, "batch->pixel"); RT_NEED(b->sample, what, "batch->sample");
         RT_NEED(b->origin, what, "batch->origin"); RT_NEED(b->dir, what, "batch->dir"); RT_NEED(b->event, what, "batch->event");
     }
-    if (width < 2 || height < 2) return fail(RT_ERR_INVALID_ARGUMENT, "%s: width and height must be >= 2 (are %d, %d)", what, width, height);
-    if (int rc = check_flags(what, flags)) return rc;
-    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (int rc = check_frame_dims(what, width, height)) return rc;
+    if (int rc = check_no_flags(what, flags, kNoun)) return rc;
+    if (int rc = check_context(ctx, what, false, false)) return rc;
     if (b->n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     *go = true;
@@ -169,7 +148,7 @@ int begin_scatter(const rt_context *ctx, uint32_t flags, const rt_scatter_batch 
     const char *what = "rt_scatter";
     *go = false;
     RT_NEED(b, what, "batch");
-    if (int rc = check_n(what, b->n)) return rc;
+    if (int rc = check_count(what, b->n)) return rc;
     if (b->n > 0) {
         RT_NEED(b->dir, what, "batch->dir"); RT_NEED(b->index, what, "batch->index"); RT_NEED(b->point, what, "batch->point");
         RT_NEED(b->normal, what, "batch->normal"); RT_NEED(b->front_face, what, "batch->front_face");
@@ -177,9 +156,8 @@ int begin_scatter(const rt_context *ctx, uint32_t flags, const rt_scatter_batch 
         RT_NEED(b->out_origin, what, "batch->out_origin"); RT_NEED(b->out_dir, what, "batch->out_dir");
         RT_NEED(b->attenuation, what, "batch->attenuation"); RT_NEED(b->status, what, "batch->status");
     }
-    if (int rc = check_flags(what, flags)) return rc;
-    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
-    if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
+    if (int rc = check_no_flags(what, flags, kNoun)) return rc;
+    if (int rc = check_context(ctx, what, false, true)) return rc;
     if (b->n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     *go = true;
@@ -192,10 +170,10 @@ int begin_accumulate(const rt_context *ctx, const rt_accumulate_batch *b, const 
     *go = false;
     RT_NEED(b, what, "batch");
     RT_NEED(fix, what, "fix");
-    if (int rc = check_n(what, b->n)) return rc;
+    if (int rc = check_count(what, b->n)) return rc;
     if (b->n > 0) { RT_NEED(b->pixel, what, "batch->pixel"); RT_NEED(b->weight, what, "batch->weight"); }
-    if (npix <= 0 || npix > (int64_t)1 << 32) return fail(RT_ERR_INVALID_ARGUMENT, "%s: npix must be in [1, 2^32] (is %lld)", what, (long long)npix);
-    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    if (int rc = check_npix(what, npix)) return rc;
+    if (int rc = check_context(ctx, what, false, false)) return rc;
     if (b->n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
     *go = true;
@@ -212,15 +190,12 @@ int rt_camera_rays_device(rt_context *ctx, const rt_camera *cam, int32_t width, 
     bool go;
     int rc = begin_camera_rays(ctx, cam, width, height, flags, b, &go);
     if (rc || !go) return rc;
-    rt::KCamera kc;
-    static_assert(sizeof(rt::KCamera) == sizeof(rt_camera), "camera layouts must match");
-    memcpy(&kc, cam, sizeof(rt_camera));
     rt::CameraRayArgs a;
     memset(&a, 0, sizeof(a));
     a.pixel = b->pixel; a.sample = b->sample; a.origin = b->origin; a.dir = b->dir; a.event = b->event; a.n = (long long)b->n;
     a.width = width; a.height = height;
     a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
-    hipLaunchKernelGGL(rt::camera_rays_kernel, dim3(shade_grid(a.n)), dim3(rt::kShadeBlock), 0, (hipStream_t)stream_v, kc, a);
+    hipLaunchKernelGGL(rt::camera_rays_kernel, dim3(shade_grid(a.n)), dim3(rt::kShadeBlock), 0, (hipStream_t)stream_v, to_kcamera(cam), a);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
@@ -231,23 +206,16 @@ int rt_camera_rays(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t
     bool go;
     int rc = begin_camera_rays(ctx, cam, width, height, flags, b, &go);
     if (rc || !go) return rc;
-    const size_t n = (size_t)b->n, w32 = n * sizeof(uint32_t), v3 = n * 3 * sizeof(double);
+    const size_t n = (size_t)b->n;
     Stage st(ctx);
-    const size_t b_pixel = st.add(w32), b_sample = st.add(w32), b_origin = st.add(v3), b_dir = st.add(v3), b_event = st.add(w32);
+    const auto pixel = st.in(b->pixel, n), sample = st.in(b->sample, n);
+    const auto origin = st.out(b->origin, 3 * n), dir = st.out(b->dir, 3 * n);
+    const auto event = st.out(b->event, n);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_pixel, b->pixel, w32));
-    RT_HIP(st.up(b_sample, b->sample, w32));
-    rt_camera_batch d;
-    d.pixel = st.at<uint32_t>(b_pixel); d.sample = st.at<uint32_t>(b_sample);
-    d.origin = st.at<double>(b_origin); d.dir = st.at<double>(b_dir); d.event = st.at<uint32_t>(b_event); d.n = b->n;
-    return timed_section(ctx, "rt_camera_rays", kernel_ms,
-        [&] { return rt_camera_rays_device(ctx, cam, width, height, seed, flags, &d, ctx->own_stream); },
-        [&] {
-            hipError_t he = st.down(b->origin, b_origin, v3);
-            if (he == hipSuccess) he = st.down(b->dir, b_dir, v3);
-            if (he == hipSuccess) he = st.down(b->event, b_event, w32);
-            return he;
-        });
+    RT_HIP(st.upload());
+    const rt_camera_batch d = {st.ptr(pixel), st.ptr(sample), st.ptr(origin), st.ptr(dir), st.ptr(event), b->n};
+    return timed_section(ctx, "rt_camera_rays", kernel_ms, st,
+        [&] { return rt_camera_rays_device(ctx, cam, width, height, seed, flags, &d, ctx->own_stream); });
 }
 
 int rt_scatter_device(rt_context *ctx, uint64_t seed, uint32_t flags, const rt_scatter_batch *b, void *stream_v)
@@ -272,40 +240,30 @@ int rt_scatter(rt_context *ctx, uint64_t seed, uint32_t flags, const rt_scatter_
     bool go;
     int rc = begin_scatter(ctx, flags, b, &go);
     if (rc || !go) return rc;
-    const size_t n = (size_t)b->n, w32 = n * sizeof(uint32_t), v3 = n * 3 * sizeof(double);
+    const size_t n = (size_t)b->n;
+    // out_dir == dir: ONE block serves both fields -- the directions go up, the step writes the scattered ones over their own, and the
+    // block comes down into out_dir
     const bool in_place = b->out_dir == b->dir;
     Stage st(ctx);
-    const size_t b_dir = st.add(v3), b_index = st.add(n * sizeof(int32_t)), b_point = st.add(v3), b_normal = st.add(v3), b_front = st.add(n);
-    const size_t b_pixel = st.add(w32), b_sample = st.add(w32), b_event = st.add(w32);
-    const size_t b_oorg = st.add(v3), b_odir = in_place ? b_dir : st.add(v3), b_att = st.add(v3), b_status = st.add(n);
+    Staged<const double> dir;
+    Staged<double> out_dir;
+    if (in_place) out_dir = st.inout(b->out_dir, 3 * n);
+    else dir = st.in(b->dir, 3 * n);
+    const auto index = st.in(b->index, n);
+    const auto point = st.in(b->point, 3 * n), normal = st.in(b->normal, 3 * n);
+    const auto front = st.in(b->front_face, n);
+    const auto pixel = st.in(b->pixel, n), sample = st.in(b->sample, n);
+    const auto event = st.inout(b->event, n);
+    // what the step leaves unwritten keeps the caller's bytes: the outputs go up as they are (inout), all but the status
+    const auto out_origin = st.inout(b->out_origin, 3 * n);
+    if (!in_place) out_dir = st.inout(b->out_dir, 3 * n);
+    const auto attenuation = st.inout(b->attenuation, 3 * n);
+    const auto status = st.out(b->status, n);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_dir, b->dir, v3));
-    RT_HIP(st.up(b_index, b->index, n * sizeof(int32_t)));
-    RT_HIP(st.up(b_point, b->point, v3));
-    RT_HIP(st.up(b_normal, b->normal, v3));
-    RT_HIP(st.up(b_front, b->front_face, n));
-    RT_HIP(st.up(b_pixel, b->pixel, w32));
-    RT_HIP(st.up(b_sample, b->sample, w32));
-    RT_HIP(st.up(b_event, b->event, w32));
-    // what the step leaves unwritten keeps the caller's bytes: the outputs go up as they are
-    RT_HIP(st.up(b_oorg, b->out_origin, v3));
-    if (!in_place) RT_HIP(st.up(b_odir, b->out_dir, v3));
-    RT_HIP(st.up(b_att, b->attenuation, v3));
-    rt_scatter_batch d;
-    d.dir = st.at<double>(b_dir); d.index = st.at<int32_t>(b_index); d.point = st.at<double>(b_point); d.normal = st.at<double>(b_normal);
-    d.front_face = st.at<uint8_t>(b_front); d.pixel = st.at<uint32_t>(b_pixel); d.sample = st.at<uint32_t>(b_sample);
-    d.event = st.at<uint32_t>(b_event); d.out_origin = st.at<double>(b_oorg); d.out_dir = st.at<double>(b_odir);
-    d.attenuation = st.at<double>(b_att); d.status = st.at<uint8_t>(b_status); d.n = b->n;
-    return timed_section(ctx, "rt_scatter", kernel_ms,
-        [&] { return rt_scatter_device(ctx, seed, flags, &d, ctx->own_stream); },
-        [&] {
-            hipError_t he = st.down(b->event, b_event, w32);
-            if (he == hipSuccess) he = st.down(b->out_origin, b_oorg, v3);
-            if (he == hipSuccess) he = st.down(b->out_dir, b_odir, v3);
-            if (he == hipSuccess) he = st.down(b->attenuation, b_att, v3);
-            if (he == hipSuccess) he = st.down(b->status, b_status, n);
-            return he;
-        });
+    RT_HIP(st.upload());
+    const rt_scatter_batch d = {in_place ? st.ptr(out_dir) : st.ptr(dir), st.ptr(index), st.ptr(point), st.ptr(normal), st.ptr(front), st.ptr(pixel), st.ptr(sample),
+                                st.ptr(event), st.ptr(out_origin), st.ptr(out_dir), st.ptr(attenuation), st.ptr(status), b->n};
+    return timed_section(ctx, "rt_scatter", kernel_ms, st, [&] { return rt_scatter_device(ctx, seed, flags, &d, ctx->own_stream); });
 }
 
 int rt_accumulate_device(rt_context *ctx, const rt_accumulate_batch *b, void *d_fix, int64_t npix, void *stream_v)
@@ -327,22 +285,17 @@ int rt_accumulate(rt_context *ctx, const rt_accumulate_batch *b, uint64_t *fix, 
     bool go;
     int rc = begin_accumulate(ctx, b, fix, npix, &go);
     if (rc || !go) return rc;
-    const size_t n = (size_t)b->n, w32 = n * sizeof(uint32_t), v3 = n * 3 * sizeof(double), fb = (size_t)npix * 3 * sizeof(uint64_t);
+    const size_t n = (size_t)b->n;
     Stage st(ctx);
-    const size_t b_pixel = st.add(w32), b_weight = st.add(v3), b_sky = st.add(b->sky_dir ? v3 : 0), b_select = st.add(b->select ? n : 0);
-    const size_t b_fix = st.add(fb);
+    const auto pixel = st.in(b->pixel, n);
+    const auto weight = st.in(b->weight, 3 * n), sky_dir = st.in(b->sky_dir, 3 * n);
+    const auto select = st.in(b->select, n);
+    const auto sums = st.inout(fix, (size_t)npix * 3);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_pixel, b->pixel, w32));
-    RT_HIP(st.up(b_weight, b->weight, v3));
-    if (b->sky_dir) RT_HIP(st.up(b_sky, b->sky_dir, v3));
-    if (b->select) RT_HIP(st.up(b_select, b->select, n));
-    RT_HIP(st.up(b_fix, fix, fb));
-    rt_accumulate_batch d;
-    d.pixel = st.at<uint32_t>(b_pixel); d.weight = st.at<double>(b_weight);
-    d.sky_dir = b->sky_dir ? st.at<double>(b_sky) : nullptr; d.select = b->select ? st.at<uint8_t>(b_select) : nullptr; d.n = b->n;
-    return timed_section(ctx, "rt_accumulate", kernel_ms,
-        [&] { return rt_accumulate_device(ctx, &d, st.at(b_fix), npix, ctx->own_stream); },
-        [&] { return st.down(fix, b_fix, fb); });
+    RT_HIP(st.upload());
+    const rt_accumulate_batch d = {st.ptr(pixel), st.ptr(weight), st.ptr(sky_dir), st.ptr(select), b->n};
+    return timed_section(ctx, "rt_accumulate", kernel_ms, st,
+        [&] { return rt_accumulate_device(ctx, &d, st.ptr(sums), npix, ctx->own_stream); });
 }
 
 } // extern "C"

@@ -8,17 +8,15 @@ int rt_filter_products_device(rt_context *ctx, const float *r1, const float *r2,
     if (!ctx || !r1 || !r2 || !s || !out_hb || !out_q) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     RT_HIP(hipSetDevice(ctx->device));
     Stage st(ctx);
-    const size_t b_r1 = st.add(256 * 4), b_r2 = st.add(256 * 4), b_s = st.add(64 * 4), b_hb = st.add(1024 * 4), b_q = st.add(1024 * 4);
+    const auto d_r1 = st.in(r1, 256), d_r2 = st.in(r2, 256), d_s = st.in(s, 64);
+    const auto d_hb = st.out(out_hb, 1024), d_q = st.out(out_q, 1024);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_r1, r1, 256 * 4));
-    RT_HIP(st.up(b_r2, r2, 256 * 4));
-    RT_HIP(st.up(b_s, s, 64 * 4));
+    RT_HIP(st.upload());
     hipLaunchKernelGGL(rt::filter_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
-                       st.at<const float>(b_r1), st.at<const float>(b_r2), st.at<const float>(b_s), (int)bf16x3, st.at<float>(b_hb), st.at<float>(b_q));
+                       st.ptr(d_r1), st.ptr(d_r2), st.ptr(d_s), (int)bf16x3, st.ptr(d_hb), st.ptr(d_q));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out_hb, b_hb, 1024 * 4));
-    RT_HIP(st.down(out_q, b_q, 1024 * 4));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     return RT_OK;
 }
@@ -33,19 +31,17 @@ int rt_filter_lifted_device(rt_context *ctx, const double *o, const double *d, c
     memcpy(out_C, C, sizeof(C));
     uint4 tile[128];
     lifted_tile(C, tile);
-    const size_t R_b = 64 * rt::kLiftTerms * 4;
     Stage st(ctx);
-    const size_t b_o = st.add(1536), b_d = st.add(1536), b_tile = st.add(sizeof(tile)), b_D = st.add(1024 * 4), b_R = st.add(R_b);
+    const auto d_o = st.in(o, 64 * 3), d_d = st.in(d, 64 * 3);
+    const auto d_tile = st.in(tile, 128);
+    const auto d_D = st.out(out_D, 1024), d_R = st.out(out_R, 64 * (size_t)rt::kLiftTerms);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_o, o, 1536));
-    RT_HIP(st.up(b_d, d, 1536));
-    RT_HIP(st.up(b_tile, tile, sizeof(tile)));
+    RT_HIP(st.upload());
     hipLaunchKernelGGL(rt::lifted_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
-                       st.at<const double>(b_o), st.at<const double>(b_d), st.at<const uint4>(b_tile), st.at<float>(b_D), st.at<float>(b_R));
+                       st.ptr(d_o), st.ptr(d_d), st.ptr(d_tile), st.ptr(d_D), st.ptr(d_R));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out_D, b_D, 1024 * 4));
-    RT_HIP(st.down(out_R, b_R, R_b));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     return RT_OK;
 }
@@ -58,24 +54,20 @@ int rt_grid_cells_device(rt_context *ctx, const double *o, const double *d, int3
     if (grid_dim < 1 || grid_dim > rt_scene::kMaxGridDim) return fail(RT_ERR_INVALID_ARGUMENT, "grid_dim must be 1..%d", rt_scene::kMaxGridDim);
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t ob = (size_t)n * 3 * sizeof(double), rb = (size_t)n * 5 * sizeof(int32_t), wb = out_runs ? (size_t)n * 126 * sizeof(int32_t) : 0;
+    int32_t bad = 0;
     Stage st(ctx);
-    const size_t b_o = st.add(ob), b_d = st.add(ob), b_rect = st.add(rb), b_runs = st.add(wb), b_bad = st.add(sizeof(int32_t));
+    const auto d_o = st.in(o, (size_t)n * 3), d_d = st.in(d, (size_t)n * 3);
+    const auto d_rect = st.out(out_rect, (size_t)n * 5), d_runs = st.out(out_runs, (size_t)n * 126);
+    const auto d_bad = st.inout(&bad, 1);               // (goes up as 0)
     int rc = st.commit();
     if (rc) return rc;
     rt::GridArgs ga;
     for (int k = 0; k < 8; ++k) ga.g[k] = grid[k];
-    RT_HIP(st.up(b_o, o, ob));
-    RT_HIP(st.up(b_d, d, ob));
-    RT_HIP(hipMemsetAsync(st.at(b_bad), 0, sizeof(int32_t), ctx->own_stream));
+    RT_HIP(st.upload());
     hipLaunchKernelGGL(rt::grid_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream,
-                       st.at<const double>(b_o), st.at<const double>(b_d), (int)n, ga, (int)grid_dim, scale, st.at<int32_t>(b_rect),
-                       out_runs ? st.at<int32_t>(b_runs) : nullptr, st.at<int32_t>(b_bad));
+                       st.ptr(d_o), st.ptr(d_d), (int)n, ga, (int)grid_dim, scale, st.ptr(d_rect), st.ptr(d_runs), st.ptr(d_bad));
     RT_HIP(hipGetLastError());
-    int32_t bad = 0;
-    RT_HIP(st.down(out_rect, b_rect, rb));
-    if (out_runs) RT_HIP(st.down(out_runs, b_runs, wb));
-    RT_HIP(st.down(&bad, b_bad, sizeof(int32_t)));
+    RT_HIP(st.download());
     RT_HIP(st.sync());
     if (bad) return fail(RT_ERR_HIP, "rt_grid_cells_device: grid_cells with and without GridSeg disagree on some ray");
     return RT_OK;
