@@ -282,6 +282,25 @@ const _: () = assert!(offset_of!(rt_lighting, emission) == 48);
 const _: () = assert!(offset_of!(rt_lighting, n_emission) == 56);
 const _: () = assert!(offset_of!(rt_lighting, flags) == 60);
 const _: () = assert!(64 == size_of::<rt_lighting>());
+
+/// Bit 31 of a path's `event` word: its last scatter sampled the lights directly (`rt_paths_step_nee_device`).
+pub const RT_PATH_EVENT_DIRECT: u32 = 0x8000_0000;
+/// The only legal step flag of `rt_paths_step_nee_device`: the step neither samples lights nor sets the bit.
+pub const RT_STEP_NO_DIRECT: u32 = 1;
+
+/// The lights that next-event estimation samples (`rt_paths_step_nee_device`, `rt_render_wavefront_nee_device`): `lights`:
+/// `[n_lights]` sphere indices, a DEVICE pointer; `rt_light_list` makes the list of an emission table on the host.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_direct {
+    pub lights: *const i32,
+    pub n_lights: i32,
+    pub flags: u32,
+}
+
+const _: () = assert!(offset_of!(rt_direct, n_lights) == 8);
+const _: () = assert!(offset_of!(rt_direct, flags) == 12);
+const _: () = assert!(16 == size_of::<rt_direct>());
 const _: () = assert!(offset_of!(rt_path_queue, count) == 8);
 const _: () = assert!(offset_of!(rt_path_queue, scratch) == 64);
 const _: () = assert!(72 == size_of::<rt_path_queue>());
@@ -419,6 +438,18 @@ extern "C" {
                                           d_fix: *mut c_void, d_rays: *mut c_void, stream: *mut c_void) -> i32;
     pub fn rt_render_wavefront_lit(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
                                    fix: *mut u64, rays_traced: *mut u64, kernel_ms: *mut f32) -> i32;
+    /// Direct lighting (next-event estimation) in the lit path queue: at a Lambertian hit one light of `direct` is sampled by area and
+    /// a shadow ray decides whether it adds; the same expectation as the lit forms.  `rt_light_list` is a pure host function.
+    pub fn rt_light_list(emission: *const f64, n_emission: i32, lights_out: *mut i32, n_lights_out: *mut i32) -> i32;
+    pub fn rt_paths_step_nee_device(ctx: *mut rt_context, seed: u64, flags: u32, t_min: f64, input: *const rt_path_queue,
+                                    output: *const rt_path_queue, d_fix: *mut c_void, npix: i64, d_rays: *mut c_void,
+                                    light: *const rt_lighting, direct: *const rt_direct, step_flags: u32, d_shadow_rays: *mut c_void,
+                                    stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_nee_device(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                          direct: *const rt_direct, d_fix: *mut c_void, d_rays: *mut c_void, d_shadow_rays: *mut c_void,
+                                          stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_nee(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                   fix: *mut u64, rays_traced: *mut u64, shadow_rays: *mut u64, kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -9,7 +9,7 @@
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
-//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]...]
+//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -46,6 +46,9 @@
 // where the unit ray direction's y is -1, T where it is +1; the reference's is 1,1,1:0.5,0.7,1 -- and by emissive spheres -- sphere INDEX of
 // the scene's list radiates (r, g, b), a path that reaches it adds throughput * (r, g, b) and ends -- (rt_render_wavefront_lit, DESIGN.md
 // section 20).  --sky 0,0,0:0,0,0 --emit 0:4,3.2,2.4 is a night frame lit by one sphere.
+// --direct, only with --wavefront and at least one --emit: next-event estimation -- at every Lambertian hit a shadow ray towards a point of
+// one emissive sphere, so that small lights are found at sample counts where the random walk alone hits them almost never; the same
+// expectation as without it (rt_render_wavefront_nee).  The number of shadow rays goes to stderr.
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -108,6 +111,7 @@ int main(int argc, char **argv)
     bool pick = false;
     int pick_i = 0, pick_j = 0;
     bool lit = false;                            // --sky / --emit: the lit wavefront frame
+    bool direct = false;                         // --direct: ... with shadow rays towards the lights (next-event estimation)
     rt_lighting light{};
     light.sky_bottom[0] = light.sky_bottom[1] = light.sky_bottom[2] = 1.0;
     light.sky_top[0] = 0.5; light.sky_top[1] = 0.7; light.sky_top[2] = 1.0;
@@ -152,6 +156,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--uniform53")) uniform53 = true;
         else if (!std::strcmp(argv[i], "--two-calls")) two_calls = true;
         else if (!std::strcmp(argv[i], "--wavefront")) wavefront = true;
+        else if (!std::strcmp(argv[i], "--direct")) direct = true;
         else if (arg("--passes")) passes = std::atoi(argv[++i]);
         else if (arg("--adaptive")) { adaptive = true; threshold = std::atof(argv[++i]); }
         else if (arg("--step")) step = std::atoi(argv[++i]);
@@ -386,6 +391,10 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--sky and --emit light the frame of the device path queue only: they need --wavefront\n");
         return 2;
     }
+    if (direct && (!wavefront || emits.empty())) {
+        std::fprintf(stderr, "--direct samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
+        return 2;
+    }
     std::vector<double> emission;                // --emit: one (r, g, b) per sphere of the list
     if (!emits.empty()) {
         emission.assign(flat.size() * 3, 0.0);
@@ -476,7 +485,12 @@ int main(int argc, char **argv)
         } else if (wavefront) {                  // the device path queue: the same sums, then the same resolve
             std::vector<uint64_t> fix(npix * 3);
             uint64_t rays = 0;
-            if (lit) {
+            if (direct) {
+                uint64_t shadow = 0;
+                rc = rt_render_wavefront_nee(ctx, &rc_cam, &p, &light, fix.data(), &rays, &shadow, &st.kernel_ms);
+                if (rc) return die("rt_render_wavefront_nee", rc);
+                std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
+            } else if (lit) {
                 rc = rt_render_wavefront_lit(ctx, &rc_cam, &p, &light, fix.data(), &rays, &st.kernel_ms);
                 if (rc) return die("rt_render_wavefront_lit", rc);
             } else {

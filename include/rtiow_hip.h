@@ -803,6 +803,65 @@ int rt_render_wavefront_lit_device(rt_context *ctx, const rt_camera *cam, const 
 int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix,
                             uint64_t *rays_traced, float *kernel_ms);
 
+/* ---- direct lighting: next-event estimation in the lit path queue -------------------------------------- */
+
+/* Shadow rays towards the lights at Lambertian hits.  The light is sampled BY AREA: a uniform point of the
+ * sphere from the rejection-sampled unit vector, so that pi cancels (Lambertian BRDF albedo / pi, area pdf 1 / (4 pi r^2)) and the
+ * whole estimator is + - * / and one sqrt in binary64, without contraction: bit-exact like everything else here.
+ *
+ * RT_PATH_EVENT_DIRECT, bit 31 of a path's `event` word: the path's last scatter sampled the lights directly.  rt_paths_begin_device never
+ * sets it; the NEE step reads it, masks it off before any Philox use, and writes it.  The unlit and lit steps know nothing of it: handed
+ * a queue with the bit set they take it for part of the event and draw another Philox block. */
+#define RT_PATH_EVENT_DIRECT 0x80000000u
+/* the only legal step flag: the step neither samples lights nor sets the bit */
+#define RT_STEP_NO_DIRECT 1u
+
+typedef struct {
+    const int32_t *lights;   /* [n_lights] sphere indices (list order of the upload); a DEVICE pointer in the _device forms */
+    int32_t n_lights;
+    uint32_t flags;          /* 0                                                                                         */
+} rt_direct;                 /* 16 bytes */
+
+/* Pure host function: the indices s in [0, n_emission) with e.x > 0 || e.y > 0 || e.z > 0 for e = emission[s] (what the lit step takes
+ * for a light), ascending, to lights_out (room for n_emission entries; may be NULL when n_emission is 0), their number to *n_lights_out.
+ * RT_ERR_INVALID_ARGUMENT: n_emission < 0, a NULL output, emission or lights_out NULL with n_emission > 0. */
+int rt_light_list(const double *emission, int32_t n_emission, int32_t *lights_out, int32_t *n_lights_out);
+
+/* One NEE bounce: rt_paths_step_lit_device -- the same order, compaction, *out->count, d_rays and NaN rules -- except at two places.
+ *  - a HIT on a light s: front = dot(dir, p - centre_s) < 0.0 with p = origin + dir * t.  A path that carries RT_PATH_EVENT_DIRECT and meets
+ *    the front face ends and adds nothing (the previous hit's shadow ray counted that face); every other hit on a light adds
+ *    quantize(throughput * e) as in the lit step.  A light's inner face is never sampled directly, so it always adds.
+ *  - a HIT on a Lambertian sphere that is not a light, with n_lights > 0 and without RT_STEP_NO_DIRECT: the scatter runs first and
+ *    unchanged (the same blocks, event, direction and albedo).  Then, with ev_in the path's event on entry (bit 31 masked off):
+ *      b0 = philox(pixel, sample, ev_in, 1);  j = ((uint64)b0.x * n_lights) >> 32;  li = lights[j]
+ *      (li outside [0, n_spheres) or outside the emission table: no contribution)
+ *      unit-sphere tries (b0.y, b0.z, b0.w), then (x, y, z) of philox(pixel, sample, ev_in, 1 + m), m = 1, 2, ... until accepted
+ *      u = unit_vector(u11 of the accepted try);  q = centre_li + u * sqrt(r2_li);  dv = q - p
+ *      ns = dot(n, dv) (n: the record's normal);  nl = 0.0 - dot(u, dv);  dd = dot(dv, dv);  nothing unless ns > 0.0 && nl > 0.0
+ *      w = ((4.0 * r2_li) * (double)n_lights) * ((ns * nl) / (dd * dd));  c = ((throughput * albedo) * e_li) * w
+ *      the shadow ray (p, dv) with t_min and t_max = +inf: the light is visible iff its CLOSEST hit is sphere li (no epsilon);
+ *      if visible and pixel < npix, d_fix[pixel] gains quantize(c).
+ *    The path continues with event | RT_PATH_EVENT_DIRECT.  Every other scatter clears the bit.
+ * With n_lights == 0 or RT_STEP_NO_DIRECT, on a queue without the bit, the step is rt_paths_step_lit_device byte for byte; with lights every
+ * queue array and d_rays equal that step's except bit 31 of `event`, and the sums: NEE changes what is added, never where paths go.
+ * d_shadow_rays (may be NULL): one device u64 that gains the number of shadow rays traced (atomic adds); d_rays counts path rays only.
+ *
+ * The frame forms run rt_render_wavefront_lit*'s loop with this step; step max_depth, the LAST of each batch, runs with
+ * RT_STEP_NO_DIRECT (its shadow ray would stand for the lit frame's step max_depth + 1, which does not exist), so the NEE frame and the
+ * lit frame have the same expectation at every max_depth.  *d_rays equals the lit frame's.  d_shadow_rays / shadow_rays (may be NULL) is
+ * zeroed first.  rt_render_wavefront_nee builds the list itself with rt_light_list from the emission table it is given.
+ *
+ * RT_ERR_INVALID_ARGUMENT, found before anything is touched: first every context-free check of the lit form, in its order; then a NULL
+ * direct; direct->flags != 0; n_lights < 0; lights == NULL with n_lights != 0; step_flags other than 0 or RT_STEP_NO_DIRECT; then the context
+ * checks and the table's length as in the lit form; then n_lights > the uploaded sphere count. */
+int rt_paths_step_nee_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                             void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, const rt_direct *direct, uint32_t step_flags,
+                             void *d_shadow_rays, void *stream);
+int rt_render_wavefront_nee_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_direct *direct,
+                                   void *d_fix, void *d_rays, void *d_shadow_rays, void *stream);
+int rt_render_wavefront_nee(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix,
+                            uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

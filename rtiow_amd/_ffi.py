@@ -84,6 +84,10 @@ class rt_lighting(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class rt_direct(C.Structure):
+    _fields_ = [("lights", C.c_void_p), ("n_lights", C.c_int32), ("flags", C.c_uint32)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -96,6 +100,8 @@ RT_DENOISE_MAX_LEVELS = 8
 RT_DENOISE_ALBEDO_FLOOR = 0.015625
 RT_TEMPORAL_CLAMP = 0x1
 RT_TEMPORAL_MAX_LEN = 65535
+RT_PATH_EVENT_DIRECT = 0x80000000
+RT_STEP_NO_DIRECT = 0x1
 RT_SCATTER_ABSORBED, RT_SCATTER_SCATTERED, RT_SCATTER_MISS, RT_SCATTER_BAD_INDEX = 0, 1, 2, 3
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)
@@ -160,6 +166,13 @@ SYMBOLS = [
     ("rt_render_wavefront_lit_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), _VP, _VP, _VP]),
     ("rt_render_wavefront_lit", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), _VP, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_float)]),
+    ("rt_light_list", C.c_int, [_VP, C.c_int32, _VP, C.POINTER(C.c_int32)]),
+    ("rt_paths_step_nee_device", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(rt_path_queue), C.POINTER(rt_path_queue), _VP,
+                                           C.c_int64, _VP, C.POINTER(rt_lighting), C.POINTER(rt_direct), C.c_uint32, _VP, _VP]),
+    ("rt_render_wavefront_nee_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), C.POINTER(rt_direct), _VP,
+                                                 _VP, _VP, _VP]),
+    ("rt_render_wavefront_nee", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), _VP, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -1,14 +1,17 @@
 // rt_paths.hip -- the device path queue: a fused bounce step on device-resident paths and the frame rendered from it (rtiow_hip.h, "path
 // queue").
 //
-// The eleventh translation unit of librtiow_hip.so.  Five kernels of its own:
+// The eleventh translation unit of librtiow_hip.so.  Six kernels of its own:
 //   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
 //   bounce_kernel         one wave per 64 consecutive slots, grid-stride over the live slots: closest hit (first_hit_wave<false> whole, the
 //                         record in registers), then the sky add of a miss or Scatter::scatter -- both from rt_shade_core.hpp --; the new
 //                         state is written IN PLACE, and per wave the number of survivors and their ballot go to the queue's scratch.
-//   bounce_lit_kernel     the same trip (bounce_trip<LIT>, stated once) with the sky's two colours from its argument and emissive spheres: a hit
+//   bounce_lit_kernel     the same trip (bounce_trip<MODE>, stated once) with the sky's two colours from its argument and emissive spheres: a hit
 //                         on a sphere whose entry of the emission table has a channel > 0 adds throughput * e and ends the path (rtiow_hip.h,
 //                         "lighting").
+//   bounce_nee_kernel     the lit trip with next-event estimation: a Lambertian hit also samples one light by area and traces a shadow ray
+//                         to it -- first_hit_wave<false> a second time in the trip, wave-wide -- (rtiow_hip.h, "direct lighting"; DESIGN.md
+//                         section 21).
 //   queue_scan_kernel     ONE workgroup: the exclusive scan of the waves' counts, in place; *out->count; d_rays.
 //   queue_compact_kernel  one wave per 64 slots: the survivors move to `out` at offset + rank, so their order is kept.
 // The live count is a word of device memory every kernel reads for itself; the host sizes the grids from the capacity and never waits.
@@ -20,6 +23,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "rt_host.hpp"
 #include "rt_first_hit.hpp"
@@ -81,6 +85,17 @@ struct LitArgs {
     int32_t n_emission;
 };
 
+// What an NEE step knows beyond L (rtiow_hip.h, "direct lighting").  lights: [n_lights] device sphere indices;
+// no_direct: RT_STEP_NO_DIRECT; shadow_rays: the device u64 that gains the shadow rays traced, or NULL.
+struct NeeArgs {
+    const int32_t *lights;
+    unsigned long long *shadow_rays;
+    int32_t n_lights;
+    uint32_t no_direct;
+};
+
+constexpr int kUnlit = 0, kLit = 1, kNee = 2;       // bounce_trip's MODE
+
 // the three 64-bit adds of a path that ends with radiance v (contract C5); g_pix: inside the frame
 __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, const D3 &v)
 {
@@ -88,12 +103,16 @@ __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, con
     atomicAdd(px + 0, quantize(v.x)); atomicAdd(px + 1, quantize(v.y)); atomicAdd(px + 2, quantize(v.z));
 }
 
-// One trip of a wave over the 64 slots from 64 wv on: the body of both bounce kernels.  LIT: the sky's two colours come from L, and a hit
-// on a sphere whose entry of L.emission has a channel > 0 adds throughput * e and ends the path before its material is read.
-template <bool LIT>
-__device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays &Q, const unsigned long long npix, const LitArgs &L, uint4 *stage,
-                                            const int lane, const long long wv, const long long n)
+// One trip of a wave over the 64 slots from 64 wv on: the body of the three bounce kernels.  MODE >= kLit: the sky's two colours come from
+// L, and a hit on a sphere whose entry of L.emission has a channel > 0 adds throughput * e and ends the path before its material is read.
+// MODE == kNee: the path's event carries RT_PATH_EVENT_DIRECT in bit 31 (masked off before any Philox use); a path that carries it adds
+// nothing on a light's front face; a Lambertian hit samples one light of N.lights (nee_sample) and, after the new state has been stored,
+// the wave traces the shadow rays together: only the contribution, the pixel and the light's index are live across that scan.
+template <int MODE>
+__device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays &Q, const unsigned long long npix, const LitArgs &L, const NeeArgs &N,
+                                            uint4 *stage, const int lane, const long long wv, const long long n)
 {
+    constexpr bool LIT = MODE >= kLit, NEE = MODE == kNee;
     const long long k = wv * 64 + lane;
     // lanes past the live count stay in the wave: rows that keep nothing, nothing written
     const bool valid = k < n;
@@ -103,11 +122,15 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
         o = ld3(Q.origin + 3 * k); d = ld3(Q.dir + 3 * k); thr = ld3(Q.thr + 3 * k);
         g_pix = Q.pixel[k]; g_s = Q.sample[k]; ev = Q.event[k];
     }
+    bool was_direct = false;
+    if constexpr (NEE) { was_direct = (ev & RT_PATH_EVENT_DIRECT) != 0u; ev &= ~RT_PATH_EVENT_DIRECT; }
     FirstHit fh = {__builtin_inf(), -1};                // mod.rs:56: closest_so_far = t_max = +inf
     ScanCounts cnt = {true};
     first_hit_wave<false>(P, stage, lane, o, d, valid, fh, cnt);
 
-    bool alive = false;
+    bool alive = false, shadow = false;
+    D3 so = mk(0.0, 0.0, 0.0), sd = mk(0.0, 0.0, 0.0), sc = mk(0.0, 0.0, 0.0);
+    int li = -1;
     if (valid) {
         if (fh.hit < 0) {
             // contract C5, as rt_accumulate with sky_dir: the path ends in the sky
@@ -122,19 +145,32 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
                 if (L.emission && fh.hit < L.n_emission) {
                     const D3 e = ld3(L.emission + 3 * (size_t)fh.hit);
                     light = e.x > 0.0 || e.y > 0.0 || e.z > 0.0;    // a NaN or a non-positive channel compares false
+                    bool adds = light && (unsigned long long)g_pix < npix;
+                    // (NEE: the previous hit's shadow ray already counted a light's front face)
+                    if constexpr (NEE) adds = adds && !(was_direct && light_front(P, o, d, fh.hit, fh.closest));
                     // both faces emit; no draw; the path ends; a pixel outside the frame adds nothing
-                    if (light && (unsigned long long)g_pix < npix) add_sample(P, g_pix, thr * e);
+                    if (adds) add_sample(P, g_pix, thr * e);
                 }
             }
             if (!light) {
                 const HitRecord rec = hit_record(P, o, d, fh);      // (in registers: never written to memory)
                 D3 ndir, albedo;
+                [[maybe_unused]] const uint32_t ev_in = ev;
                 alive = !scatter_path(rec.mrec, d, rec.normal, rec.front, g_pix, g_s, ev, P.k0, P.k1, ndir, albedo);
                 if (alive) {
+                    bool direct = false;
+                    if constexpr (NEE) direct = N.n_lights > 0 && !N.no_direct && (int)rec.mrec[5] == RT_KIND_LAMBERTIAN;
+                    if (direct) ev |= RT_PATH_EVENT_DIRECT;
                     store3(Q.origin, k, rec.p);
                     store3(Q.dir, k, ndir);
                     store3(Q.thr, k, thr * albedo);
                     Q.event[k] = ev;
+                    if constexpr (NEE) {
+                        if (direct) {
+                            shadow = nee_sample(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
+                            so = rec.p;
+                        }
+                    }
                 }
             }
         }
@@ -144,10 +180,21 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
         uint32_t *s = Q.scratch + kScratchPerWave * wv;
         s[0] = (uint32_t)__popcll(live); s[1] = (uint32_t)live; s[2] = (uint32_t)(live >> 32);
     }
+    if constexpr (NEE) {
+        // the shadow rays of the wave, traced together: idle lanes are rows that keep nothing; no lane branches around the scan
+        const unsigned long long rays = __ballot(shadow);
+        if (rays == 0ull) return;
+        if (lane == 0 && N.shadow_rays) atomicAdd(N.shadow_rays, (unsigned long long)__popcll(rays));
+        FirstHit sh = {__builtin_inf(), -1};
+        ScanCounts scnt = {true};
+        first_hit_wave<false>(P, stage, lane, so, sd, shadow, sh, scnt);
+        // visible iff the CLOSEST hit is the sampled light itself: no epsilon
+        if (shadow && sh.hit == li && (unsigned long long)g_pix < npix) add_sample(P, g_pix, sc);
+    }
 }
 
-// the waves' grid-stride loop over the live slots, one trip per 64 of them: the same text in both kernels, with the LDS stage a kernel's own
-#define RT_BOUNCE_LOOP(LIT, L) \
+// the waves' grid-stride loop over the live slots, one trip per 64 of them: the same text in the three kernels, with the LDS stage a kernel's own
+#define RT_BOUNCE_LOOP(MODE, L, N) \
     __shared__ uint4 s_stage[kPathWaves][64 * 4]; \
     const int lane = (int)threadIdx.x & 63; \
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); \
@@ -155,19 +202,29 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
     const long long n = (long long)live_count(Q); \
     const long long n_trips = (n + 63) >> 6; \
     const long long n_waves = (long long)gridDim.x * kPathWaves; \
-    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) bounce_trip<LIT>(P, Q, npix, L, stage, lane, wv, n)
+    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) bounce_trip<MODE>(P, Q, npix, L, N, stage, lane, wv, n)
 
 // One bounce of the live paths.  P: the scene's tables, t_min, the key (k0, k1) and the sums (fix); npix: entries of P.fix.
 __global__ __launch_bounds__(kPathBlock) void bounce_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix)
 {
     const LitArgs none = {};
-    RT_BOUNCE_LOOP(false, none);
+    const NeeArgs no_direct = {};
+    RT_BOUNCE_LOOP(kUnlit, none, no_direct);
 }
 
 // ... with a settable sky and emissive spheres (rt_paths_step_lit_device)
 __global__ __launch_bounds__(kPathBlock) void bounce_lit_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L)
 {
-    RT_BOUNCE_LOOP(true, L);
+    const NeeArgs no_direct = {};
+    RT_BOUNCE_LOOP(kLit, L, no_direct);
+}
+
+// ... and with next-event estimation at Lambertian hits (rt_paths_step_nee_device).  amdgpu_waves_per_eu(4): left to itself the compiler
+// takes 129 vector registers, one more than occupancy 4 allows; told to fit it takes 111 and spills none.
+__global__ __launch_bounds__(kPathBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void bounce_nee_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L, const NeeArgs N)
+{
+    RT_BOUNCE_LOOP(kNee, L, N);
 }
 #undef RT_BOUNCE_LOOP
 
@@ -292,6 +349,36 @@ int check_light_count(const rt_context *ctx, const char *what, const rt_lighting
     return RT_OK;
 }
 
+// What an NEE call has beyond a lit one; a NULL NeeCall: the call is none.  direct->lights: a device pointer.
+struct NeeCall {
+    const rt_direct *direct;
+    uint32_t step_flags;
+    void *d_shadow_rays;
+};
+
+// the context-free part of the direct-lighting checks, after the lighting's
+int check_direct(const char *what, const NeeCall *nee)
+{
+    const rt_direct *direct = nee->direct;
+    RT_NEED(direct, what, "direct");
+    if (direct->flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown direct->flags 0x%x (only 0 is legal)", what, direct->flags);
+    if (direct->n_lights < 0) return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct->n_lights must be >= 0 (is %d)", what, direct->n_lights);
+    if (!direct->lights && direct->n_lights != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct->n_lights must be 0 when direct->lights is NULL (is %d)", what, direct->n_lights);
+    if (nee->step_flags & ~RT_STEP_NO_DIRECT)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown step_flags 0x%x (only 0 and RT_STEP_NO_DIRECT are legal)", what, nee->step_flags);
+    return RT_OK;
+}
+
+// ... and the part that needs the uploaded scene: a list names each sphere at most once
+int check_direct_count(const rt_context *ctx, const char *what, const NeeCall *nee)
+{
+    if (nee->direct->n_lights > ctx->n_spheres)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct->n_lights (%d) must be <= the uploaded sphere count (%d)", what, nee->direct->n_lights,
+                    ctx->n_spheres);
+    return RT_OK;
+}
+
 int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint32_t flags, int32_t spp, int32_t sample_begin,
                 int64_t first_item, int64_t n, const rt_path_queue *q)
 {
@@ -312,9 +399,9 @@ int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int3
     return check_context(ctx, what, true, false);
 }
 
-// light: NULL for the unlit step (lit: whether the call is a lit one)
+// light: NULL for the unlit step (lit: whether the call is a lit one); nee: NULL unless it is an NEE one
 int check_step(const rt_context *ctx, const char *what, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out, const void *d_fix,
-               int64_t npix, bool lit, const rt_lighting *light)
+               int64_t npix, bool lit, const rt_lighting *light, const NeeCall *nee = nullptr)
 {
     if (int rc = check_queue(what, "in", in)) return rc;
     if (int rc = check_queue(what, "out", out)) return rc;
@@ -332,8 +419,12 @@ int check_step(const rt_context *ctx, const char *what, uint32_t flags, double t
     if (int rc = check_t_min(what, t_min)) return rc;
     if (lit)
         if (int rc = check_light(what, light, false)) return rc;
+    if (nee)
+        if (int rc = check_direct(what, nee)) return rc;
     if (int rc = check_context(ctx, what, true, true)) return rc;
-    return lit ? check_light_count(ctx, what, light) : RT_OK;
+    if (lit)
+        if (int rc = check_light_count(ctx, what, light)) return rc;
+    return nee ? check_direct_count(ctx, what, nee) : RT_OK;
 }
 
 rt::QueueArrays arrays_of(const rt_path_queue *q)
@@ -358,9 +449,10 @@ int launch_begin(const rt_camera *cam, int32_t width, int32_t height, uint64_t s
     return RT_OK;
 }
 
-// light: NULL launches bounce_kernel, else bounce_lit_kernel with the struct's values (light->emission: a device pointer)
+// light: NULL launches bounce_kernel, else bounce_lit_kernel with the struct's values (light->emission: a device pointer), or with nee
+// bounce_nee_kernel
 int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_path_queue *in, const rt_path_queue *out, void *d_fix, int64_t npix,
-                void *d_rays, const rt_lighting *light, hipStream_t stream)
+                void *d_rays, const rt_lighting *light, const NeeCall *nee, hipStream_t stream)
 {
     rt::KParams kp;
     memset(&kp, 0, sizeof(kp));
@@ -380,7 +472,15 @@ int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_pat
         memcpy(la.sky_bottom, light->sky_bottom, sizeof(la.sky_bottom));
         memcpy(la.sky_top, light->sky_top, sizeof(la.sky_top));
         la.emission = light->emission; la.n_emission = light->emission ? light->n_emission : 0;
-        hipLaunchKernelGGL(rt::bounce_lit_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la);
+        if (nee) {
+            rt::NeeArgs na;
+            memset(&na, 0, sizeof(na));
+            na.lights = nee->direct->lights; na.n_lights = nee->direct->lights ? nee->direct->n_lights : 0;
+            na.shadow_rays = (unsigned long long *)nee->d_shadow_rays; na.no_direct = nee->step_flags & RT_STEP_NO_DIRECT;
+            hipLaunchKernelGGL(rt::bounce_nee_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
+        } else {
+            hipLaunchKernelGGL(rt::bounce_lit_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la);
+        }
     }
     if (parts & 2) hipLaunchKernelGGL(rt::queue_scan_kernel, dim3(1), dim3(rt::kScanBlock), 0, stream, qi, out->count, (unsigned long long *)d_rays);
     if (parts & 4) hipLaunchKernelGGL(rt::queue_compact_kernel, grid, block, 0, stream, qi, qo);
@@ -423,9 +523,9 @@ long long batch_items()
     return v > kMaxCapacity ? (long long)kMaxCapacity : v;
 }
 
-// lit / light / host_table as in check_step and check_light
+// lit / light / host_table / nee as in check_step and check_light
 int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const void *fix, bool lit = false,
-                 const rt_lighting *light = nullptr, bool host_table = false)
+                 const rt_lighting *light = nullptr, bool host_table = false, const NeeCall *nee = nullptr)
 {
     RT_NEED(cam, what, "cam");
     RT_NEED(p, what, "params");
@@ -436,27 +536,38 @@ int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, 
     if (!std::isfinite(p->t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, p->t_min);
     if (lit)
         if (int rc = check_light(what, light, host_table)) return rc;
+    if (nee)
+        if (int rc = check_direct(what, nee)) return rc;
     if (int rc = check_context(ctx, what, true, true)) return rc;
-    return lit ? check_light_count(ctx, what, light) : RT_OK;
+    if (lit)
+        if (int rc = check_light_count(ctx, what, light)) return rc;
+    return nee ? check_direct_count(ctx, what, nee) : RT_OK;
 }
 
 // The frame of both device forms (validated arguments): per batch one begin, then max_depth steps from one queue to the other; nothing
 // here waits for the device.  (A step on an empty queue leaves at once; what the empty steps of a batch cost is in profiles/paths.txt.)
-int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, void *d_fix, void *d_rays, hipStream_t stream)
+// nee: the frame's direct lighting (step_flags 0); the LAST step of a batch runs with RT_STEP_NO_DIRECT
+int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const NeeCall *nee, void *d_fix, void *d_rays,
+                 hipStream_t stream)
 {
     const long long npix = (long long)p->width * p->height, total = npix * p->spp;
     RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(uint64_t), stream));
     if (d_rays) RT_HIP(hipMemsetAsync(d_rays, 0, sizeof(uint64_t), stream));
+    if (nee && nee->d_shadow_rays) RT_HIP(hipMemsetAsync(nee->d_shadow_rays, 0, sizeof(uint64_t), stream));
     if (total == 0) return RT_OK;
     const long long batch = batch_items() < total ? batch_items() : total;
     const OwnedQueues own(batch);
     if (int rc = ensure(&ctx->paths.ptr, &ctx->paths.bytes, own.layout.total)) return rc;
     const rt_path_queue q[2] = {own.queue(ctx->paths.ptr, 0, batch), own.queue(ctx->paths.ptr, 1, batch)};
+    NeeCall last = {};
+    if (nee) { last = *nee; last.step_flags = RT_STEP_NO_DIRECT; }
     for (long long first = 0; first < total; first += batch) {
         const long long n = total - first < batch ? total - first : batch;
         if (int rc = launch_begin(cam, p->width, p->height, p->seed, p->spp, p->sample_begin, first, n, &q[0], stream)) return rc;
-        for (int depth = 0; depth < p->max_depth; ++depth)
-            if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, light, stream)) return rc;
+        for (int depth = 0; depth < p->max_depth; ++depth) {
+            const NeeCall *step_nee = nee && depth + 1 == p->max_depth ? &last : nee;
+            if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, light, step_nee, stream)) return rc;
+        }
     }
     return RT_OK;
 }
@@ -484,7 +595,7 @@ int rt_paths_step_device(rt_context *ctx, uint64_t seed, uint32_t flags, double 
 {
     if (int rc = check_step(ctx, "rt_paths_step", flags, t_min, in, out, d_fix, npix, false, nullptr)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, nullptr, (hipStream_t)stream_v);
+    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, nullptr, nullptr, (hipStream_t)stream_v);
 }
 
 int rt_paths_step_lit_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
@@ -492,14 +603,24 @@ int rt_paths_step_lit_device(rt_context *ctx, uint64_t seed, uint32_t flags, dou
 {
     if (int rc = check_step(ctx, "rt_paths_step_lit", flags, t_min, in, out, d_fix, npix, true, light)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, light, (hipStream_t)stream_v);
+    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, light, nullptr, (hipStream_t)stream_v);
+}
+
+int rt_paths_step_nee_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                             void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, const rt_direct *direct, uint32_t step_flags,
+                             void *d_shadow_rays, void *stream_v)
+{
+    const NeeCall nee = {direct, step_flags, d_shadow_rays};
+    if (int rc = check_step(ctx, "rt_paths_step_nee", flags, t_min, in, out, d_fix, npix, true, light, &nee)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, light, &nee, (hipStream_t)stream_v);
 }
 
 int rt_render_wavefront_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, void *d_fix, void *d_rays, void *stream_v)
 {
     if (int rc = check_render(ctx, "rt_render_wavefront", cam, p, d_fix)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return render_frame(ctx, cam, p, nullptr, d_fix, d_rays, (hipStream_t)stream_v);
+    return render_frame(ctx, cam, p, nullptr, nullptr, d_fix, d_rays, (hipStream_t)stream_v);
 }
 
 int rt_render_wavefront_lit_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, void *d_fix, void *d_rays,
@@ -507,7 +628,16 @@ int rt_render_wavefront_lit_device(rt_context *ctx, const rt_camera *cam, const 
 {
     if (int rc = check_render(ctx, "rt_render_wavefront_lit", cam, p, d_fix, true, light, false)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return render_frame(ctx, cam, p, light, d_fix, d_rays, (hipStream_t)stream_v);
+    return render_frame(ctx, cam, p, light, nullptr, d_fix, d_rays, (hipStream_t)stream_v);
+}
+
+int rt_render_wavefront_nee_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_direct *direct,
+                                   void *d_fix, void *d_rays, void *d_shadow_rays, void *stream_v)
+{
+    const NeeCall nee = {direct, 0u, d_shadow_rays};
+    if (int rc = check_render(ctx, "rt_render_wavefront_nee", cam, p, d_fix, true, light, false, &nee)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return render_frame(ctx, cam, p, light, &nee, d_fix, d_rays, (hipStream_t)stream_v);
 }
 
 int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *fix, uint64_t *rays_traced, float *kernel_ms)
@@ -537,7 +667,52 @@ int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_para
     dev.emission = st.ptr(emission);
     if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
     return timed_section(ctx, "rt_render_wavefront_lit", kernel_ms, st,
-        [&] { return render_frame(ctx, cam, p, &dev, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
+        [&] { return render_frame(ctx, cam, p, &dev, nullptr, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
+}
+
+int rt_light_list(const double *emission, int32_t n_emission, int32_t *lights_out, int32_t *n_lights_out)
+{
+    const char *what = "rt_light_list";
+    if (n_emission < 0) return fail(RT_ERR_INVALID_ARGUMENT, "%s: n_emission must be >= 0 (is %d)", what, n_emission);
+    RT_NEED(n_lights_out, what, "n_lights_out");
+    if (n_emission > 0) {
+        RT_NEED(emission, what, "emission");
+        RT_NEED(lights_out, what, "lights_out");
+    }
+    int32_t n = 0;
+    for (int32_t s = 0; s < n_emission; ++s) {
+        const double *e = emission + 3 * (size_t)s;
+        if (e[0] > 0.0 || e[1] > 0.0 || e[2] > 0.0) lights_out[n++] = s;       // what the lit step takes for a light
+    }
+    *n_lights_out = n;
+    return RT_OK;
+}
+
+int rt_render_wavefront_nee(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix, uint64_t *rays_traced,
+                            uint64_t *shadow_rays, float *kernel_ms)
+{
+    if (int rc = check_render(ctx, "rt_render_wavefront_nee", cam, p, fix, true, light, true)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    // the list is rebuilt from the table the call can see
+    std::vector<int32_t> list((size_t)(light->emission ? light->n_emission : 0));
+    int32_t n_lights = 0;
+    if (int rc = rt_light_list(light->emission, (int32_t)list.size(), list.data(), &n_lights)) return rc;
+    Stage st(ctx);
+    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
+    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);     // (counted whether or not the caller asks)
+    const auto shadow = shadow_rays ? st.out(shadow_rays, 1) : st.scratch<uint64_t>(1);
+    const auto emission = st.in(light->emission, (size_t)light->n_emission * 3);
+    const auto lights = st.in(static_cast<const int32_t *>(list.data()), (size_t)n_lights);
+    if (int rc = st.commit()) return rc;
+    RT_HIP(st.upload());
+    rt_lighting dev = *light;                           // the same lighting with the table on the device
+    dev.emission = st.ptr(emission);
+    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
+    rt_direct direct = {st.ptr(lights), n_lights, 0u};
+    if (!direct.lights) direct.n_lights = 0;
+    const NeeCall nee = {&direct, 0u, st.ptr(shadow)};
+    return timed_section(ctx, "rt_render_wavefront_nee", kernel_ms, st,
+        [&] { return render_frame(ctx, cam, p, &dev, &nee, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
 }
 
 } // extern "C"

@@ -1,5 +1,6 @@
 // rt_shade_core.hpp -- the per-path bodies of the wavefront steps: the camera ray of a (pixel, sample), Scatter::scatter of the three
-// materials on the keyed Philox stream, and the sky sample.  Values in, values out: no global load except the material record, no store.
+// materials on the keyed Philox stream, the sky sample, and the light sample of next-event estimation.  Values in, values out: no global
+// load except the material record (the light sample: one entry each of the light list, the geometry and the emission table), no store.
 // wavefront/rt_shade.hip (one step per kernel: load -> call -> store) and wavefront/rt_paths.hip (the fused bounce step of the device path
 // queue) call the same functions, so the arithmetic is stated once.  They COMPOSE rt_device.hpp (philox4x32_10, u01, u11,
 // unit_sphere_accepts, unit_disk_accepts, reflect, refract, reflectance, min_1, unit_vector) and state none of it again.
@@ -127,6 +128,50 @@ __device__ __forceinline__ D3 sky_blend(const D3 &weight, const D3 &dir, const D
 __device__ __forceinline__ D3 sky_sample(const D3 &weight, const D3 &dir)
 {
     return sky_blend(weight, dir, mk(1.0, 1.0, 1.0), mk(0.5, 0.7, 1.0));
+}
+
+// ---- next-event estimation: one light sampled by area at a Lambertian hit (rtiow_hip.h, "direct lighting") ---------
+// Stated HERE and nowhere else.  Everything is + - * / and one sqrt in binary64, no contraction: the Lambertian BRDF albedo / pi and the
+// area pdf 1 / (4 pi r^2 n_lights) leave no pi.
+
+// Which face of sphere `hit` the ray (o, d) meets at the root t: the sign of dot(d, p - centre); the radius is not multiplied in.
+__device__ __forceinline__ bool light_front(const KParams &P, const D3 &o, const D3 &d, int hit, double t)
+{
+    const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)hit);
+    const D3 p = o + d * t;                                                              // ray.rs:15-17, as hit_record
+    return dot(d, p - mk(g.x, g.y, g.z)) < 0.0;
+}
+
+// The light sample of the path (g_pix, g_s) whose event on entry -- DIRECT bit masked off -- was ev_in, at the hit point p with the
+// record's normal n; weight: throughput * albedo, the path's new throughput.  The draws are the blocks (g_pix, g_s, ev_in, 1 + m), m = 0,
+// 1, ...: word 3 >= 1 is used by nothing else and ev_in is unique per bounce, so the path's own stream is not touched.  Block 0: x chooses
+// the light, (y, z, w) is the first unit-sphere try; every further block holds one try (x, y, z).  Returns whether there is a shadow ray
+// to trace -- (p, dv), not normalised -- and then c, the radiance to add if the closest hit along it is sphere li.
+__device__ __forceinline__ bool nee_sample(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t n_lights,
+                                           const D3 &p, const D3 &n, const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv, D3 &c,
+                                           int &li)
+{
+    U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
+    const uint32_t j = (uint32_t)(((unsigned long long)b.x * (unsigned long long)(uint32_t)n_lights) >> 32);
+    li = lights[j];
+    // a list entry that names no sphere or no table entry: no contribution (no content of the list makes a read leave the tables)
+    if (li < 0 || li >= P.n_spheres || !emission || li >= n_emission) return false;
+    uint32_t tx = b.y, ty = b.z, tz = b.w;
+    for (uint32_t m = 1u; !unit_sphere_accepts(tx, ty, tz); ++m) {                       // vec3.rs:37-45: a plain loop to acceptance
+        b = philox4x32_10(g_pix, g_s, ev_in, 1u + m, P.k0, P.k1);
+        tx = b.x; ty = b.y; tz = b.z;
+    }
+    const D3 u = unit_vector(mk(u11(tx), u11(ty), u11(tz)));
+    const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)li);        // centre, r^2
+    const D3 q = mk(g.x, g.y, g.z) + u * __builtin_sqrt(g.w);                            // a uniform point of the light's surface
+    dv = q - p;
+    const double ns = dot(n, dv);
+    const double nl = 0.0 - dot(u, dv);
+    const double dd = dot(dv, dv);
+    if (!(ns > 0.0 && nl > 0.0)) return false;                                           // below either horizon; a NaN fails this
+    const double w = ((4.0 * g.w) * (double)n_lights) * ((ns * nl) / (dd * dd));
+    c = (weight * ld3(emission + 3 * (size_t)li)) * w;
+    return true;
 }
 
 } // namespace rt

@@ -389,7 +389,7 @@ class Lighting:
         if len(self.sky_bottom) != 3 or len(self.sky_top) != 3:
             raise ValueError("sky_bottom and sky_top are (r, g, b)")
         self.emission = emission
-        self._device_table = None
+        self._device_table = self._device_lights = self._device_list = None
 
     def _is_tensor(self):
         return hasattr(self.emission, "data_ptr")
@@ -427,26 +427,56 @@ class Lighting:
         _torch_check(torch, renderer, [("emission", t, torch.float64, (t.shape[0] if t.dim() else 0, 3))])
         return t
 
+    def light_list(self, n_spheres):
+        """rt_light_list of the emission table: the indices of the spheres that are lights, ascending, as an int32 array -- what direct
+        lighting (direct=True) samples."""
+        table = self.table(n_spheres)
+        rows = 0 if table is None else int(table.shape[0])
+        out, n = np.zeros(max(rows, 1), dtype=np.int32), C.c_int32(0)
+        _ffi.check(_ffi.load().rt_light_list(table.ctypes.data if rows else None, rows, out.ctypes.data, C.byref(n)), "rt_light_list")
+        return out[:n.value].copy()
+
+    def device_lights(self, renderer, direct=True):
+        """The light list as an int32 tensor on the renderer's device (kept alive by this object): light_list() for direct=True, else
+        `direct` itself -- a sequence of sphere indices or an int32 tensor on the device."""
+        import torch
+        dev = torch.device("cuda", renderer.device_id)
+        if direct is True:
+            key = (renderer.n_spheres or 0, renderer.device_id)
+            if self._device_lights is None or self._device_lights[0] != key:
+                self._device_lights = (key, torch.from_numpy(self.light_list(key[0])).to(dev))
+            t = self._device_lights[1]
+        elif hasattr(direct, "data_ptr"):
+            t = direct
+        else:
+            t = self._device_list = torch.tensor([int(x) for x in direct], dtype=torch.int32, device=dev)
+        _torch_check(torch, renderer, [("direct", t, torch.int32, (t.shape[0] if t.dim() else 0,))])
+        return t
+
     def struct(self, emission_ptr=None, n_emission=0):
         """The rt_lighting naming `emission_ptr` (host or device, as the entry point wants it)."""
         return _ffi.rt_lighting((C.c_double * 3)(*self.sky_bottom), (C.c_double * 3)(*self.sky_top), emission_ptr or None, int(n_emission), 0)
 
 
-def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, lighting=None):
+def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, lighting=None, direct=False, no_direct=False, shadow_rays=None):
     """rt_paths_step_device on two PathQueues, on torch.cuda.current_stream(): one bounce of the live paths of `qin`; the survivors go to
     `qout` in order.  fix: an int64 tensor [..., 3] holding the u64 sums' bits, added to; rays: an int64 tensor [1] that gains the live
     count, or None.  lighting: a Lighting (rt_paths_step_lit_device; its emission a float64 tensor [n, 3] on the device, or what
-    Lighting.device_table makes of it), None: the unlit step.  No host wait."""
+    Lighting.device_table makes of it), None: the unlit step.  direct: True (rt_paths_step_nee_device with the lighting's own light
+    list) or a list of sphere indices / an int32 tensor on the device; no_direct: RT_STEP_NO_DIRECT; shadow_rays: an int64 tensor [1] that
+    gains the shadow rays traced, or None.  No host wait."""
     import torch
     _check_queue(renderer, qin, "qin")
     _check_queue(renderer, qout, "qout")
     items = [("fix", fix, torch.int64, tuple(fix.shape))] + ([("rays", rays, torch.int64, (1,))] if rays is not None else [])
+    items += [("shadow_rays", shadow_rays, torch.int64, (1,))] if shadow_rays is not None else []
     _torch_check(torch, renderer, items)
     if fix.dim() < 1 or fix.shape[-1] != 3:
         raise ValueError(f"fix must be [..., 3] (is {tuple(fix.shape)})")
     with torch.cuda.device(qin.device):
         renderer.paths_step_device(seed, qin.struct(), qout.struct(), fix.data_ptr(), fix.numel() // 3, rays.data_ptr() if rays is not None else 0,
-                                   t_min, torch.cuda.current_stream().cuda_stream, lighting=lighting)
+                                   t_min, torch.cuda.current_stream().cuda_stream, lighting=lighting, direct=direct, no_direct=no_direct,
+                                   d_shadow_rays_ptr=shadow_rays.data_ptr() if shadow_rays is not None else 0)
 
 
 class Renderer:
@@ -830,41 +860,76 @@ class Renderer:
         table = lighting.device_table(self)
         return lighting.struct(table.data_ptr() if table is not None else None, table.shape[0] if table is not None else 0), table
 
-    def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0, lighting=None):
-        """rt_paths_step_device, or with a Lighting rt_paths_step_lit_device; qin, qout: _ffi.rt_path_queue structs of device pointers;
-        asynchronous on `stream`."""
+    def _device_direct(self, lighting, direct):
+        """(the rt_direct of a device form, the tensor it names -- to be kept until the call has been made)."""
+        if lighting is None:
+            raise ValueError("direct lighting needs a Lighting")
+        lights = lighting.device_lights(self, direct)
+        n = int(lights.shape[0])
+        return _ffi.rt_direct(lights.data_ptr() if n else None, n, 0), lights
+
+    def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0, lighting=None, direct=False,
+                          no_direct=False, d_shadow_rays_ptr=0):
+        """rt_paths_step_device, or with a Lighting rt_paths_step_lit_device, or with direct (True: the lighting's own light list, else
+        the indices) rt_paths_step_nee_device -- no_direct: RT_STEP_NO_DIRECT; d_shadow_rays_ptr: a device u64 or 0 --; qin, qout:
+        _ffi.rt_path_queue structs of device pointers; asynchronous on `stream`."""
         head = (self._h, int(seed), int(flags), float(t_min), C.byref(qin), C.byref(qout), C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
                 C.c_void_p(d_rays_ptr) if d_rays_ptr else None)
         if lighting is None:
             _ffi.check(self._lib.rt_paths_step_device(*head, C.c_void_p(stream)), "rt_paths_step_device")
             return
+        if direct is not False:
+            d, _keep_list = self._device_direct(lighting, direct)
+            light, _keep = self._device_lighting(lighting)
+            _ffi.check(self._lib.rt_paths_step_nee_device(*head, C.byref(light), C.byref(d), _ffi.RT_STEP_NO_DIRECT if no_direct else 0,
+                                                          C.c_void_p(d_shadow_rays_ptr) if d_shadow_rays_ptr else None, C.c_void_p(stream)),
+                       "rt_paths_step_nee_device")
+            return
+        if no_direct:
+            raise ValueError("no_direct belongs to the direct-lighting step (direct=...)")
         light, _keep = self._device_lighting(lighting)
         _ffi.check(self._lib.rt_paths_step_lit_device(*head, C.byref(light), C.c_void_p(stream)), "rt_paths_step_lit_device")
 
-    def render_wavefront(self, cam, params, lighting=None):
+    def render_wavefront(self, cam, params, lighting=None, direct=False):
         """rt_render_wavefront: the frame through the device path queue -> (the exact sums u64 [H, W, 3], the rays traced): what
         Renderer.render returns as `fix` and as stats["rays_traced"].  lighting: a Lighting (rt_render_wavefront_lit: a settable sky and
-        emissive spheres), None: the unlit frame."""
+        emissive spheres), None: the unlit frame.  direct=True (rt_render_wavefront_nee: shadow rays towards the lighting's lights at
+        Lambertian hits) -> (the sums, the rays traced, stats) with stats["shadow_rays"] the shadow rays traced."""
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         fix = np.zeros((params.height, params.width, 3), dtype=np.uint64)
         rays = C.c_uint64(0)
+        if direct and lighting is None:
+            raise ValueError("direct lighting needs a Lighting")
         if lighting is None:
             _ffi.check(self._lib.rt_render_wavefront(self._h, C.byref(rc), C.byref(params), fix.ctypes.data_as(C.c_void_p), C.byref(rays), None),
                        "rt_render_wavefront")
             return fix, int(rays.value)
         table = lighting.table(self.n_spheres or 0)
         light = lighting.struct(table.ctypes.data if table is not None else None, table.shape[0] if table is not None else 0)
+        if direct:
+            shadow = C.c_uint64(0)
+            _ffi.check(self._lib.rt_render_wavefront_nee(self._h, C.byref(rc), C.byref(params), C.byref(light), fix.ctypes.data_as(C.c_void_p),
+                                                         C.byref(rays), C.byref(shadow), None), "rt_render_wavefront_nee")
+            return fix, int(rays.value), {"rays_traced": int(rays.value), "shadow_rays": int(shadow.value)}
         _ffi.check(self._lib.rt_render_wavefront_lit(self._h, C.byref(rc), C.byref(params), C.byref(light), fix.ctypes.data_as(C.c_void_p),
                                                      C.byref(rays), None), "rt_render_wavefront_lit")
         return fix, int(rays.value)
 
-    def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0, lighting=None):
+    def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0, lighting=None, direct=False, d_shadow_rays_ptr=0):
         """rt_render_wavefront_device on raw device pointers (d_fix [H][W][3] u64, d_rays one u64 or 0); asynchronous on `stream`.
-        lighting: a Lighting (rt_render_wavefront_lit_device; its emission as in paths_step_torch), None: the unlit frame."""
+        lighting: a Lighting (rt_render_wavefront_lit_device; its emission as in paths_step_torch), None: the unlit frame.  direct (as
+        in paths_step_device): rt_render_wavefront_nee_device; d_shadow_rays_ptr: a device u64 that receives the shadow rays traced, or 0."""
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         tail = (C.c_void_p(d_fix_ptr) if d_fix_ptr else None, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream))
         if lighting is None:
             _ffi.check(self._lib.rt_render_wavefront_device(self._h, C.byref(rc), C.byref(params), *tail), "rt_render_wavefront_device")
+            return
+        if direct is not False:
+            d, _keep_list = self._device_direct(lighting, direct)
+            light, _keep = self._device_lighting(lighting)
+            _ffi.check(self._lib.rt_render_wavefront_nee_device(self._h, C.byref(rc), C.byref(params), C.byref(light), C.byref(d), tail[0], tail[1],
+                                                                C.c_void_p(d_shadow_rays_ptr) if d_shadow_rays_ptr else None, tail[2]),
+                       "rt_render_wavefront_nee_device")
             return
         light, _keep = self._device_lighting(lighting)
         _ffi.check(self._lib.rt_render_wavefront_lit_device(self._h, C.byref(rc), C.byref(params), C.byref(light), *tail),
