@@ -212,9 +212,9 @@ int rt_select_pixels_device(rt_context *ctx, const void *d_fix, const void *d_ha
     const uint32_t blocks = (npix + rt::kSelBlock - 1) / rt::kSelBlock;
     // scratch: noisy[npix], active[npix] (bytes, each rounded up to 256), the workgroups' counts [blocks]
     const size_t flags_bytes = ((size_t)npix + 255) / 256 * 256;
-    rc = ensure(&ctx->d_sel, &ctx->sel_bytes, 2 * flags_bytes + (size_t)blocks * sizeof(uint32_t));
+    rc = ensure(ctx->sel, 2 * flags_bytes + (size_t)blocks * sizeof(uint32_t));
     if (rc) return rc;
-    uint8_t *noisy = (uint8_t *)ctx->d_sel, *active = noisy + flags_bytes;
+    uint8_t *noisy = (uint8_t *)ctx->sel.ptr, *active = noisy + flags_bytes;
     uint32_t *block_count = (uint32_t *)(active + flags_bytes);
     const double sc = 1.0 / ((double)n * 4294967296.0);
     hipLaunchKernelGGL(rt::select_noisy_kernel, dim3(blocks), dim3(rt::kSelBlock), 0, stream, (const unsigned long long *)d_fix,
@@ -244,19 +244,24 @@ int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p
     if (!out_fix || !out_count) return fail(RT_ERR_INVALID_ARGUMENT, "out_fix/out_count is NULL");
     if (ctx->n_spheres < 0) return fail(RT_ERR_NO_SCENE, "rt_upload_scene has not been called");
     RT_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->own_stream;
+    hipStream_t stream = ctx->own_stream;
     const size_t npix = (size_t)p->width * p->height;
-    const size_t sums = npix * 3 * sizeof(uint64_t);
-    // the frame's state, all on the device: fix | half | one pass's compact sums | count | list | running counters (5 x u64), list length
-    Stage stage(ctx);
-    const size_t b_fix = stage.add(sums), b_half = stage.add(sums), b_pass = stage.add(sums);
-    const size_t b_count = stage.add(npix * sizeof(uint32_t)), b_list = stage.add(npix * sizeof(uint32_t)), b_total = stage.add(64);
-    if ((rc = stage.commit())) return rc;
-    void *d_fix = stage.at(b_fix), *d_half = stage.at(b_half), *d_pass = stage.at(b_pass);
-    uint32_t *d_count = stage.at<uint32_t>(b_count), *d_list = stage.at<uint32_t>(b_list);
-    unsigned long long *d_total = stage.at<unsigned long long>(b_total);
+    // the frame's state, all on the device: fix | half | one pass's compact sums | count | list | the 64-byte counter block: the running
+    // counters (5 x u64), then the list length (one word)
+    unsigned long long total[8];
+    Stage st(ctx);
+    const auto fix = st.out(out_fix, npix * 3);
+    const auto half = out_half ? st.out(out_half, npix * 3) : st.scratch<uint64_t>(npix * 3);       // (the selection reads it either way)
+    const auto pass = st.scratch<uint64_t>(npix * 3);
+    const auto count = st.out(out_count, npix);
+    const auto list = st.scratch<uint32_t>(npix);
+    const auto counters = st.out(total, 8);
+    if ((rc = st.commit())) return rc;
+    uint64_t *d_fix = st.ptr(fix), *d_half = st.ptr(half), *d_pass = st.ptr(pass);
+    uint32_t *d_count = st.ptr(count), *d_list = st.ptr(list);
+    unsigned long long *d_total = st.ptr(counters);
     uint32_t *d_n = (uint32_t *)(d_total + 5);
-    RT_HIP(hipMemsetAsync(d_total, 0, 64, st));
+    RT_HIP(hipMemsetAsync(d_total, 0, sizeof(total), stream));
 
     const uint32_t step = (uint32_t)a->step;
     float kernel_ms = 0.0f;
@@ -264,7 +269,7 @@ int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p
     rt_stats shape{};                                                    // grid, variant ... of the latest launch
     int round_slots[2] = {0, 0};
     auto after_pass = [&](int k) -> int {                                // the launch's counters -> the running total; remember its events
-        hipLaunchKernelGGL(rt::stats_accumulate_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)ctx->d_stats, d_total);
+        hipLaunchKernelGGL(rt::stats_accumulate_kernel, dim3(1), dim3(64), 0, stream, (const unsigned long long *)ctx->d_stats, d_total);
         RT_HIP(hipGetLastError());
         zero_depth += ctx->zero_depth_samples;
         round_slots[k] = ctx->cur;
@@ -283,44 +288,39 @@ int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p
     q.spp = (int32_t)step;
     // round 1: every pixel, through the dense kernel.  Pass 0 -> fix, a copy of it is `half`, pass 1 is added to fix.
     q.sample_begin = 0; q.flags = p->flags & ~RT_FLAG_ACCUMULATE;
-    rc = rt_render_device(ctx, cam, &q, d_fix, st);
+    rc = rt_render_device(ctx, cam, &q, d_fix, stream);
     if (rc) return rc;
     if ((rc = after_pass(0))) return rc;
-    RT_HIP(hipMemcpyAsync(d_half, d_fix, sums, hipMemcpyDeviceToDevice, st));
+    RT_HIP(hipMemcpyAsync(d_half, d_fix, npix * 3 * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
     q.sample_begin = (int32_t)step; q.flags = p->flags | RT_FLAG_ACCUMULATE;
-    rc = rt_render_device(ctx, cam, &q, d_fix, st);
+    rc = rt_render_device(ctx, cam, &q, d_fix, stream);
     if (rc) return rc;
     if ((rc = after_pass(1))) return rc;
-    hipLaunchKernelGGL(rt::fill_u32_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, d_count, 2u * step, (uint32_t)npix);
+    hipLaunchKernelGGL(rt::fill_u32_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, d_count, 2u * step, (uint32_t)npix);
     RT_HIP(hipGetLastError());
     q.flags = p->flags & ~RT_FLAG_ACCUMULATE;
     for (uint32_t n = 2u * step; ; n += 2u * step) {
         uint32_t n_list = 0;
         if (n < (uint32_t)p->spp) {
-            rc = rt_select_pixels_device(ctx, d_fix, d_half, d_count, p->width, p->height, (int32_t)n, a, d_list, d_n, st);
+            rc = rt_select_pixels_device(ctx, d_fix, d_half, d_count, p->width, p->height, (int32_t)n, a, d_list, d_n, stream);
             if (rc) return rc;
-            RT_HIP(hipMemcpyAsync(&n_list, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));    // the round's ONE word
+            RT_HIP(hipMemcpyAsync(&n_list, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));    // the round's ONE word
         }
-        RT_HIP(hipStreamSynchronize(st));
+        RT_HIP(st.sync());
         if ((rc = round_time())) return rc;
         if (n_list == 0u) break;
         for (int k = 0; k < 2; ++k) {                                    // passes n / step (even: also into half) and n / step + 1
             q.sample_begin = (int32_t)(n + (uint32_t)k * step);
-            rc = rt_render_pixels_device(ctx, cam, &q, d_list, (int64_t)n_list, d_pass, st);
+            rc = rt_render_pixels_device(ctx, cam, &q, d_list, (int64_t)n_list, d_pass, stream);
             if (rc) return rc;
             if ((rc = after_pass(k))) return rc;
-            hipLaunchKernelGGL(rt::add_back_kernel, dim3((n_list + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)d_list, n_list,
+            hipLaunchKernelGGL(rt::add_back_kernel, dim3((n_list + 255u) / 256u), dim3(256), 0, stream, (const uint32_t *)d_list, n_list,
                                (const unsigned long long *)d_pass, (unsigned long long *)d_fix,
                                k == 0 ? (unsigned long long *)d_half : (unsigned long long *)nullptr, d_count, step);
             RT_HIP(hipGetLastError());
         }
     }
-    unsigned long long total[5];
-    RT_HIP(hipMemcpyAsync(out_fix, d_fix, sums, hipMemcpyDeviceToHost, st));
-    if (out_half) RT_HIP(hipMemcpyAsync(out_half, d_half, sums, hipMemcpyDeviceToHost, st));
-    RT_HIP(hipMemcpyAsync(out_count, d_count, npix * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    RT_HIP(hipMemcpyAsync(total, d_total, sizeof(total), hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
+    RT_HIP(st.finish());                                // the sums, half if asked for, the counts and the counter block
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->n_spheres = shape.n_spheres; stats->grid_blocks = shape.grid_blocks; stats->block_threads = shape.block_threads;

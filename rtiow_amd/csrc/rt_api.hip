@@ -82,12 +82,12 @@ int shard_rows(const rt_params *p)
 
 } // namespace
 
-int rt_host::ensure(void **ptr, size_t *have, size_t need)
+int rt_host::ensure(DeviceBlock &block, size_t need)
 {
-    if (*have >= need && *ptr) return RT_OK;
-    if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; *have = 0; }
-    RT_HIP(hipMalloc(ptr, need ? need : 16));
-    *have = need;
+    if (block.bytes >= need && block.ptr) return RT_OK;
+    if (block.ptr) { (void)hipFree(block.ptr); block.ptr = nullptr; block.bytes = 0; }
+    RT_HIP(hipMalloc(&block.ptr, need ? need : 16));
+    block.bytes = need;
     return RT_OK;
 }
 
@@ -453,9 +453,8 @@ int rt_destroy(rt_context *ctx)
         if (ctx->e0_slots[k]) (void)hipEventDestroy(ctx->e0_slots[k]);
         if (ctx->e1_slots[k]) (void)hipEventDestroy(ctx->e1_slots[k]);
     }
-    (void)hipFree(ctx->d_arena); (void)hipFree(ctx->d_sel);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;                                         // (the arena, the selection scratch and the path queues: DeviceBlock members)
     return RT_OK;
 }
 
@@ -644,19 +643,18 @@ int rt_render(rt_context *ctx, const rt_camera *cam, const rt_params *p,
     if (count > 0 && !out_sum && !out_fix) return fail(RT_ERR_INVALID_ARGUMENT, "no output buffer");
     RT_HIP(hipSetDevice(ctx->device));
     Stage st(ctx);
-    const size_t b_fix = st.add(count * sizeof(uint64_t)), b_sum = st.add(count * sizeof(float));
+    const auto sums = out_fix ? st.out(out_fix, count) : st.scratch<uint64_t>(count);      // (rendered whether or not the caller asks)
+    const auto f32 = st.out(out_sum, count);
     if ((rc = st.commit())) return rc;
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_device(ctx, cam, &q, st.at(b_fix), ctx->own_stream);
+    rc = rt_render_device(ctx, cam, &q, st.ptr(sums), ctx->own_stream);
     if (rc) return rc;
     if (out_sum) {
-        rc = rt_fix_to_f32_device(ctx, st.at(b_fix), (int64_t)count, st.at(b_sum), ctx->own_stream);
+        rc = rt_fix_to_f32_device(ctx, st.ptr(sums), (int64_t)count, st.ptr(f32), ctx->own_stream);
         if (rc) return rc;
-        RT_HIP(st.down(out_sum, b_sum, count * sizeof(float)));
     }
-    if (out_fix) RT_HIP(st.down(out_fix, b_fix, count * sizeof(uint64_t)));
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }
@@ -671,14 +669,14 @@ int rt_resolve_rgba8(rt_context *ctx, const uint64_t *fix, int32_t width, int32_
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)width * rows;
     Stage st(ctx);
-    const size_t b_fix = st.add(npix * 3 * sizeof(uint64_t)), b_rgba = st.add(npix * 4);
+    const auto sums = st.in(fix, npix * 3);
+    const auto rgba = st.out(out_rgba, npix * 4);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_fix, fix, npix * 3 * sizeof(uint64_t)));
-    rc = rt_resolve_rgba8_device(ctx, st.at(b_fix), width, rows, spp, flip, st.at(b_rgba), ctx->own_stream);
+    RT_HIP(st.upload());
+    rc = rt_resolve_rgba8_device(ctx, st.ptr(sums), width, rows, spp, flip, st.ptr(rgba), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(st.down(out_rgba, b_rgba, npix * 4));
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 
@@ -697,18 +695,18 @@ int rt_render_rgba8(rt_context *ctx, const rt_camera *cam, const rt_params *p, i
     if (npix > 0 && !out_rgba) return fail(RT_ERR_INVALID_ARGUMENT, "out_rgba is NULL");
     RT_HIP(hipSetDevice(ctx->device));
     Stage st(ctx);
-    const size_t b_fix = st.add(npix * 3 * sizeof(uint64_t)), b_rgba = st.add(npix * 4);
+    const auto sums = st.scratch<uint64_t>(npix * 3);
+    const auto rgba = st.out(out_rgba, npix * 4);
     if ((rc = st.commit())) return rc;
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_device(ctx, cam, &q, st.at(b_fix), ctx->own_stream);
+    rc = rt_render_device(ctx, cam, &q, st.ptr(sums), ctx->own_stream);
     if (rc) return rc;
     if (npix > 0) {
-        rc = rt_resolve_rgba8_device(ctx, st.at(b_fix), p->width, rows, (int64_t)p->spp, flip, st.at(b_rgba), ctx->own_stream);
+        rc = rt_resolve_rgba8_device(ctx, st.ptr(sums), p->width, rows, (int64_t)p->spp, flip, st.ptr(rgba), ctx->own_stream);
         if (rc) return rc;
-        RT_HIP(st.down(out_rgba, b_rgba, npix * 4));
     }
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }
@@ -759,17 +757,16 @@ int rt_render_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, 
         if ((long long)pixels[k] >= npix_frame)
             return fail(RT_ERR_INVALID_ARGUMENT, "pixels[%lld] = %u is not a pixel of a %d x %d frame", (long long)k, pixels[k], p->width, p->height);
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t count = (size_t)n_pixels * 3;
     Stage st(ctx);
-    const size_t b_fix = st.add(count * sizeof(uint64_t)), b_list = st.add((size_t)n_pixels * sizeof(uint32_t));
+    const auto sums = st.out(out_fix, (size_t)n_pixels * 3);
+    const auto list = st.in(pixels, (size_t)n_pixels);
     if ((rc = st.commit())) return rc;
-    RT_HIP(st.up(b_list, pixels, (size_t)n_pixels * sizeof(uint32_t)));
+    RT_HIP(st.upload());
     rt_params q = *p;
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
-    rc = rt_render_pixels_device(ctx, cam, &q, st.at<const uint32_t>(b_list), n_pixels, st.at(b_fix), ctx->own_stream);
+    rc = rt_render_pixels_device(ctx, cam, &q, st.ptr(list), n_pixels, st.ptr(sums), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(st.down(out_fix, b_fix, count * sizeof(uint64_t)));
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }
@@ -798,15 +795,15 @@ int rt_resolve_rgba8_counts(rt_context *ctx, const uint64_t *fix, const uint32_t
     RT_HIP(hipSetDevice(ctx->device));
     const size_t npix = (size_t)width * rows;
     Stage st(ctx);
-    const size_t b_fix = st.add(npix * 3 * sizeof(uint64_t)), b_rgba = st.add(npix * 4), b_count = st.add(npix * sizeof(uint32_t));
+    const auto sums = st.in(fix, npix * 3);
+    const auto rgba = st.out(out_rgba, npix * 4);
+    const auto counts = st.in(count, npix);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_fix, fix, npix * 3 * sizeof(uint64_t)));
-    RT_HIP(st.up(b_count, count, npix * sizeof(uint32_t)));
-    rc = rt_resolve_rgba8_counts_device(ctx, st.at(b_fix), st.at(b_count), width, rows, flip, st.at(b_rgba), ctx->own_stream);
+    RT_HIP(st.upload());
+    rc = rt_resolve_rgba8_counts_device(ctx, st.ptr(sums), st.ptr(counts), width, rows, flip, st.ptr(rgba), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(st.down(out_rgba, b_rgba, npix * 4));
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 
@@ -827,20 +824,17 @@ int rt_filter_tube_device(rt_context *ctx, const double *o, const double *d, con
     RT_HIP(hipSetDevice(ctx->device));
     rt_scene::Word4 tile[64];
     const float rho = *out_rho = rt_scene::full_tile(spheres32, tile, out_bound);
-    const size_t h_b = 64 * 32 * 2 * 4, rows_b = 64 * 9 * 4;
-    Stage st(ctx);
-    const size_t b_o = st.add(1536), b_d = st.add(1536), b_tile = st.add(sizeof(tile)), b_h = st.add(h_b), b_rows = st.add(rows_b);
+    Stage st(ctx);                                      // 64 rays, one tile of 64 operand words, 32 columns x 2 products and 9 row values per ray
+    const auto ro = st.in(o, 64 * 3), rd = st.in(d, 64 * 3);
+    const auto words = st.in(reinterpret_cast<const uint4 *>(tile), 64);
+    const auto h = st.out(out_h, 64 * 32 * 2), rows = st.out(out_rows, 64 * 9);
     int rc = st.commit();
     if (rc) return rc;
-    RT_HIP(st.up(b_o, o, 1536));
-    RT_HIP(st.up(b_d, d, 1536));
-    RT_HIP(st.up(b_tile, tile, sizeof(tile)));
+    RT_HIP(st.upload());
     hipLaunchKernelGGL(rt::tube_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
-                       st.at<const double>(b_o), st.at<const double>(b_d), st.at<const uint4>(b_tile), rho, st.at<float>(b_h), st.at<float>(b_rows));
+                       st.ptr(ro), st.ptr(rd), st.ptr(words), rho, st.ptr(h), st.ptr(rows));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.down(out_h, b_h, h_b));
-    RT_HIP(st.down(out_rows, b_rows, rows_b));
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 

@@ -259,8 +259,7 @@ int rt_features_to_f32(rt_context *ctx, const uint64_t *feat, int32_t width, int
     RT_HIP(st.upload());
     rc = rt_features_to_f32_device(ctx, st.ptr(words), width, rows, spp, st.ptr(f32), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 

@@ -113,8 +113,7 @@ int rt_render_frames(rt_context *ctx, const rt_camera *cams, int32_t n_frames, i
     q.flags &= ~RT_FLAG_ACCUMULATE;                     // host form always starts from zero
     rc = rt_render_frames_device(ctx, st.ptr(d_cams), n_frames, sample_stride, &q, st.ptr(sums), ctx->own_stream);
     if (rc) return rc;
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }
@@ -154,8 +153,7 @@ int rt_render_frames_rgba8(rt_context *ctx, const rt_camera *cams, int32_t n_fra
             if (rc) return rc;
         }
     }
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     if (stats) return rt_last_stats(ctx, stats);
     return RT_OK;
 }

@@ -1,7 +1,8 @@
 // rt_host.hpp -- what EVERY translation unit of librtiow_hip.so shares: the context, the error path, parameter validation, the scene's
-// fields of the kernel-argument block (set_scene_params) and the plumbing of the host-buffer entry points: StageLayout / StagePlan / Stage
-// (one device arena per context, laid out per call: a buffer is DECLARED once -- host pointer, element count, direction -- and its offset,
-// its copies and its device pointer follow from that), timed_section (a pair of events of the call's own around its kernels) and grid_256.
+// fields of the kernel-argument block (set_scene_params), DeviceBlock (the one owner of a device buffer that grows with its use: ensure)
+// and the plumbing of the host-buffer entry points: StageLayout / StagePlan / Stage (one device arena per context, laid out per call: a
+// buffer is DECLARED once -- host pointer, element count, direction -- and its offset, its copies and its device pointer follow from that;
+// there is no other way into the arena), timed_section (a pair of events of the call's own around its kernels) and grid_256.
 // Also the argument checks the ray and path families share (rt_trace.hip, wavefront/rt_shade.hip, wavefront/rt_paths.hip): RT_NEED,
 // check_no_flags / check_count / check_t_min / check_npix / check_frame_dims / check_context, and capped_grid and to_kcamera.
 // rt_api.hip defines the functions declared here.  The render kernel is not among what is shared: this header takes its argument block
@@ -28,7 +29,7 @@ int fail(int code, const char *fmt, ...);          // records the thread's rt_la
 }
 
 namespace rt_host {
-// a device allocation a context owns and releases with itself
+// a device allocation a context owns, grows with ensure() and releases with itself (rt_destroy selects the device, then deletes the context)
 struct DeviceBlock {
     void *ptr = nullptr; size_t bytes = 0;
     DeviceBlock() = default;
@@ -80,15 +81,15 @@ struct rt_context {
     rt_stats last{};
     // The staging arena of the host-buffer entry points (rt_host::Stage below): whatever the call in progress laid out in it, nothing
     // between calls.  Device-form entry points never touch it.
-    void *d_arena = nullptr; size_t arena_bytes = 0;
+    rt_host::DeviceBlock arena;
     int blocks_per_cu = 0;     // 0 = occupancy query
     // rt_select_pixels_device's scratch (noisy / active flags, the workgroups' counts): a device form's, on the caller's stream, so not
     // in the arena -- rt_render_adaptive calls it while its own frame state lives there
-    void *d_sel = nullptr; size_t sel_bytes = 0;
+    rt_host::DeviceBlock sel;
     int last_dense_body = 0;              // rt_last_dense_body (rtiow_hip_diag.h): 1 when the latest rt_render_device launch ran a capped-redraw kernel of rt_dense.hip, else 0
     int ring_min_spp = 0;                 // RTIOW_RING_MIN_SPP (diagnostic): spp per launch from which block sums are kept in LDS (0: the kernel's own minimum)
     // rt_render_wavefront_device's two path queues (wavefront/rt_paths.hip): a device form's, so not in the arena; allocated on first use,
-    // regrown when a batch is larger, freed by rt_destroy (which selects the device, then deletes the context: the member's destructor)
+    // regrown when a batch is larger
     rt_host::DeviceBlock paths;
 };
 
@@ -97,7 +98,8 @@ namespace rt_host {
 int validate_params(const rt_params *p);
 // what a pixel-list render accepts beyond validate_params (rt_api.hip; the adaptive driver of rt_adaptive.hip asks it too)
 int validate_pixel_list(const rt_context *ctx, const rt_camera *cam, const rt_params *p, int64_t n_pixels);
-int ensure(void **ptr, size_t *have, size_t need);
+// the block holds at least `need` bytes: never shrunk; regrown by free + allocate, so contents are not preserved and the block may MOVE
+int ensure(DeviceBlock &block, size_t need);
 void set_scene_params(const rt_context *ctx, rt::KParams &kp);
 
 // the grid of the element-wise kernels: 256 threads a block, at most 8 192 blocks (their grid-stride loops take the rest)
@@ -151,58 +153,59 @@ struct StagePlan {
 // a declared buffer of elements T: only a name for the block -- its device pointer is Stage::ptr's to give, after commit()
 template <class T> struct Staged { int block = -1; };
 
-// One host-form call's use of the arena.  THE RULE: device-form entry points never touch the arena; a host-form entry point lays its
-// blocks out once (declare or add ... commit), before its first copy, and from then on calls only device forms -- so nothing can move or
-// reuse a block while the call's work is in flight on own_stream.  commit() grows the arena to this call's total with ensure(): never
-// shrunk, contents not preserved; the arena may MOVE when it grows, which is why a declaration returns a Staged and not a pointer.
-// The declared layer: in / out / inout(host, count) and scratch<T>(count) declare a buffer once; upload() copies every in and inout
-// buffer the caller gave, download() every out and inout one, in declaration order; ptr(handle) is the device copy, nullptr for a buffer
-// the caller left out.  The primitive layer below it -- add / at / up / down on byte offsets -- is what rt_api.hip and rt_adaptive.hip
-// use; both share one layout.  The copies and sync are hipMemcpyAsync / hipStreamSynchronize on ctx->own_stream.
+// One host-form call's use of the arena.  THE RULE: device-form entry points never touch the arena; a host-form entry point declares its
+// buffers once, commits, and from then on calls only device forms -- so nothing can move or reuse a block while the call's work is in
+// flight on own_stream.  in / out / inout(host, count) and scratch<T>(count) declare a buffer; commit() grows the arena to the call's
+// total with ensure(), and the arena may MOVE when it grows, which is why a declaration returns a Staged and not a pointer.  After
+// commit(): ptr(handle) is the device copy, nullptr for a buffer the caller left out; upload() copies every in and inout buffer the caller
+// gave, download() every out and inout one, in declaration order (hipMemcpyAsync on ctx->own_stream); sync() waits for the stream;
+// finish() is download() then sync(), the end of a host form that is not timed.  Sizes are element counts, stated where the buffer is
+// declared and nowhere else.
 class Stage {
 public:
     explicit Stage(rt_context *ctx) : ctx_(ctx) {}
-    size_t add(size_t bytes) { return plan_.layout.add(bytes); }
-    int commit()
-    {
-        if (plan_.overflow) return fail(RT_ERR_INVALID_ARGUMENT, "Stage: a call declared more than %d buffers", StagePlan::kCapacity);
-        return ensure(&ctx_->d_arena, &ctx_->arena_bytes, plan_.layout.total);
-    }
-    template <class T = void> T *at(size_t block) const { return reinterpret_cast<T *>(static_cast<char *>(ctx_->d_arena) + block); }
-    hipError_t up(size_t block, const void *src, size_t bytes) const { return hipMemcpyAsync(at(block), src, bytes, hipMemcpyHostToDevice, ctx_->own_stream); }
-    hipError_t down(void *dst, size_t block, size_t bytes) const { return hipMemcpyAsync(dst, at(block), bytes, hipMemcpyDeviceToHost, ctx_->own_stream); }
-    hipError_t sync() const { return hipStreamSynchronize(ctx_->own_stream); }
-
     template <class T> Staged<const T> in(const T *host, size_t count) { return {plan_.declare(StageDir::in, host, count * sizeof(T))}; }
     template <class T> Staged<T> out(T *host, size_t count) { return {plan_.declare(StageDir::out, host, count * sizeof(T))}; }
     template <class T> Staged<T> inout(T *host, size_t count) { return {plan_.declare(StageDir::inout, host, count * sizeof(T))}; }
     template <class T> Staged<T> scratch(size_t count) { return {plan_.declare(StageDir::scratch, nullptr, count * sizeof(T))}; }
-    template <class T> T *ptr(Staged<T> h) const { return plan_.present(h.block) ? at<T>(plan_.blocks[h.block].offset) : nullptr; }
+    int commit()
+    {
+        if (plan_.overflow) return fail(RT_ERR_INVALID_ARGUMENT, "Stage: a call declared more than %d buffers", StagePlan::kCapacity);
+        return ensure(ctx_->arena, plan_.layout.total);
+    }
+    template <class T> T *ptr(Staged<T> h) const { return plan_.present(h.block) ? reinterpret_cast<T *>(at(h.block)) : nullptr; }
     hipError_t upload() const
     {
         hipError_t he = hipSuccess;
         for (int k = 0; k < plan_.n && he == hipSuccess; ++k)
-            if (plan_.goes_up(k)) he = up(plan_.blocks[k].offset, plan_.blocks[k].host, plan_.blocks[k].bytes);
+            if (plan_.goes_up(k)) he = hipMemcpyAsync(at(k), plan_.blocks[k].host, plan_.blocks[k].bytes, hipMemcpyHostToDevice, ctx_->own_stream);
         return he;
     }
     hipError_t download() const
     {
         hipError_t he = hipSuccess;
         for (int k = 0; k < plan_.n && he == hipSuccess; ++k)
-            if (plan_.comes_down(k)) he = down(plan_.blocks[k].host, plan_.blocks[k].offset, plan_.blocks[k].bytes);
+            if (plan_.comes_down(k)) he = hipMemcpyAsync(plan_.blocks[k].host, at(k), plan_.blocks[k].bytes, hipMemcpyDeviceToHost, ctx_->own_stream);
         return he;
     }
+    hipError_t sync() const { return hipStreamSynchronize(ctx_->own_stream); }
+    hipError_t finish() const
+    {
+        const hipError_t he = download();
+        return he == hipSuccess ? sync() : he;
+    }
 private:
+    char *at(int k) const { return static_cast<char *>(ctx_->arena.ptr) + plan_.blocks[k].offset; }       // block k's device copy
     rt_context *ctx_;
     StagePlan plan_;
 };
 
 // Times what body() enqueues on ctx->own_stream with a pair of events of this call's own (the context's belong to its launch slots),
 // created here and destroyed on every path: the first is recorded before body -- after the caller's uploads --, the second after it and
-// before downloads(), so *kernel_ms (may be NULL) covers the kernels only; then the stream is synchronised.  body returns a device
-// form's code, which is passed on as it is with its own message; downloads returns a hipError_t; a HIP failure is "<name>: <error>".
-template <class Body, class Downloads>
-int timed_section(rt_context *ctx, const char *name, float *kernel_ms, Body body, Downloads downloads)
+// before st.finish(), so *kernel_ms (may be NULL) covers the kernels only.  body returns a device form's code, which is passed on as it
+// is with its own message; a HIP failure is "<name>: <error>".
+template <class Body>
+int timed_section(rt_context *ctx, const char *name, float *kernel_ms, const Stage &st, Body body)
 {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     RT_HIP(hipEventCreate(&e0));
@@ -211,8 +214,7 @@ int timed_section(rt_context *ctx, const char *name, float *kernel_ms, Body body
     if (he == hipSuccess) he = hipEventRecord(e0, ctx->own_stream);
     if (he == hipSuccess && !(rc = body())) {
         he = hipEventRecord(e1, ctx->own_stream);
-        if (he == hipSuccess) he = downloads();
-        if (he == hipSuccess) he = hipStreamSynchronize(ctx->own_stream);
+        if (he == hipSuccess) he = st.finish();
         float ms = 0.0f;
         if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
         if (he == hipSuccess && kernel_ms) *kernel_ms = ms;
@@ -222,13 +224,6 @@ int timed_section(rt_context *ctx, const char *name, float *kernel_ms, Body body
     if (rc) return rc;
     if (he != hipSuccess) return fail(RT_ERR_HIP, "%s: %s", name, hipGetErrorString(he));
     return RT_OK;
-}
-
-// ... of a host form on the declared layer: its downloads are st.download()
-template <class Body>
-int timed_section(rt_context *ctx, const char *name, float *kernel_ms, const Stage &st, Body body)
-{
-    return timed_section(ctx, name, kernel_ms, body, [&st] { return st.download(); });
 }
 
 // ---- the argument checks the ray and path families share (rt_trace.hip, wavefront/rt_shade.hip, wavefront/rt_paths.hip).  An entry point

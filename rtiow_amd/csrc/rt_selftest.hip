@@ -71,8 +71,7 @@ int rt_f64_div_sqrt_device(rt_context *ctx, const double *a, const double *b, in
     hipLaunchKernelGGL(rt::f64_div_sqrt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream,
                        st.ptr(d_a), st.ptr(d_b), (int)n, st.ptr(d_q), st.ptr(d_r));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 
@@ -89,8 +88,7 @@ int rt_quantize_device(rt_context *ctx, const double *x, int32_t n, uint64_t *ou
     RT_HIP(st.upload());
     hipLaunchKernelGGL(rt::quantize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.ptr(d_x), (int)n, st.ptr(d_q));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 
@@ -109,8 +107,7 @@ int rt_unit_accept_device(rt_context *ctx, const uint32_t *words, int32_t n, uin
     hipLaunchKernelGGL(rt::unit_accept_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream, st.ptr(d_w), (int)n, st.ptr(d_a),
                        st.ptr(d_u));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 
@@ -128,8 +125,7 @@ int rt_philox_device(rt_context *ctx, const uint32_t ctr[4], const uint32_t key[
     if (rc) return rc;
     hipLaunchKernelGGL(rt::philox_kat_kernel, dim3(1), dim3(1), 0, ctx->own_stream, ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], st.ptr(d_out));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 

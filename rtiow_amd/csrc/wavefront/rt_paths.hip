@@ -557,7 +557,7 @@ int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, cons
     if (total == 0) return RT_OK;
     const long long batch = batch_items() < total ? batch_items() : total;
     const OwnedQueues own(batch);
-    if (int rc = ensure(&ctx->paths.ptr, &ctx->paths.bytes, own.layout.total)) return rc;
+    if (int rc = ensure(ctx->paths, own.layout.total)) return rc;
     const rt_path_queue q[2] = {own.queue(ctx->paths.ptr, 0, batch), own.queue(ctx->paths.ptr, 1, batch)};
     NeeCall last = {};
     if (nee) { last = *nee; last.step_flags = RT_STEP_NO_DIRECT; }
@@ -570,6 +570,39 @@ int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, cons
         }
     }
     return RT_OK;
+}
+
+// The body of the three host frames.  mode: kUnlit (light is not looked at), kLit, or kNee: the frame samples its lights directly, their
+// list rebuilt from the table the call can see.  The counters are counted whether or not the caller asks; a frame without direct lighting
+// has no shadow counter (shadow_rays NULL: absent).
+int render_frame_host(rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const rt_lighting *light, int mode, uint64_t *fix,
+                      uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms)
+{
+    const bool lit = mode >= rt::kLit, direct = mode == rt::kNee;
+    if (int rc = check_render(ctx, what, cam, p, fix, lit, light, true)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    const double *table = lit ? light->emission : nullptr;
+    const size_t n_table = table ? (size_t)light->n_emission : 0;
+    std::vector<int32_t> list(direct ? n_table : 0);
+    int32_t n_lights = 0;
+    if (int rc = rt_light_list(table, (int32_t)list.size(), list.data(), &n_lights)) return rc;
+    Stage st(ctx);
+    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
+    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);
+    const auto shadow = direct && !shadow_rays ? st.scratch<uint64_t>(1) : st.out(shadow_rays, 1);
+    const auto emission = st.in(table, n_table * 3);
+    const auto lights = st.in(static_cast<const int32_t *>(list.data()), (size_t)n_lights);
+    if (int rc = st.commit()) return rc;
+    RT_HIP(st.upload());
+    rt_lighting dev = lit ? *light : rt_lighting{};     // the same lighting with the table on the device
+    dev.emission = st.ptr(emission);
+    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
+    rt_direct on_device = {st.ptr(lights), n_lights, 0u};
+    if (!on_device.lights) on_device.n_lights = 0;
+    const NeeCall nee = {&on_device, 0u, st.ptr(shadow)};
+    return timed_section(ctx, what, kernel_ms, st, [&] {
+        return render_frame(ctx, cam, p, lit ? &dev : nullptr, direct ? &nee : nullptr, st.ptr(sums), st.ptr(rays), ctx->own_stream);
+    });
 }
 
 } // namespace
@@ -640,36 +673,6 @@ int rt_render_wavefront_nee_device(rt_context *ctx, const rt_camera *cam, const 
     return render_frame(ctx, cam, p, light, &nee, d_fix, d_rays, (hipStream_t)stream_v);
 }
 
-int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *fix, uint64_t *rays_traced, float *kernel_ms)
-{
-    if (int rc = check_render(ctx, "rt_render_wavefront", cam, p, fix)) return rc;
-    RT_HIP(hipSetDevice(ctx->device));
-    Stage st(ctx);
-    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
-    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);     // (counted whether or not the caller asks)
-    if (int rc = st.commit()) return rc;
-    return timed_section(ctx, "rt_render_wavefront", kernel_ms, st,
-        [&] { return rt_render_wavefront_device(ctx, cam, p, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
-}
-
-int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix, uint64_t *rays_traced,
-                            float *kernel_ms)
-{
-    if (int rc = check_render(ctx, "rt_render_wavefront_lit", cam, p, fix, true, light, true)) return rc;
-    RT_HIP(hipSetDevice(ctx->device));
-    Stage st(ctx);
-    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
-    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);     // (counted whether or not the caller asks)
-    const auto emission = st.in(light->emission, (size_t)light->n_emission * 3);
-    if (int rc = st.commit()) return rc;
-    RT_HIP(st.upload());
-    rt_lighting dev = *light;                           // the same lighting with the table on the device
-    dev.emission = st.ptr(emission);
-    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
-    return timed_section(ctx, "rt_render_wavefront_lit", kernel_ms, st,
-        [&] { return render_frame(ctx, cam, p, &dev, nullptr, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
-}
-
 int rt_light_list(const double *emission, int32_t n_emission, int32_t *lights_out, int32_t *n_lights_out)
 {
     const char *what = "rt_light_list";
@@ -688,31 +691,21 @@ int rt_light_list(const double *emission, int32_t n_emission, int32_t *lights_ou
     return RT_OK;
 }
 
+int rt_render_wavefront(rt_context *ctx, const rt_camera *cam, const rt_params *p, uint64_t *fix, uint64_t *rays_traced, float *kernel_ms)
+{
+    return render_frame_host(ctx, "rt_render_wavefront", cam, p, nullptr, rt::kUnlit, fix, rays_traced, nullptr, kernel_ms);
+}
+
+int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix, uint64_t *rays_traced,
+                            float *kernel_ms)
+{
+    return render_frame_host(ctx, "rt_render_wavefront_lit", cam, p, light, rt::kLit, fix, rays_traced, nullptr, kernel_ms);
+}
+
 int rt_render_wavefront_nee(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix, uint64_t *rays_traced,
                             uint64_t *shadow_rays, float *kernel_ms)
 {
-    if (int rc = check_render(ctx, "rt_render_wavefront_nee", cam, p, fix, true, light, true)) return rc;
-    RT_HIP(hipSetDevice(ctx->device));
-    // the list is rebuilt from the table the call can see
-    std::vector<int32_t> list((size_t)(light->emission ? light->n_emission : 0));
-    int32_t n_lights = 0;
-    if (int rc = rt_light_list(light->emission, (int32_t)list.size(), list.data(), &n_lights)) return rc;
-    Stage st(ctx);
-    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
-    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);     // (counted whether or not the caller asks)
-    const auto shadow = shadow_rays ? st.out(shadow_rays, 1) : st.scratch<uint64_t>(1);
-    const auto emission = st.in(light->emission, (size_t)light->n_emission * 3);
-    const auto lights = st.in(static_cast<const int32_t *>(list.data()), (size_t)n_lights);
-    if (int rc = st.commit()) return rc;
-    RT_HIP(st.upload());
-    rt_lighting dev = *light;                           // the same lighting with the table on the device
-    dev.emission = st.ptr(emission);
-    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
-    rt_direct direct = {st.ptr(lights), n_lights, 0u};
-    if (!direct.lights) direct.n_lights = 0;
-    const NeeCall nee = {&direct, 0u, st.ptr(shadow)};
-    return timed_section(ctx, "rt_render_wavefront_nee", kernel_ms, st,
-        [&] { return render_frame(ctx, cam, p, &dev, &nee, st.ptr(sums), st.ptr(rays), ctx->own_stream); });
+    return render_frame_host(ctx, "rt_render_wavefront_nee", cam, p, light, rt::kNee, fix, rays_traced, shadow_rays, kernel_ms);
 }
 
 } // extern "C"

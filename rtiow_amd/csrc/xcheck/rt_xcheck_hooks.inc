@@ -16,8 +16,7 @@ int rt_filter_products_device(rt_context *ctx, const float *r1, const float *r2,
     hipLaunchKernelGGL(rt::filter_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
                        st.ptr(d_r1), st.ptr(d_r2), st.ptr(d_s), (int)bf16x3, st.ptr(d_hb), st.ptr(d_q));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 
@@ -41,8 +40,7 @@ int rt_filter_lifted_device(rt_context *ctx, const double *o, const double *d, c
     hipLaunchKernelGGL(rt::lifted_products_kernel, dim3(1), dim3(64), 0, ctx->own_stream,
                        st.ptr(d_o), st.ptr(d_d), st.ptr(d_tile), st.ptr(d_D), st.ptr(d_R));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     return RT_OK;
 }
 
@@ -67,8 +65,7 @@ int rt_grid_cells_device(rt_context *ctx, const double *o, const double *d, int3
     hipLaunchKernelGGL(rt::grid_cells_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->own_stream,
                        st.ptr(d_o), st.ptr(d_d), (int)n, ga, (int)grid_dim, scale, st.ptr(d_rect), st.ptr(d_runs), st.ptr(d_bad));
     RT_HIP(hipGetLastError());
-    RT_HIP(st.download());
-    RT_HIP(st.sync());
+    RT_HIP(st.finish());
     if (bad) return fail(RT_ERR_HIP, "rt_grid_cells_device: grid_cells with and without GridSeg disagree on some ray");
     return RT_OK;
 }

@@ -5,9 +5,11 @@ bit for bit, the same call on a context created for that call alone -- whose are
 optional buffer that is absent right after a call that had it (rt_denoise without counts after one with, rt_temporal without history
 after one with) must not see the stale block: tests/test_stage_layout_host.py checks on the CPU that the denoise input used here gives
 different results with and without its counts.  The ray queries, the wavefront steps and the wavefront frames go through the same
-sequence with and without their optional buffers (t_max and the hit's fields, sky_dir and select, the emission table), rt_scatter also
-with out_dir being dirs itself: one block that goes up and comes down.  The file asserts nothing about the arena itself, only about
-results, messages and times."""
+sequence with and without their optional buffers (t_max and the hit's fields, sky_dir and select, the emission table and the light list
+made from it, the counters a caller may leave out: rays_traced and shadow_rays NULL through raw ctypes), rt_scatter also with out_dir
+being dirs itself: one block that goes up and comes down.  rt_render_adaptive goes through with and without out_half, and
+rt_filter_tube_device, whose buffers have one fixed size, sits among the calls that change the arena's.  The file asserts nothing about
+the arena itself, only about results, messages and times."""
 import ctypes as C
 import time
 
@@ -35,6 +37,29 @@ def render_fix_only(r, cam, p):
     c = cam.to_rt_camera()
     _ffi.check(r._lib.rt_render(r._h, C.byref(c), C.byref(p), None, out.ctypes.data_as(C.c_void_p), None), "rt_render")
     return out
+
+
+def wavefront_counters_null(r, cam, p, lighting=None, direct=False):
+    """A wavefront host frame with rays_traced = NULL (direct: rt_render_wavefront_nee, shadow_rays = NULL too): the counters the kernels
+    add to are scratch of the call, not buffers of the caller's (Renderer.render_wavefront always asks for them)"""
+    fix = np.zeros((p.height, p.width, 3), dtype=np.uint64)
+    c = cam.to_rt_camera()
+    head, out = (r._h, C.byref(c), C.byref(p)), fix.ctypes.data_as(C.c_void_p)
+    if lighting is None:
+        _ffi.check(r._lib.rt_render_wavefront(*head, out, None, None), "rt_render_wavefront")
+        return (fix,)
+    table = lighting.table(r.n_spheres)
+    light = lighting.struct(table.ctypes.data if table is not None else None, table.shape[0] if table is not None else 0)
+    if direct:
+        _ffi.check(r._lib.rt_render_wavefront_nee(*head, C.byref(light), out, None, None, None), "rt_render_wavefront_nee")
+    else:
+        _ffi.check(r._lib.rt_render_wavefront_lit(*head, C.byref(light), out, None, None), "rt_render_wavefront_lit")
+    return (fix,)
+
+
+def wavefront_nee(r, cam, p, lighting):
+    fix, rays, stats = r.render_wavefront(cam, p, lighting=lighting, direct=True)
+    return fix, np.uint64(rays), np.uint64(stats["shadow_rays"])
 
 
 def path_inputs(w, h, n_spheres):
@@ -75,8 +100,9 @@ def accumulate(r, v, **optional):
     return fix, r.accumulate(fix, v["pixel"], v["weight"], **optional)
 
 
-def calls(w, h, n_spheres):
-    """[(name, f(renderer) -> tuple of arrays [, kernel ms last for the names in TIMED])]: the sequence at one frame size."""
+def calls(w, h, flat):
+    """[(name, f(renderer) -> tuple of arrays [, kernel ms last for the names in TIMED])]: the sequence at one frame size; flat: the scene."""
+    n_spheres = len(flat)
     cam, cams = rt.book1_camera(w, h), rt.orbit_cameras(2, w, h)
     p = rt.make_params(w, h, SPP, seed=1)
     (fix, count, spp, feat, feat_spp), (pfix, plen, pfeat, pspp) = staging_inputs(w, h)
@@ -86,6 +112,9 @@ def calls(w, h, n_spheres):
     v = path_inputs(w, h, n_spheres)
     wp = rt.make_params(w, h, SPP, max_depth=WAVEFRONT_DEPTH, seed=1)
     lights = rt.Lighting((0.3, 0.2, 0.1), (0.1, 0.2, 0.9), {0: (0.25, 0.125, 0.0625), 5: (4.0, 3.0, 2.0)})
+    no_table = rt.Lighting(lights.sky_bottom, lights.sky_top)
+    tube = path_inputs(8, 8, n_spheres)                                  # (64 rays: one wave of the known-answer kernel, whatever the frame)
+    ap, ad = rt.make_params(w, h, ADAPTIVE_SPP, seed=1), rt.make_adaptive(ADAPTIVE_STEP, 0.05)
     return [
         ("render_both", lambda r: r.render(cam, p)[:2]),
         ("render_sum", lambda r: r.render(cam, p, want_fix=False)[:1]),
@@ -104,7 +133,9 @@ def calls(w, h, n_spheres):
         ("temporal_no_history", lambda r: r.temporal(fix, spp, feat, feat_spp, cam, None, tp)),
         ("resolve_rgba8", lambda r: (r.resolve_rgba8(fix, spp),)),
         ("resolve_rgba8_counts", lambda r: (r.resolve_rgba8_counts(fix, count),)),
-        ("render_adaptive", lambda r: r.render_adaptive(cam, rt.make_params(w, h, ADAPTIVE_SPP, seed=1), rt.make_adaptive(ADAPTIVE_STEP, 0.05))[:3]),
+        ("render_adaptive", lambda r: r.render_adaptive(cam, ap, ad)[:3]),
+        ("render_adaptive_no_half", lambda r: (lambda fix, _, count, st: (fix, count))(*r.render_adaptive(cam, ap, ad, want_half=False))),
+        ("filter_tube", lambda r: (lambda h, rows, bound, rho: (h, rows, bound, np.float32(rho)))(*r.filter_tube(tube["origins"], tube["dirs"], flat[:32]))),
         ("quantize", lambda r: (r.quantize(x),)),
         ("philox", lambda r: (np.array(r.philox((w, h, 3, 4), (5, 6)), dtype=np.uint64),)),
         ("trace_rays_all_tmax", lambda r: timed(r.trace_rays(v["origins"], v["dirs"], t_max=v["t_max"]), "index", "t", "point", "normal", "front_face")),
@@ -117,8 +148,12 @@ def calls(w, h, n_spheres):
         ("accumulate_plain", lambda r: accumulate(r, v)),
         ("render_wavefront", lambda r: (lambda fix, rays: (fix, np.uint64(rays)))(*r.render_wavefront(cam, wp))),
         ("render_wavefront_lit_table", lambda r: (lambda fix, rays: (fix, np.uint64(rays)))(*r.render_wavefront(cam, wp, lighting=lights))),
-        ("render_wavefront_lit_none", lambda r: (lambda fix, rays: (fix, np.uint64(rays)))(
-            *r.render_wavefront(cam, wp, lighting=rt.Lighting(lights.sky_bottom, lights.sky_top)))),
+        ("render_wavefront_lit_none", lambda r: (lambda fix, rays: (fix, np.uint64(rays)))(*r.render_wavefront(cam, wp, lighting=no_table))),
+        ("render_wavefront_nee_table", lambda r: wavefront_nee(r, cam, wp, lights)),
+        ("render_wavefront_nee_none", lambda r: wavefront_nee(r, cam, wp, no_table)),                     # (no light list, emission NULL)
+        ("render_wavefront_nee_no_counters", lambda r: wavefront_counters_null(r, cam, wp, lights, direct=True)),
+        ("render_wavefront_no_counter", lambda r: wavefront_counters_null(r, cam, wp)),
+        ("render_wavefront_lit_no_counter", lambda r: wavefront_counters_null(r, cam, wp, lights)),
     ]
 
 
@@ -134,7 +169,7 @@ def fresh(book1_flat):
     def get(size):
         if size not in cache:
             cache[size] = {}
-            for name, call in calls(*size, len(book1_flat)):
+            for name, call in calls(*size, book1_flat):
                 with rt.Renderer(0) as r:
                     r.upload_scene(book1_flat)
                     cache[size][name] = arrays(name, call(r))
@@ -151,7 +186,7 @@ def test_one_context_through_every_host_form(book1_flat, fresh):
         r.upload_scene(book1_flat)
         for step, size in enumerate(ORDER):
             want = fresh(size)
-            for name, call in calls(*size, len(book1_flat)):
+            for name, call in calls(*size, book1_flat):
                 if name == "temporal_history_count":                  # a rejected call in mid-sequence: its usual message, and the next call correct
                     (fix, _, spp, feat, feat_spp), _ = staging_inputs(*size)
                     with pytest.raises(_ffi.RtiowHipError, match=r"denoise: levels must be 1\.\.\d+ \(is 0\)"):
@@ -176,6 +211,13 @@ def test_the_sequence_tells_a_present_buffer_from_an_absent_one(fresh):
         assert not np.array_equal(want["accumulate_sky_select"][0], want["accumulate_plain"][0])
         assert not np.array_equal(want["render_wavefront_lit_table"][0], want["render_wavefront_lit_none"][0])
         assert not np.array_equal(want["render_wavefront_lit_none"][0], want["render_wavefront"][0])      # (the sky is not the default's)
+        assert not np.array_equal(want["render_wavefront_nee_table"][0], want["render_wavefront_nee_none"][0])
+        # a counter left out changes nothing in the sums; a frame without lights traces no shadow ray
+        assert np.array_equal(want["render_wavefront_nee_no_counters"][0], want["render_wavefront_nee_table"][0])
+        assert np.array_equal(want["render_wavefront_no_counter"][0], want["render_wavefront"][0])
+        assert np.array_equal(want["render_wavefront_lit_no_counter"][0], want["render_wavefront_lit_table"][0])
+        assert want["render_wavefront_nee_none"][2] == 0
+        assert all(np.array_equal(a, b) for a, b in zip(want["render_adaptive_no_half"], want["render_adaptive"][::2]))
         # rt_scatter in place: a scattered path's new direction is in `dirs`, every other path's old one still is; not in place: dirs untouched
         dirs, _, out_dir, _, status = want["scatter"][:5]
         went_on = status == _ffi.RT_SCATTER_SCATTERED
@@ -183,3 +225,5 @@ def test_the_sequence_tells_a_present_buffer_from_an_absent_one(fresh):
         assert np.array_equal(want["scatter_in_place"][0], np.where(went_on[:, None], out_dir, dirs))
     # ... and rt_render_adaptive went past its first round (selection and pixel-list passes beside its frame state in the arena)
     assert any((fresh(size)["render_adaptive"][2] > 2 * ADAPTIVE_STEP).any() for size in set(SIZES))
+    # ... and the NEE frame traced shadow rays (its light list and its shadow counter were blocks of the call)
+    assert any(fresh(size)["render_wavefront_nee_table"][2] > 0 for size in set(SIZES))
