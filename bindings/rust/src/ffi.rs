@@ -287,6 +287,8 @@ const _: () = assert!(64 == size_of::<rt_lighting>());
 pub const RT_PATH_EVENT_DIRECT: u32 = 0x8000_0000;
 /// The only legal step flag of `rt_paths_step_nee_device`: the step neither samples lights nor sets the bit.
 pub const RT_STEP_NO_DIRECT: u32 = 1;
+/// The only legal bit of `rt_direct.flags`: the light is sampled by solid angle (a uniform direction of the cone it subtends), not by area.
+pub const RT_DIRECT_CONE: u32 = 2;
 
 /// The lights that next-event estimation samples (`rt_paths_step_nee_device`, `rt_render_wavefront_nee_device`): `lights`:
 /// `[n_lights]` sphere indices, a DEVICE pointer; `rt_light_list` makes the list of an emission table on the host.
@@ -450,6 +452,9 @@ extern "C" {
                                           stream: *mut c_void) -> i32;
     pub fn rt_render_wavefront_nee(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
                                    fix: *mut u64, rays_traced: *mut u64, shadow_rays: *mut u64, kernel_ms: *mut f32) -> i32;
+    pub fn rt_render_wavefront_nee_sampled(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                           direct_flags: u32, fix: *mut u64, rays_traced: *mut u64, shadow_rays: *mut u64,
+                                           kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -9,7 +9,7 @@
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
-//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct]]
+//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct | --direct-cone]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -49,6 +49,9 @@
 // --direct, only with --wavefront and at least one --emit: next-event estimation -- at every Lambertian hit a shadow ray towards a point of
 // one emissive sphere, so that small lights are found at sample counts where the random walk alone hits them almost never; the same
 // expectation as without it (rt_render_wavefront_nee).  The number of shadow rays goes to stderr.
+// --direct-cone: --direct with the light sampled by solid angle -- a uniform direction of the cone the sphere subtends -- instead of by area:
+// a bounded weight however close the light, no sample lost on its far side, two to three times the shadow rays
+// (rt_render_wavefront_nee_sampled with RT_DIRECT_CONE).  The rules of --direct; not together with it.
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -111,6 +114,7 @@ int main(int argc, char **argv)
     bool pick = false;
     int pick_i = 0, pick_j = 0;
     bool lit = false;                            // --sky / --emit: the lit wavefront frame
+    bool direct_cone = false;                    // --direct-cone: ... sampled by solid angle instead of by area
     bool direct = false;                         // --direct: ... with shadow rays towards the lights (next-event estimation)
     rt_lighting light{};
     light.sky_bottom[0] = light.sky_bottom[1] = light.sky_bottom[2] = 1.0;
@@ -157,6 +161,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--two-calls")) two_calls = true;
         else if (!std::strcmp(argv[i], "--wavefront")) wavefront = true;
         else if (!std::strcmp(argv[i], "--direct")) direct = true;
+        else if (!std::strcmp(argv[i], "--direct-cone")) direct_cone = true;
         else if (arg("--passes")) passes = std::atoi(argv[++i]);
         else if (arg("--adaptive")) { adaptive = true; threshold = std::atof(argv[++i]); }
         else if (arg("--step")) step = std::atoi(argv[++i]);
@@ -395,6 +400,14 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--direct samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
         return 2;
     }
+    if (direct_cone && direct) {
+        std::fprintf(stderr, "--direct and --direct-cone are two ways to sample the same lights: give one of them\n");
+        return 2;
+    }
+    if (direct_cone && (!wavefront || emits.empty())) {
+        std::fprintf(stderr, "--direct-cone samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
+        return 2;
+    }
     std::vector<double> emission;                // --emit: one (r, g, b) per sphere of the list
     if (!emits.empty()) {
         emission.assign(flat.size() * 3, 0.0);
@@ -489,6 +502,11 @@ int main(int argc, char **argv)
                 uint64_t shadow = 0;
                 rc = rt_render_wavefront_nee(ctx, &rc_cam, &p, &light, fix.data(), &rays, &shadow, &st.kernel_ms);
                 if (rc) return die("rt_render_wavefront_nee", rc);
+                std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
+            } else if (direct_cone) {
+                uint64_t shadow = 0;
+                rc = rt_render_wavefront_nee_sampled(ctx, &rc_cam, &p, &light, RT_DIRECT_CONE, fix.data(), &rays, &shadow, &st.kernel_ms);
+                if (rc) return die("rt_render_wavefront_nee_sampled", rc);
                 std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
             } else if (lit) {
                 rc = rt_render_wavefront_lit(ctx, &rc_cam, &p, &light, fix.data(), &rays, &st.kernel_ms);

@@ -819,8 +819,10 @@ int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_para
 typedef struct {
     const int32_t *lights;   /* [n_lights] sphere indices (list order of the upload); a DEVICE pointer in the _device forms */
     int32_t n_lights;
-    uint32_t flags;          /* 0                                                                                         */
+    uint32_t flags;          /* 0 or RT_DIRECT_CONE                                                                       */
 } rt_direct;                 /* 16 bytes */
+/* the only legal bit of rt_direct.flags: the light is sampled BY SOLID ANGLE, a uniform direction of the cone it subtends (below) */
+#define RT_DIRECT_CONE 2u
 
 /* Pure host function: the indices s in [0, n_emission) with e.x > 0 || e.y > 0 || e.z > 0 for e = emission[s] (what the lit step takes
  * for a light), ascending, to lights_out (room for n_emission entries; may be NULL when n_emission is 0), their number to *n_lights_out.
@@ -852,7 +854,7 @@ int rt_light_list(const double *emission, int32_t n_emission, int32_t *lights_ou
  * zeroed first.  rt_render_wavefront_nee builds the list itself with rt_light_list from the emission table it is given.
  *
  * RT_ERR_INVALID_ARGUMENT, found before anything is touched: first every context-free check of the lit form, in its order; then a NULL
- * direct; direct->flags != 0; n_lights < 0; lights == NULL with n_lights != 0; step_flags other than 0 or RT_STEP_NO_DIRECT; then the context
+ * direct; direct->flags other than 0 and RT_DIRECT_CONE; n_lights < 0; lights == NULL with n_lights != 0; step_flags other than 0 or RT_STEP_NO_DIRECT; then the context
  * checks and the table's length as in the lit form; then n_lights > the uploaded sphere count. */
 int rt_paths_step_nee_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
                              void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, const rt_direct *direct, uint32_t step_flags,
@@ -861,6 +863,38 @@ int rt_render_wavefront_nee_device(rt_context *ctx, const rt_camera *cam, const 
                                    void *d_fix, void *d_rays, void *d_shadow_rays, void *stream);
 int rt_render_wavefront_nee(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint64_t *fix,
                             uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms);
+
+/* ---- direct lighting by solid angle --------------------------------------------- */
+
+/* direct->flags == RT_DIRECT_CONE: the NEE step above in every respect -- the state bit, front-face suppression, when the bit is set
+ * (decided before sampling; also when the sample yields nothing), RT_STEP_NO_DIRECT, the order and the compaction, d_rays, "visible iff
+ * the closest hit is sphere li" -- except the light sample.  Area sampling weighs a sample with 4 r^2 n (ns nl) / dd^2, which is unbounded
+ * as the hit point approaches the light, and throws away every sample of the far hemisphere; a uniform direction inside the cone the
+ * sphere subtends has the weight 2 (1 - cos theta_max) n_lights ns <= 2 n_lights whatever the geometry.  It needs no sin or cos: one u01
+ * for the polar angle and one rejection-sampled point of the unit disk, normalised, for (cos phi, sin phi); pi cancels (BRDF albedo / pi,
+ * cone pdf 1 / (2 pi (1 - cos theta_max))).  With p, n and throughput * albedo as above, blocks philox(pixel, sample, ev_in, 1 + m),
+ * everything binary64 without contraction in exactly this order:
+ *    1. b0 = block 0;  j = ((uint64)b0.x * n_lights) >> 32;  li = lights[j]   (li outside the tables: no contribution)
+ *    2. (c, r2) = geo[li];  wv = c - p;  d2 = (wv.x*wv.x + wv.y*wv.y) + wv.z*wv.z;  nothing unless d2 > r2 (p inside or on the light; NaN)
+ *    3. q = r2 / d2;  cm = sqrt(1.0 - q);  k = q / (1.0 + cm)            (1 - cos theta_max without the cancellation)
+ *    4. s = u01(b0.y) * k;  ct = 1.0 - s;  st = sqrt(s * (1.0 + ct))
+ *    5. unit-disk tries (b0.z, b0.w), then (x, y) of block m = 1, 2, ... until accepted;  hx = u11(tx);  hy = u11(ty);
+ *       il = 1.0 / sqrt(hx*hx + hy*hy);  cphi = hx * il;  sphi = hy * il   (the all-zero try gives NaNs, which step 9 drops)
+ *    6. w = wv * (1.0 / sqrt(d2))
+ *    7. a = fabs(w.x) > 0.9 ? (0, 1, 0) : (1, 0, 0);  t0 = cross(a, w) = (a.y*w.z - a.z*w.y, a.z*w.x - a.x*w.z, a.x*w.y - a.y*w.x);
+ *       t = t0 * (1.0 / sqrt(dot(t0, t0)));  b = cross(w, t), the same form
+ *    8. dir = (t * (st * cphi) + b * (st * sphi)) + w * ct
+ *    9. ns = dot(n, dir);  nothing unless ns > 0.0
+ *   10. wgt = ((2.0 * k) * (double)n_lights) * ns;  cadd = ((throughput * albedo) * e_li) * wgt
+ *   11. the shadow ray (p, dir) with t_min and t_max = +inf: visible iff its closest hit is sphere li, either face; if visible and
+ *       pixel < npix, d_fix[pixel] gains quantize(cadd).
+ * d_shadow_rays counts these rays.  Every queue array and d_rays equal the area step's; only the sums and the shadow count differ.
+ * rt_paths_step_nee_device and rt_render_wavefront_nee_device honour the bit through the rt_direct they take; direct->flags other than 0
+ * and RT_DIRECT_CONE is rejected where direct->flags != 0 was.  The host form takes no rt_direct, so it has a sibling:
+ * rt_render_wavefront_nee_sampled is rt_render_wavefront_nee with direct_flags for the list it builds (0: that function bit for bit).
+ * direct_flags other than 0 and RT_DIRECT_CONE: RT_ERR_INVALID_ARGUMENT after the lit form's context-free checks and before the context. */
+int rt_render_wavefront_nee_sampled(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint32_t direct_flags,
+                                    uint64_t *fix, uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms);
 
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);

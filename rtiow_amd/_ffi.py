@@ -102,6 +102,7 @@ RT_TEMPORAL_CLAMP = 0x1
 RT_TEMPORAL_MAX_LEN = 65535
 RT_PATH_EVENT_DIRECT = 0x80000000
 RT_STEP_NO_DIRECT = 0x1
+RT_DIRECT_CONE = 0x2
 RT_SCATTER_ABSORBED, RT_SCATTER_SCATTERED, RT_SCATTER_MISS, RT_SCATTER_BAD_INDEX = 0, 1, 2, 3
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)
@@ -173,6 +174,8 @@ SYMBOLS = [
                                                  _VP, _VP, _VP]),
     ("rt_render_wavefront_nee", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), _VP, C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("rt_render_wavefront_nee_sampled", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), C.c_uint32, _VP,
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -1,7 +1,7 @@
 // rt_paths.hip -- the device path queue: a fused bounce step on device-resident paths and the frame rendered from it (rtiow_hip.h, "path
 // queue").
 //
-// The eleventh translation unit of librtiow_hip.so.  Six kernels of its own:
+// The eleventh translation unit of librtiow_hip.so.  Seven kernels of its own:
 //   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
 //   bounce_kernel         one wave per 64 consecutive slots, grid-stride over the live slots: closest hit (first_hit_wave<false> whole, the
 //                         record in registers), then the sky add of a miss or Scatter::scatter -- both from rt_shade_core.hpp --; the new
@@ -12,6 +12,8 @@
 //   bounce_nee_kernel     the lit trip with next-event estimation: a Lambertian hit also samples one light by area and traces a shadow ray
 //                         to it -- first_hit_wave<false> a second time in the trip, wave-wide -- (rtiow_hip.h, "direct lighting"; DESIGN.md
 //                         section 21).
+//   bounce_cone_kernel    the NEE trip with the light sampled by solid angle instead of by area (rtiow_hip.h, "direct lighting by solid
+//                         angle").
 //   queue_scan_kernel     ONE workgroup: the exclusive scan of the waves' counts, in place; *out->count; d_rays.
 //   queue_compact_kernel  one wave per 64 slots: the survivors move to `out` at offset + rank, so their order is kept.
 // The live count is a word of device memory every kernel reads for itself; the host sizes the grids from the capacity and never waits.
@@ -94,7 +96,7 @@ struct NeeArgs {
     uint32_t no_direct;
 };
 
-constexpr int kUnlit = 0, kLit = 1, kNee = 2;       // bounce_trip's MODE
+constexpr int kUnlit = 0, kLit = 1, kNee = 2, kNeeCone = 3;     // bounce_trip's MODE
 
 // the three 64-bit adds of a path that ends with radiance v (contract C5); g_pix: inside the frame
 __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, const D3 &v)
@@ -108,11 +110,12 @@ __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, con
 // MODE == kNee: the path's event carries RT_PATH_EVENT_DIRECT in bit 31 (masked off before any Philox use); a path that carries it adds
 // nothing on a light's front face; a Lambertian hit samples one light of N.lights (nee_sample) and, after the new state has been stored,
 // the wave traces the shadow rays together: only the contribution, the pixel and the light's index are live across that scan.
+// MODE == kNeeCone: the same trip with the light sampled by solid angle (nee_sample_cone).
 template <int MODE>
 __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays &Q, const unsigned long long npix, const LitArgs &L, const NeeArgs &N,
                                             uint4 *stage, const int lane, const long long wv, const long long n)
 {
-    constexpr bool LIT = MODE >= kLit, NEE = MODE == kNee;
+    constexpr bool LIT = MODE >= kLit, NEE = MODE >= kNee, CONE = MODE == kNeeCone;
     const long long k = wv * 64 + lane;
     // lanes past the live count stay in the wave: rows that keep nothing, nothing written
     const bool valid = k < n;
@@ -167,7 +170,8 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
                     Q.event[k] = ev;
                     if constexpr (NEE) {
                         if (direct) {
-                            shadow = nee_sample(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
+                            if constexpr (CONE) shadow = nee_sample_cone(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
+                            else shadow = nee_sample(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
                             so = rec.p;
                         }
                     }
@@ -225,6 +229,14 @@ __global__ __launch_bounds__(kPathBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void bounce_nee_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L, const NeeArgs N)
 {
     RT_BOUNCE_LOOP(kNee, L, N);
+}
+
+// ... with the light sampled by solid angle instead of by area (rt_direct.flags & RT_DIRECT_CONE): bounce_nee_kernel's
+// shape, the sampler swapped.  (Defined here, not last: tools/isa_fingerprint.py counts the padding behind a translation unit's last kernel.)
+__global__ __launch_bounds__(kPathBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void bounce_cone_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L, const NeeArgs N)
+{
+    RT_BOUNCE_LOOP(kNeeCone, L, N);
 }
 #undef RT_BOUNCE_LOOP
 
@@ -361,7 +373,8 @@ int check_direct(const char *what, const NeeCall *nee)
 {
     const rt_direct *direct = nee->direct;
     RT_NEED(direct, what, "direct");
-    if (direct->flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown direct->flags 0x%x (only 0 is legal)", what, direct->flags);
+    if (direct->flags & ~RT_DIRECT_CONE)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown direct->flags 0x%x (only 0 and RT_DIRECT_CONE are legal)", what, direct->flags);
     if (direct->n_lights < 0) return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct->n_lights must be >= 0 (is %d)", what, direct->n_lights);
     if (!direct->lights && direct->n_lights != 0)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct->n_lights must be 0 when direct->lights is NULL (is %d)", what, direct->n_lights);
@@ -477,7 +490,8 @@ int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_pat
             memset(&na, 0, sizeof(na));
             na.lights = nee->direct->lights; na.n_lights = nee->direct->lights ? nee->direct->n_lights : 0;
             na.shadow_rays = (unsigned long long *)nee->d_shadow_rays; na.no_direct = nee->step_flags & RT_STEP_NO_DIRECT;
-            hipLaunchKernelGGL(rt::bounce_nee_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
+            if (nee->direct->flags & RT_DIRECT_CONE) hipLaunchKernelGGL(rt::bounce_cone_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
+            else hipLaunchKernelGGL(rt::bounce_nee_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
         } else {
             hipLaunchKernelGGL(rt::bounce_lit_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la);
         }
@@ -572,14 +586,17 @@ int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, cons
     return RT_OK;
 }
 
-// The body of the three host frames.  mode: kUnlit (light is not looked at), kLit, or kNee: the frame samples its lights directly, their
+// The body of the four host frames.  mode: kUnlit (light is not looked at), kLit, or kNee: the frame samples its lights directly, their
 // list rebuilt from the table the call can see.  The counters are counted whether or not the caller asks; a frame without direct lighting
 // has no shadow counter (shadow_rays NULL: absent).
 int render_frame_host(rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const rt_lighting *light, int mode, uint64_t *fix,
-                      uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms)
+                      uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms, uint32_t direct_flags = 0u)
 {
     const bool lit = mode >= rt::kLit, direct = mode == rt::kNee;
-    if (int rc = check_render(ctx, what, cam, p, fix, lit, light, true)) return rc;
+    // (direct_flags: the flags of the list this frame builds; checked where a device form checks direct->flags)
+    const rt_direct no_list = {nullptr, 0, direct_flags};
+    const NeeCall flags_only = {&no_list, 0u, nullptr};
+    if (int rc = check_render(ctx, what, cam, p, fix, lit, light, true, direct ? &flags_only : nullptr)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
     const double *table = lit ? light->emission : nullptr;
     const size_t n_table = table ? (size_t)light->n_emission : 0;
@@ -597,7 +614,7 @@ int render_frame_host(rt_context *ctx, const char *what, const rt_camera *cam, c
     rt_lighting dev = lit ? *light : rt_lighting{};     // the same lighting with the table on the device
     dev.emission = st.ptr(emission);
     if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
-    rt_direct on_device = {st.ptr(lights), n_lights, 0u};
+    rt_direct on_device = {st.ptr(lights), n_lights, direct_flags};
     if (!on_device.lights) on_device.n_lights = 0;
     const NeeCall nee = {&on_device, 0u, st.ptr(shadow)};
     return timed_section(ctx, what, kernel_ms, st, [&] {
@@ -706,6 +723,12 @@ int rt_render_wavefront_nee(rt_context *ctx, const rt_camera *cam, const rt_para
                             uint64_t *shadow_rays, float *kernel_ms)
 {
     return render_frame_host(ctx, "rt_render_wavefront_nee", cam, p, light, rt::kNee, fix, rays_traced, shadow_rays, kernel_ms);
+}
+
+int rt_render_wavefront_nee_sampled(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint32_t direct_flags,
+                                    uint64_t *fix, uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms)
+{
+    return render_frame_host(ctx, "rt_render_wavefront_nee_sampled", cam, p, light, rt::kNee, fix, rays_traced, shadow_rays, kernel_ms, direct_flags);
 }
 
 } // extern "C"

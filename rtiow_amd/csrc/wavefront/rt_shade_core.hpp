@@ -174,4 +174,48 @@ __device__ __forceinline__ bool nee_sample(const KParams &P, const double *emiss
     return true;
 }
 
+// ---- ... or by solid angle: a uniform direction of the cone the light subtends from p (RT_DIRECT_CONE) -------------
+// nee_sample's arguments, blocks and result.  Block 0: x chooses the light, y is the polar draw, (z, w) the first unit-disk try, whose
+// normalised point is (cos phi, sin phi); every further block holds one try (x, y).  + - * / and sqrt in binary64, no contraction: the
+// BRDF albedo / pi and the cone pdf 1 / (2 pi (1 - cos theta_max) n_lights) leave no pi, and the weight 2 k n_lights ns is bounded by
+// 2 n_lights whatever the geometry (k <= 1, ns <= 1).  dv is a unit vector up to rounding.
+__device__ __forceinline__ bool nee_sample_cone(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t n_lights,
+                                                const D3 &p, const D3 &n, const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv, D3 &c,
+                                                int &li)
+{
+    U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
+    const uint32_t j = (uint32_t)(((unsigned long long)b.x * (unsigned long long)(uint32_t)n_lights) >> 32);
+    li = lights[j];
+    if (li < 0 || li >= P.n_spheres || !emission || li >= n_emission) return false;      // as nee_sample
+    const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)li);        // centre, r^2
+    const D3 wv = mk(g.x, g.y, g.z) - p;
+    const double d2 = (wv.x * wv.x + wv.y * wv.y) + wv.z * wv.z;
+    if (!(d2 > g.w)) return false;                                                       // p inside or on the light; a NaN fails this
+    const double q = g.w / d2;
+    const double cm = __builtin_sqrt(1.0 - q);                                           // cos theta_max
+    const double k = q / (1.0 + cm);                                                     // 1 - cos theta_max, without the cancellation
+    const double s = u01(b.y) * k;
+    const double ct = 1.0 - s;
+    const double st = __builtin_sqrt(s * (1.0 + ct));
+    uint32_t tx = b.z, ty = b.w;
+    for (uint32_t m = 1u; !unit_disk_accepts(tx, ty); ++m) {                             // vec3.rs:59-68: a plain loop to acceptance
+        b = philox4x32_10(g_pix, g_s, ev_in, 1u + m, P.k0, P.k1);
+        tx = b.x; ty = b.y;
+    }
+    const double hx = u11(tx), hy = u11(ty);
+    const double il = 1.0 / __builtin_sqrt(hx * hx + hy * hy);                           // (the all-zero try: NaNs, which ns > 0.0 drops)
+    const double cphi = hx * il, sphi = hy * il;
+    const D3 w = wv * (1.0 / __builtin_sqrt(d2));
+    const D3 a = __builtin_fabs(w.x) > 0.9 ? mk(0.0, 1.0, 0.0) : mk(1.0, 0.0, 0.0);
+    const D3 t0 = mk(a.y * w.z - a.z * w.y, a.z * w.x - a.x * w.z, a.x * w.y - a.y * w.x);
+    const D3 t = t0 * (1.0 / __builtin_sqrt(dot(t0, t0)));
+    const D3 bt = mk(w.y * t.z - w.z * t.y, w.z * t.x - w.x * t.z, w.x * t.y - w.y * t.x);
+    dv = (t * (st * cphi) + bt * (st * sphi)) + w * ct;
+    const double ns = dot(n, dv);
+    if (!(ns > 0.0)) return false;                                                       // below the hit's horizon; a NaN fails this
+    const double wgt = ((2.0 * k) * (double)n_lights) * ns;
+    c = (weight * ld3(emission + 3 * (size_t)li)) * wgt;
+    return true;
+}
+
 } // namespace rt

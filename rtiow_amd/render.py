@@ -458,13 +458,23 @@ class Lighting:
         return _ffi.rt_lighting((C.c_double * 3)(*self.sky_bottom), (C.c_double * 3)(*self.sky_top), emission_ptr or None, int(n_emission), 0)
 
 
-def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, lighting=None, direct=False, no_direct=False, shadow_rays=None):
+def _direct_flags(sampling, direct):
+    """rt_direct.flags of sampling="area" (the light sampled by area: 0) or "cone" (by solid angle: RT_DIRECT_CONE)."""
+    if sampling not in ("area", "cone"):
+        raise ValueError(f'sampling must be "area" or "cone" (is {sampling!r})')
+    if sampling == "cone" and direct is False:
+        raise ValueError('sampling="cone" belongs to direct lighting (direct=...)')
+    return _ffi.RT_DIRECT_CONE if sampling == "cone" else 0
+
+
+def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, lighting=None, direct=False, no_direct=False, shadow_rays=None,
+                     sampling="area"):
     """rt_paths_step_device on two PathQueues, on torch.cuda.current_stream(): one bounce of the live paths of `qin`; the survivors go to
     `qout` in order.  fix: an int64 tensor [..., 3] holding the u64 sums' bits, added to; rays: an int64 tensor [1] that gains the live
     count, or None.  lighting: a Lighting (rt_paths_step_lit_device; its emission a float64 tensor [n, 3] on the device, or what
     Lighting.device_table makes of it), None: the unlit step.  direct: True (rt_paths_step_nee_device with the lighting's own light
     list) or a list of sphere indices / an int32 tensor on the device; no_direct: RT_STEP_NO_DIRECT; shadow_rays: an int64 tensor [1] that
-    gains the shadow rays traced, or None.  No host wait."""
+    gains the shadow rays traced, or None; sampling: "area" or "cone", how direct lighting samples a light.  No host wait."""
     import torch
     _check_queue(renderer, qin, "qin")
     _check_queue(renderer, qout, "qout")
@@ -476,7 +486,7 @@ def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, ligh
     with torch.cuda.device(qin.device):
         renderer.paths_step_device(seed, qin.struct(), qout.struct(), fix.data_ptr(), fix.numel() // 3, rays.data_ptr() if rays is not None else 0,
                                    t_min, torch.cuda.current_stream().cuda_stream, lighting=lighting, direct=direct, no_direct=no_direct,
-                                   d_shadow_rays_ptr=shadow_rays.data_ptr() if shadow_rays is not None else 0)
+                                   d_shadow_rays_ptr=shadow_rays.data_ptr() if shadow_rays is not None else 0, sampling=sampling)
 
 
 class Renderer:
@@ -860,26 +870,28 @@ class Renderer:
         table = lighting.device_table(self)
         return lighting.struct(table.data_ptr() if table is not None else None, table.shape[0] if table is not None else 0), table
 
-    def _device_direct(self, lighting, direct):
+    def _device_direct(self, lighting, direct, flags=0):
         """(the rt_direct of a device form, the tensor it names -- to be kept until the call has been made)."""
         if lighting is None:
             raise ValueError("direct lighting needs a Lighting")
         lights = lighting.device_lights(self, direct)
         n = int(lights.shape[0])
-        return _ffi.rt_direct(lights.data_ptr() if n else None, n, 0), lights
+        return _ffi.rt_direct(lights.data_ptr() if n else None, n, flags), lights
 
     def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0, lighting=None, direct=False,
-                          no_direct=False, d_shadow_rays_ptr=0):
+                          no_direct=False, d_shadow_rays_ptr=0, sampling="area"):
         """rt_paths_step_device, or with a Lighting rt_paths_step_lit_device, or with direct (True: the lighting's own light list, else
-        the indices) rt_paths_step_nee_device -- no_direct: RT_STEP_NO_DIRECT; d_shadow_rays_ptr: a device u64 or 0 --; qin, qout:
+        the indices) rt_paths_step_nee_device -- no_direct: RT_STEP_NO_DIRECT; d_shadow_rays_ptr: a device u64 or 0; sampling: "area" or
+        "cone" (RT_DIRECT_CONE: the light sampled by solid angle) --; qin, qout:
         _ffi.rt_path_queue structs of device pointers; asynchronous on `stream`."""
+        direct_flags = _direct_flags(sampling, direct if lighting is not None else False)
         head = (self._h, int(seed), int(flags), float(t_min), C.byref(qin), C.byref(qout), C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
                 C.c_void_p(d_rays_ptr) if d_rays_ptr else None)
         if lighting is None:
             _ffi.check(self._lib.rt_paths_step_device(*head, C.c_void_p(stream)), "rt_paths_step_device")
             return
         if direct is not False:
-            d, _keep_list = self._device_direct(lighting, direct)
+            d, _keep_list = self._device_direct(lighting, direct, direct_flags)
             light, _keep = self._device_lighting(lighting)
             _ffi.check(self._lib.rt_paths_step_nee_device(*head, C.byref(light), C.byref(d), _ffi.RT_STEP_NO_DIRECT if no_direct else 0,
                                                           C.c_void_p(d_shadow_rays_ptr) if d_shadow_rays_ptr else None, C.c_void_p(stream)),
@@ -890,11 +902,13 @@ class Renderer:
         light, _keep = self._device_lighting(lighting)
         _ffi.check(self._lib.rt_paths_step_lit_device(*head, C.byref(light), C.c_void_p(stream)), "rt_paths_step_lit_device")
 
-    def render_wavefront(self, cam, params, lighting=None, direct=False):
+    def render_wavefront(self, cam, params, lighting=None, direct=False, sampling="area"):
         """rt_render_wavefront: the frame through the device path queue -> (the exact sums u64 [H, W, 3], the rays traced): what
         Renderer.render returns as `fix` and as stats["rays_traced"].  lighting: a Lighting (rt_render_wavefront_lit: a settable sky and
         emissive spheres), None: the unlit frame.  direct=True (rt_render_wavefront_nee: shadow rays towards the lighting's lights at
-        Lambertian hits) -> (the sums, the rays traced, stats) with stats["shadow_rays"] the shadow rays traced."""
+        Lambertian hits) -> (the sums, the rays traced, stats) with stats["shadow_rays"] the shadow rays traced.  sampling="cone"
+        (rt_render_wavefront_nee_sampled with RT_DIRECT_CONE): the lights are sampled by solid angle instead of by area."""
+        direct_flags = _direct_flags(sampling, direct if direct else False)
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         fix = np.zeros((params.height, params.width, 3), dtype=np.uint64)
         rays = C.c_uint64(0)
@@ -908,24 +922,32 @@ class Renderer:
         light = lighting.struct(table.ctypes.data if table is not None else None, table.shape[0] if table is not None else 0)
         if direct:
             shadow = C.c_uint64(0)
-            _ffi.check(self._lib.rt_render_wavefront_nee(self._h, C.byref(rc), C.byref(params), C.byref(light), fix.ctypes.data_as(C.c_void_p),
-                                                         C.byref(rays), C.byref(shadow), None), "rt_render_wavefront_nee")
+            if direct_flags:
+                _ffi.check(self._lib.rt_render_wavefront_nee_sampled(self._h, C.byref(rc), C.byref(params), C.byref(light), direct_flags,
+                                                                     fix.ctypes.data_as(C.c_void_p), C.byref(rays), C.byref(shadow), None),
+                           "rt_render_wavefront_nee_sampled")
+            else:
+                _ffi.check(self._lib.rt_render_wavefront_nee(self._h, C.byref(rc), C.byref(params), C.byref(light), fix.ctypes.data_as(C.c_void_p),
+                                                             C.byref(rays), C.byref(shadow), None), "rt_render_wavefront_nee")
             return fix, int(rays.value), {"rays_traced": int(rays.value), "shadow_rays": int(shadow.value)}
         _ffi.check(self._lib.rt_render_wavefront_lit(self._h, C.byref(rc), C.byref(params), C.byref(light), fix.ctypes.data_as(C.c_void_p),
                                                      C.byref(rays), None), "rt_render_wavefront_lit")
         return fix, int(rays.value)
 
-    def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0, lighting=None, direct=False, d_shadow_rays_ptr=0):
+    def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0, lighting=None, direct=False, d_shadow_rays_ptr=0,
+                                sampling="area"):
         """rt_render_wavefront_device on raw device pointers (d_fix [H][W][3] u64, d_rays one u64 or 0); asynchronous on `stream`.
         lighting: a Lighting (rt_render_wavefront_lit_device; its emission as in paths_step_torch), None: the unlit frame.  direct (as
-        in paths_step_device): rt_render_wavefront_nee_device; d_shadow_rays_ptr: a device u64 that receives the shadow rays traced, or 0."""
+        in paths_step_device): rt_render_wavefront_nee_device; d_shadow_rays_ptr: a device u64 that receives the shadow rays traced, or 0;
+        sampling: "area" or "cone", as in paths_step_device."""
+        direct_flags = _direct_flags(sampling, direct if lighting is not None else False)
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         tail = (C.c_void_p(d_fix_ptr) if d_fix_ptr else None, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream))
         if lighting is None:
             _ffi.check(self._lib.rt_render_wavefront_device(self._h, C.byref(rc), C.byref(params), *tail), "rt_render_wavefront_device")
             return
         if direct is not False:
-            d, _keep_list = self._device_direct(lighting, direct)
+            d, _keep_list = self._device_direct(lighting, direct, direct_flags)
             light, _keep = self._device_lighting(lighting)
             _ffi.check(self._lib.rt_render_wavefront_nee_device(self._h, C.byref(rc), C.byref(params), C.byref(light), C.byref(d), tail[0], tail[1],
                                                                 C.c_void_p(d_shadow_rays_ptr) if d_shadow_rays_ptr else None, tail[2]),
