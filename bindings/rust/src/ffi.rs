@@ -287,8 +287,11 @@ const _: () = assert!(64 == size_of::<rt_lighting>());
 pub const RT_PATH_EVENT_DIRECT: u32 = 0x8000_0000;
 /// The only legal step flag of `rt_paths_step_nee_device`: the step neither samples lights nor sets the bit.
 pub const RT_STEP_NO_DIRECT: u32 = 1;
-/// The only legal bit of `rt_direct.flags`: the light is sampled by solid angle (a uniform direction of the cone it subtends), not by area.
+/// A bit of `rt_direct.flags`: the light is sampled by solid angle (a uniform direction of the cone it subtends), not by area.
 pub const RT_DIRECT_CONE: u32 = 2;
+/// A bit of `rt_direct.flags`, legal only together with `RT_DIRECT_CONE` (the legal values are 0, 2 and 10): the light is chosen by
+/// what it can contribute at the hit point, `(r^2 / d^2) max(e)`, not uniformly.
+pub const RT_DIRECT_WEIGHTED: u32 = 8;
 
 /// The lights that next-event estimation samples (`rt_paths_step_nee_device`, `rt_render_wavefront_nee_device`): `lights`:
 /// `[n_lights]` sphere indices, a DEVICE pointer; `rt_light_list` makes the list of an emission table on the host.

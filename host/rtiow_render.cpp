@@ -9,7 +9,7 @@
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
-//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct | --direct-cone]]
+//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct | --direct-cone | --direct-weighted]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -52,6 +52,9 @@
 // --direct-cone: --direct with the light sampled by solid angle -- a uniform direction of the cone the sphere subtends -- instead of by area:
 // a bounded weight however close the light, no sample lost on its far side, two to three times the shadow rays
 // (rt_render_wavefront_nee_sampled with RT_DIRECT_CONE).  The rules of --direct; not together with it.
+// --direct-weighted: --direct-cone with the light chosen by what it can contribute at the hit point -- (r^2 / d^2) max(e) -- instead of
+// uniformly: what a frame lit by many small lights needs (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE).  The rules of
+// --direct; not together with either of the other two.
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -115,6 +118,7 @@ int main(int argc, char **argv)
     int pick_i = 0, pick_j = 0;
     bool lit = false;                            // --sky / --emit: the lit wavefront frame
     bool direct_cone = false;                    // --direct-cone: ... sampled by solid angle instead of by area
+    bool direct_weighted = false;                // --direct-weighted: ... and chosen by their contribution at the hit point
     bool direct = false;                         // --direct: ... with shadow rays towards the lights (next-event estimation)
     rt_lighting light{};
     light.sky_bottom[0] = light.sky_bottom[1] = light.sky_bottom[2] = 1.0;
@@ -162,6 +166,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--wavefront")) wavefront = true;
         else if (!std::strcmp(argv[i], "--direct")) direct = true;
         else if (!std::strcmp(argv[i], "--direct-cone")) direct_cone = true;
+        else if (!std::strcmp(argv[i], "--direct-weighted")) direct_weighted = true;
         else if (arg("--passes")) passes = std::atoi(argv[++i]);
         else if (arg("--adaptive")) { adaptive = true; threshold = std::atof(argv[++i]); }
         else if (arg("--step")) step = std::atoi(argv[++i]);
@@ -404,6 +409,14 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--direct and --direct-cone are two ways to sample the same lights: give one of them\n");
         return 2;
     }
+    if (direct_weighted && (direct || direct_cone)) {
+        std::fprintf(stderr, "--direct, --direct-cone and --direct-weighted are three ways to sample the same lights: give one of them\n");
+        return 2;
+    }
+    if (direct_weighted && (!wavefront || emits.empty())) {
+        std::fprintf(stderr, "--direct-weighted samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
+        return 2;
+    }
     if (direct_cone && (!wavefront || emits.empty())) {
         std::fprintf(stderr, "--direct-cone samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
         return 2;
@@ -503,9 +516,10 @@ int main(int argc, char **argv)
                 rc = rt_render_wavefront_nee(ctx, &rc_cam, &p, &light, fix.data(), &rays, &shadow, &st.kernel_ms);
                 if (rc) return die("rt_render_wavefront_nee", rc);
                 std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
-            } else if (direct_cone) {
+            } else if (direct_cone || direct_weighted) {
                 uint64_t shadow = 0;
-                rc = rt_render_wavefront_nee_sampled(ctx, &rc_cam, &p, &light, RT_DIRECT_CONE, fix.data(), &rays, &shadow, &st.kernel_ms);
+                const uint32_t direct_flags = direct_weighted ? (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) : RT_DIRECT_CONE;
+                rc = rt_render_wavefront_nee_sampled(ctx, &rc_cam, &p, &light, direct_flags, fix.data(), &rays, &shadow, &st.kernel_ms);
                 if (rc) return die("rt_render_wavefront_nee_sampled", rc);
                 std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
             } else if (lit) {

@@ -819,10 +819,13 @@ int rt_render_wavefront_lit(rt_context *ctx, const rt_camera *cam, const rt_para
 typedef struct {
     const int32_t *lights;   /* [n_lights] sphere indices (list order of the upload); a DEVICE pointer in the _device forms */
     int32_t n_lights;
-    uint32_t flags;          /* 0 or RT_DIRECT_CONE                                                                       */
+    uint32_t flags;          /* 0, RT_DIRECT_CONE, or RT_DIRECT_WEIGHTED | RT_DIRECT_CONE                                 */
 } rt_direct;                 /* 16 bytes */
-/* the only legal bit of rt_direct.flags: the light is sampled BY SOLID ANGLE, a uniform direction of the cone it subtends (below) */
+/* the bits of rt_direct.flags.  CONE: the light is sampled BY SOLID ANGLE, a uniform direction of the cone it subtends.  WEIGHTED, legal
+ * only together with CONE: the light is CHOSEN by what it can contribute at the hit point, not uniformly (both below).  The legal values
+ * are 0, 2 and 10. */
 #define RT_DIRECT_CONE 2u
+#define RT_DIRECT_WEIGHTED 8u
 
 /* Pure host function: the indices s in [0, n_emission) with e.x > 0 || e.y > 0 || e.z > 0 for e = emission[s] (what the lit step takes
  * for a light), ascending, to lights_out (room for n_emission entries; may be NULL when n_emission is 0), their number to *n_lights_out.
@@ -854,7 +857,7 @@ int rt_light_list(const double *emission, int32_t n_emission, int32_t *lights_ou
  * zeroed first.  rt_render_wavefront_nee builds the list itself with rt_light_list from the emission table it is given.
  *
  * RT_ERR_INVALID_ARGUMENT, found before anything is touched: first every context-free check of the lit form, in its order; then a NULL
- * direct; direct->flags other than 0 and RT_DIRECT_CONE; n_lights < 0; lights == NULL with n_lights != 0; step_flags other than 0 or RT_STEP_NO_DIRECT; then the context
+ * direct; direct->flags other than 0, RT_DIRECT_CONE and RT_DIRECT_WEIGHTED | RT_DIRECT_CONE; n_lights < 0; lights == NULL with n_lights != 0; step_flags other than 0 or RT_STEP_NO_DIRECT; then the context
  * checks and the table's length as in the lit form; then n_lights > the uploaded sphere count. */
 int rt_paths_step_nee_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
                              void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, const rt_direct *direct, uint32_t step_flags,
@@ -889,12 +892,39 @@ int rt_render_wavefront_nee(rt_context *ctx, const rt_camera *cam, const rt_para
  *   11. the shadow ray (p, dir) with t_min and t_max = +inf: visible iff its closest hit is sphere li, either face; if visible and
  *       pixel < npix, d_fix[pixel] gains quantize(cadd).
  * d_shadow_rays counts these rays.  Every queue array and d_rays equal the area step's; only the sums and the shadow count differ.
- * rt_paths_step_nee_device and rt_render_wavefront_nee_device honour the bit through the rt_direct they take; direct->flags other than 0
- * and RT_DIRECT_CONE is rejected where direct->flags != 0 was.  The host form takes no rt_direct, so it has a sibling:
+ * rt_paths_step_nee_device and rt_render_wavefront_nee_device honour the bit through the rt_direct they take; direct->flags other than 0,
+ * RT_DIRECT_CONE and RT_DIRECT_WEIGHTED | RT_DIRECT_CONE (below) is rejected where direct->flags != 0 was.  The host form takes no rt_direct, so it has a sibling:
  * rt_render_wavefront_nee_sampled is rt_render_wavefront_nee with direct_flags for the list it builds (0: that function bit for bit).
- * direct_flags other than 0 and RT_DIRECT_CONE: RT_ERR_INVALID_ARGUMENT after the lit form's context-free checks and before the context. */
+ * direct_flags other than those: RT_ERR_INVALID_ARGUMENT after the lit form's context-free checks and before the context. */
 int rt_render_wavefront_nee_sampled(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, uint32_t direct_flags,
                                     uint64_t *fix, uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms);
+
+/* ---- direct lighting with a weighted choice of the light ------------------------ */
+
+/* direct->flags == (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE), or that value as direct_flags of rt_render_wavefront_nee_sampled: the cone step
+ * above in every respect -- the state bit, set before sampling and also when nothing is sampled; front-face suppression;
+ * RT_STEP_NO_DIRECT; the order and the compaction; d_rays; "visible iff the closest hit is sphere li"; the blocks
+ * philox(pixel, sample, ev_in, 1 + m); word y of block 0 as the polar draw and (z, w) as the first disk try; steps 2 to 9 and 11 for the
+ * chosen light -- except steps 1 and 10.  The uniform choice is the dominant noise with many lights: most are far from a given hit point,
+ * and the rare near one arrives with the weight 2 k n_lights ns.  Here light i is chosen with a probability proportional to
+ * (r^2 / d^2) max(e), the solid angle it subtends at p (up to the factor the cone sample's k brings) times its largest channel: one
+ * division per light, no sqrt, no table.  Binary64 without contraction, in exactly this order; p is the hit point:
+ *   1a. for i = 0 .. n_lights - 1 in list order: s = lights[i]; s outside [0, n_spheres) or outside the emission table: imp_i = 0.
+ *       Otherwise (c, r2) = geo[s];  wv = c - p;  d2 = (wv.x*wv.x + wv.y*wv.y) + wv.z*wv.z;  e = emission[s];
+ *       em = max2(max2(e.x, e.y), e.z) with max2(a, b) = a > b ? a : b (a NaN on the left is dropped, one on the right is taken);
+ *       v = (r2 / d2) * em;  imp_i = (d2 > r2 && v > 0.0) ? v : 0.0   (a NaN fails either test)
+ *   1b. tot = ((0.0 + imp_0) + imp_1) + ..., adding only the imp_i > 0.0, in order.  !(tot > 0.0): no shadow ray, no contribution; the
+ *       state bit is still set.
+ *   1c. x = u01(b0.x) * tot.  The list is walked again, imp_i recomputed with the same expressions and summed into the same running sum
+ *       acc;  j = the first i with imp_i > 0.0 && x < acc;  if none qualifies (x rounded up to tot), the last i with imp_i > 0.0;
+ *       li = lights[j].
+ *   10'. wgt = ((2.0 * k) * ns) * (tot / imp_j);  cadd = ((throughput * albedo) * e_li) * wgt
+ * Consequences.  k <= r2 / d2 and e / em <= 1 per channel, so one light sample adds at most 2 * sum_i max(e_i) per unit of throughput,
+ * whatever the geometry.  With a list of one valid light tot / imp_j is exactly 1.0, and the step and the frame are the cone step and
+ * frame bit for bit: sums, queues, d_rays, the shadow count.  Every queue array and d_rays after a weighted step equal the cone step's;
+ * only the sums and the shadow count differ.  A list entry that names no sphere, a sphere that does not emit, or a light that contains
+ * p is never chosen, where the cone step chooses it and gets nothing.  The cost is two walks over the list per Lambertian hit.
+ * RT_DIRECT_WEIGHTED alone (8), and every value other than 0, 2 and 10, is rejected where and how an unknown flag was. */
 
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);

@@ -103,6 +103,7 @@ RT_TEMPORAL_MAX_LEN = 65535
 RT_PATH_EVENT_DIRECT = 0x80000000
 RT_STEP_NO_DIRECT = 0x1
 RT_DIRECT_CONE = 0x2
+RT_DIRECT_WEIGHTED = 0x8
 RT_SCATTER_ABSORBED, RT_SCATTER_SCATTERED, RT_SCATTER_MISS, RT_SCATTER_BAD_INDEX = 0, 1, 2, 3
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)

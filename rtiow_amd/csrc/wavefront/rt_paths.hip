@@ -1,7 +1,7 @@
 // rt_paths.hip -- the device path queue: a fused bounce step on device-resident paths and the frame rendered from it (rtiow_hip.h, "path
 // queue").
 //
-// The eleventh translation unit of librtiow_hip.so.  Seven kernels of its own:
+// The eleventh translation unit of librtiow_hip.so.  Eight kernels of its own:
 //   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
 //   bounce_kernel         one wave per 64 consecutive slots, grid-stride over the live slots: closest hit (first_hit_wave<false> whole, the
 //                         record in registers), then the sky add of a miss or Scatter::scatter -- both from rt_shade_core.hpp --; the new
@@ -14,6 +14,8 @@
 //                         section 21).
 //   bounce_cone_kernel    the NEE trip with the light sampled by solid angle instead of by area (rtiow_hip.h, "direct lighting by solid
 //                         angle").
+//   bounce_weighted_kernel  the cone trip with the light chosen by its contribution at the hit point instead of uniformly (rtiow_hip.h,
+//                         "direct lighting with a weighted choice").
 //   queue_scan_kernel     ONE workgroup: the exclusive scan of the waves' counts, in place; *out->count; d_rays.
 //   queue_compact_kernel  one wave per 64 slots: the survivors move to `out` at offset + rank, so their order is kept.
 // The live count is a word of device memory every kernel reads for itself; the host sizes the grids from the capacity and never waits.
@@ -96,7 +98,7 @@ struct NeeArgs {
     uint32_t no_direct;
 };
 
-constexpr int kUnlit = 0, kLit = 1, kNee = 2, kNeeCone = 3;     // bounce_trip's MODE
+constexpr int kUnlit = 0, kLit = 1, kNee = 2, kNeeCone = 3, kNeeWeighted = 4;     // bounce_trip's MODE
 
 // the three 64-bit adds of a path that ends with radiance v (contract C5); g_pix: inside the frame
 __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, const D3 &v)
@@ -111,11 +113,12 @@ __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, con
 // nothing on a light's front face; a Lambertian hit samples one light of N.lights (nee_sample) and, after the new state has been stored,
 // the wave traces the shadow rays together: only the contribution, the pixel and the light's index are live across that scan.
 // MODE == kNeeCone: the same trip with the light sampled by solid angle (nee_sample_cone).
+// MODE == kNeeWeighted: ... and chosen by its contribution at the hit point (nee_sample_weighted).
 template <int MODE>
 __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays &Q, const unsigned long long npix, const LitArgs &L, const NeeArgs &N,
                                             uint4 *stage, const int lane, const long long wv, const long long n)
 {
-    constexpr bool LIT = MODE >= kLit, NEE = MODE >= kNee, CONE = MODE == kNeeCone;
+    constexpr bool LIT = MODE >= kLit, NEE = MODE >= kNee, CONE = MODE == kNeeCone, WEIGHTED = MODE == kNeeWeighted;
     const long long k = wv * 64 + lane;
     // lanes past the live count stay in the wave: rows that keep nothing, nothing written
     const bool valid = k < n;
@@ -170,7 +173,8 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
                     Q.event[k] = ev;
                     if constexpr (NEE) {
                         if (direct) {
-                            if constexpr (CONE) shadow = nee_sample_cone(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
+                            if constexpr (WEIGHTED) shadow = nee_sample_weighted(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
+                            else if constexpr (CONE) shadow = nee_sample_cone(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
                             else shadow = nee_sample(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
                             so = rec.p;
                         }
@@ -237,6 +241,14 @@ __global__ __launch_bounds__(kPathBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void bounce_cone_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L, const NeeArgs N)
 {
     RT_BOUNCE_LOOP(kNeeCone, L, N);
+}
+
+// ... and with the light chosen by its contribution at the hit point (rt_direct.flags == RT_DIRECT_WEIGHTED | RT_DIRECT_CONE; DESIGN.md
+// section 23): bounce_cone_kernel's shape, the sampler swapped.  (Defined here, not last, for bounce_cone_kernel's reason.)
+__global__ __launch_bounds__(kPathBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void bounce_weighted_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L, const NeeArgs N)
+{
+    RT_BOUNCE_LOOP(kNeeWeighted, L, N);
 }
 #undef RT_BOUNCE_LOOP
 
@@ -373,8 +385,9 @@ int check_direct(const char *what, const NeeCall *nee)
 {
     const rt_direct *direct = nee->direct;
     RT_NEED(direct, what, "direct");
-    if (direct->flags & ~RT_DIRECT_CONE)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown direct->flags 0x%x (only 0 and RT_DIRECT_CONE are legal)", what, direct->flags);
+    if (direct->flags != 0u && direct->flags != RT_DIRECT_CONE && direct->flags != (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE))
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown direct->flags 0x%x (only 0, RT_DIRECT_CONE and RT_DIRECT_WEIGHTED | RT_DIRECT_CONE are legal)", what,
+                    direct->flags);
     if (direct->n_lights < 0) return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct->n_lights must be >= 0 (is %d)", what, direct->n_lights);
     if (!direct->lights && direct->n_lights != 0)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct->n_lights must be 0 when direct->lights is NULL (is %d)", what, direct->n_lights);
@@ -490,7 +503,8 @@ int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_pat
             memset(&na, 0, sizeof(na));
             na.lights = nee->direct->lights; na.n_lights = nee->direct->lights ? nee->direct->n_lights : 0;
             na.shadow_rays = (unsigned long long *)nee->d_shadow_rays; na.no_direct = nee->step_flags & RT_STEP_NO_DIRECT;
-            if (nee->direct->flags & RT_DIRECT_CONE) hipLaunchKernelGGL(rt::bounce_cone_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
+            if (nee->direct->flags & RT_DIRECT_WEIGHTED) hipLaunchKernelGGL(rt::bounce_weighted_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
+            else if (nee->direct->flags & RT_DIRECT_CONE) hipLaunchKernelGGL(rt::bounce_cone_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
             else hipLaunchKernelGGL(rt::bounce_nee_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
         } else {
             hipLaunchKernelGGL(rt::bounce_lit_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la);

@@ -1,6 +1,6 @@
 // rt_shade_core.hpp -- the per-path bodies of the wavefront steps: the camera ray of a (pixel, sample), Scatter::scatter of the three
 // materials on the keyed Philox stream, the sky sample, and the light sample of next-event estimation.  Values in, values out: no global
-// load except the material record (the light sample: one entry each of the light list, the geometry and the emission table), no store.
+// load except the material record (the light sample: one entry each of the light list, the geometry and the emission table; the weighted choice: one per list entry), no store.
 // wavefront/rt_shade.hip (one step per kernel: load -> call -> store) and wavefront/rt_paths.hip (the fused bounce step of the device path
 // queue) call the same functions, so the arithmetic is stated once.  They COMPOSE rt_device.hpp (philox4x32_10, u01, u11,
 // unit_sphere_accepts, unit_disk_accepts, reflect, refract, reflectance, min_1, unit_vector) and state none of it again.
@@ -214,6 +214,84 @@ __device__ __forceinline__ bool nee_sample_cone(const KParams &P, const double *
     const double ns = dot(n, dv);
     if (!(ns > 0.0)) return false;                                                       // below the hit's horizon; a NaN fails this
     const double wgt = ((2.0 * k) * (double)n_lights) * ns;
+    c = (weight * ld3(emission + 3 * (size_t)li)) * wgt;
+    return true;
+}
+
+// ---- ... with the light chosen by what it can contribute at p (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) ---------------
+// The importance of list entry i at p: (r^2 / d^2) max(e) for an entry that names a sphere of both tables, emits, and does not contain p;
+// else 0.  One division, no sqrt.  i, the list, the geometry and the emission table are wave-uniform: only p is the lane's own.
+__device__ __forceinline__ double light_importance(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t i,
+                                                   const D3 &p)
+{
+    const int s = lights[i];
+    if (s < 0 || s >= P.n_spheres || !emission || s >= n_emission) return 0.0;
+    const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)s);         // centre, r^2
+    const D3 e = ld3(emission + 3 * (size_t)s);
+    const D3 wv = mk(g.x, g.y, g.z) - p;
+    const double d2 = (wv.x * wv.x + wv.y * wv.y) + wv.z * wv.z;
+    double em = e.x > e.y ? e.x : e.y;                                                   // (a NaN on the left of > is dropped, one on the
+    em = em > e.z ? em : e.z;                                                            //  right is taken and fails v > 0.0)
+    const double v = (g.w / d2) * em;
+    return (d2 > g.w && v > 0.0) ? v : 0.0;                                              // a NaN fails either test
+}
+
+// nee_sample_cone's arguments, blocks and result.  Word x of block 0 chooses the light with probability imp_j / tot instead of 1 / n_lights:
+// two walks over the list, the first for the total, the second -- the same expressions, the same running sum -- for the first entry whose
+// partial sum exceeds u01(x) tot.  Then steps 2 to 9 of the cone sample for that light, and the weight 2 k ns (tot / imp_j) in the place
+// of 2 k n_lights ns: k <= r^2 / d^2 and e / max(e) <= 1, so one sample adds at most 2 sum_i max(e_i) per unit of throughput, and with
+// one valid light tot / imp_j is exactly 1.0 and the sample is nee_sample_cone's, bit for bit.
+__device__ __forceinline__ bool nee_sample_weighted(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t n_lights,
+                                                    const D3 &p, const D3 &n, const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv,
+                                                    D3 &c, int &li)
+{
+    U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
+    double tot = 0.0;
+    for (int32_t i = 0; i < n_lights; ++i) {
+        const double imp = light_importance(P, emission, n_emission, lights, i, p);
+        if (imp > 0.0) tot += imp;
+    }
+    if (!(tot > 0.0)) return false;                                                      // no light can contribute at p
+    const double x = u01(b.x) * tot;
+    double acc = 0.0, imp_j = 0.0;
+    int32_t j = -1;
+    bool found = false;
+    for (int32_t i = 0; i < n_lights; ++i) {
+        const double imp = light_importance(P, emission, n_emission, lights, i, p);
+        if (imp > 0.0) {
+            acc += imp;
+            if (!found) { j = i; imp_j = imp; found = x < acc; }                         // (x rounded up to tot: the last positive entry stays)
+        }
+    }
+    if (j < 0) return false;                                                             // (tot > 0.0 has decided this already)
+    li = lights[j];
+    const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)li);        // centre, r^2
+    const D3 wv = mk(g.x, g.y, g.z) - p;
+    const double d2 = (wv.x * wv.x + wv.y * wv.y) + wv.z * wv.z;
+    if (!(d2 > g.w)) return false;                                                       // (so has imp_j > 0.0)
+    const double q = g.w / d2;
+    const double cm = __builtin_sqrt(1.0 - q);                                           // cos theta_max
+    const double k = q / (1.0 + cm);                                                     // 1 - cos theta_max, without the cancellation
+    const double s = u01(b.y) * k;
+    const double ct = 1.0 - s;
+    const double st = __builtin_sqrt(s * (1.0 + ct));
+    uint32_t tx = b.z, ty = b.w;
+    for (uint32_t m = 1u; !unit_disk_accepts(tx, ty); ++m) {                             // vec3.rs:59-68: a plain loop to acceptance
+        b = philox4x32_10(g_pix, g_s, ev_in, 1u + m, P.k0, P.k1);
+        tx = b.x; ty = b.y;
+    }
+    const double hx = u11(tx), hy = u11(ty);
+    const double il = 1.0 / __builtin_sqrt(hx * hx + hy * hy);                           // (the all-zero try: NaNs, which ns > 0.0 drops)
+    const double cphi = hx * il, sphi = hy * il;
+    const D3 w = wv * (1.0 / __builtin_sqrt(d2));
+    const D3 a = __builtin_fabs(w.x) > 0.9 ? mk(0.0, 1.0, 0.0) : mk(1.0, 0.0, 0.0);
+    const D3 t0 = mk(a.y * w.z - a.z * w.y, a.z * w.x - a.x * w.z, a.x * w.y - a.y * w.x);
+    const D3 t = t0 * (1.0 / __builtin_sqrt(dot(t0, t0)));
+    const D3 bt = mk(w.y * t.z - w.z * t.y, w.z * t.x - w.x * t.z, w.x * t.y - w.y * t.x);
+    dv = (t * (st * cphi) + bt * (st * sphi)) + w * ct;
+    const double ns = dot(n, dv);
+    if (!(ns > 0.0)) return false;                                                       // below the hit's horizon; a NaN fails this
+    const double wgt = ((2.0 * k) * ns) * (tot / imp_j);
     c = (weight * ld3(emission + 3 * (size_t)li)) * wgt;
     return true;
 }

@@ -459,12 +459,13 @@ class Lighting:
 
 
 def _direct_flags(sampling, direct):
-    """rt_direct.flags of sampling="area" (the light sampled by area: 0) or "cone" (by solid angle: RT_DIRECT_CONE)."""
-    if sampling not in ("area", "cone"):
-        raise ValueError(f'sampling must be "area" or "cone" (is {sampling!r})')
-    if sampling == "cone" and direct is False:
-        raise ValueError('sampling="cone" belongs to direct lighting (direct=...)')
-    return _ffi.RT_DIRECT_CONE if sampling == "cone" else 0
+    """rt_direct.flags of sampling="area" (the light sampled by area: 0), "cone" (by solid angle: RT_DIRECT_CONE) or
+    "weighted" (by solid angle, the light chosen by its contribution at the hit point: RT_DIRECT_WEIGHTED | RT_DIRECT_CONE; section 23)."""
+    if sampling not in ("area", "cone", "weighted"):
+        raise ValueError(f'sampling must be "area", "cone" or "weighted" (is {sampling!r})')
+    if sampling != "area" and direct is False:
+        raise ValueError(f'sampling="{sampling}" belongs to direct lighting (direct=...)')
+    return {"area": 0, "cone": _ffi.RT_DIRECT_CONE, "weighted": _ffi.RT_DIRECT_WEIGHTED | _ffi.RT_DIRECT_CONE}[sampling]
 
 
 def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, lighting=None, direct=False, no_direct=False, shadow_rays=None,
@@ -474,7 +475,7 @@ def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, ligh
     count, or None.  lighting: a Lighting (rt_paths_step_lit_device; its emission a float64 tensor [n, 3] on the device, or what
     Lighting.device_table makes of it), None: the unlit step.  direct: True (rt_paths_step_nee_device with the lighting's own light
     list) or a list of sphere indices / an int32 tensor on the device; no_direct: RT_STEP_NO_DIRECT; shadow_rays: an int64 tensor [1] that
-    gains the shadow rays traced, or None; sampling: "area" or "cone", how direct lighting samples a light.  No host wait."""
+    gains the shadow rays traced, or None; sampling: "area", "cone" or "weighted", how direct lighting samples a light.  No host wait."""
     import torch
     _check_queue(renderer, qin, "qin")
     _check_queue(renderer, qout, "qout")
@@ -881,8 +882,8 @@ class Renderer:
     def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0, lighting=None, direct=False,
                           no_direct=False, d_shadow_rays_ptr=0, sampling="area"):
         """rt_paths_step_device, or with a Lighting rt_paths_step_lit_device, or with direct (True: the lighting's own light list, else
-        the indices) rt_paths_step_nee_device -- no_direct: RT_STEP_NO_DIRECT; d_shadow_rays_ptr: a device u64 or 0; sampling: "area" or
-        "cone" (RT_DIRECT_CONE: the light sampled by solid angle) --; qin, qout:
+        the indices) rt_paths_step_nee_device -- no_direct: RT_STEP_NO_DIRECT; d_shadow_rays_ptr: a device u64 or 0; sampling: "area",
+        "cone" (RT_DIRECT_CONE: the light sampled by solid angle) or "weighted" (... and chosen by its contribution at the hit) --; qin, qout:
         _ffi.rt_path_queue structs of device pointers; asynchronous on `stream`."""
         direct_flags = _direct_flags(sampling, direct if lighting is not None else False)
         head = (self._h, int(seed), int(flags), float(t_min), C.byref(qin), C.byref(qout), C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
@@ -907,7 +908,8 @@ class Renderer:
         Renderer.render returns as `fix` and as stats["rays_traced"].  lighting: a Lighting (rt_render_wavefront_lit: a settable sky and
         emissive spheres), None: the unlit frame.  direct=True (rt_render_wavefront_nee: shadow rays towards the lighting's lights at
         Lambertian hits) -> (the sums, the rays traced, stats) with stats["shadow_rays"] the shadow rays traced.  sampling="cone"
-        (rt_render_wavefront_nee_sampled with RT_DIRECT_CONE): the lights are sampled by solid angle instead of by area."""
+        (rt_render_wavefront_nee_sampled with RT_DIRECT_CONE): the lights are sampled by solid angle instead of by area;
+        sampling="weighted" (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE): ... and chosen by their contribution at the hit point, not uniformly."""
         direct_flags = _direct_flags(sampling, direct if direct else False)
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         fix = np.zeros((params.height, params.width, 3), dtype=np.uint64)
@@ -939,7 +941,7 @@ class Renderer:
         """rt_render_wavefront_device on raw device pointers (d_fix [H][W][3] u64, d_rays one u64 or 0); asynchronous on `stream`.
         lighting: a Lighting (rt_render_wavefront_lit_device; its emission as in paths_step_torch), None: the unlit frame.  direct (as
         in paths_step_device): rt_render_wavefront_nee_device; d_shadow_rays_ptr: a device u64 that receives the shadow rays traced, or 0;
-        sampling: "area" or "cone", as in paths_step_device."""
+        sampling: "area", "cone" or "weighted", as in paths_step_device."""
         direct_flags = _direct_flags(sampling, direct if lighting is not None else False)
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         tail = (C.c_void_p(d_fix_ptr) if d_fix_ptr else None, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream))
