@@ -458,6 +458,19 @@ extern "C" {
     pub fn rt_render_wavefront_nee_sampled(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
                                            direct_flags: u32, fix: *mut u64, rays_traced: *mut u64, shadow_rays: *mut u64,
                                            kernel_ms: *mut f32) -> i32;
+    /// Wavefront frames over pixel lists (frame-addressed sums, RT_FLAG_ACCUMULATE) and the adaptive loop over them.
+    pub fn rt_paths_begin_pixels_device(ctx: *mut rt_context, cam: *const rt_camera, width: i32, height: i32, seed: u64, flags: u32,
+                                        spp: i32, sample_begin: i32, first_item: i64, n: i64, d_pixels: *const u32, n_pixels: i64,
+                                        q: *const rt_path_queue, stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_pixels_device(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                             direct: *const rt_direct, d_pixels: *const u32, n_pixels: i64, d_fix: *mut c_void,
+                                             d_rays: *mut c_void, d_shadow_rays: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_pixels(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                      direct: i32, direct_flags: u32, pixels: *const u32, n_pixels: i64, fix: *mut u64,
+                                      rays_traced: *mut u64, shadow_rays: *mut u64, kernel_ms: *mut f32) -> i32;
+    pub fn rt_render_wavefront_adaptive(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, a: *const rt_adaptive,
+                                        light: *const rt_lighting, direct: i32, direct_flags: u32, out_fix: *mut u64, out_half: *mut u64,
+                                        out_count: *mut u32, rays_traced: *mut u64, shadow_rays: *mut u64, kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

@@ -55,6 +55,8 @@
 // --direct-weighted: --direct-cone with the light chosen by what it can contribute at the hit point -- (r^2 / d^2) max(e) -- instead of
 // uniformly: what a frame lit by many small lights needs (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE).  The rules of
 // --direct; not together with either of the other two.
+// --wavefront ... --adaptive THRESHOLD [--step N]: the adaptive loop over the device path queue's frame (rt_render_wavefront_adaptive, DESIGN.md
+// section 24), with --sky, --emit and --direct* as without it; the resolve and the summary line are --adaptive's.  Not with --denoise.
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -393,8 +395,8 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--adaptive runs on one device and goes with none of --devices, --passes, --two-calls, --uniform53\n");
         return 2;
     }
-    if (wavefront && (!devices.empty() || adaptive || denoise || passes > 1 || two_calls || uniform53 || !features_file.empty())) {
-        std::fprintf(stderr, "--wavefront runs on one device and goes with none of --devices, --adaptive, --denoise, --passes, --two-calls, --uniform53, --features\n");
+    if (wavefront && (!devices.empty() || denoise || passes > 1 || two_calls || uniform53 || !features_file.empty())) {
+        std::fprintf(stderr, "--wavefront runs on one device and goes with none of --devices, --denoise, --passes, --two-calls, --uniform53, --features\n");
         return 2;
     }
     if (lit && !wavefront) {
@@ -452,7 +454,29 @@ int main(int argc, char **argv)
         if (rc) return die("rt_upload_scene", rc);
         std::vector<uint64_t> dn_fix;                // --denoise: the frame's sums ...
         std::vector<uint32_t> dn_count;              // ... and, with --adaptive, every pixel's own number of samples
-        if (adaptive) {
+        if (adaptive && wavefront) {             // the adaptive loop over the device path queue's frame, lit or not; then the resolve with counts
+            rt_adaptive ad{};
+            ad.step = step; ad.reserved = 0; ad.threshold = threshold; ad.dark_floor = 0.01;
+            std::vector<uint64_t> fix(npix * 3);
+            std::vector<uint32_t> count(npix);
+            const bool any_direct = direct || direct_cone || direct_weighted;
+            const uint32_t direct_flags = direct_weighted ? (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) : direct_cone ? RT_DIRECT_CONE : 0u;
+            uint64_t rays = 0, shadow = 0;
+            rc = rt_render_wavefront_adaptive(ctx, &rc_cam, &p, &ad, lit ? &light : nullptr, any_direct ? 1 : 0, direct_flags, fix.data(), nullptr,
+                                              count.data(), &rays, &shadow, &st.kernel_ms);
+            if (rc) return die("rt_render_wavefront_adaptive", rc);
+            if (any_direct) std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
+            rc = rt_resolve_rgba8_counts(ctx, fix.data(), count.data(), width, height, 1, rgba.data());
+            if (rc) return die("rt_resolve_rgba8_counts", rc);
+            uint32_t cmin = count[0], cmax = count[0];
+            uint64_t samples = 0;
+            for (uint32_t c : count) { cmin = c < cmin ? c : cmin; cmax = c > cmax ? c : cmax; samples += c; }
+            st.rays_traced = rays; st.samples = samples;
+            char note[160];
+            std::snprintf(note, sizeof(note), " adaptive threshold %g step %d: %.1f samples per pixel (min %u, max %u),", threshold, step,
+                          (double)st.samples / (double)npix, cmin, cmax);
+            count_note = note;
+        } else if (adaptive) {
             rt_adaptive ad{};
             ad.step = step; ad.reserved = 0; ad.threshold = threshold; ad.dark_floor = 0.01;
             std::vector<uint64_t> fix(npix * 3);

@@ -926,6 +926,70 @@ int rt_render_wavefront_nee_sampled(rt_context *ctx, const rt_camera *cam, const
  * p is never chosen, where the cone step chooses it and gets nothing.  The cost is two walks over the list per Lambertian hit.
  * RT_DIRECT_WEIGHTED alone (8), and every value other than 0, 2 and 10, is rejected where and how an unknown flag was. */
 
+/* ---- wavefront frames over pixel lists, accumulated and adaptively sampled ------- */
+
+/* rt_paths_begin_device over a LIST: slot k in [0, n) becomes item first_item + k of n_pixels listed pixels with spp samples each,
+ * list-major: idx = item / spp, pixel = d_pixels[idx], sample = sample_begin + item % spp; origin, dir and event are rt_camera_rays' for
+ * that (pixel, sample) over the FULL frame's width - 1, height - 1; throughput (1, 1, 1); *q->count = n.  Slots at or past n keep their
+ * bytes.  d_pixels: device [n_pixels] u32 global pixel numbers g = j * width + i, any order, duplicates allowed.  A device list cannot be
+ * validated on the host: a listed g >= width * height yields a path with that pixel word and the camera ray of (g % width, g / width), for
+ * which the steps add nothing (their pixel >= npix rule); every bit pattern means something and nothing is read or written outside a
+ * buffer.  Needs first_item + n <= n_pixels * spp.  RT_ERR_INVALID_ARGUMENT: rt_paths_begin_device's checks in their order, the items
+ * measured against n_pixels * spp; then, still before the context, a NULL list with n_pixels != 0; then n_pixels outside [0, 2^31 - 1].
+ * Needs no uploaded scene. */
+int rt_paths_begin_pixels_device(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, uint32_t flags, int32_t spp,
+                                 int32_t sample_begin, int64_t first_item, int64_t n, const uint32_t *d_pixels, int64_t n_pixels,
+                                 const rt_path_queue *q, void *stream);
+
+/* The frame of rt_render_wavefront*_device for the listed pixels only, optionally ADDED to what the buffers hold: ONE driver for the
+ * unlit, the lit and the NEE frame.  light == NULL: the unlit step (the reference's sky, no lights); direct == NULL: no direct lighting;
+ * direct without light is rejected (light is NULL); direct->flags chooses the light sample as in rt_render_wavefront_nee_device.
+ * d_pixels as above; d_pixels == NULL is the identity list 0, 1, ..., width * height - 1, and n_pixels must then be width * height: a
+ * dense frame that can accumulate.  The n_pixels * spp items go in batches of RTIOW_WAVEFRONT_BATCH, per batch one begin over the list
+ * and max_depth steps, the last with RT_STEP_NO_DIRECT, between the context's two queues; sample_begin is honoured; no host wait.
+ *
+ * d_fix is FRAME-ADDRESSED: [height][width][3] u64, and listed pixel g adds into entry g -- unlike rt_render_pixels_device, whose output
+ * is COMPACT (entry k belongs to d_pixels[k]).  An entry of an unlisted pixel is zeroed or kept like the rest and gains nothing.  A
+ * pixel listed m times receives its samples' sums m times.  A listed g >= width * height adds nothing and costs its rays, which
+ * d_rays and d_shadow_rays count.  Sample s of listed pixel g is the sample the dense frame gives that pixel, and the sums are exact
+ * integers: a list frame, a resumed frame and a dense frame of the same samples hold the same bits.
+ *
+ * p->flags: 0 or RT_FLAG_ACCUMULATE.  Without the flag d_fix (the whole frame), *d_rays and *d_shadow_rays are zeroed first; with it
+ * nothing is zeroed and all three are added to.  n_pixels == 0 (with a list) succeeds and does nothing but that zeroing.
+ *
+ * RT_ERR_INVALID_ARGUMENT, found before anything is touched: the context-free checks of rt_render_wavefront_device in their order
+ * (RT_FLAG_ACCUMULATE passes; every other flag and shard_count != 1 are rejected as there); with a light or a direct, the lighting checks
+ * of the lit form; with a direct, the direct checks of the NEE form; then d_pixels == NULL with n_pixels != width * height; n_pixels
+ * outside [0, 2^31 - 1]; in the host form a listed number >= width * height; then the context checks, the table's length and the list's
+ * length as in the NEE form.
+ *
+ * The host form: light as in rt_render_wavefront_lit (emission a HOST pointer), or NULL; direct != 0 samples the lights of that table
+ * (rt_light_list) with direct_flags as in rt_render_wavefront_nee_sampled (direct == 0: direct_flags must be 0, checked first); pixels: host
+ * [n_pixels] u32 or NULL.  With RT_FLAG_ACCUMULATE fix, *rays_traced and *shadow_rays are copied in first and come back added to.
+ * rays_traced, shadow_rays and kernel_ms may be NULL.  Synchronous. */
+int rt_render_wavefront_pixels_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_direct *direct,
+                                      const uint32_t *d_pixels, int64_t n_pixels, void *d_fix, void *d_rays, void *d_shadow_rays, void *stream);
+int rt_render_wavefront_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, int32_t direct,
+                               uint32_t direct_flags, const uint32_t *pixels, int64_t n_pixels, uint64_t *fix, uint64_t *rays_traced,
+                               uint64_t *shadow_rays, float *kernel_ms);
+
+/* rt_render_adaptive's loop and rule, unchanged, over the wavefront frame: the same rt_adaptive, the same rt_select_pixels_device, the
+ * same out_fix / out_half / out_count (out_half holds the EVEN-numbered passes and may be NULL; a pixel that leaves the active set never
+ * returns), one word of host read-back per round.  Round 1 renders every pixel; pass k of a later round renders samples
+ * [n + k step, n + (k + 1) step) of the active list through the driver above.  light, direct and direct_flags as in
+ * rt_render_wavefront_pixels.  rays_traced, shadow_rays (both summed over the passes) and kernel_ms (the rounds' device time, the
+ * selections included) may be NULL.  The samples rendered are the sum of out_count.  Synchronous.
+ *
+ * RT_ERR_INVALID_ARGUMENT, before anything is touched: NULL cam, params, out_fix or out_count; the parameter and rt_adaptive validation
+ * of rt_render_adaptive; sample_begin != 0; spp not a multiple of 2 * step, or > 32766; direct_flags != 0 with direct == 0; then flags != 0, shard_count != 1 and t_min as
+ * in rt_render_wavefront; then the lighting and the direct checks as above; then the one rejection of its own: with direct lighting a
+ * sample adds up to max_depth clamped terms of at most 2^48 each (max_depth - 1 light samples and one terminal term), so the selection's
+ * signed differences need spp * max_depth * 2^48 < 2^63, and (int64)spp * max_depth > 32767 is rejected when direct != 0; then the
+ * context checks. */
+int rt_render_wavefront_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_adaptive *a, const rt_lighting *light,
+                                 int32_t direct, uint32_t direct_flags, uint64_t *out_fix, uint64_t *out_half, uint32_t *out_count,
+                                 uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

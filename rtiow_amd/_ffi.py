@@ -177,6 +177,15 @@ SYMBOLS = [
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("rt_render_wavefront_nee_sampled", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), C.c_uint32, _VP,
                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("rt_paths_begin_pixels_device", C.c_int, [_VP, C.POINTER(rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_int64,
+                                               C.c_int64, _VP, C.c_int64, C.POINTER(rt_path_queue), _VP]),
+    ("rt_render_wavefront_pixels_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), C.POINTER(rt_direct), _VP,
+                                                    C.c_int64, _VP, _VP, _VP, _VP]),
+    ("rt_render_wavefront_pixels", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), C.c_int32, C.c_uint32, _VP,
+                                             C.c_int64, _VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    ("rt_render_wavefront_adaptive", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive), C.POINTER(rt_lighting),
+                                               C.c_int32, C.c_uint32, _VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "rt_host.hpp"
+#include "rt_adaptive_check.hpp"
 
 using namespace rt_host;
 
@@ -145,9 +146,7 @@ __global__ void stats_accumulate_kernel(const unsigned long long *__restrict__ s
 
 } // namespace rt
 
-namespace {
-
-int validate_adaptive(const rt_adaptive *a)
+int rt_host::validate_adaptive(const rt_adaptive *a)
 {
     if (!a) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive is NULL");
     if (a->step < 1) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive.step must be >= 1 (is %d)", a->step);
@@ -158,7 +157,7 @@ int validate_adaptive(const rt_adaptive *a)
     return RT_OK;
 }
 
-constexpr int kAdaptiveMaxSpp = 32766;     // n * 2^48 < 2^63: the half-buffer differences fit a signed 64-bit integer whatever the scene
+namespace {
 
 int validate_select(const void *fix, const void *half, const void *count, int32_t width, int32_t height, int32_t n, const rt_adaptive *a,
                     const void *list_out, const void *n_out)

@@ -1,8 +1,11 @@
 // rt_paths.hip -- the device path queue: a fused bounce step on device-resident paths and the frame rendered from it (rtiow_hip.h, "path
 // queue").
 //
-// The eleventh translation unit of librtiow_hip.so.  Eight kernels of its own:
+// The eleventh translation unit of librtiow_hip.so.  Ten kernels of its own:
 //   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
+//   path_begin_pixels_kernel  the same over a list of pixels: item -> (list index, sample), the pixel read from the list (rtiow_hip.h,
+//                         "wavefront frames over pixel lists").
+//   pass_add_listed_kernel  rt_render_wavefront_adaptive's: an even pass's frame-addressed sums into fix and half at the listed pixels.
 //   bounce_kernel         one wave per 64 consecutive slots, grid-stride over the live slots: closest hit (first_hit_wave<false> whole, the
 //                         record in registers), then the sky add of a miss or Scatter::scatter -- both from rt_shade_core.hpp --; the new
 //                         state is written IN PLACE, and per wave the number of survivors and their ballot go to the queue's scratch.
@@ -30,6 +33,7 @@
 #include <vector>
 
 #include "rt_host.hpp"
+#include "rt_adaptive_check.hpp"
 #include "rt_first_hit.hpp"
 #include "rt_shade_core.hpp"
 
@@ -78,6 +82,49 @@ __global__ __launch_bounds__(kPathBlock) void path_begin_kernel(const KCamera ca
         store3(Q.origin, k, origin);
         store3(Q.dir, k, dir);
         Q.thr[3 * k] = 1.0; Q.thr[3 * k + 1] = 1.0; Q.thr[3 * k + 2] = 1.0;
+    }
+}
+
+// ... over a list (rt_paths_begin_pixels_device): item -> (list index, sample), the pixel from the list.  The host
+// has checked first_item + n <= n_pixels * spp, so every read of `pixels` lies inside the list; the pixel word itself is not looked at:
+// one at or past width * height gets the camera ray of (g % width, g / width) and adds nothing in the steps.
+__global__ __launch_bounds__(kPathBlock) void path_begin_pixels_kernel(const KCamera cam, const QueueArrays Q, const BeginArgs A,
+                                                                       const uint32_t *__restrict__ pixels)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *Q.count = (uint32_t)A.n;
+    const double wm1 = (double)(A.width - 1), hm1 = (double)(A.height - 1);
+    const long long stride = (long long)gridDim.x * kPathBlock;
+    for (long long k = (long long)blockIdx.x * kPathBlock + threadIdx.x; k < A.n; k += stride) {
+        const unsigned long long item = (unsigned long long)(A.first_item + k);
+        const unsigned long long idx = item / A.spp;                    // list-major: item = index * spp + sample
+        const uint32_t g_pix = pixels[idx], g_s = A.sample_begin + (uint32_t)(item - idx * A.spp);
+        D3 origin, dir;
+        const uint32_t ev = sample_ray(cam, (uint32_t)A.width, wm1, hm1, g_pix, g_s, A.k0, A.k1, origin, dir);
+        Q.pixel[k] = g_pix; Q.sample[k] = g_s; Q.event[k] = ev;
+        store3(Q.origin, k, origin);
+        store3(Q.dir, k, dir);
+        Q.thr[3 * k] = 1.0; Q.thr[3 * k + 1] = 1.0; Q.thr[3 * k + 2] = 1.0;
+    }
+}
+
+// An even-numbered pass of rt_render_wavefront_adaptive, rendered into a frame-addressed pass buffer, back into the frame's state at the
+// listed pixels (a selection's list: ascending, no duplicates, every entry inside the frame): fix += pass, half += pass, the entries read
+// are zeroed for the next round, count += count_add (the round's two passes: the odd one goes straight into fix).
+__global__ __launch_bounds__(256) void pass_add_listed_kernel(const uint32_t *__restrict__ list, uint32_t n_list, unsigned long long *__restrict__ pass,
+                                                              unsigned long long *__restrict__ fix, unsigned long long *__restrict__ half,
+                                                              uint32_t *__restrict__ count, uint32_t count_add, uint32_t npix)
+{
+    const uint32_t stride = gridDim.x * 256u;
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n_list; k += stride) {
+        const size_t g = list[k];
+        if (g >= (size_t)npix) continue;                                // (cannot happen; a store never leaves the frame whatever the list holds)
+        for (int c = 0; c < 3; ++c) {
+            const unsigned long long v = pass[g * 3u + c];
+            pass[g * 3u + c] = 0ull;
+            fix[g * 3u + c] += v;
+            half[g * 3u + c] += v;
+        }
+        count[g] += count_add;
     }
 }
 
@@ -405,10 +452,36 @@ int check_direct_count(const rt_context *ctx, const char *what, const NeeCall *n
     return RT_OK;
 }
 
-int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint32_t flags, int32_t spp, int32_t sample_begin,
-                int64_t first_item, int64_t n, const rt_path_queue *q)
+// A list of global pixel numbers as an entry point was handed it.  identity_ok: a NULL list stands for 0, 1, ...,
+// width * height - 1 and n_pixels must be that many (the frame forms); else a NULL list must be empty (the begin).  host: the call may
+// read the entries.
+constexpr int64_t kMaxListed = 0x7fffffffLL;
+
+struct PixelList {
+    const uint32_t *pixels;
+    int64_t n_pixels;
+    bool identity_ok, host;
+};
+
+int check_list(const char *what, const PixelList &list, long long npix)
 {
-    const char *what = "rt_paths_begin";
+    if (!list.pixels && list.identity_ok && list.n_pixels != npix)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: n_pixels must be width * height = %lld when the list is NULL (is %lld)", what, npix, (long long)list.n_pixels);
+    if (!list.pixels && !list.identity_ok && list.n_pixels != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: n_pixels must be 0 when the list is NULL (is %lld)", what, (long long)list.n_pixels);
+    if (list.n_pixels < 0 || list.n_pixels > kMaxListed)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: n_pixels must be in [0, 2^31 - 1] (is %lld)", what, (long long)list.n_pixels);
+    if (list.host && list.pixels)
+        for (int64_t k = 0; k < list.n_pixels; ++k)
+            if ((long long)list.pixels[k] >= npix)
+                return fail(RT_ERR_INVALID_ARGUMENT, "%s: pixels[%lld] = %u lies outside the frame of %lld pixels", what, (long long)k, list.pixels[k], npix);
+    return RT_OK;
+}
+
+// list: NULL for rt_paths_begin_device, whose items are the frame's; else the items are the list's
+int check_begin(const rt_context *ctx, const char *what, const rt_camera *cam, int32_t width, int32_t height, uint32_t flags, int32_t spp,
+                int32_t sample_begin, int64_t first_item, int64_t n, const rt_path_queue *q, const PixelList *list = nullptr)
+{
     RT_NEED(cam, what, "cam");
     if (int rc = check_queue(what, "queue", q)) return rc;
     if (n < 0 || n > q->capacity)
@@ -418,10 +491,16 @@ int check_begin(const rt_context *ctx, const rt_camera *cam, int32_t width, int3
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: width * height does not fit the 32-bit Philox pixel counter", what);
     if (spp < 1 || sample_begin < 0 || (long long)spp + sample_begin > 0x7fffffffLL)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: spp must be >= 1, sample_begin >= 0 and spp + sample_begin <= 2^31 - 1 (are %d, %d)", what, spp, sample_begin);
-    if (first_item < 0 || first_item + n > (long long)width * height * spp)
+    if (!list && (first_item < 0 || first_item + n > (long long)width * height * spp))
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: the items [first_item, first_item + n) must lie in [0, width * height * spp) (first_item %lld, n %lld)",
                     what, (long long)first_item, (long long)n);
+    // (a count outside [0, 2^31 - 1] has its own message below; inside it n_pixels * spp < 2^62)
+    if (list && (first_item < 0 || (list->n_pixels >= 0 && list->n_pixels <= kMaxListed && first_item + n > list->n_pixels * spp)))
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: the items [first_item, first_item + n) must lie in [0, n_pixels * spp) (first_item %lld, n %lld, n_pixels %lld)",
+                    what, (long long)first_item, (long long)n, (long long)list->n_pixels);
     if (int rc = check_no_flags(what, flags, kNoun)) return rc;
+    if (list)
+        if (int rc = check_list(what, *list, (long long)width * height)) return rc;
     return check_context(ctx, what, true, false);
 }
 
@@ -461,16 +540,17 @@ rt::QueueArrays arrays_of(const rt_path_queue *q)
     return a;
 }
 
-// (validated arguments from here on)
+// (validated arguments from here on)  d_pixels: NULL launches path_begin_kernel (the items are the frame's), else path_begin_pixels_kernel
 int launch_begin(const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, int32_t spp, int32_t sample_begin, int64_t first_item, int64_t n,
-                 const rt_path_queue *q, hipStream_t stream)
+                 const rt_path_queue *q, hipStream_t stream, const uint32_t *d_pixels = nullptr)
 {
     rt::BeginArgs a;
     memset(&a, 0, sizeof(a));
     a.n = (long long)n; a.first_item = (long long)first_item; a.spp = (uint32_t)spp; a.sample_begin = (uint32_t)sample_begin;
     a.width = width; a.height = height; a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
     // (at least one workgroup: an empty batch still writes the count)
-    hipLaunchKernelGGL(rt::path_begin_kernel, dim3(paths_grid(grid_256(a.n))), dim3(rt::kPathBlock), 0, stream, to_kcamera(cam), arrays_of(q), a);
+    if (!d_pixels) hipLaunchKernelGGL(rt::path_begin_kernel, dim3(paths_grid(grid_256(a.n))), dim3(rt::kPathBlock), 0, stream, to_kcamera(cam), arrays_of(q), a);
+    else hipLaunchKernelGGL(rt::path_begin_pixels_kernel, dim3(paths_grid(grid_256(a.n))), dim3(rt::kPathBlock), 0, stream, to_kcamera(cam), arrays_of(q), a, d_pixels);
     RT_HIP(hipGetLastError());
     return RT_OK;
 }
@@ -551,37 +631,57 @@ long long batch_items()
     return v > kMaxCapacity ? (long long)kMaxCapacity : v;
 }
 
-// lit / light / host_table / nee as in check_step and check_light
+// the part of a frame's checks that every frame form has first; accumulate_ok: RT_FLAG_ACCUMULATE passes (the list forms)
+int check_frame_params(const char *what, const rt_params *p, bool accumulate_ok)
+{
+    if (accumulate_ok && !(p->flags & RT_FLAG_UNIFORM53)) {
+        if (p->flags & ~RT_FLAG_ACCUMULATE)
+            return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown flags 0x%x (only 0 and RT_FLAG_ACCUMULATE are legal)", what, p->flags);
+    } else if (int rc = check_no_flags(what, p->flags, kNoun)) return rc;
+    if (p->shard_count != 1) return fail(RT_ERR_INVALID_ARGUMENT, "%s: shard_count must be 1 (is %d)", what, p->shard_count);
+    if (!std::isfinite(p->t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, p->t_min);
+    return RT_OK;
+}
+
+// lit / light / host_table / nee as in check_step and check_light; list: the list forms' (RT_FLAG_ACCUMULATE passes), NULL for the others;
+// extra: a check of the caller's own between the context-free ones and the context's (rt_render_wavefront_adaptive), or NULL
 int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const void *fix, bool lit = false,
-                 const rt_lighting *light = nullptr, bool host_table = false, const NeeCall *nee = nullptr)
+                 const rt_lighting *light = nullptr, bool host_table = false, const NeeCall *nee = nullptr, const PixelList *list = nullptr,
+                 int (*extra)(const char *, const rt_params *, bool) = nullptr)
 {
     RT_NEED(cam, what, "cam");
     RT_NEED(p, what, "params");
     RT_NEED(fix, what, "fix");
     if (int rc = validate_params(p)) return rc;
-    if (int rc = check_no_flags(what, p->flags, kNoun)) return rc;
-    if (p->shard_count != 1) return fail(RT_ERR_INVALID_ARGUMENT, "%s: shard_count must be 1 (is %d)", what, p->shard_count);
-    if (!std::isfinite(p->t_min)) return fail(RT_ERR_INVALID_ARGUMENT, "%s: t_min must be > 0 and finite (is %g)", what, p->t_min);
+    if (int rc = check_frame_params(what, p, list != nullptr)) return rc;
     if (lit)
         if (int rc = check_light(what, light, host_table)) return rc;
     if (nee)
         if (int rc = check_direct(what, nee)) return rc;
+    if (list)
+        if (int rc = check_list(what, *list, (long long)p->width * p->height)) return rc;
+    if (extra)
+        if (int rc = extra(what, p, nee != nullptr)) return rc;
     if (int rc = check_context(ctx, what, true, true)) return rc;
     if (lit)
         if (int rc = check_light_count(ctx, what, light)) return rc;
     return nee ? check_direct_count(ctx, what, nee) : RT_OK;
 }
 
-// The frame of both device forms (validated arguments): per batch one begin, then max_depth steps from one queue to the other; nothing
+// The frame of every device form (validated arguments): per batch one begin, then max_depth steps from one queue to the other; nothing
 // here waits for the device.  (A step on an empty queue leaves at once; what the empty steps of a batch cost is in profiles/paths.txt.)
-// nee: the frame's direct lighting (step_flags 0); the LAST step of a batch runs with RT_STEP_NO_DIRECT
-int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const NeeCall *nee, void *d_fix, void *d_rays,
-                 hipStream_t stream)
+// nee: the frame's direct lighting (step_flags 0); the LAST step of a batch runs with RT_STEP_NO_DIRECT.
+// d_pixels / n_pixels: the pixels whose samples are rendered -- NULL: all width * height of them, in order --;
+// d_fix is frame-addressed either way.  p->flags & RT_FLAG_ACCUMULATE: nothing is zeroed, the sums and both counters are added to.
+int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const NeeCall *nee, const uint32_t *d_pixels,
+                 long long n_pixels, void *d_fix, void *d_rays, hipStream_t stream)
 {
-    const long long npix = (long long)p->width * p->height, total = npix * p->spp;
-    RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(uint64_t), stream));
-    if (d_rays) RT_HIP(hipMemsetAsync(d_rays, 0, sizeof(uint64_t), stream));
-    if (nee && nee->d_shadow_rays) RT_HIP(hipMemsetAsync(nee->d_shadow_rays, 0, sizeof(uint64_t), stream));
+    const long long npix = (long long)p->width * p->height, total = n_pixels * p->spp;
+    if (!(p->flags & RT_FLAG_ACCUMULATE)) {
+        RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(uint64_t), stream));
+        if (d_rays) RT_HIP(hipMemsetAsync(d_rays, 0, sizeof(uint64_t), stream));
+        if (nee && nee->d_shadow_rays) RT_HIP(hipMemsetAsync(nee->d_shadow_rays, 0, sizeof(uint64_t), stream));
+    }
     if (total == 0) return RT_OK;
     const long long batch = batch_items() < total ? batch_items() : total;
     const OwnedQueues own(batch);
@@ -591,7 +691,7 @@ int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, cons
     if (nee) { last = *nee; last.step_flags = RT_STEP_NO_DIRECT; }
     for (long long first = 0; first < total; first += batch) {
         const long long n = total - first < batch ? total - first : batch;
-        if (int rc = launch_begin(cam, p->width, p->height, p->seed, p->spp, p->sample_begin, first, n, &q[0], stream)) return rc;
+        if (int rc = launch_begin(cam, p->width, p->height, p->seed, p->spp, p->sample_begin, first, n, &q[0], stream, d_pixels)) return rc;
         for (int depth = 0; depth < p->max_depth; ++depth) {
             const NeeCall *step_nee = nee && depth + 1 == p->max_depth ? &last : nee;
             if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, light, step_nee, stream)) return rc;
@@ -603,26 +703,32 @@ int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, cons
 // The body of the four host frames.  mode: kUnlit (light is not looked at), kLit, or kNee: the frame samples its lights directly, their
 // list rebuilt from the table the call can see.  The counters are counted whether or not the caller asks; a frame without direct lighting
 // has no shadow counter (shadow_rays NULL: absent).
+// pixel_list: the list form's host list (rt_render_wavefront_pixels), NULL for the four dense frames; with it RT_FLAG_ACCUMULATE passes, and
+// the sums and the counters the caller gave are then copied in first.
 int render_frame_host(rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const rt_lighting *light, int mode, uint64_t *fix,
-                      uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms, uint32_t direct_flags = 0u)
+                      uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms, uint32_t direct_flags = 0u, const PixelList *pixel_list = nullptr)
 {
     const bool lit = mode >= rt::kLit, direct = mode == rt::kNee;
     // (direct_flags: the flags of the list this frame builds; checked where a device form checks direct->flags)
     const rt_direct no_list = {nullptr, 0, direct_flags};
     const NeeCall flags_only = {&no_list, 0u, nullptr};
-    if (int rc = check_render(ctx, what, cam, p, fix, lit, light, true, direct ? &flags_only : nullptr)) return rc;
+    if (int rc = check_render(ctx, what, cam, p, fix, lit, light, true, direct ? &flags_only : nullptr, pixel_list)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
     const double *table = lit ? light->emission : nullptr;
     const size_t n_table = table ? (size_t)light->n_emission : 0;
     std::vector<int32_t> list(direct ? n_table : 0);
     int32_t n_lights = 0;
     if (int rc = rt_light_list(table, (int32_t)list.size(), list.data(), &n_lights)) return rc;
+    const bool adds = (p->flags & RT_FLAG_ACCUMULATE) != 0u;          // (only a list form gets here with the flag)
+    const size_t n_sums = (size_t)p->width * p->height * 3;
     Stage st(ctx);
-    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
-    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);
-    const auto shadow = direct && !shadow_rays ? st.scratch<uint64_t>(1) : st.out(shadow_rays, 1);
+    const auto sums = adds ? st.inout(fix, n_sums) : st.out(fix, n_sums);
+    const auto rays = !rays_traced ? st.scratch<uint64_t>(1) : adds ? st.inout(rays_traced, 1) : st.out(rays_traced, 1);
+    const auto shadow = direct && !shadow_rays ? st.scratch<uint64_t>(1) : adds ? st.inout(shadow_rays, 1) : st.out(shadow_rays, 1);
     const auto emission = st.in(table, n_table * 3);
     const auto lights = st.in(static_cast<const int32_t *>(list.data()), (size_t)n_lights);
+    const auto pixels = st.in(pixel_list ? pixel_list->pixels : nullptr, pixel_list && pixel_list->pixels ? (size_t)pixel_list->n_pixels : 0);
+    const long long n_pixels = pixel_list ? (long long)pixel_list->n_pixels : (long long)p->width * p->height;
     if (int rc = st.commit()) return rc;
     RT_HIP(st.upload());
     rt_lighting dev = lit ? *light : rt_lighting{};     // the same lighting with the table on the device
@@ -632,9 +738,29 @@ int render_frame_host(rt_context *ctx, const char *what, const rt_camera *cam, c
     if (!on_device.lights) on_device.n_lights = 0;
     const NeeCall nee = {&on_device, 0u, st.ptr(shadow)};
     return timed_section(ctx, what, kernel_ms, st, [&] {
-        return render_frame(ctx, cam, p, lit ? &dev : nullptr, direct ? &nee : nullptr, st.ptr(sums), st.ptr(rays), ctx->own_stream);
+        return render_frame(ctx, cam, p, lit ? &dev : nullptr, direct ? &nee : nullptr, st.ptr(pixels), n_pixels, st.ptr(sums), st.ptr(rays), ctx->own_stream);
     });
 }
+
+// rt_render_wavefront_adaptive's own rejection, between the context-free checks of the frame and the context's (check_render's `extra`)
+int check_adaptive_terms(const char *what, const rt_params *p, bool direct)
+{
+    if (direct && (long long)p->spp * p->max_depth > 32767)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: with direct lighting a sample adds up to max_depth terms of at most 2^48, and the selection's signed "
+                    "differences need spp * max_depth * 2^48 < 2^63: spp * max_depth must be <= 32767 (is %lld)", what, (long long)p->spp * p->max_depth);
+    return RT_OK;
+}
+
+// a pair of events around each round of rt_render_wavefront_adaptive, destroyed on every path
+struct RoundTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0.0f;
+    ~RoundTimer()
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
 
 } // namespace
 
@@ -649,7 +775,7 @@ int64_t rt_path_scratch_words(int64_t capacity)
 int rt_paths_begin_device(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, uint32_t flags, int32_t spp,
                           int32_t sample_begin, int64_t first_item, int64_t n, const rt_path_queue *q, void *stream_v)
 {
-    if (int rc = check_begin(ctx, cam, width, height, flags, spp, sample_begin, first_item, n, q)) return rc;
+    if (int rc = check_begin(ctx, "rt_paths_begin", cam, width, height, flags, spp, sample_begin, first_item, n, q)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
     return launch_begin(cam, width, height, seed, spp, sample_begin, first_item, n, q, (hipStream_t)stream_v);
 }
@@ -684,7 +810,7 @@ int rt_render_wavefront_device(rt_context *ctx, const rt_camera *cam, const rt_p
 {
     if (int rc = check_render(ctx, "rt_render_wavefront", cam, p, d_fix)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return render_frame(ctx, cam, p, nullptr, nullptr, d_fix, d_rays, (hipStream_t)stream_v);
+    return render_frame(ctx, cam, p, nullptr, nullptr, nullptr, (long long)p->width * p->height, d_fix, d_rays, (hipStream_t)stream_v);
 }
 
 int rt_render_wavefront_lit_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, void *d_fix, void *d_rays,
@@ -692,7 +818,7 @@ int rt_render_wavefront_lit_device(rt_context *ctx, const rt_camera *cam, const 
 {
     if (int rc = check_render(ctx, "rt_render_wavefront_lit", cam, p, d_fix, true, light, false)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return render_frame(ctx, cam, p, light, nullptr, d_fix, d_rays, (hipStream_t)stream_v);
+    return render_frame(ctx, cam, p, light, nullptr, nullptr, (long long)p->width * p->height, d_fix, d_rays, (hipStream_t)stream_v);
 }
 
 int rt_render_wavefront_nee_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_direct *direct,
@@ -701,7 +827,148 @@ int rt_render_wavefront_nee_device(rt_context *ctx, const rt_camera *cam, const 
     const NeeCall nee = {direct, 0u, d_shadow_rays};
     if (int rc = check_render(ctx, "rt_render_wavefront_nee", cam, p, d_fix, true, light, false, &nee)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    return render_frame(ctx, cam, p, light, &nee, d_fix, d_rays, (hipStream_t)stream_v);
+    return render_frame(ctx, cam, p, light, &nee, nullptr, (long long)p->width * p->height, d_fix, d_rays, (hipStream_t)stream_v);
+}
+
+int rt_paths_begin_pixels_device(rt_context *ctx, const rt_camera *cam, int32_t width, int32_t height, uint64_t seed, uint32_t flags, int32_t spp,
+                                 int32_t sample_begin, int64_t first_item, int64_t n, const uint32_t *d_pixels, int64_t n_pixels,
+                                 const rt_path_queue *q, void *stream_v)
+{
+    const PixelList list = {d_pixels, n_pixels, false, false};
+    if (int rc = check_begin(ctx, "rt_paths_begin_pixels", cam, width, height, flags, spp, sample_begin, first_item, n, q, &list)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    // (an empty list: n is 0, and the frame's kernel writes the count without a list to read)
+    return launch_begin(cam, width, height, seed, spp, sample_begin, first_item, n, q, (hipStream_t)stream_v, d_pixels);
+}
+
+int rt_render_wavefront_pixels_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_direct *direct,
+                                      const uint32_t *d_pixels, int64_t n_pixels, void *d_fix, void *d_rays, void *d_shadow_rays, void *stream_v)
+{
+    const char *what = "rt_render_wavefront_pixels";
+    const NeeCall nee = {direct, 0u, d_shadow_rays};
+    const PixelList list = {d_pixels, n_pixels, true, false};
+    if (int rc = check_render(ctx, what, cam, p, d_fix, light || direct, light, false, direct ? &nee : nullptr, &list)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    // (a frame without direct lighting traces no shadow ray: its counter is zeroed like the others and gains nothing)
+    if (!direct && d_shadow_rays && !(p->flags & RT_FLAG_ACCUMULATE)) RT_HIP(hipMemsetAsync(d_shadow_rays, 0, sizeof(uint64_t), stream));
+    return render_frame(ctx, cam, p, light, direct ? &nee : nullptr, d_pixels, (long long)n_pixels, d_fix, d_rays, stream);
+}
+
+int rt_render_wavefront_pixels(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, int32_t direct,
+                               uint32_t direct_flags, const uint32_t *pixels, int64_t n_pixels, uint64_t *fix, uint64_t *rays_traced,
+                               uint64_t *shadow_rays, float *kernel_ms)
+{
+    const char *what = "rt_render_wavefront_pixels";
+    const PixelList list = {pixels, n_pixels, true, true};
+    const int mode = direct ? rt::kNee : light ? rt::kLit : rt::kUnlit;
+    if (!direct && direct_flags)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct_flags must be 0 without direct lighting (is 0x%x)", what, direct_flags);
+    const bool adds = p && (p->flags & RT_FLAG_ACCUMULATE);
+    const int rc = render_frame_host(ctx, what, cam, p, light, mode, fix, rays_traced, direct ? shadow_rays : nullptr, kernel_ms, direct_flags, &list);
+    if (!rc && !direct && shadow_rays && !adds) *shadow_rays = 0;
+    return rc;
+}
+
+int rt_render_wavefront_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_adaptive *a, const rt_lighting *light,
+                                 int32_t direct, uint32_t direct_flags, uint64_t *out_fix, uint64_t *out_half, uint32_t *out_count,
+                                 uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms)
+{
+    const char *what = "rt_render_wavefront_adaptive";
+    RT_NEED(cam, what, "cam");
+    RT_NEED(p, what, "params");
+    RT_NEED(out_fix, what, "out_fix");
+    RT_NEED(out_count, what, "out_count");
+    if (int rc = validate_params(p)) return rc;
+    if (int rc = validate_adaptive(a)) return rc;
+    if (p->sample_begin != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s numbers its own passes: sample_begin must be 0 (is %d)", what, p->sample_begin);
+    if (p->spp < 2 * (long long)a->step || p->spp % (2 * (long long)a->step) != 0 || p->spp > kAdaptiveMaxSpp)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: spp = %d (the most samples a pixel may get) must be a multiple of 2 * step = %lld and <= %d", what,
+                    p->spp, 2 * (long long)a->step, kAdaptiveMaxSpp);
+    if (!direct && direct_flags)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct_flags must be 0 without direct lighting (is 0x%x)", what, direct_flags);
+    const bool lit = light || direct;
+    const rt_direct no_list = {nullptr, 0, direct_flags};
+    const NeeCall flags_only = {&no_list, 0u, nullptr};
+    if (int rc = check_render(ctx, what, cam, p, out_fix, lit, light, true, direct ? &flags_only : nullptr, nullptr, check_adaptive_terms)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->own_stream;
+    const double *table = lit ? light->emission : nullptr;
+    const size_t n_table = table ? (size_t)light->n_emission : 0;
+    std::vector<int32_t> light_list(direct ? n_table : 0);
+    int32_t n_lights = 0;
+    if (int rc = rt_light_list(table, (int32_t)light_list.size(), light_list.data(), &n_lights)) return rc;
+    // the frame's state, all on the device: fix | half | the even pass's frame-addressed sums | count | list | the two counters | the list's length
+    const size_t npix = (size_t)p->width * p->height;
+    uint64_t counters[2] = {0, 0};
+    Stage st(ctx);
+    const auto fix = st.out(out_fix, npix * 3);
+    const auto half = out_half ? st.out(out_half, npix * 3) : st.scratch<uint64_t>(npix * 3);       // (the selection reads it either way)
+    const auto pass = st.scratch<uint64_t>(npix * 3);
+    const auto count = st.out(out_count, npix);
+    const auto list = st.scratch<uint32_t>(npix);
+    const auto totals = st.out(counters, 2);
+    const auto length = st.scratch<uint32_t>(1);
+    const auto emission = st.in(table, n_table * 3);
+    const auto lights = st.in(static_cast<const int32_t *>(light_list.data()), (size_t)n_lights);
+    if (int rc = st.commit()) return rc;
+    RT_HIP(st.upload());
+    uint64_t *d_fix = st.ptr(fix), *d_half = st.ptr(half), *d_pass = st.ptr(pass), *d_totals = st.ptr(totals);
+    uint32_t *d_count = st.ptr(count), *d_list = st.ptr(list), *d_n = st.ptr(length);
+    rt_lighting dev = lit ? *light : rt_lighting{};     // the same lighting with the table on the device
+    dev.emission = st.ptr(emission);
+    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }
+    rt_direct on_device = {st.ptr(lights), n_lights, direct_flags};
+    if (!on_device.lights) on_device.n_lights = 0;
+    const NeeCall nee = {&on_device, 0u, d_totals + 1};
+    const rt_lighting *frame_light = lit ? &dev : nullptr;
+    const NeeCall *frame_nee = direct ? &nee : nullptr;
+
+    RoundTimer timer;
+    RT_HIP(hipEventCreate(&timer.e0));
+    RT_HIP(hipEventCreate(&timer.e1));
+    const uint32_t step = (uint32_t)a->step;
+    rt_params q = *p;
+    q.spp = (int32_t)step;
+    // round 1: every pixel.  Pass 0 -> fix (which zeroes it and both counters), a copy of it is `half`, pass 1 is added to fix.
+    RT_HIP(hipEventRecord(timer.e0, stream));
+    RT_HIP(hipMemsetAsync(d_totals, 0, sizeof(counters), stream));
+    RT_HIP(hipMemsetAsync(d_pass, 0, npix * 3 * sizeof(uint64_t), stream));
+    q.sample_begin = 0; q.flags = 0u;
+    if (int rc = render_frame(ctx, cam, &q, frame_light, frame_nee, nullptr, (long long)npix, d_fix, d_totals, stream)) return rc;
+    RT_HIP(hipMemcpyAsync(d_half, d_fix, npix * 3 * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream));
+    q.sample_begin = (int32_t)step; q.flags = RT_FLAG_ACCUMULATE;
+    if (int rc = render_frame(ctx, cam, &q, frame_light, frame_nee, nullptr, (long long)npix, d_fix, d_totals, stream)) return rc;
+    RT_HIP(hipMemsetD32Async((hipDeviceptr_t)d_count, (int)(2u * step), npix, stream));
+    for (uint32_t n = 2u * step; ; n += 2u * step) {
+        uint32_t n_list = 0;
+        if (n < (uint32_t)p->spp) {
+            if (int rc = rt_select_pixels_device(ctx, d_fix, d_half, d_count, p->width, p->height, (int32_t)n, a, d_list, d_n, stream)) return rc;
+        }
+        RT_HIP(hipEventRecord(timer.e1, stream));
+        if (n < (uint32_t)p->spp) RT_HIP(hipMemcpyAsync(&n_list, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));    // the round's ONE word
+        RT_HIP(st.sync());
+        float ms = 0.0f;
+        RT_HIP(hipEventElapsedTime(&ms, timer.e0, timer.e1));
+        timer.ms += ms;
+        if (n_list == 0u) break;
+        RT_HIP(hipEventRecord(timer.e0, stream));
+        // pass n / step (even) -> the pass buffer, then into fix and half at the listed pixels; pass n / step + 1 (odd) straight into fix:
+        // `half` never sees it
+        q.sample_begin = (int32_t)n;
+        if (int rc = render_frame(ctx, cam, &q, frame_light, frame_nee, d_list, (long long)n_list, d_pass, d_totals, stream)) return rc;
+        hipLaunchKernelGGL(rt::pass_add_listed_kernel, dim3(grid_256((long long)n_list)), dim3(256), 0, stream, (const uint32_t *)d_list, n_list,
+                           (unsigned long long *)d_pass, (unsigned long long *)d_fix, (unsigned long long *)d_half, d_count, 2u * step, (uint32_t)npix);
+        RT_HIP(hipGetLastError());
+        q.sample_begin = (int32_t)(n + step);
+        if (int rc = render_frame(ctx, cam, &q, frame_light, frame_nee, d_list, (long long)n_list, d_fix, d_totals, stream)) return rc;
+    }
+    RT_HIP(st.finish());                                // the sums, half if asked for, the counts and the two counters
+    if (rays_traced) *rays_traced = counters[0];
+    if (shadow_rays) *shadow_rays = counters[1];
+    if (kernel_ms) *kernel_ms = timer.ms;
+    return RT_OK;
 }
 
 int rt_light_list(const double *emission, int32_t n_emission, int32_t *lights_out, int32_t *n_lights_out)

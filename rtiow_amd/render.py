@@ -377,6 +377,19 @@ def paths_begin_torch(renderer, cam, width, height, seed, spp, sample_begin, fir
         renderer.paths_begin_device(cam, width, height, seed, spp, sample_begin, first_item, n, queue.struct(), torch.cuda.current_stream().cuda_stream)
 
 
+def paths_begin_pixels_torch(renderer, cam, width, height, seed, spp, sample_begin, first_item, n, pixels, queue):
+    """rt_paths_begin_pixels_device on a PathQueue, on torch.cuda.current_stream(): slots [0, n) become the items first_item ..
+    first_item + n - 1 of the LIST (index = item // spp, pixel = pixels[index], sample = sample_begin + item % spp) with their camera rays
+    over the full width x height frame, throughput 1; count = n.  pixels: an int32 tensor on the renderer's device holding the u32 pixel
+    numbers.  No host wait."""
+    import torch
+    _check_queue(renderer, queue, "queue")
+    _torch_check(torch, renderer, [("pixels", pixels, torch.int32, (pixels.shape[0] if pixels.dim() else 0,))])
+    with torch.cuda.device(queue.device):
+        renderer.paths_begin_pixels_device(cam, width, height, seed, spp, sample_begin, first_item, n, pixels.data_ptr(), int(pixels.shape[0]),
+                                           queue.struct(), torch.cuda.current_stream().cuda_stream)
+
+
 class Lighting:
     """What lights a frame of the path queue (rt_lighting): the sky's colour where the unit direction's y is -1
     (sky_bottom) and +1 (sky_top), and the radiance of emissive spheres.  emission: None (no lights), an [n, 3] array with one row per
@@ -958,6 +971,90 @@ class Renderer:
         light, _keep = self._device_lighting(lighting)
         _ffi.check(self._lib.rt_render_wavefront_lit_device(self._h, C.byref(rc), C.byref(params), C.byref(light), *tail),
                    "rt_render_wavefront_lit_device")
+
+    # -- wavefront frames over pixel lists, accumulated and adaptively sampled ----
+    def paths_begin_pixels_device(self, cam, width, height, seed, spp, sample_begin, first_item, n, d_pixels_ptr, n_pixels, queue, stream=0, flags=0):
+        """rt_paths_begin_pixels_device; d_pixels_ptr: device [n_pixels] u32 (0: no list); queue: an _ffi.rt_path_queue; asynchronous on `stream`."""
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        _ffi.check(self._lib.rt_paths_begin_pixels_device(self._h, C.byref(rc), int(width), int(height), int(seed), int(flags), int(spp),
+                                                          int(sample_begin), int(first_item), int(n), C.c_void_p(d_pixels_ptr) if d_pixels_ptr else None,
+                                                          int(n_pixels), C.byref(queue), C.c_void_p(stream)), "rt_paths_begin_pixels_device")
+
+    def _host_lighting(self, lighting):
+        """(the rt_lighting of a host form or None, the table it names -- to be kept until the call has been made)."""
+        if lighting is None:
+            return None, None
+        table = lighting.table(self.n_spheres or 0)
+        return lighting.struct(table.ctypes.data if table is not None else None, table.shape[0] if table is not None else 0), table
+
+    def render_wavefront_pixels(self, cam, params, pixels=None, lighting=None, direct=False, sampling="area", into=None):
+        """rt_render_wavefront_pixels: params.spp samples of the listed pixels (g = j * W + i, j = 0 the bottom row; any order; a pixel listed m
+        times gets its samples' sums m times; None: every pixel) through the device path queue -> (fix u64 [H, W, 3], stats).  The frame
+        is FRAME-ADDRESSED: pixel g's sums are at fix[g // W, g % W] -- Renderer.render_pixels' result is compact --, an unlisted pixel's
+        are zero.  lighting, direct and sampling as in render_wavefront.  into: a frame of sums u64 [H, W, 3] to ADD this call's samples to
+        (RT_FLAG_ACCUMULATE is set for the call; the array is not written, the sum is returned).  stats: rays_traced, shadow_rays and
+        kernel_ms of THIS call."""
+        direct_flags = _direct_flags(sampling, direct if direct else False)
+        if direct and lighting is None:
+            raise ValueError("direct lighting needs a Lighting")
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        h, w = params.height, params.width
+        p = _ffi.rt_params.from_buffer_copy(params)
+        if into is None:
+            fix = np.zeros((h, w, 3), dtype=np.uint64)
+        else:
+            fix = np.array(into, dtype=np.uint64, order="C", copy=True).reshape(h, w, 3)
+            p.flags |= _ffi.RT_FLAG_ACCUMULATE
+        px = None if pixels is None else np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        n = h * w if px is None else len(px)
+        keep = np.zeros(1, dtype=np.uint32)                                      # (an empty list is still a list: a pointer that is not NULL)
+        ptr = None if px is None else (px if len(px) else keep).ctypes.data_as(C.c_void_p)
+        light, _keep = self._host_lighting(lighting)
+        rays, shadow, ms = C.c_uint64(0), C.c_uint64(0), C.c_float(0.0)
+        _ffi.check(self._lib.rt_render_wavefront_pixels(self._h, C.byref(rc), C.byref(p), C.byref(light) if light is not None else None,
+                                                        int(bool(direct)), direct_flags, ptr, n, fix.ctypes.data_as(C.c_void_p), C.byref(rays),
+                                                        C.byref(shadow), C.byref(ms)), "rt_render_wavefront_pixels")
+        return fix, {"rays_traced": int(rays.value), "shadow_rays": int(shadow.value), "kernel_ms": float(ms.value)}
+
+    def render_wavefront_pixels_device(self, cam, params, d_pixels_ptr, n_pixels, d_fix_ptr, d_rays_ptr=0, stream=0, lighting=None, direct=False,
+                                       d_shadow_rays_ptr=0, sampling="area"):
+        """rt_render_wavefront_pixels_device on raw device pointers: d_pixels [n_pixels] u32 (0: the identity list, n_pixels = W * H), d_fix
+        [H][W][3] u64 frame-addressed, d_rays / d_shadow_rays one u64 each or 0; params.flags may hold RT_FLAG_ACCUMULATE; asynchronous on
+        `stream`.  lighting, direct, sampling: as in render_wavefront_device."""
+        direct_flags = _direct_flags(sampling, direct if lighting is not None else False)
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        opt = lambda ptr: C.c_void_p(ptr) if ptr else None
+        light = d = _keep = _keep_list = None
+        if lighting is not None:
+            light, _keep = self._device_lighting(lighting)
+        if direct is not False:
+            d, _keep_list = self._device_direct(lighting, direct, direct_flags)
+        _ffi.check(self._lib.rt_render_wavefront_pixels_device(self._h, C.byref(rc), C.byref(params), C.byref(light) if light is not None else None,
+                                                               C.byref(d) if d is not None else None, opt(d_pixels_ptr), int(n_pixels), opt(d_fix_ptr),
+                                                               opt(d_rays_ptr), opt(d_shadow_rays_ptr), C.c_void_p(stream)),
+                   "rt_render_wavefront_pixels_device")
+
+    def render_wavefront_adaptive(self, cam, params, adaptive, lighting=None, direct=False, sampling="area", want_half=True):
+        """rt_render_wavefront_adaptive: render_adaptive's loop and rule over the wavefront frame, lit or not; params.spp is the cap.  Returns
+        (fix u64 [H,W,3], half u64 [H,W,3] or None, count u32 [H,W], stats) with stats["rays"] the path rays, stats["shadow_rays"] the
+        shadow rays, stats["samples"] the samples rendered (the sum of count) and stats["kernel_ms"] the rounds' device time."""
+        direct_flags = _direct_flags(sampling, direct if direct else False)
+        if direct and lighting is None:
+            raise ValueError("direct lighting needs a Lighting")
+        rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
+        h, w = params.height, params.width
+        fix = np.zeros((h, w, 3), dtype=np.uint64)
+        half = np.zeros((h, w, 3), dtype=np.uint64) if want_half else None
+        count = np.zeros((h, w), dtype=np.uint32)
+        light, _keep = self._host_lighting(lighting)
+        rays, shadow, ms = C.c_uint64(0), C.c_uint64(0), C.c_float(0.0)
+        _ffi.check(self._lib.rt_render_wavefront_adaptive(self._h, C.byref(rc), C.byref(params), C.byref(adaptive),
+                                                          C.byref(light) if light is not None else None, int(bool(direct)), direct_flags,
+                                                          fix.ctypes.data_as(C.c_void_p), half.ctypes.data_as(C.c_void_p) if want_half else None,
+                                                          count.ctypes.data_as(C.c_void_p), C.byref(rays), C.byref(shadow), C.byref(ms)),
+                   "rt_render_wavefront_adaptive")
+        return fix, half, count, {"rays": int(rays.value), "shadow_rays": int(shadow.value), "samples": int(count.sum(dtype=np.uint64)),
+                                  "kernel_ms": float(ms.value)}
 
     # -- denoiser: an edge-avoiding a-trous filter driven by the feature buffers -------
     def denoise(self, fix, spp, feat, feat_spp, denoise=None, count=None):

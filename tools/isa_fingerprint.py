@@ -8,7 +8,8 @@ The default output lists the kernels of rt_api.hip; --frames adds, after them, t
 path steps (wavefront/rt_shade.hip: a folder of its own, so --all, which is pinned to the kernels of the source split, does not list them),
 --paths the seven kernels of the device path queue (wavefront/rt_paths.hip, the same folder for the same reason); --weighted, with
 --paths, lists bounce_weighted_kernel too, in its place behind bounce_cone_kernel (profiles/isa_fingerprint_weighted.txt: the seven
-lines of --paths are pinned by tests that count them).
+lines of --paths are pinned by tests that count them); --pixels, with --paths, likewise lists the two kernels of the wavefront list frames and
+their adaptive loop, path_begin_pixels_kernel and pass_add_listed_kernel, behind path_begin_kernel (profiles/isa_fingerprint_wavefront_pixels.txt).
 --all: every kernel of every rtiow_amd/csrc/rt_*.hip, whatever its name, sorted by name and without the s_nop padding behind its
 last instruction -- so a line does not depend on which translation unit the kernel lives in, nor on whether it is the last one there
 (profiles/isa_fingerprint_source_split.txt, tests/test_source_layout_host.py).  The other outputs count that padding, as they always did."""
@@ -42,7 +43,8 @@ lines = []
 for name, ops in seqs.items():
     if not everything and not any(k in name for k in ("render_kernel", "resolve", "features_kernel", "trace_kernel", "camera_rays_kernel", "scatter_kernel",
                                                             "accumulate_kernel", "path_begin_kernel", "bounce_kernel", "bounce_lit_kernel", "bounce_nee_kernel", "bounce_cone_kernel", "queue_scan_kernel",
-                                                            "queue_compact_kernel") + (("bounce_weighted_kernel",) if "--weighted" in args else ())):
+                                                            "queue_compact_kernel") + (("bounce_weighted_kernel",) if "--weighted" in args else ())
+                                                           + (("path_begin_pixels_kernel", "pass_add_listed_kernel") if "--pixels" in args else ())):
         continue
     while everything and ops and ops[-1] == "s_nop":       # the padding behind a kernel: longest behind the LAST kernel of a translation unit
         ops.pop()
