@@ -144,6 +144,8 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     constexpr int kRingDepth = kWideRing ? 2 : 4;
     constexpr int kRingSlots = kWideRing ? 16 : 8;
     constexpr bool kMaskVotes = CAPPED && kRingDepth == 2;      // PHASE 5 on wave masks (the capped kernels with the ring of two)
+    // PHASE 1 on wave masks: the capped kernels but the large-grid one on blocks of 1 024, which has no scalar headroom for it (63 parked scalars: 67 with it)
+    constexpr bool kMaskHandout = CAPPED && (SMALLGRID || ITEMS == kItemBlockDense);
     static_assert(kRingDepth * kRingSlots == rt::kRingDepth * rt::kRingSlots, "same LDS either way");
     __shared__ uint16_t cand[MODE == 1 ? kCandCap : 1][MODE == 1 ? kBlock : 1];     // MODE 1: per-lane candidate lists
     constexpr bool MATRIX = (MODE >= 2);
@@ -279,9 +281,43 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
         bool fresh = false;                                         // this lane starts a sample in this pass
         double cam_u = 0.0, cam_v = 0.0;
         uint32_t lens_wx = 0u, lens_wy = 0u;
+        // The capped dense kernels (kMaskHandout) hand out on WAVE MASKS.  `fresh` and `dead` as lane booleans carried round the loop below cost a scalar
+        // merge of three instructions per boolean at the loop's head and again at its latch, and a select and a compare to vote on each.  There the
+        // takers are ONE mask on the scalar unit, want_m: the lanes without a path at the top of the pass, less those that have taken an entry.  The
+        // first trip is straight-line -- what the queue holds --, and takers that remain find the queue empty, so every further trip is refill, then
+        // take: the loop's own order, trip for trip (rank among the takers, q_head, q_count, blk_next), and so the same entry for every lane.
+        // No lane is marked dead: once the device-wide counter has said that no block is left, the queue is empty and the wave's block is used up
+        // for good, so a lane without a path asks again in every pass, gets the same answer from queue_empty without an atomic, and takes nothing.
+        // The lanes that start a camera ray are the takers that are takers no more.
+        unsigned long long want_m = 0ull;
+        if constexpr (kMaskHandout) {
+            // (read by the lanes that take an entry only: no zeros to write for the others)
+            cam_u = unread_f64(); cam_v = unread_f64(); lens_wx = unread_u32(); lens_wy = unread_u32();
+            want_m = ~__ballot(alive);
+            if (q_count != 0u) {
+                const uint32_t r = rank_below(want_m);
+                const unsigned long long take_m = want_m & __ballot(r < q_count);
+                const bool take = __builtin_amdgcn_inverse_ballot_w64(take_m);     // (the lanes' branch runs on the mask as it is)
+                RT_LDS_QUEUE_READS(take, q_head + r);
+                if (take) {
+                    const uint32_t e = q_head + r;
+                    cam_u = quv_w[0 * 64 + e]; cam_v = quv_w[1 * 64 + e];
+                    lens_wx = qid_w[0 * 64 + e]; lens_wy = qid_w[1 * 64 + e];
+                    pix_global = qid_w[2 * 64 + e];
+                    s = (int)qid_w[3 * 64 + e];
+                    const uint32_t meta = qid_w[4 * 64 + e];
+                    ev = meta >> 8;
+                    pix_local = blk_pix0 + (meta & 255u);
+                    my_blk = (blk_seq << 4) | (meta & 15u);
+                }
+                want_m &= ~take_m;
+                const uint32_t took = (uint32_t)__popcll(take_m);               // = min(takers, q_count)
+                q_head += took; q_count -= took;
+            }
+        }
         for (;;) {
-            const bool want = !alive && !dead && !fresh;
-            const unsigned long long m = __ballot(want);
+            const bool want = kMaskHandout ? false : !alive && !dead && !fresh;
+            const unsigned long long m = kMaskHandout ? want_m : __ballot(want);
             if (m == 0ull) break;
             if (q_count == 0u) {
                 RT_STAMP(0);
@@ -297,6 +333,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     }
                     if (nb >= P.n_blocks) {                         // no work left anywhere: these lanes are done
                         queue_empty = true;
+                        if constexpr (kMaskHandout) break;
                         if (want) dead = true;
                         break;
                     }
@@ -417,6 +454,27 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                 __builtin_amdgcn_wave_barrier();
                 RT_STAMP(8);
             }
+            if constexpr (kMaskHandout) {                           // (the first trip's take, once more)
+                const uint32_t r = rank_below(want_m);
+                const unsigned long long take_m = want_m & __ballot(r < q_count);
+                const bool take = __builtin_amdgcn_inverse_ballot_w64(take_m);     // (the lanes' branch runs on the mask as it is)
+                RT_LDS_QUEUE_READS(take, q_head + r);
+                if (take) {
+                    const uint32_t e = q_head + r;
+                    cam_u = quv_w[0 * 64 + e]; cam_v = quv_w[1 * 64 + e];
+                    lens_wx = qid_w[0 * 64 + e]; lens_wy = qid_w[1 * 64 + e];
+                    pix_global = qid_w[2 * 64 + e];
+                    s = (int)qid_w[3 * 64 + e];
+                    const uint32_t meta = qid_w[4 * 64 + e];
+                    ev = meta >> 8;
+                    pix_local = blk_pix0 + (meta & 255u);
+                    my_blk = (blk_seq << 4) | (meta & 15u);
+                }
+                want_m &= ~take_m;
+                const uint32_t took = (uint32_t)__popcll(take_m);               // = min(takers, q_count)
+                q_head += took; q_count -= took;
+                continue;
+            }
             const uint32_t r = rank_below(m);
             RT_LDS_QUEUE_READS(want && r < q_count, q_head + r);
             if (want && r < q_count) {
@@ -436,6 +494,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
             const uint32_t took = cnt < q_count ? cnt : q_count;
             q_head += took; q_count -= took;
         }
+        if constexpr (kMaskHandout) fresh = __builtin_amdgcn_inverse_ballot_w64(__ballot(!alive) & ~want_m);
         RT_STAMP(0);
         // ==== PHASE 2: start_camera_rays =======================================================================================
         if (fresh) {                                                // camera.rs:47-54

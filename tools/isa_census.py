@@ -210,7 +210,9 @@ def phases_table(lines, counts):
         ("always-exact list, out-of-range rays", always0, seed0 - 1, c["always_extra"], 1),   # loop control + the whole-list scan of a ray outside the
                                                                                           # filter's range: (all but) never on these scenes
         ("refill: start 64 samples (item -> pixel, Philox, lens)", refill0, refill_end, c["refills"], 1),
-        ("take samples from the queue", take0, cam0 - 1, 1.0 + c["refills"], 1),
+        # (the kernels that hand out on wave masks -- rt_kernels.hpp, kMaskHandout -- take once per pass above the loop, straight-line; their take behind
+        #  a refill lies inside the refill's lines and runs at its rate.  The loop of the others runs its head once per trip: 1 + refills.)
+        ("take samples from the queue", take0, cam0 - 1, 1.0 if c.get("mask_handout") else 1.0 + c["refills"], 1),
         ("camera ray of fresh lanes (camera.rs:47-54)", cam0, hit0 - 1, 1.0, 1),
         ("unit-sphere retry loop (3 static blocks + 4 tries per trip)", retry_loop, retry_end, c["retry_blocks"], "philox"),
         ("hit record, material fetch, first Philox block, try 0", shade0, retry_loop - 1, 1.0, 1),
@@ -256,6 +258,7 @@ def main():
               if tenk else
               {"looks": 15.22, "keeps": 10.18, "halves": 16.24, "pool_rounds": 1.62, "enum_trips": 4.6, "tiles": 5.35, "refills": 0.377,
                "retry_blocks": 3.72, "flushes": 0.377 / 4.0, "always_extra": 0.1, "full_share": FULL_BOOK})
+    counts["mask_handout"] = "--dense" in args       # (rt_kernels.hpp, kMaskHandout: the small-grid capped pair and the large-grid one on blocks of 256)
     elf, dis = build(extra, src)
     ins = kernel_instructions(dis, want)
     if not ins:
