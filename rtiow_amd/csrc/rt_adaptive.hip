@@ -157,6 +157,15 @@ int rt_host::validate_adaptive(const rt_adaptive *a)
     return RT_OK;
 }
 
+int rt_host::check_adaptive_frame(const char *what, const rt_params *p, const rt_adaptive *a)
+{
+    if (p->sample_begin != 0) return fail(RT_ERR_INVALID_ARGUMENT, "%s numbers its own passes: sample_begin must be 0 (is %d)", what, p->sample_begin);
+    if (p->spp < 2 * (long long)a->step || p->spp % (2 * (long long)a->step) != 0 || p->spp > kAdaptiveMaxSpp)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: spp = %d (the most samples a pixel may get) must be a multiple of 2 * step = %lld and <= %d", what,
+                    p->spp, 2 * (long long)a->step, kAdaptiveMaxSpp);
+    return RT_OK;
+}
+
 namespace {
 
 int validate_select(const void *fix, const void *half, const void *count, int32_t width, int32_t height, int32_t n, const rt_adaptive *a,
@@ -234,10 +243,8 @@ int rt_render_adaptive(rt_context *ctx, const rt_camera *cam, const rt_params *p
     if (rc) return rc;
     rc = validate_adaptive(a);
     if (rc) return rc;
-    if (p->sample_begin != 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive numbers its own passes: sample_begin must be 0 (is %d)", p->sample_begin);
-    if (p->spp < 2 * (long long)a->step || p->spp % (2 * (long long)a->step) != 0 || p->spp > kAdaptiveMaxSpp)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive: spp = %d (the most samples a pixel may get) must be a multiple of 2 * step = %lld "
-                    "and <= %d", p->spp, 2 * (long long)a->step, kAdaptiveMaxSpp);
+    rc = check_adaptive_frame("rt_render_adaptive", p, a);
+    if (rc) return rc;
     rc = validate_pixel_list(ctx, cam, p, 0);
     if (rc) return rc;
     if (!out_fix || !out_count) return fail(RT_ERR_INVALID_ARGUMENT, "out_fix/out_count is NULL");

@@ -3,8 +3,8 @@
 //
 // The eleventh translation unit of librtiow_hip.so.  Ten kernels of its own:
 //   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
-//   path_begin_pixels_kernel  the same over a list of pixels: item -> (list index, sample), the pixel read from the list (rtiow_hip.h,
-//                         "wavefront frames over pixel lists").
+//   path_begin_pixels_kernel  the same body (path_begin<LISTED>, stated once) over a list of pixels: item -> (list index, sample), the pixel
+//                         read from the list (rtiow_hip.h, "wavefront frames over pixel lists").
 //   pass_add_listed_kernel  rt_render_wavefront_adaptive's: an even pass's frame-addressed sums into fix and half at the listed pixels.
 //   bounce_kernel         one wave per 64 consecutive slots, grid-stride over the live slots: closest hit (first_hit_wave<false> whole, the
 //                         record in registers), then the sky add of a miss or Scatter::scatter -- both from rt_shade_core.hpp --; the new
@@ -67,15 +67,22 @@ __device__ __forceinline__ uint32_t live_count(const QueueArrays &Q)
     return n < Q.capacity ? n : Q.capacity;
 }
 
-__global__ __launch_bounds__(kPathBlock) void path_begin_kernel(const KCamera cam, const QueueArrays Q, const BeginArgs A)
+// The body of the two begin kernels.  LISTED (rt_paths_begin_pixels_device): item -> (list index, sample), the pixel
+// read from the list; else item -> (pixel, sample) and `pixels` is not looked at.  The host has checked first_item + n <= n_pixels * spp,
+// so every read of `pixels` lies inside the list; the pixel word itself is not looked at: one at or past width * height gets the camera
+// ray of (g % width, g / width) and adds nothing in the steps.
+template <bool LISTED>
+__device__ __forceinline__ void path_begin(const KCamera &cam, const QueueArrays &Q, const BeginArgs &A, const uint32_t *pixels)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) *Q.count = (uint32_t)A.n;
     const double wm1 = (double)(A.width - 1), hm1 = (double)(A.height - 1);
     const long long stride = (long long)gridDim.x * kPathBlock;
     for (long long k = (long long)blockIdx.x * kPathBlock + threadIdx.x; k < A.n; k += stride) {
         const unsigned long long item = (unsigned long long)(A.first_item + k);
-        const unsigned long long pix = item / A.spp;                    // pixel-major: item = pixel * spp + sample
-        const uint32_t g_pix = (uint32_t)pix, g_s = A.sample_begin + (uint32_t)(item - pix * A.spp);
+        const unsigned long long idx = item / A.spp;                    // pixel-major (list-major): item = pixel (index) * spp + sample
+        uint32_t g_pix = (uint32_t)idx;
+        if constexpr (LISTED) g_pix = pixels[idx];
+        const uint32_t g_s = A.sample_begin + (uint32_t)(item - idx * A.spp);
         D3 origin, dir;
         const uint32_t ev = sample_ray(cam, (uint32_t)A.width, wm1, hm1, g_pix, g_s, A.k0, A.k1, origin, dir);
         Q.pixel[k] = g_pix; Q.sample[k] = g_s; Q.event[k] = ev;
@@ -85,26 +92,15 @@ __global__ __launch_bounds__(kPathBlock) void path_begin_kernel(const KCamera ca
     }
 }
 
-// ... over a list (rt_paths_begin_pixels_device): item -> (list index, sample), the pixel from the list.  The host
-// has checked first_item + n <= n_pixels * spp, so every read of `pixels` lies inside the list; the pixel word itself is not looked at:
-// one at or past width * height gets the camera ray of (g % width, g / width) and adds nothing in the steps.
+__global__ __launch_bounds__(kPathBlock) void path_begin_kernel(const KCamera cam, const QueueArrays Q, const BeginArgs A)
+{
+    path_begin<false>(cam, Q, A, nullptr);
+}
+
 __global__ __launch_bounds__(kPathBlock) void path_begin_pixels_kernel(const KCamera cam, const QueueArrays Q, const BeginArgs A,
                                                                        const uint32_t *__restrict__ pixels)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *Q.count = (uint32_t)A.n;
-    const double wm1 = (double)(A.width - 1), hm1 = (double)(A.height - 1);
-    const long long stride = (long long)gridDim.x * kPathBlock;
-    for (long long k = (long long)blockIdx.x * kPathBlock + threadIdx.x; k < A.n; k += stride) {
-        const unsigned long long item = (unsigned long long)(A.first_item + k);
-        const unsigned long long idx = item / A.spp;                    // list-major: item = index * spp + sample
-        const uint32_t g_pix = pixels[idx], g_s = A.sample_begin + (uint32_t)(item - idx * A.spp);
-        D3 origin, dir;
-        const uint32_t ev = sample_ray(cam, (uint32_t)A.width, wm1, hm1, g_pix, g_s, A.k0, A.k1, origin, dir);
-        Q.pixel[k] = g_pix; Q.sample[k] = g_s; Q.event[k] = ev;
-        store3(Q.origin, k, origin);
-        store3(Q.dir, k, dir);
-        Q.thr[3 * k] = 1.0; Q.thr[3 * k + 1] = 1.0; Q.thr[3 * k + 2] = 1.0;
-    }
+    path_begin<true>(cam, Q, A, pixels);
 }
 
 // An even-numbered pass of rt_render_wavefront_adaptive, rendered into a frame-addressed pass buffer, back into the frame's state at the
@@ -145,8 +141,6 @@ struct NeeArgs {
     uint32_t no_direct;
 };
 
-constexpr int kUnlit = 0, kLit = 1, kNee = 2, kNeeCone = 3, kNeeWeighted = 4;     // bounce_trip's MODE
-
 // the three 64-bit adds of a path that ends with radiance v (contract C5); g_pix: inside the frame
 __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, const D3 &v)
 {
@@ -161,11 +155,12 @@ __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, con
 // the wave traces the shadow rays together: only the contribution, the pixel and the light's index are live across that scan.
 // MODE == kNeeCone: the same trip with the light sampled by solid angle (nee_sample_cone).
 // MODE == kNeeWeighted: ... and chosen by its contribution at the hit point (nee_sample_weighted).
+// The modes are rt_shade_core.hpp's, and so is the choice of the sampler among them (nee_sample_for<MODE>).
 template <int MODE>
 __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays &Q, const unsigned long long npix, const LitArgs &L, const NeeArgs &N,
                                             uint4 *stage, const int lane, const long long wv, const long long n)
 {
-    constexpr bool LIT = MODE >= kLit, NEE = MODE >= kNee, CONE = MODE == kNeeCone, WEIGHTED = MODE == kNeeWeighted;
+    constexpr bool LIT = MODE >= kLit, NEE = MODE >= kNee;
     const long long k = wv * 64 + lane;
     // lanes past the live count stay in the wave: rows that keep nothing, nothing written
     const bool valid = k < n;
@@ -220,9 +215,7 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
                     Q.event[k] = ev;
                     if constexpr (NEE) {
                         if (direct) {
-                            if constexpr (WEIGHTED) shadow = nee_sample_weighted(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
-                            else if constexpr (CONE) shadow = nee_sample_cone(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
-                            else shadow = nee_sample(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
+                            shadow = nee_sample_for<MODE>(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
                             so = rec.p;
                         }
                     }
@@ -583,9 +576,9 @@ int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_pat
             memset(&na, 0, sizeof(na));
             na.lights = nee->direct->lights; na.n_lights = nee->direct->lights ? nee->direct->n_lights : 0;
             na.shadow_rays = (unsigned long long *)nee->d_shadow_rays; na.no_direct = nee->step_flags & RT_STEP_NO_DIRECT;
-            if (nee->direct->flags & RT_DIRECT_WEIGHTED) hipLaunchKernelGGL(rt::bounce_weighted_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
-            else if (nee->direct->flags & RT_DIRECT_CONE) hipLaunchKernelGGL(rt::bounce_cone_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
-            else hipLaunchKernelGGL(rt::bounce_nee_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
+            const uint32_t how = nee->direct->flags;    // (the three NEE kernels have one signature)
+            const auto kernel = how & RT_DIRECT_WEIGHTED ? rt::bounce_weighted_kernel : how & RT_DIRECT_CONE ? rt::bounce_cone_kernel : rt::bounce_nee_kernel;
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na);
         } else {
             hipLaunchKernelGGL(rt::bounce_lit_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la);
         }
@@ -700,6 +693,51 @@ int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, cons
     return RT_OK;
 }
 
+// A host form's lighting on its way to the device (render_frame_host, rt_render_wavefront_adaptive): the caller's `light`, its table in host
+// memory; direct: the frame samples its lights, their list (flags direct_flags) rebuilt from the table the call can see.  checked(): what
+// check_render takes where a device form checks direct->flags.  declare(): on the caller's Stage before commit(), where the table and the
+// list stand among its buffers.  resolve(): after upload(); then frame_light() and frame_nee() are what a device form takes, NULL for none.
+struct HostLighting {
+    const rt_lighting *const light;
+    const bool lit, direct;
+    const rt_direct no_list;
+    const NeeCall flags_only;
+    std::vector<int32_t> list;
+    Staged<const double> emission;
+    Staged<const int32_t> lights;
+    rt_lighting dev = {};
+    rt_direct on_device = {};
+    NeeCall nee = {};
+
+    HostLighting(const rt_lighting *light, bool lit, bool direct, uint32_t direct_flags)
+        : light(light), lit(lit), direct(direct), no_list{nullptr, 0, direct_flags}, flags_only{&no_list, 0u, nullptr} {}
+    HostLighting(const HostLighting &) = delete;        // (flags_only and nee point into the struct)
+
+    const NeeCall *checked() const { return direct ? &flags_only : nullptr; }
+    int declare(Stage &st)
+    {
+        const double *table = lit ? light->emission : nullptr;
+        const size_t n_table = table ? (size_t)light->n_emission : 0;
+        list.resize(direct ? n_table : 0);
+        if (int rc = rt_light_list(table, (int32_t)list.size(), list.data(), &on_device.n_lights)) return rc;
+        emission = st.in(table, n_table * 3);
+        lights = st.in(static_cast<const int32_t *>(list.data()), (size_t)on_device.n_lights);
+        return RT_OK;
+    }
+    // d_shadow_rays: the device u64 that gains the frame's shadow rays
+    void resolve(const Stage &st, void *d_shadow_rays)
+    {
+        dev = lit ? *light : rt_lighting{};             // the same lighting with the table on the device
+        dev.emission = st.ptr(emission);
+        if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
+        on_device.lights = st.ptr(lights); on_device.flags = no_list.flags;
+        if (!on_device.lights) on_device.n_lights = 0;
+        nee = {&on_device, 0u, d_shadow_rays};
+    }
+    const rt_lighting *frame_light() const { return lit ? &dev : nullptr; }
+    const NeeCall *frame_nee() const { return direct ? &nee : nullptr; }
+};
+
 // The body of the four host frames.  mode: kUnlit (light is not looked at), kLit, or kNee: the frame samples its lights directly, their
 // list rebuilt from the table the call can see.  The counters are counted whether or not the caller asks; a frame without direct lighting
 // has no shadow counter (shadow_rays NULL: absent).
@@ -709,36 +747,23 @@ int render_frame_host(rt_context *ctx, const char *what, const rt_camera *cam, c
                       uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms, uint32_t direct_flags = 0u, const PixelList *pixel_list = nullptr)
 {
     const bool lit = mode >= rt::kLit, direct = mode == rt::kNee;
-    // (direct_flags: the flags of the list this frame builds; checked where a device form checks direct->flags)
-    const rt_direct no_list = {nullptr, 0, direct_flags};
-    const NeeCall flags_only = {&no_list, 0u, nullptr};
-    if (int rc = check_render(ctx, what, cam, p, fix, lit, light, true, direct ? &flags_only : nullptr, pixel_list)) return rc;
+    HostLighting lighting(light, lit, direct, direct_flags);
+    if (int rc = check_render(ctx, what, cam, p, fix, lit, light, true, lighting.checked(), pixel_list)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
-    const double *table = lit ? light->emission : nullptr;
-    const size_t n_table = table ? (size_t)light->n_emission : 0;
-    std::vector<int32_t> list(direct ? n_table : 0);
-    int32_t n_lights = 0;
-    if (int rc = rt_light_list(table, (int32_t)list.size(), list.data(), &n_lights)) return rc;
     const bool adds = (p->flags & RT_FLAG_ACCUMULATE) != 0u;          // (only a list form gets here with the flag)
     const size_t n_sums = (size_t)p->width * p->height * 3;
     Stage st(ctx);
     const auto sums = adds ? st.inout(fix, n_sums) : st.out(fix, n_sums);
     const auto rays = !rays_traced ? st.scratch<uint64_t>(1) : adds ? st.inout(rays_traced, 1) : st.out(rays_traced, 1);
     const auto shadow = direct && !shadow_rays ? st.scratch<uint64_t>(1) : adds ? st.inout(shadow_rays, 1) : st.out(shadow_rays, 1);
-    const auto emission = st.in(table, n_table * 3);
-    const auto lights = st.in(static_cast<const int32_t *>(list.data()), (size_t)n_lights);
+    if (int rc = lighting.declare(st)) return rc;
     const auto pixels = st.in(pixel_list ? pixel_list->pixels : nullptr, pixel_list && pixel_list->pixels ? (size_t)pixel_list->n_pixels : 0);
     const long long n_pixels = pixel_list ? (long long)pixel_list->n_pixels : (long long)p->width * p->height;
     if (int rc = st.commit()) return rc;
     RT_HIP(st.upload());
-    rt_lighting dev = lit ? *light : rt_lighting{};     // the same lighting with the table on the device
-    dev.emission = st.ptr(emission);
-    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }    // (a table of no entries lights nothing)
-    rt_direct on_device = {st.ptr(lights), n_lights, direct_flags};
-    if (!on_device.lights) on_device.n_lights = 0;
-    const NeeCall nee = {&on_device, 0u, st.ptr(shadow)};
+    lighting.resolve(st, st.ptr(shadow));
     return timed_section(ctx, what, kernel_ms, st, [&] {
-        return render_frame(ctx, cam, p, lit ? &dev : nullptr, direct ? &nee : nullptr, st.ptr(pixels), n_pixels, st.ptr(sums), st.ptr(rays), ctx->own_stream);
+        return render_frame(ctx, cam, p, lighting.frame_light(), lighting.frame_nee(), st.ptr(pixels), n_pixels, st.ptr(sums), st.ptr(rays), ctx->own_stream);
     });
 }
 
@@ -881,24 +906,13 @@ int rt_render_wavefront_adaptive(rt_context *ctx, const rt_camera *cam, const rt
     RT_NEED(out_count, what, "out_count");
     if (int rc = validate_params(p)) return rc;
     if (int rc = validate_adaptive(a)) return rc;
-    if (p->sample_begin != 0)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s numbers its own passes: sample_begin must be 0 (is %d)", what, p->sample_begin);
-    if (p->spp < 2 * (long long)a->step || p->spp % (2 * (long long)a->step) != 0 || p->spp > kAdaptiveMaxSpp)
-        return fail(RT_ERR_INVALID_ARGUMENT, "%s: spp = %d (the most samples a pixel may get) must be a multiple of 2 * step = %lld and <= %d", what,
-                    p->spp, 2 * (long long)a->step, kAdaptiveMaxSpp);
+    if (int rc = check_adaptive_frame(what, p, a)) return rc;
     if (!direct && direct_flags)
         return fail(RT_ERR_INVALID_ARGUMENT, "%s: direct_flags must be 0 without direct lighting (is 0x%x)", what, direct_flags);
-    const bool lit = light || direct;
-    const rt_direct no_list = {nullptr, 0, direct_flags};
-    const NeeCall flags_only = {&no_list, 0u, nullptr};
-    if (int rc = check_render(ctx, what, cam, p, out_fix, lit, light, true, direct ? &flags_only : nullptr, nullptr, check_adaptive_terms)) return rc;
+    HostLighting lighting(light, light || direct, direct, direct_flags);
+    if (int rc = check_render(ctx, what, cam, p, out_fix, lighting.lit, light, true, lighting.checked(), nullptr, check_adaptive_terms)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
     hipStream_t stream = ctx->own_stream;
-    const double *table = lit ? light->emission : nullptr;
-    const size_t n_table = table ? (size_t)light->n_emission : 0;
-    std::vector<int32_t> light_list(direct ? n_table : 0);
-    int32_t n_lights = 0;
-    if (int rc = rt_light_list(table, (int32_t)light_list.size(), light_list.data(), &n_lights)) return rc;
     // the frame's state, all on the device: fix | half | the even pass's frame-addressed sums | count | list | the two counters | the list's length
     const size_t npix = (size_t)p->width * p->height;
     uint64_t counters[2] = {0, 0};
@@ -910,20 +924,14 @@ int rt_render_wavefront_adaptive(rt_context *ctx, const rt_camera *cam, const rt
     const auto list = st.scratch<uint32_t>(npix);
     const auto totals = st.out(counters, 2);
     const auto length = st.scratch<uint32_t>(1);
-    const auto emission = st.in(table, n_table * 3);
-    const auto lights = st.in(static_cast<const int32_t *>(light_list.data()), (size_t)n_lights);
+    if (int rc = lighting.declare(st)) return rc;
     if (int rc = st.commit()) return rc;
     RT_HIP(st.upload());
     uint64_t *d_fix = st.ptr(fix), *d_half = st.ptr(half), *d_pass = st.ptr(pass), *d_totals = st.ptr(totals);
     uint32_t *d_count = st.ptr(count), *d_list = st.ptr(list), *d_n = st.ptr(length);
-    rt_lighting dev = lit ? *light : rt_lighting{};     // the same lighting with the table on the device
-    dev.emission = st.ptr(emission);
-    if (!dev.emission || !dev.n_emission) { dev.emission = nullptr; dev.n_emission = 0; }
-    rt_direct on_device = {st.ptr(lights), n_lights, direct_flags};
-    if (!on_device.lights) on_device.n_lights = 0;
-    const NeeCall nee = {&on_device, 0u, d_totals + 1};
-    const rt_lighting *frame_light = lit ? &dev : nullptr;
-    const NeeCall *frame_nee = direct ? &nee : nullptr;
+    lighting.resolve(st, d_totals + 1);
+    const rt_lighting *frame_light = lighting.frame_light();
+    const NeeCall *frame_nee = lighting.frame_nee();
 
     RoundTimer timer;
     RT_HIP(hipEventCreate(&timer.e0));

@@ -142,6 +142,17 @@ __device__ __forceinline__ bool light_front(const KParams &P, const D3 &o, const
     return dot(d, p - mk(g.x, g.y, g.z)) < 0.0;
 }
 
+// List entry s names no sphere of both tables: no contribution (no content of the list makes a read leave the tables).  A macro, not a
+// function: bounce_nee_kernel's machine code is pinned (profiles/isa_fingerprint_nee.txt), and behind an inlined call the compiler
+// schedules that kernel's Philox rounds in another order.
+#define RT_NAMES_NO_LIGHT(P, emission, n_emission, s) ((s) < 0 || (s) >= (P).n_spheres || !(emission) || (s) >= (n_emission))
+
+// The uniform choice among n list entries from one Philox word: floor(word * n / 2^32).
+__device__ __forceinline__ uint32_t uniform_pick(uint32_t word, int32_t n)
+{
+    return (uint32_t)(((unsigned long long)word * (unsigned long long)(uint32_t)n) >> 32);
+}
+
 // The light sample of the path (g_pix, g_s) whose event on entry -- DIRECT bit masked off -- was ev_in, at the hit point p with the
 // record's normal n; weight: throughput * albedo, the path's new throughput.  The draws are the blocks (g_pix, g_s, ev_in, 1 + m), m = 0,
 // 1, ...: word 3 >= 1 is used by nothing else and ev_in is unique per bounce, so the path's own stream is not touched.  Block 0: x chooses
@@ -152,10 +163,8 @@ __device__ __forceinline__ bool nee_sample(const KParams &P, const double *emiss
                                            int &li)
 {
     U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
-    const uint32_t j = (uint32_t)(((unsigned long long)b.x * (unsigned long long)(uint32_t)n_lights) >> 32);
-    li = lights[j];
-    // a list entry that names no sphere or no table entry: no contribution (no content of the list makes a read leave the tables)
-    if (li < 0 || li >= P.n_spheres || !emission || li >= n_emission) return false;
+    li = lights[uniform_pick(b.x, n_lights)];
+    if (RT_NAMES_NO_LIGHT(P, emission, n_emission, li)) return false;
     uint32_t tx = b.y, ty = b.z, tz = b.w;
     for (uint32_t m = 1u; !unit_sphere_accepts(tx, ty, tz); ++m) {                       // vec3.rs:37-45: a plain loop to acceptance
         b = philox4x32_10(g_pix, g_s, ev_in, 1u + m, P.k0, P.k1);
@@ -175,25 +184,21 @@ __device__ __forceinline__ bool nee_sample(const KParams &P, const double *emiss
 }
 
 // ---- ... or by solid angle: a uniform direction of the cone the light subtends from p (RT_DIRECT_CONE) -------------
-// nee_sample's arguments, blocks and result.  Block 0: x chooses the light, y is the polar draw, (z, w) the first unit-disk try, whose
-// normalised point is (cos phi, sin phi); every further block holds one try (x, y).  + - * / and sqrt in binary64, no contraction: the
-// BRDF albedo / pi and the cone pdf 1 / (2 pi (1 - cos theta_max) n_lights) leave no pi, and the weight 2 k n_lights ns is bounded by
-// 2 n_lights whatever the geometry (k <= 1, ns <= 1).  dv is a unit vector up to rounding.
-__device__ __forceinline__ bool nee_sample_cone(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t n_lights,
-                                                const D3 &p, const D3 &n, const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv, D3 &c,
-                                                int &li)
+// Steps 2 to 9 of the cone sample, for the light li (a sphere of the geometry table) whatever chose it: nee_sample_cone's and
+// nee_sample_weighted's, stated HERE and nowhere else.  b: block 0 of the sample, of which y is the polar draw and (z, w) the first
+// unit-disk try, whose normalised point is (cos phi, sin phi); every further block holds one try (x, y).  + - * / and sqrt in binary64, no
+// contraction, in this order.  Returns whether there is a shadow ray (p, dv) -- dv a unit vector up to rounding --, and then k = 1 - cos
+// theta_max and ns = dot(n, dv) for the caller's weight.
+__device__ __forceinline__ bool cone_toward(const KParams &P, int li, const D3 &p, const D3 &n, U4 b, uint32_t g_pix, uint32_t g_s, uint32_t ev_in,
+                                            D3 &dv, double &k, double &ns)
 {
-    U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
-    const uint32_t j = (uint32_t)(((unsigned long long)b.x * (unsigned long long)(uint32_t)n_lights) >> 32);
-    li = lights[j];
-    if (li < 0 || li >= P.n_spheres || !emission || li >= n_emission) return false;      // as nee_sample
     const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)li);        // centre, r^2
     const D3 wv = mk(g.x, g.y, g.z) - p;
     const double d2 = (wv.x * wv.x + wv.y * wv.y) + wv.z * wv.z;
     if (!(d2 > g.w)) return false;                                                       // p inside or on the light; a NaN fails this
     const double q = g.w / d2;
     const double cm = __builtin_sqrt(1.0 - q);                                           // cos theta_max
-    const double k = q / (1.0 + cm);                                                     // 1 - cos theta_max, without the cancellation
+    k = q / (1.0 + cm);                                                                  // 1 - cos theta_max, without the cancellation
     const double s = u01(b.y) * k;
     const double ct = 1.0 - s;
     const double st = __builtin_sqrt(s * (1.0 + ct));
@@ -211,8 +216,22 @@ __device__ __forceinline__ bool nee_sample_cone(const KParams &P, const double *
     const D3 t = t0 * (1.0 / __builtin_sqrt(dot(t0, t0)));
     const D3 bt = mk(w.y * t.z - w.z * t.y, w.z * t.x - w.x * t.z, w.x * t.y - w.y * t.x);
     dv = (t * (st * cphi) + bt * (st * sphi)) + w * ct;
-    const double ns = dot(n, dv);
-    if (!(ns > 0.0)) return false;                                                       // below the hit's horizon; a NaN fails this
+    ns = dot(n, dv);
+    return ns > 0.0;                                                                     // below the hit's horizon: none; a NaN fails this
+}
+
+// nee_sample's arguments, blocks and result.  Block 0: x chooses the light (step 1), the rest is cone_toward's.  The BRDF albedo / pi and
+// the cone pdf 1 / (2 pi (1 - cos theta_max) n_lights) leave no pi, and the weight 2 k n_lights ns (step 10) is bounded by 2 n_lights
+// whatever the geometry (k <= 1, ns <= 1).
+__device__ __forceinline__ bool nee_sample_cone(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t n_lights,
+                                                const D3 &p, const D3 &n, const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv, D3 &c,
+                                                int &li)
+{
+    const U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
+    li = lights[uniform_pick(b.x, n_lights)];
+    if (RT_NAMES_NO_LIGHT(P, emission, n_emission, li)) return false;
+    double k, ns;
+    if (!cone_toward(P, li, p, n, b, g_pix, g_s, ev_in, dv, k, ns)) return false;
     const double wgt = ((2.0 * k) * (double)n_lights) * ns;
     c = (weight * ld3(emission + 3 * (size_t)li)) * wgt;
     return true;
@@ -225,7 +244,7 @@ __device__ __forceinline__ double light_importance(const KParams &P, const doubl
                                                    const D3 &p)
 {
     const int s = lights[i];
-    if (s < 0 || s >= P.n_spheres || !emission || s >= n_emission) return 0.0;
+    if (RT_NAMES_NO_LIGHT(P, emission, n_emission, s)) return 0.0;
     const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)s);         // centre, r^2
     const D3 e = ld3(emission + 3 * (size_t)s);
     const D3 wv = mk(g.x, g.y, g.z) - p;
@@ -238,14 +257,14 @@ __device__ __forceinline__ double light_importance(const KParams &P, const doubl
 
 // nee_sample_cone's arguments, blocks and result.  Word x of block 0 chooses the light with probability imp_j / tot instead of 1 / n_lights:
 // two walks over the list, the first for the total, the second -- the same expressions, the same running sum -- for the first entry whose
-// partial sum exceeds u01(x) tot.  Then steps 2 to 9 of the cone sample for that light, and the weight 2 k ns (tot / imp_j) in the place
-// of 2 k n_lights ns: k <= r^2 / d^2 and e / max(e) <= 1, so one sample adds at most 2 sum_i max(e_i) per unit of throughput, and with
-// one valid light tot / imp_j is exactly 1.0 and the sample is nee_sample_cone's, bit for bit.
+// partial sum exceeds u01(x) tot.  Then cone_toward for that light (imp_j > 0.0 has decided its d2 > r^2 already), and the weight
+// 2 k ns (tot / imp_j) in the place of 2 k n_lights ns: k <= r^2 / d^2 and e / max(e) <= 1, so one sample adds at most 2 sum_i max(e_i) per
+// unit of throughput, and with one valid light tot / imp_j is exactly 1.0 and the sample is nee_sample_cone's, bit for bit.
 __device__ __forceinline__ bool nee_sample_weighted(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t n_lights,
                                                     const D3 &p, const D3 &n, const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv,
                                                     D3 &c, int &li)
 {
-    U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
+    const U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
     double tot = 0.0;
     for (int32_t i = 0; i < n_lights; ++i) {
         const double imp = light_importance(P, emission, n_emission, lights, i, p);
@@ -265,35 +284,28 @@ __device__ __forceinline__ bool nee_sample_weighted(const KParams &P, const doub
     }
     if (j < 0) return false;                                                             // (tot > 0.0 has decided this already)
     li = lights[j];
-    const double4 g = *reinterpret_cast<const double4 *>(P.geo + 4 * (size_t)li);        // centre, r^2
-    const D3 wv = mk(g.x, g.y, g.z) - p;
-    const double d2 = (wv.x * wv.x + wv.y * wv.y) + wv.z * wv.z;
-    if (!(d2 > g.w)) return false;                                                       // (so has imp_j > 0.0)
-    const double q = g.w / d2;
-    const double cm = __builtin_sqrt(1.0 - q);                                           // cos theta_max
-    const double k = q / (1.0 + cm);                                                     // 1 - cos theta_max, without the cancellation
-    const double s = u01(b.y) * k;
-    const double ct = 1.0 - s;
-    const double st = __builtin_sqrt(s * (1.0 + ct));
-    uint32_t tx = b.z, ty = b.w;
-    for (uint32_t m = 1u; !unit_disk_accepts(tx, ty); ++m) {                             // vec3.rs:59-68: a plain loop to acceptance
-        b = philox4x32_10(g_pix, g_s, ev_in, 1u + m, P.k0, P.k1);
-        tx = b.x; ty = b.y;
-    }
-    const double hx = u11(tx), hy = u11(ty);
-    const double il = 1.0 / __builtin_sqrt(hx * hx + hy * hy);                           // (the all-zero try: NaNs, which ns > 0.0 drops)
-    const double cphi = hx * il, sphi = hy * il;
-    const D3 w = wv * (1.0 / __builtin_sqrt(d2));
-    const D3 a = __builtin_fabs(w.x) > 0.9 ? mk(0.0, 1.0, 0.0) : mk(1.0, 0.0, 0.0);
-    const D3 t0 = mk(a.y * w.z - a.z * w.y, a.z * w.x - a.x * w.z, a.x * w.y - a.y * w.x);
-    const D3 t = t0 * (1.0 / __builtin_sqrt(dot(t0, t0)));
-    const D3 bt = mk(w.y * t.z - w.z * t.y, w.z * t.x - w.x * t.z, w.x * t.y - w.y * t.x);
-    dv = (t * (st * cphi) + bt * (st * sphi)) + w * ct;
-    const double ns = dot(n, dv);
-    if (!(ns > 0.0)) return false;                                                       // below the hit's horizon; a NaN fails this
+    double k, ns;
+    if (!cone_toward(P, li, p, n, b, g_pix, g_s, ev_in, dv, k, ns)) return false;
     const double wgt = ((2.0 * k) * ns) * (tot / imp_j);
     c = (weight * ld3(emission + 3 * (size_t)li)) * wgt;
     return true;
 }
+
+// bounce_trip's MODE (wavefront/rt_paths.hip); from kNee on, which sampler a Lambertian hit calls
+constexpr int kUnlit = 0, kLit = 1, kNee = 2, kNeeCone = 3, kNeeWeighted = 4;
+
+// the sampler of MODE: nee_sample's arguments and result
+template <int MODE>
+__device__ __forceinline__ bool nee_sample_for(const KParams &P, const double *emission, int32_t n_emission, const int32_t *lights, int32_t n_lights,
+                                               const D3 &p, const D3 &n, const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv, D3 &c,
+                                               int &li)
+{
+    static_assert(MODE == kNee || MODE == kNeeCone || MODE == kNeeWeighted, "a mode without direct lighting has no sampler");
+    if constexpr (MODE == kNeeWeighted) return nee_sample_weighted(P, emission, n_emission, lights, n_lights, p, n, weight, g_pix, g_s, ev_in, dv, c, li);
+    else if constexpr (MODE == kNeeCone) return nee_sample_cone(P, emission, n_emission, lights, n_lights, p, n, weight, g_pix, g_s, ev_in, dv, c, li);
+    else return nee_sample(P, emission, n_emission, lights, n_lights, p, n, weight, g_pix, g_s, ev_in, dv, c, li);
+}
+
+#undef RT_NAMES_NO_LIGHT
 
 } // namespace rt

@@ -15,7 +15,7 @@ import nee_ref as nr
 import oracle
 import paths_ref as pr
 import wavefront_ref as wr
-from trace_ref import Scene, canonical, fast_hit
+from trace_ref import Scene, fast_hit
 
 CONE = 2                                           # RT_DIRECT_CONE
 DIRECT, MASK64 = nr.DIRECT, nr.MASK64
@@ -89,58 +89,25 @@ def sample_light_cone(scene, seed, light, lights, pixel, sample, ev_in, p, n, we
     return out
 
 
-def bounce_cone(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4, flags=CONE):
-    """nee_ref.bounce_nee with the light sample of direct->flags (CONE: sample_light_cone; 0: nee_ref.sample_light) -> (the new state per
-    INPUT slot, the fate of each, the additions u64 [npix, 3], per slot the light sample or None)."""
+def sampler_of(flags):
+    """The light sample of direct->flags: CONE: sample_light_cone; 0: nee_ref.sample_light."""
     assert flags in (0, CONE)
-    sampler = sample_light_cone if flags & CONE else nr.sample_light
-    if not isinstance(scene, Scene):
-        scene = Scene(scene)
-    # what does not depend on the sampler: nee_ref's, run without a list
-    new, fates, adds, samples = nr.bounce_nee(scene, queue, seed, npix, light, (), no_direct, t_min)
-    new = {f: np.array(new[f], copy=True) for f in pr.FIELDS}
-    if len(lights) > 0 and not no_direct:
-        lib = oracle.load()
-        for k in range(len(fates)):
-            if fates[k] != "lambertian":
-                continue
-            idx, _, p, nrm, _ = fast_hit(scene, queue["origin"][k].tolist(), queue["dir"][k].tolist(), t_min)
-            pixel = int(queue["pixel"][k])
-            s = sampler(scene, seed, light, lights, pixel, int(queue["sample"][k]), int(queue["event"][k]) & (DIRECT ^ 0xFFFFFFFF), p, nrm,
-                        new["throughput"][k].tolist(), t_min)
-            samples[k] = s
-            new["event"][k] |= np.uint32(DIRECT)
-            if s["visible"] and pixel < npix:
-                for c in range(3):
-                    adds[pixel, c] = np.uint64((int(adds[pixel, c]) + int(lib.oracle_b_quantize(float(s["c"][c])))) & MASK64)
-    return new, fates, adds, samples
+    return sample_light_cone if flags & CONE else nr.sample_light
+
+
+def bounce_cone(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4, flags=CONE):
+    """nee_ref.bounce_direct with the light sample of direct->flags."""
+    return nr.bounce_direct(scene, queue, seed, npix, light, lights, sampler_of(flags), no_direct, t_min)
 
 
 def step_cone(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4, flags=CONE):
-    """rt_paths_step_nee_device with direct->flags -> (the out queue, the additions u64 [npix, 3], the live count, the shadow rays traced)."""
-    new, fates, adds, samples = bounce_cone(scene, queue, seed, npix, light, lights, no_direct, t_min, flags)
-    keep = np.array([f in lr.SURVIVES for f in fates], dtype=bool)
-    out = {f: new[f][keep] for f in pr.FIELDS}
-    for f in ("origin", "dir", "throughput"):
-        out[f] = canonical(out[f])
-    return out, adds, len(fates), sum(1 for s in samples if s is not None and s["shadow"])
+    """nee_ref.step_direct with the light sample of direct->flags."""
+    return nr.step_direct(scene, queue, seed, npix, light, lights, sampler_of(flags), no_direct, t_min)
 
 
-def render_cone(flat, ocam, width, height, spp, light, *, max_depth=50, seed=1, t_min=1e-4, sample_begin=0, batch=1 << 20, flags=CONE):
-    """rt_render_wavefront_nee_sampled: nee_ref.render_nee's loop with step_cone -> (fix u64 [H, W, 3], rays traced, shadow rays traced)."""
-    scene = Scene(flat)
-    lights = nr.light_list(light.emission)
-    npix = width * height
-    fix = np.zeros((npix, 3), dtype=np.uint64)
-    rays = shadow = 0
-    for first in range(0, npix * spp, batch):
-        q = pr.begin(ocam, width, height, seed, spp, sample_begin, first, min(batch, npix * spp - first))
-        for depth in range(max_depth):
-            q, adds, live, sh = step_cone(scene, q, seed, npix, light, lights, depth + 1 == max_depth, t_min, flags)
-            fix += adds                                                         # (u64: wraps as the device's adds do)
-            rays += live
-            shadow += sh
-    return fix.reshape(height, width, 3), rays, shadow
+def render_cone(flat, ocam, width, height, spp, light, *, flags=CONE, **frame):
+    """rt_render_wavefront_nee_sampled: nee_ref.render_direct (whose keywords `frame` holds) with the light sample of direct_flags."""
+    return nr.render_direct(flat, ocam, width, height, spp, light, sampler_of(flags), **frame)
 
 
 # ---- the hand-built cone queue of the GPU tests: hard by construction, checked by tests/test_cone_host.py -----------------------------------

@@ -14,13 +14,13 @@ import numpy as np
 import oracle
 import paths_ref as pr
 import wavefront_ref as wr
-from trace_ref import Scene, canonical, fast_hit
+from trace_ref import Scene, fast_hit
 
 Light = collections.namedtuple("Light", "sky_bottom sky_top emission")
 REFERENCE_SKY = ((1.0, 1.0, 1.0), (0.5, 0.7, 1.0))
 REFERENCE = Light(*REFERENCE_SKY, None)
 MASK64 = (1 << 64) - 1
-SURVIVES = ("lambertian", "metal", "refract", "reflect", "tir")
+SURVIVES = pr.SURVIVES
 
 
 def is_light(e):
@@ -81,26 +81,14 @@ def bounce_lit(scene, queue, seed, npix, light, t_min=1e-4):
 
 def step_lit(scene, queue, seed, npix, light, t_min=1e-4):
     """rt_paths_step_lit_device -> (the out queue, the additions u64 [npix, 3], the live count of `queue`)."""
-    new, fates, adds = bounce_lit(scene, queue, seed, npix, light, t_min)
-    keep = np.array([f in SURVIVES for f in fates], dtype=bool)
-    out = {f: new[f][keep] for f in pr.FIELDS}
-    for f in ("origin", "dir", "throughput"):
-        out[f] = canonical(out[f])
-    return out, adds, len(fates)
+    return pr.compact(*bounce_lit(scene, queue, seed, npix, light, t_min))
 
 
 def render_lit(flat, ocam, width, height, spp, light, *, max_depth=50, seed=1, t_min=1e-4, sample_begin=0, batch=1 << 20):
-    """rt_render_wavefront_lit: paths_ref.render's loop with the lit step -> (fix u64 [H, W, 3], rays traced)."""
-    scene = Scene(flat)
-    npix = width * height
-    fix = np.zeros((npix, 3), dtype=np.uint64)
-    rays = 0
-    for first in range(0, npix * spp, batch):
-        q = pr.begin(ocam, width, height, seed, spp, sample_begin, first, min(batch, npix * spp - first))
-        for _ in range(max_depth):
-            q, adds, live = step_lit(scene, q, seed, npix, light, t_min)
-            fix += adds                                                         # (u64: wraps as the device's adds do)
-            rays += live
+    """rt_render_wavefront_lit: paths_ref.frame with the lit step -> (fix u64 [H, W, 3], rays traced)."""
+    scene, npix = Scene(flat), width * height
+    fix, rays, _ = pr.frame(lambda first, n: pr.begin(ocam, width, height, seed, spp, sample_begin, first, n),
+                            lambda q, last: step_lit(scene, q, seed, npix, light, t_min), npix, npix * spp, max_depth, batch)
     return fix.reshape(height, width, 3), rays
 
 

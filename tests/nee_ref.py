@@ -15,7 +15,7 @@ import lights_ref as lr
 import oracle
 import paths_ref as pr
 import wavefront_ref as wr
-from trace_ref import Scene, canonical, fast_hit
+from trace_ref import Scene, fast_hit
 
 DIRECT = 0x80000000                                # RT_PATH_EVENT_DIRECT
 NO_DIRECT = 1                                      # RT_STEP_NO_DIRECT
@@ -83,9 +83,11 @@ def sample_light(scene, seed, light, lights, pixel, sample, ev_in, p, n, weight,
     return out
 
 
-def bounce_nee(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4):
-    """One NEE bounce of every path of `queue` -> (the new state per INPUT slot, the fate of each -- lights_ref.bounce_lit's, or
-    "light_counted" for a DIRECT path on a light's front face --, the additions u64 [npix, 3], per slot the light sample or None)."""
+def bounce_direct(scene, queue, seed, npix, light, lights, sampler, no_direct=False, t_min=1e-4):
+    """One bounce with direct lighting of every path of `queue`, the light sample at a Lambertian hit being `sampler`'s (sample_light, or a
+    function of its arguments and result keys) -> (the new state per INPUT slot, the fate of each -- lights_ref.bounce_lit's, or
+    "light_counted" for a DIRECT path on a light's front face --, the additions u64 [npix, 3], per slot the light sample or None).
+    With an empty list or no_direct: the part that no sampler changes."""
     if not isinstance(scene, Scene):
         scene = Scene(scene)
     n = len(queue["pixel"])
@@ -113,8 +115,7 @@ def bounce_nee(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1
             idx, _, p, nrm, _ = hits[k]
             assert int(scene.flat[idx]["kind"]) == wr.LAMBERTIAN
             pixel = int(queue["pixel"][k])
-            s = sample_light(scene, seed, light, lights, pixel, int(queue["sample"][k]), int(masked["event"][k]), p, nrm,
-                             new["throughput"][k].tolist(), t_min)
+            s = sampler(scene, seed, light, lights, pixel, int(queue["sample"][k]), int(masked["event"][k]), p, nrm, new["throughput"][k].tolist(), t_min)
             samples[k] = s
             new["event"][k] |= np.uint32(DIRECT)
             if s["visible"] and pixel < npix:
@@ -123,32 +124,35 @@ def bounce_nee(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1
     return new, fates, adds, samples
 
 
-def step_nee(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4):
-    """rt_paths_step_nee_device -> (the out queue, the additions u64 [npix, 3], the live count of `queue`, the shadow rays traced)."""
-    new, fates, adds, samples = bounce_nee(scene, queue, seed, npix, light, lights, no_direct, t_min)
-    keep = np.array([f in lr.SURVIVES for f in fates], dtype=bool)
-    out = {f: new[f][keep] for f in pr.FIELDS}
-    for f in ("origin", "dir", "throughput"):
-        out[f] = canonical(out[f])
-    return out, adds, len(fates), sum(1 for s in samples if s is not None and s["shadow"])
+def step_direct(scene, queue, seed, npix, light, lights, sampler, no_direct=False, t_min=1e-4):
+    """rt_paths_step_nee_device with the sampler of direct->flags -> (the out queue, the additions u64 [npix, 3], the live count of
+    `queue`, the shadow rays traced)."""
+    new, fates, adds, samples = bounce_direct(scene, queue, seed, npix, light, lights, sampler, no_direct, t_min)
+    return pr.compact(new, fates, adds) + (sum(1 for s in samples if s is not None and s["shadow"]),)
 
 
-def render_nee(flat, ocam, width, height, spp, light, *, max_depth=50, seed=1, t_min=1e-4, sample_begin=0, batch=1 << 20):
-    """rt_render_wavefront_nee: lights_ref.render_lit's loop with the NEE step, the list from the table, the LAST step of each batch
+def render_direct(flat, ocam, width, height, spp, light, sampler, *, max_depth=50, seed=1, t_min=1e-4, sample_begin=0, batch=1 << 20):
+    """rt_render_wavefront_nee and _nee_sampled: paths_ref.frame with step_direct, the list from the table, the LAST step of each batch
     with NO_DIRECT -> (fix u64 [H, W, 3], rays traced, shadow rays traced)."""
-    scene = Scene(flat)
-    lights = light_list(light.emission)
-    npix = width * height
-    fix = np.zeros((npix, 3), dtype=np.uint64)
-    rays = shadow = 0
-    for first in range(0, npix * spp, batch):
-        q = pr.begin(ocam, width, height, seed, spp, sample_begin, first, min(batch, npix * spp - first))
-        for depth in range(max_depth):
-            q, adds, live, sh = step_nee(scene, q, seed, npix, light, lights, depth + 1 == max_depth, t_min)
-            fix += adds                                                         # (u64: wraps as the device's adds do)
-            rays += live
-            shadow += sh
+    scene, npix, lights = Scene(flat), width * height, light_list(light.emission)
+    fix, rays, shadow = pr.frame(lambda first, n: pr.begin(ocam, width, height, seed, spp, sample_begin, first, n),
+                                 lambda q, last: step_direct(scene, q, seed, npix, light, lights, sampler, last, t_min), npix, npix * spp, max_depth, batch)
     return fix.reshape(height, width, 3), rays, shadow
+
+
+def bounce_nee(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4):
+    """bounce_direct with the area sample."""
+    return bounce_direct(scene, queue, seed, npix, light, lights, sample_light, no_direct, t_min)
+
+
+def step_nee(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4):
+    """step_direct with the area sample (direct->flags = 0)."""
+    return step_direct(scene, queue, seed, npix, light, lights, sample_light, no_direct, t_min)
+
+
+def render_nee(flat, ocam, width, height, spp, light, **frame):
+    """rt_render_wavefront_nee: render_direct (whose keywords `frame` holds) with the area sample."""
+    return render_direct(flat, ocam, width, height, spp, light, sample_light, **frame)
 
 
 # ---- the hand-built NEE queue of the GPU tests: hard by construction, checked by tests/test_nee_host.py -------------------------------------

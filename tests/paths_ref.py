@@ -16,6 +16,7 @@ from trace_ref import Scene, canonical, fast_hit
 FIELDS = ("pixel", "sample", "event", "origin", "dir", "throughput")
 MASK64 = (1 << 64) - 1
 FATES = ("miss", "absorbed", "lambertian", "metal", "refract", "reflect", "tir")
+SURVIVES = FATES[2:]                               # the fates of a path that goes on: every step keeps these and no other
 
 
 def empty(n):
@@ -67,32 +68,46 @@ def bounce(scene, queue, seed, npix, t_min=1e-4):
     return new, fates, adds
 
 
-def step(scene, queue, seed, npix, t_min=1e-4):
-    """rt_paths_step_device -> (the out queue: the survivors in the order they had, the additions u64 [npix, 3], the live count of `queue`)."""
-    new, fates, adds = bounce(scene, queue, seed, npix, t_min)
-    keep = np.array([f not in ("miss", "absorbed") for f in fates], dtype=bool)
+def compact(new, fates, adds):
+    """The tail of every step, from a bounce's answer: the survivors in the order they had -> (the out queue, the additions u64 [npix, 3],
+    the live count of the queue that went in)."""
+    keep = np.array([f in SURVIVES for f in fates], dtype=bool)
     out = {f: new[f][keep] for f in FIELDS}
     for f in ("origin", "dir", "throughput"):
         out[f] = canonical(out[f])
     return out, adds, len(fates)
 
 
+def step(scene, queue, seed, npix, t_min=1e-4):
+    """rt_paths_step_device -> compact's three."""
+    return compact(*bounce(scene, queue, seed, npix, t_min))
+
+
 def prefix(queue, n):
     return {f: queue[f][:n] for f in FIELDS}
 
 
-def render(flat, ocam, width, height, spp, *, max_depth=50, seed=1, t_min=1e-4, sample_begin=0, batch=1 << 20):
-    """rt_render_wavefront: batches of `batch` items, per batch begin and then max_depth steps -> (fix u64 [H, W, 3], rays traced)."""
-    scene = Scene(flat)
-    npix = width * height
+def frame(begin, step, npix, total, max_depth, batch):
+    """The loop of every frame form over `total` items: batches of `batch`, per batch q = begin(first_item, n) and then max_depth times
+    step(q, last: this is the batch's last step), which answers (the out queue, the additions, the live count[, the shadow rays traced])
+    -> (fix u64 [npix, 3], rays traced, shadow rays traced)."""
     fix = np.zeros((npix, 3), dtype=np.uint64)
-    rays = 0
-    for first in range(0, npix * spp, batch):
-        q = begin(ocam, width, height, seed, spp, sample_begin, first, min(batch, npix * spp - first))
-        for _ in range(max_depth):
-            q, adds, live = step(scene, q, seed, npix, t_min)
+    rays = shadow = 0
+    for first in range(0, total, batch):
+        q = begin(first, min(batch, total - first))
+        for depth in range(max_depth):
+            q, adds, live, *sh = step(q, depth + 1 == max_depth)
             fix += adds                                                         # (u64: wraps as the device's adds do)
             rays += live
+            shadow += sum(sh)
+    return fix, rays, shadow
+
+
+def render(flat, ocam, width, height, spp, *, max_depth=50, seed=1, t_min=1e-4, sample_begin=0, batch=1 << 20):
+    """rt_render_wavefront: frame() over begin and step -> (fix u64 [H, W, 3], rays traced)."""
+    scene, npix = Scene(flat), width * height
+    fix, rays, _ = frame(lambda first, n: begin(ocam, width, height, seed, spp, sample_begin, first, n),
+                         lambda q, last: step(scene, q, seed, npix, t_min), npix, npix * spp, max_depth, batch)
     return fix.reshape(height, width, 3), rays
 
 

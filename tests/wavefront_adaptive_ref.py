@@ -32,18 +32,16 @@ def begin_pixels(ocam, width, height, seed, spp, sample_begin, first_item, n, pi
     return q
 
 
+SAMPLERS = {AREA: nr.sample_light, CONE: cr.sample_light_cone, WEIGHTED: wt.sample_light_weighted}
+
+
 def _step(scene, q, seed, npix, light, lights, flags, no_direct, t_min):
-    """One step of the frame's kind -> (the out queue, the additions, the live count, the shadow rays traced)."""
+    """One step of the frame's kind -> (the out queue, the additions, the live count[, the shadow rays traced])."""
     if light is None:
-        return pr.step(scene, q, seed, npix, t_min) + (0,)
+        return pr.step(scene, q, seed, npix, t_min)
     if lights is None:
-        return lr.step_lit(scene, q, seed, npix, light, t_min) + (0,)
-    if flags == AREA:
-        return nr.step_nee(scene, q, seed, npix, light, lights, no_direct, t_min)
-    if flags == CONE:
-        return cr.step_cone(scene, q, seed, npix, light, lights, no_direct, t_min)
-    assert flags == WEIGHTED
-    return wt.step_weighted(scene, q, seed, npix, light, lights, no_direct, t_min)
+        return lr.step_lit(scene, q, seed, npix, light, t_min)
+    return nr.step_direct(scene, q, seed, npix, light, lights, SAMPLERS[flags], no_direct, t_min)
 
 
 def render_pixels(flat, ocam, width, height, spp, pixels=None, light=None, direct=False, flags=AREA, *, max_depth=50, seed=1, t_min=1e-4,
@@ -54,16 +52,8 @@ def render_pixels(flat, ocam, width, height, spp, pixels=None, light=None, direc
     npix = width * height
     pixels = np.arange(npix, dtype=np.uint32) if pixels is None else np.asarray(pixels, dtype=np.uint32).reshape(-1)
     lights = nr.light_list(light.emission) if direct else None
-    fix = np.zeros((npix, 3), dtype=np.uint64)
-    rays = shadow = 0
-    total = len(pixels) * spp
-    for first in range(0, total, batch):
-        q = begin_pixels(ocam, width, height, seed, spp, sample_begin, first, min(batch, total - first), pixels)
-        for depth in range(max_depth):
-            q, adds, live, sh = _step(scene, q, seed, npix, light, lights, flags, depth + 1 == max_depth, t_min)
-            fix += adds                                                         # (u64: wraps as the device's adds do)
-            rays += live
-            shadow += sh
+    fix, rays, shadow = pr.frame(lambda first, n: begin_pixels(ocam, width, height, seed, spp, sample_begin, first, n, pixels),
+                                 lambda q, last: _step(scene, q, seed, npix, light, lights, flags, last, t_min), npix, len(pixels) * spp, max_depth, batch)
     return fix.reshape(height, width, 3), rays, shadow
 
 

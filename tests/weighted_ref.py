@@ -16,7 +16,7 @@ import nee_ref as nr
 import oracle
 import paths_ref as pr
 import wavefront_ref as wr
-from trace_ref import Scene, canonical, fast_hit
+from trace_ref import Scene, fast_hit
 
 CONE = cr.CONE                                     # RT_DIRECT_CONE
 WEIGHTED = 8                                       # RT_DIRECT_WEIGHTED
@@ -95,55 +95,18 @@ def sample_light_weighted(scene, seed, light, lights, pixel, sample, ev_in, p, n
 
 
 def bounce_weighted(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4):
-    """cone_ref.bounce_cone with sample_light_weighted in the sampler's place -> (the new state per INPUT slot, the fate of each, the
-    additions u64 [npix, 3], per slot the light sample or None)."""
-    if not isinstance(scene, Scene):
-        scene = Scene(scene)
-    new, fates, adds, samples = nr.bounce_nee(scene, queue, seed, npix, light, (), no_direct, t_min)     # what no sampler changes
-    new = {f: np.array(new[f], copy=True) for f in pr.FIELDS}
-    if len(lights) > 0 and not no_direct:
-        lib = oracle.load()
-        for k in range(len(fates)):
-            if fates[k] != "lambertian":
-                continue
-            idx, _, p, nrm, _ = fast_hit(scene, queue["origin"][k].tolist(), queue["dir"][k].tolist(), t_min)
-            pixel = int(queue["pixel"][k])
-            s = sample_light_weighted(scene, seed, light, lights, pixel, int(queue["sample"][k]), int(queue["event"][k]) & (DIRECT ^ 0xFFFFFFFF), p,
-                                      nrm, new["throughput"][k].tolist(), t_min)
-            samples[k] = s
-            new["event"][k] |= np.uint32(DIRECT)
-            if s["visible"] and pixel < npix:
-                for c in range(3):
-                    adds[pixel, c] = np.uint64((int(adds[pixel, c]) + int(lib.oracle_b_quantize(float(s["c"][c])))) & MASK64)
-    return new, fates, adds, samples
+    """nee_ref.bounce_direct with sample_light_weighted."""
+    return nr.bounce_direct(scene, queue, seed, npix, light, lights, sample_light_weighted, no_direct, t_min)
 
 
 def step_weighted(scene, queue, seed, npix, light, lights, no_direct=False, t_min=1e-4):
-    """rt_paths_step_nee_device with direct->flags = 10 -> (the out queue, the additions u64 [npix, 3], the live count, the shadow rays)."""
-    new, fates, adds, samples = bounce_weighted(scene, queue, seed, npix, light, lights, no_direct, t_min)
-    keep = np.array([f in lr.SURVIVES for f in fates], dtype=bool)
-    out = {f: new[f][keep] for f in pr.FIELDS}
-    for f in ("origin", "dir", "throughput"):
-        out[f] = canonical(out[f])
-    return out, adds, len(fates), sum(1 for s in samples if s is not None and s["shadow"])
+    """nee_ref.step_direct with sample_light_weighted (direct->flags = 10)."""
+    return nr.step_direct(scene, queue, seed, npix, light, lights, sample_light_weighted, no_direct, t_min)
 
 
-def render_weighted(flat, ocam, width, height, spp, light, *, max_depth=50, seed=1, t_min=1e-4, sample_begin=0, batch=1 << 20):
-    """rt_render_wavefront_nee_sampled with direct_flags = 10: cone_ref.render_cone's loop with step_weighted -> (fix u64 [H, W, 3], rays
-    traced, shadow rays traced)."""
-    scene = Scene(flat)
-    lights = nr.light_list(light.emission)
-    npix = width * height
-    fix = np.zeros((npix, 3), dtype=np.uint64)
-    rays = shadow = 0
-    for first in range(0, npix * spp, batch):
-        q = pr.begin(ocam, width, height, seed, spp, sample_begin, first, min(batch, npix * spp - first))
-        for depth in range(max_depth):
-            q, adds, live, sh = step_weighted(scene, q, seed, npix, light, lights, depth + 1 == max_depth, t_min)
-            fix += adds                                                         # (u64: wraps as the device's adds do)
-            rays += live
-            shadow += sh
-    return fix.reshape(height, width, 3), rays, shadow
+def render_weighted(flat, ocam, width, height, spp, light, **frame):
+    """rt_render_wavefront_nee_sampled with direct_flags = 10: nee_ref.render_direct (whose keywords `frame` holds) with sample_light_weighted."""
+    return nr.render_direct(flat, ocam, width, height, spp, light, sample_light_weighted, **frame)
 
 
 def weighted_sample_bound(emission=None, lights=None):
