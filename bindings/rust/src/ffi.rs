@@ -387,6 +387,20 @@ extern "C" {
     /// The same filter on host buffers, no device needed.
     pub fn rt_denoise_host(fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64, width: i32, height: i32,
                            dn: *const rt_denoise, out_fix: *mut u64) -> i32;
+    /// The variance-guided denoiser: the same filter with its colour stop in units of the local standard deviation.  `d_half` / `half`:
+    /// the sums of half of each pixel's samples (what the adaptive drivers return, or the first of two equal accumulated passes); the
+    /// per-pixel variance they give travels through the levels.  `sigma_color` is in standard deviations and does not halve per level.
+    /// `d_work`: `rt_denoise_var_workspace_bytes` bytes of device memory (19 doubles per pixel), the caller's.
+    pub fn rt_denoise_var_workspace_bytes(width: i32, height: i32, out_bytes: *mut i64) -> i32;
+    pub fn rt_denoise_var_device(ctx: *mut rt_context, d_fix: *const c_void, d_half: *const c_void, d_count: *const c_void, spp: i64,
+                                 d_feat: *const c_void, feat_spp: i64, width: i32, height: i32, dn: *const rt_denoise,
+                                 d_work: *mut c_void, d_out_fix: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_denoise_var(ctx: *mut rt_context, fix: *const u64, half: *const u64, count: *const u32, spp: i64, feat: *const u64,
+                          feat_spp: i64, width: i32, height: i32, dn: *const rt_denoise, out_fix: *mut u64,
+                          kernel_ms: *mut f32) -> i32;
+    /// The same filter on host buffers, no device needed.
+    pub fn rt_denoise_var_host(fix: *const u64, half: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64,
+                               width: i32, height: i32, dn: *const rt_denoise, out_fix: *mut u64) -> i32;
     /// Temporal accumulation over a STATIC scene: the current frame's sums blended with the previous call's result, fetched where each
     /// pixel's first-hit point lay in the previous camera's image.  History: all four of `prev_fix`, `prev_len`, `prev_feat`, `prev_cam`
     /// or none (null: the first frame).  The cameras and the options are HOST pointers in every form.  `out_fix` is a ONE-SAMPLE frame of

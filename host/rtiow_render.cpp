@@ -8,6 +8,7 @@
 //                [--adaptive THRESHOLD [--step N]]
 //                [--cameras cams.bin | --orbit N  [--sample-stride S]] [--dump-cameras cams.bin] [--features features.npy]
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
+//                [--denoise-variance [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
 //                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct | --direct-cone | --direct-weighted]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
@@ -57,6 +58,13 @@
 // --direct; not together with either of the other two.
 // --wavefront ... --adaptive THRESHOLD [--step N]: the adaptive loop over the device path queue's frame (rt_render_wavefront_adaptive, DESIGN.md
 // section 24), with --sky, --emit and --direct* as without it; the resolve and the summary line are --adaptive's.  Not with --denoise.
+// --denoise-variance: the variance-guided denoiser (rt_denoise_var) with --denoise's option switches; --sigma-color is then
+// in standard deviations of the pixel's own noise (default 1) and does not halve per level.  The filter needs the sums of HALF of each
+// pixel's samples: without --adaptive the frame is rendered as two passes of spp / 2 (an odd --spp exits 2) -- pass 1 is kept as `half`, pass 2
+// renders the samples from sample_begin = spp / 2 on top of it, which gives the sums of one pass --; with --adaptive the loop's own half
+// and count buffers go in.  Legal with --wavefront, --sky, --emit, --direct* and --adaptive included (rt_render_wavefront_pixels with
+// RT_FLAG_ACCUMULATE, rt_render_wavefront_adaptive); then rt_render_features, rt_denoise_var and the one-sample resolve.  Not together with
+// --denoise; --wavefront --denoise stays refused.  Single device; not with --uniform53, --passes, --two-calls, --features, --cameras, --orbit.
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -113,6 +121,7 @@ int main(int argc, char **argv)
     std::string cameras_file, dump_cameras, features_file;
     int orbit = 0, sample_stride = -1;           // (-1: spp)
     bool denoise = false;
+    bool denoise_var = false, sigma_color_set = false;      // --denoise-variance: --sigma-color is in standard deviations, default 1
     int feature_spp = 8;
     struct rt_denoise dn{};
     dn.levels = 4; dn.flags = RT_DENOISE_DEMODULATE; dn.sigma_color = 0.35; dn.sigma_normal = 1.0; dn.sigma_depth = 0.2;
@@ -179,9 +188,10 @@ int main(int argc, char **argv)
         else if (arg("--dump-cameras")) dump_cameras = argv[++i];
         else if (arg("--features")) features_file = argv[++i];
         else if (!std::strcmp(argv[i], "--denoise")) denoise = true;
+        else if (!std::strcmp(argv[i], "--denoise-variance")) denoise_var = true;
         else if (arg("--feature-spp")) feature_spp = std::atoi(argv[++i]);
         else if (arg("--denoise-levels")) dn.levels = std::atoi(argv[++i]);
-        else if (arg("--sigma-color")) dn.sigma_color = std::atof(argv[++i]);
+        else if (arg("--sigma-color")) { dn.sigma_color = std::atof(argv[++i]); sigma_color_set = true; }
         else if (arg("--sigma-normal")) dn.sigma_normal = std::atof(argv[++i]);
         else if (arg("--sigma-depth")) dn.sigma_depth = std::atof(argv[++i]);
         else if (!std::strcmp(argv[i], "--temporal")) temporal = true;
@@ -280,6 +290,19 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--temporal accumulates a frame batch (--cameras / --orbit) on one device and goes with none of --devices, --passes, --adaptive, --uniform53, --two-calls\n");
         return 2;
     }
+    if (denoise_var && denoise) {
+        std::fprintf(stderr, "--denoise and --denoise-variance are two filters for the same frame: give one of them\n");
+        return 2;
+    }
+    if (denoise_var && (!devices.empty() || batch || temporal || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
+        std::fprintf(stderr, "--denoise-variance renders on one device and goes with none of --devices, --cameras, --orbit, --temporal, --uniform53, --passes, --two-calls, --features\n");
+        return 2;
+    }
+    if (denoise_var && !adaptive && (spp < 2 || spp % 2 != 0)) {
+        std::fprintf(stderr, "--denoise-variance renders the frame as two passes of spp / 2: --spp must be even and >= 2 (is %d)\n", spp);
+        return 2;
+    }
+    if (denoise_var && !sigma_color_set) dn.sigma_color = 1.0;
     if (denoise && (!devices.empty() || (batch && !temporal) || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
         std::fprintf(stderr, "--denoise renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --passes, --two-calls, --features\n");
         return 2;
@@ -454,7 +477,77 @@ int main(int argc, char **argv)
         if (rc) return die("rt_upload_scene", rc);
         std::vector<uint64_t> dn_fix;                // --denoise: the frame's sums ...
         std::vector<uint32_t> dn_count;              // ... and, with --adaptive, every pixel's own number of samples
-        if (adaptive && wavefront) {             // the adaptive loop over the device path queue's frame, lit or not; then the resolve with counts
+        if (denoise_var) {
+            // the variance-guided denoiser: the frame's sums, the sums of half of every pixel's samples and (adaptive) the counts -- from the
+            // dense kernel or the device path queue --, then the guides, the filter and the one-sample resolve
+            std::vector<uint64_t> fix(npix * 3), half(npix * 3);
+            std::vector<uint32_t> count;
+            const bool any_direct = direct || direct_cone || direct_weighted;
+            const uint32_t direct_flags = direct_weighted ? (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) : direct_cone ? RT_DIRECT_CONE : 0u;
+            uint64_t rays = 0, shadow = 0;
+            if (adaptive) {
+                rt_adaptive ad{};
+                ad.step = step; ad.reserved = 0; ad.threshold = threshold; ad.dark_floor = 0.01;
+                count.resize(npix);
+                if (wavefront) {
+                    rc = rt_render_wavefront_adaptive(ctx, &rc_cam, &p, &ad, lit ? &light : nullptr, any_direct ? 1 : 0, direct_flags, fix.data(),
+                                                      half.data(), count.data(), &rays, &shadow, &st.kernel_ms);
+                    if (rc) return die("rt_render_wavefront_adaptive", rc);
+                    st.rays_traced = rays;
+                    st.samples = 0;
+                    for (uint32_t c : count) st.samples += c;
+                } else {
+                    rc = rt_render_adaptive(ctx, &rc_cam, &p, &ad, fix.data(), half.data(), count.data(), &st);
+                    if (rc) return die("rt_render_adaptive", rc);
+                }
+                uint32_t cmin = count[0], cmax = count[0];
+                for (uint32_t c : count) { cmin = c < cmin ? c : cmin; cmax = c > cmax ? c : cmax; }
+                char note[160];
+                std::snprintf(note, sizeof(note), " adaptive threshold %g step %d: %.1f samples per pixel (min %u, max %u),", threshold, step,
+                              (double)st.samples / (double)npix, cmin, cmax);
+                count_note = note;
+            } else {
+                rt_params q = p;                 // two passes of spp / 2: the first is `half`, the second renders the later samples on top of it
+                q.spp = spp / 2;
+                if (wavefront) {
+                    float ms = 0.0f;
+                    rc = rt_render_wavefront_pixels(ctx, &rc_cam, &q, lit ? &light : nullptr, any_direct ? 1 : 0, direct_flags, nullptr, (int64_t)npix,
+                                                    half.data(), &rays, &shadow, &ms);
+                    if (rc) return die("rt_render_wavefront_pixels", rc);
+                    st.kernel_ms = ms;
+                    fix = half;
+                    q.sample_begin = spp / 2; q.flags |= RT_FLAG_ACCUMULATE;
+                    rc = rt_render_wavefront_pixels(ctx, &rc_cam, &q, lit ? &light : nullptr, any_direct ? 1 : 0, direct_flags, nullptr, (int64_t)npix,
+                                                    fix.data(), &rays, &shadow, &ms);
+                    if (rc) return die("rt_render_wavefront_pixels", rc);
+                    st.kernel_ms += ms; st.rays_traced = rays;
+                } else {
+                    rt_stats st2{};
+                    rc = rt_render(ctx, &rc_cam, &q, nullptr, half.data(), &st);
+                    if (rc) return die("rt_render", rc);
+                    q.sample_begin = spp / 2;
+                    rc = rt_render(ctx, &rc_cam, &q, nullptr, fix.data(), &st2);
+                    if (rc) return die("rt_render", rc);
+                    for (size_t k = 0; k < npix * 3; ++k) fix[k] += half[k];        // exact integer sums: what one pass of spp samples gives
+                    st.rays_traced += st2.rays_traced; st.kernel_ms += st2.kernel_ms;
+                }
+                st.samples = (uint64_t)npix * (uint64_t)spp;
+            }
+            if (any_direct) std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
+            rt_params fp = p;
+            fp.spp = feature_spp;
+            std::vector<uint64_t> feat(npix * RT_FEATURE_WORDS), clean(npix * 3);
+            float feat_ms = 0.0f, dn_ms = 0.0f;
+            rc = rt_render_features(ctx, &rc_cam, &fp, feat.data(), nullptr, &feat_ms);
+            if (rc) return die("rt_render_features", rc);
+            rc = rt_denoise_var(ctx, fix.data(), half.data(), adaptive ? count.data() : nullptr, spp, feat.data(), feature_spp, width, height, &dn,
+                                clean.data(), &dn_ms);
+            if (rc) return die("rt_denoise_var", rc);
+            rc = rt_resolve_rgba8(ctx, clean.data(), width, height, 1, 1, rgba.data());
+            if (rc) return die("rt_resolve_rgba8", rc);
+            std::printf("denoised by variance: %d levels, sigmas %g (standard deviations) / %g / %g, features at %d spp (kernel %.3f ms), filter kernels %.3f ms\n",
+                        dn.levels, dn.sigma_color, dn.sigma_normal, dn.sigma_depth, feature_spp, feat_ms, dn_ms);
+        } else if (adaptive && wavefront) {      // the adaptive loop over the device path queue's frame, lit or not; then the resolve with counts
             rt_adaptive ad{};
             ad.step = step; ad.reserved = 0; ad.threshold = threshold; ad.dark_floor = 0.01;
             std::vector<uint64_t> fix(npix * 3);

@@ -473,6 +473,55 @@ int rt_denoise(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int6
 int rt_denoise_host(const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp, int32_t width,
                     int32_t height, const struct rt_denoise *dn, uint64_t *out_fix);
 
+/* ---- variance-guided denoiser: the a-trous filter with its colour stop in units of the local standard deviation ---- */
+
+/* The denoiser above with ONE change of principle (the spatial filter of SVGF, Schied et al., HPG 2017): a per-pixel variance, estimated
+ * from the sums of HALF of each pixel's samples, travels through the levels; colour differences are measured in units of the local
+ * standard deviation, not against an absolute width; the variance is propagated with the squared weights.  DESIGN.md section 25.
+ * Buffers as above, and
+ *   half   [H][W][3] u64   the sums of half of each pixel's samples: what rt_render_adaptive and rt_render_wavefront_adaptive return as
+ *          `half`, or the first of two equal accumulated passes.  Any split into two halves of equal size is valid (the samples are
+ *          independent).  count (or spp) is meant to be even and >= 2; odd values are not rejected and have the arithmetic below.
+ * `struct rt_denoise` is the one above, unchanged; flags: RT_DENOISE_DEMODULATE only; sigma_color is in STANDARD DEVIATIONS and does not
+ * halve with the level (the variance shrinks by itself).  The output is a one-sample frame of exact sums, like rt_denoise's.
+ *
+ * The contract: IEEE binary64 throughout, in this operation order, no fused multiply-add.  samples = (double)count_p (or spp).
+ *   Prepare.  c0 = c / m, m, n, z: exactly rt_denoise's.  Per channel  d_ch = 2 * half_ch - fix_ch  in wrapping uint64 arithmetic, read
+ *     as two's complement, absolute value taken (the selection rule's d_c);  e_ch = (v(d_ch) / samples) / m_ch;
+ *     var_p = (e_r * e_r + e_g * e_g) + e_b * e_b: the squared half-difference of the two half means, an estimate of the variance of
+ *     the pixel's demodulated mean summed over the channels -- commensurate with the squared RGB distance the colour stop uses.
+ *   Level l = 0 .. levels - 1, hole step s = 2^l:  sc2 = sigma_color * sigma_color;  in, sz2: rt_denoise's.
+ *     1. g_p = the 3x3 box mean of the level's input colour, as above.
+ *     2. gv_p = the 3x3 Gaussian of the level's input variance: the in-frame neighbours q, dy = -1..1 outer, dx = -1..1 inner,
+ *        kk = (1, 2, 1; 2, 4, 2; 1, 2, 1) / 16;  sv = sv + kk * var_q and sk = sk + kk, both from 0.0;  gv_p = sv / sk.
+ *     3. izp as above;  icv = 1.0 / (sc2 * gv_p + 1e-12).  The 25 taps in rt_denoise's order with its skip rule, k, xn, xz and t(x):
+ *        xc = ((dr dr + dg dg) + db db) * icv with d = g_p - g_q;  w = ((k * (tc * tc)) * (tn * tn)) * (tz * tz);
+ *        acc_ch = acc_ch + w * c_q,ch,  ws = ws + w  and  va = va + (w * w) * var_q, all from 0.0;
+ *        c'_p,ch = acc_ch / ws  and  var'_p = va / (ws * ws).
+ *   Finish.  rt_denoise's.
+ * The same bits from the device forms, from rt_denoise_var_host and from either form of the level kernel
+ * (RTIOW_DENOISE_LEVEL_KERNEL=gather|tile, the knob of rt_denoise, read per call).
+ *
+ * RT_ERR_INVALID_ARGUMENT from every form, found before anything is touched, in this order, the checks that need no context first: NULL
+ * dn; NULL fix; NULL half; NULL feat or out; levels out of range; unknown flag bits; a sigma <= 0 or not finite; width or height < 1;
+ * width * height > 2^31; spp < 1 with a NULL count; feat_spp < 1; then a NULL workspace (device form), then a NULL context. */
+
+/* The bytes of workspace the device form needs for a width x height frame: 19 doubles per pixel (rt_denoise's 16, two variance planes
+ * and the variance's Gaussian).  This call is the only source of the number. */
+int rt_denoise_var_workspace_bytes(int32_t width, int32_t height, int64_t *out_bytes);
+/* Device form, asynchronous on `stream`.  Every pointer is a device pointer, 8-byte aligned; the buffers must not overlap.  d_work:
+ * rt_denoise_var_workspace_bytes() bytes, the caller's (contents undefined afterwards).  Takes NONE of the context's launch slots,
+ * rt_last_stats does not report on it, and it needs no uploaded scene. */
+int rt_denoise_var_device(rt_context *ctx, const void *d_fix, const void *d_half, const void *d_count, int64_t spp, const void *d_feat,
+                          int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, void *d_work, void *d_out_fix,
+                          void *stream);
+/* Host-buffer form (copies in, filters on the device, copies out); synchronous.  kernel_ms (may be NULL): the kernels' time. */
+int rt_denoise_var(rt_context *ctx, const uint64_t *fix, const uint64_t *half, const uint32_t *count, int64_t spp, const uint64_t *feat,
+                   int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, uint64_t *out_fix, float *kernel_ms);
+/* The same filter on host buffers, no device needed: the library's own CPU statement of the contract (rt_denoise_var_core.hpp). */
+int rt_denoise_var_host(const uint64_t *fix, const uint64_t *half, const uint32_t *count, int64_t spp, const uint64_t *feat,
+                        int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, uint64_t *out_fix);
+
 /* ---- temporal accumulation: last frame's result, reprojected through the first hit ---- */
 
 /* Blends the radiance sums of the current frame of an animation over a STATIC scene with the result of the previous call, fetched where

@@ -139,6 +139,11 @@ SYMBOLS = [
     ("rt_denoise_device", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, _VP, _VP]),
     ("rt_denoise", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, C.POINTER(C.c_float)]),
     ("rt_denoise_host", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP]),
+    # the variance-guided denoiser: the same struct, and the half-sample sums behind fix
+    ("rt_denoise_var_workspace_bytes", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("rt_denoise_var_device", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, _VP, _VP]),
+    ("rt_denoise_var", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, C.POINTER(C.c_float)]),
+    ("rt_denoise_var_host", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP]),
     ("rt_temporal_device", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
                                      C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, _VP]),
     ("rt_temporal", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),

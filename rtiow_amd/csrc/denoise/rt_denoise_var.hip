@@ -1,0 +1,355 @@
+// rt_denoise_var.hip -- the variance-guided a-trous denoiser fed by the half-sample sums (rtiow_hip.h, "variance-guided denoiser";
+// DESIGN.md section 25).
+//
+// The twelfth translation unit of librtiow_hip.so, a sibling of rt_denoise.hip that leaves that file and every other one as they are, so
+// every existing kernel keeps its machine code.  (It lives in a folder of its own for the reason wavefront/ does: tools/isa_fingerprint.py
+// --all is pinned to the kernels of rtiow_amd/csrc/rt_*.hip.)  The arithmetic lives in rt_denoise_var_core.hpp, once, for the kernels
+// here, for rt_denoise_var_host and for the stand-alone sanitizer program of the tests.
+//
+// Launches of one denoise, 2 + 2 levels: prepare (one lane per pixel: rt_denoise's prepare and the variance of the two half means), then
+// per level the statistics (the 3x3 box mean of the colour and the 3x3 Gaussian of the variance, one pass) and the 5x5 a-trous taps, then
+// finish.  The workspace holds 19 doubles per pixel: rt_denoise's 16, two variance planes (a level reads one and writes the other) and
+// the variance's Gaussian.  The level kernel -- the hot path, 25 taps of a record of 11 doubles -- exists in rt_denoise's two forms, which
+// give identical bits (the tap order is fixed by rt_dn::level_pixel_var):
+//   gather  one lane per pixel, the 25 records straight from global memory;
+//   tile    a workgroup takes a 16 x 16 tile of ONE residue class modulo the hole step s, stages its (16 + 4)^2 records in LDS as eleven
+//           planes of 400 doubles (35 200 bytes; plane-major: a wave's lanes read consecutive doubles of one plane) and reads the taps
+//           from there.
+// Which one a level takes: kDnVarTileDefault below, or RTIOW_DENOISE_LEVEL_KERNEL=gather|tile (rt_denoise's diagnostic knob, read per call).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "rt_host.hpp"
+#include "rt_denoise_var_core.hpp"
+
+using namespace rt_host;
+
+namespace rt {
+
+constexpr int kDvBlock = 256;
+constexpr int kDvTile = 16;                         // a workgroup's tile of one sub-lattice: 16 x 16 pixels
+constexpr int kDvSide = kDvTile + 4;                // ... and its halo of two taps on every side
+constexpr int kDvCells = kDvSide * kDvSide;
+constexpr int kDvPlanes = 11;                       // c 3, g 3, n 3, z, var
+constexpr long long kDvMaxBlocks = 1 << 20;         // grid-stride loops beyond (a launch's work-items fit 32 bits)
+
+// Which form of the level kernel ships for hole step 2^l: the one with the lower SUM of the two measured frames' times, 1200x675 and
+// 1920x1080 (profiles/denoise_var.txt, tools/denoise_var_bench.py; statistics pass + level kernel in ms, gather / tile):
+//   level 0 (with prepare and finish)  0.167 / 0.114   0.402 / 0.278   tile
+//   level 1                            0.118 / 0.083   0.277 / 0.160   tile
+//   level 2                            0.120 / 0.105   0.276 / 0.236   tile
+//   level 3                            0.117 / 0.112   0.254 / 0.285   gather (0.371 against 0.397)
+//   level 4                            0.114 / 0.128   0.230 / 0.166   tile   (0.344 against 0.294)
+//   level 5                            0.110 / 0.138   0.228 / 0.188   tile   (0.338 against 0.326)
+// Levels 6 and 7 were not measured and take level 5's form.
+constexpr bool kDnVarTileDefault[rt_dn::kMaxLevels] = {true, true, true, false, true, true, true, true};
+
+struct DvFrame {
+    const double *guide;            // [npix][4] normal xyz, depth
+    const double *cin;              // [npix][3] the level's input colour
+    const double *box;              // [npix][3] its 3x3 box mean
+    const double *vin;              // [npix] the level's input variance
+    const double *gv;               // [npix] its 3x3 Gaussian
+    double *cout;                   // [npix][3] the level's output colour
+    double *vout;                   // [npix] ... and variance
+    uint32_t width, height;
+    unsigned long long npix;
+    rt_dn::LevelConst L;
+    double sc2;                     // sigma_color^2
+};
+
+__device__ __forceinline__ void dv_load_tap(const DvFrame &F, unsigned long long p, rt_dn::TapVar *t)
+{
+    const double *c = F.cin + 3 * p, *g = F.box + 3 * p, *q = F.guide + 4 * p;
+    t->c[0] = c[0]; t->c[1] = c[1]; t->c[2] = c[2];
+    t->g[0] = g[0]; t->g[1] = g[1]; t->g[2] = g[2];
+    t->n[0] = q[0]; t->n[1] = q[1]; t->n[2] = q[2];
+    t->z = q[3];
+    t->var = F.vin[p];
+}
+
+__global__ __launch_bounds__(kDvBlock) void denoise_var_prepare_kernel(const unsigned long long *__restrict__ fix,
+                                                                       const unsigned long long *__restrict__ half,
+                                                                       const uint32_t *__restrict__ count, double spp,
+                                                                       const unsigned long long *__restrict__ feat, double feat_spp,
+                                                                       int demodulate, unsigned long long npix, double *__restrict__ guide,
+                                                                       double *__restrict__ mod, double *__restrict__ c0,
+                                                                       double *__restrict__ var0)
+{
+    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
+    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < npix; p += stride) {
+        double c[3], m[3], n[3], z;
+        const double samples = count ? (double)count[p] : spp;
+        rt_dn::prepare((const uint64_t *)fix + 3 * p, samples, (const uint64_t *)feat + 8 * p, feat_spp, demodulate != 0, c, m, n, &z);
+        var0[p] = rt_dn::prepare_var((const uint64_t *)fix + 3 * p, (const uint64_t *)half + 3 * p, samples, m);
+        c0[3 * p + 0] = c[0]; c0[3 * p + 1] = c[1]; c0[3 * p + 2] = c[2];
+        mod[3 * p + 0] = m[0]; mod[3 * p + 1] = m[1]; mod[3 * p + 2] = m[2];
+        guide[4 * p + 0] = n[0]; guide[4 * p + 1] = n[1]; guide[4 * p + 2] = n[2]; guide[4 * p + 3] = z;
+    }
+}
+
+// the level's statistics in one pass: the 3x3 box mean of the colour and the 3x3 Gaussian of the variance
+__global__ __launch_bounds__(kDvBlock) void denoise_var_stats_kernel(const double *__restrict__ cin, const double *__restrict__ vin,
+                                                                     uint32_t width, uint32_t height, unsigned long long npix,
+                                                                     double *__restrict__ box, double *__restrict__ gv)
+{
+    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
+    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < npix; p += stride) {
+        const uint32_t j = (uint32_t)p / width, i = (uint32_t)p - j * width;        // npix <= 2^31: p fits 32 bits
+        double g[3];
+        rt_dn::box_mean((long long)i, (long long)j, (long long)width, (long long)height,
+                        [cin, width](long long ii, long long jj, double c[3]) {
+                            const double *s = cin + 3 * ((unsigned long long)jj * width + (unsigned long long)ii);
+                            c[0] = s[0]; c[1] = s[1]; c[2] = s[2];
+                        }, g);
+        box[3 * p + 0] = g[0]; box[3 * p + 1] = g[1]; box[3 * p + 2] = g[2];
+        gv[p] = rt_dn::gauss_var((long long)i, (long long)j, (long long)width, (long long)height, [vin, width](long long ii, long long jj) {
+            return vin[(unsigned long long)jj * width + (unsigned long long)ii];
+        });
+    }
+}
+
+// form (a): one lane per pixel, every tap from global memory
+__global__ __launch_bounds__(kDvBlock) void denoise_var_level_gather_kernel(const DvFrame F)
+{
+    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
+    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < F.npix; p += stride) {
+        const uint32_t j = (uint32_t)p / F.width, i = (uint32_t)p - j * F.width;
+        rt_dn::TapVar centre;
+        dv_load_tap(F, p, &centre);
+        const long long s = F.L.step;
+        double out[3], var;
+        rt_dn::level_pixel_var((long long)i, (long long)j, (long long)F.width, (long long)F.height, F.L, F.sc2, F.gv[p], centre,
+                               [&](int dx, int dy, rt_dn::TapVar *t) {
+                                   // (in-frame: level_pixel_var asks for no other tap)
+                                   const long long q = (long long)p + (s * dy) * (long long)F.width + s * dx;
+                                   dv_load_tap(F, (unsigned long long)q, t);
+                               }, out, &var);
+        F.cout[3 * p + 0] = out[0]; F.cout[3 * p + 1] = out[1]; F.cout[3 * p + 2] = out[2];
+        F.vout[p] = var;
+    }
+}
+
+// form (b): a workgroup per 16 x 16 tile of one sub-lattice (pixels with i % s == ri, j % s == rj), the records staged in LDS.
+// tiles_x, tiles_y: tiles per sub-lattice (of the widest one; narrower ones have empty tiles); nri = min(s, width) residues in x.
+struct DvTiling {
+    uint32_t tiles_x, tiles_y, nri, n_tiles;
+};
+
+__global__ __launch_bounds__(kDvBlock) void denoise_var_level_tile_kernel(const DvFrame F, const DvTiling T)
+{
+    __shared__ double s_rec[kDvPlanes][kDvCells];
+    const long long s = F.L.step;
+    const long long W = (long long)F.width, H = (long long)F.height;
+    const int lx = (int)threadIdx.x & (kDvTile - 1), ly = (int)threadIdx.x >> 4;
+    const uint32_t gx = T.nri * T.tiles_x;
+    for (uint32_t t = blockIdx.x; t < T.n_tiles; t += gridDim.x) {
+        const uint32_t by = t / gx, bx = t - by * gx;
+        const uint32_t ri = bx / T.tiles_x, tx = bx - ri * T.tiles_x;
+        const uint32_t rj = by / T.tiles_y, ty = by - rj * T.tiles_y;
+        // sub-lattice coordinates (u, v) -> pixel (ri + s u, rj + s v); the tile's first cell is (16 tx - 2, 16 ty - 2)
+        const long long u0 = (long long)tx * kDvTile - 2, v0 = (long long)ty * kDvTile - 2;
+        for (int cell = (int)threadIdx.x; cell < kDvCells; cell += kDvBlock) {
+            const int cy = cell / kDvSide, cx = cell - cy * kDvSide;
+            const long long ii = (long long)ri + s * (u0 + cx), jj = (long long)rj + s * (v0 + cy);
+            if (ii < 0 || ii >= W || jj < 0 || jj >= H) continue;           // never read: level_pixel_var skips taps outside the frame
+            rt_dn::TapVar r;
+            dv_load_tap(F, (unsigned long long)(jj * W + ii), &r);
+            s_rec[0][cell] = r.c[0]; s_rec[1][cell] = r.c[1]; s_rec[2][cell] = r.c[2];
+            s_rec[3][cell] = r.g[0]; s_rec[4][cell] = r.g[1]; s_rec[5][cell] = r.g[2];
+            s_rec[6][cell] = r.n[0]; s_rec[7][cell] = r.n[1]; s_rec[8][cell] = r.n[2];
+            s_rec[9][cell] = r.z;
+            s_rec[10][cell] = r.var;
+        }
+        __syncthreads();
+        const long long i = (long long)ri + s * (u0 + 2 + lx), j = (long long)rj + s * (v0 + 2 + ly);
+        if (i < W && j < H) {
+            auto staged = [&](int dx, int dy, rt_dn::TapVar *q) {
+                const int cell = (ly + 2 + dy) * kDvSide + (lx + 2 + dx);
+                q->c[0] = s_rec[0][cell]; q->c[1] = s_rec[1][cell]; q->c[2] = s_rec[2][cell];
+                q->g[0] = s_rec[3][cell]; q->g[1] = s_rec[4][cell]; q->g[2] = s_rec[5][cell];
+                q->n[0] = s_rec[6][cell]; q->n[1] = s_rec[7][cell]; q->n[2] = s_rec[8][cell];
+                q->z = s_rec[9][cell];
+                q->var = s_rec[10][cell];
+            };
+            rt_dn::TapVar centre;
+            staged(0, 0, &centre);
+            const unsigned long long p = (unsigned long long)(j * W + i);
+            double out[3], var;
+            rt_dn::level_pixel_var(i, j, W, H, F.L, F.sc2, F.gv[p], centre, staged, out, &var);
+            F.cout[3 * p + 0] = out[0]; F.cout[3 * p + 1] = out[1]; F.cout[3 * p + 2] = out[2];
+            F.vout[p] = var;
+        }
+        __syncthreads();                                                    // the next tile overwrites the records
+    }
+}
+
+__global__ __launch_bounds__(kDvBlock) void denoise_var_finish_kernel(const double *__restrict__ c, const double *__restrict__ mod,
+                                                                      unsigned long long npix, unsigned long long *__restrict__ out)
+{
+    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
+    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < npix; p += stride) {
+        uint64_t q[3];
+        rt_dn::finish(c + 3 * p, mod + 3 * p, q);
+        out[3 * p + 0] = q[0]; out[3 * p + 1] = q[1]; out[3 * p + 2] = q[2];
+    }
+}
+
+} // namespace rt
+
+namespace {
+
+// What every form checks, before anything is touched, in rt_denoise's order with the NULL half behind the NULL fix; none of it needs a
+// context.
+int validate_denoise_var(const struct rt_denoise *dn, const void *fix, const void *half, int64_t spp, bool has_count, const void *feat,
+                         int64_t feat_spp, int32_t width, int32_t height, const void *out)
+{
+    if (!dn) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: dn is NULL");
+    if (!fix) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: a buffer is NULL (fix)");
+    if (!half) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: the half-sample sums are NULL (half)");
+    if (!feat || !out) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: a buffer is NULL (feat or out)");
+    if (dn->levels < 1 || dn->levels > RT_DENOISE_MAX_LEVELS)
+        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: levels must be 1..%d (is %d)", RT_DENOISE_MAX_LEVELS, dn->levels);
+    if (dn->flags & ~RT_DENOISE_DEMODULATE) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: unknown flags 0x%x", dn->flags);
+    if (!(dn->sigma_color > 0.0) || !(dn->sigma_normal > 0.0) || !(dn->sigma_depth > 0.0) || !std::isfinite(dn->sigma_color) ||
+        !std::isfinite(dn->sigma_normal) || !std::isfinite(dn->sigma_depth))
+        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: every sigma must be > 0 and finite (%g, %g, %g)", dn->sigma_color, dn->sigma_normal,
+                    dn->sigma_depth);
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: bad width/height (%d, %d)", width, height);
+    if ((long long)width * height > (1ll << 31))
+        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: width * height must be <= 2^31 (is %lld)", (long long)width * height);
+    if (!has_count && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: spp >= 1 without a count buffer (is %lld)", (long long)spp);
+    if (feat_spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: feat_spp >= 1 (is %lld)", (long long)feat_spp);
+    return RT_OK;
+}
+
+// RTIOW_DENOISE_LEVEL_KERNEL (diagnostic; rt_denoise.hip reads the same variable): -1 not set, 0 gather, 1 tile
+int var_level_kernel_knob()
+{
+    const char *e = getenv("RTIOW_DENOISE_LEVEL_KERNEL");
+    if (!e || !*e) return -1;
+    if (!strcmp(e, "gather")) return 0;
+    if (!strcmp(e, "tile")) return 1;
+    return -1;
+}
+
+unsigned var_blocks_for(unsigned long long items)
+{
+    unsigned long long b = (items + rt::kDvBlock - 1) / rt::kDvBlock;
+    if (b > (unsigned long long)rt::kDvMaxBlocks) b = (unsigned long long)rt::kDvMaxBlocks;
+    return (unsigned)(b < 1 ? 1 : b);
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_denoise_var_workspace_bytes(int32_t width, int32_t height, int64_t *out_bytes)
+{
+    if (!out_bytes) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var workspace: out_bytes is NULL");
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var workspace: bad width/height (%d, %d)", width, height);
+    if ((long long)width * height > (1ll << 31))
+        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var workspace: width * height must be <= 2^31 (is %lld)", (long long)width * height);
+    *out_bytes = (int64_t)width * height * rt_dn::kVarWorkDoubles * (int64_t)sizeof(double);
+    return RT_OK;
+}
+
+int rt_denoise_var_device(rt_context *ctx, const void *d_fix, const void *d_half, const void *d_count, int64_t spp, const void *d_feat,
+                          int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, void *d_work, void *d_out_fix,
+                          void *stream_v)
+{
+    int rc = validate_denoise_var(dn, d_fix, d_half, spp, d_count != nullptr, d_feat, feat_spp, width, height, d_out_fix);
+    if (rc) return rc;
+    if (!d_work) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: the workspace is NULL");
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = (hipStream_t)stream_v;
+    // (no launch slot: rt_last_stats does not report on a denoise; no scene needed)
+    const unsigned long long npix = (unsigned long long)width * (unsigned long long)height;
+    double *guide = (double *)d_work, *mod = guide + 4 * npix, *ca = mod + 3 * npix, *cb = ca + 3 * npix, *box = cb + 3 * npix;
+    double *va = box + 3 * npix, *vb = va + npix, *gv = vb + npix;
+    const unsigned grid = var_blocks_for(npix);
+    hipLaunchKernelGGL(rt::denoise_var_prepare_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, (const unsigned long long *)d_fix,
+                       (const unsigned long long *)d_half, (const uint32_t *)d_count, (double)spp, (const unsigned long long *)d_feat,
+                       (double)feat_spp, (dn->flags & RT_DENOISE_DEMODULATE) ? 1 : 0, npix, guide, mod, ca, va);
+    RT_HIP(hipGetLastError());
+    const int knob = var_level_kernel_knob();
+    for (int l = 0; l < dn->levels; ++l) {
+        hipLaunchKernelGGL(rt::denoise_var_stats_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, (const double *)ca, (const double *)va,
+                           (uint32_t)width, (uint32_t)height, npix, box, gv);
+        RT_HIP(hipGetLastError());
+        rt::DvFrame F;
+        F.guide = guide; F.cin = ca; F.box = box; F.vin = va; F.gv = gv; F.cout = cb; F.vout = vb;
+        F.width = (uint32_t)width; F.height = (uint32_t)height; F.npix = npix;
+        F.L = rt_dn::level_const(dn->sigma_color, dn->sigma_normal, dn->sigma_depth, l);
+        F.sc2 = dn->sigma_color * dn->sigma_color;
+        // the tiling of the sub-lattices: min(s, width) x min(s, height) of them, each ceil(ceil(width / s) / 16) tiles wide
+        const unsigned long long s = (unsigned long long)F.L.step;
+        const unsigned long long nri = s < (unsigned long long)width ? s : (unsigned long long)width;
+        const unsigned long long nrj = s < (unsigned long long)height ? s : (unsigned long long)height;
+        const unsigned long long tiles_x = (((unsigned long long)width + s - 1) / s + rt::kDvTile - 1) / rt::kDvTile;
+        const unsigned long long tiles_y = (((unsigned long long)height + s - 1) / s + rt::kDvTile - 1) / rt::kDvTile;
+        const unsigned long long n_tiles = nri * tiles_x * nrj * tiles_y;
+        bool tile = knob < 0 ? rt::kDnVarTileDefault[l] : knob == 1;
+        if (n_tiles >= (1ull << 31)) tile = false;                          // (the tile number is a 32-bit integer)
+        if (tile) {
+            rt::DvTiling T;
+            T.tiles_x = (uint32_t)tiles_x; T.tiles_y = (uint32_t)tiles_y; T.nri = (uint32_t)nri; T.n_tiles = (uint32_t)n_tiles;
+            const unsigned tgrid = (unsigned)(n_tiles > (unsigned long long)rt::kDvMaxBlocks ? (unsigned long long)rt::kDvMaxBlocks : n_tiles);
+            hipLaunchKernelGGL(rt::denoise_var_level_tile_kernel, dim3(tgrid), dim3(rt::kDvBlock), 0, stream, F, T);
+        } else {
+            hipLaunchKernelGGL(rt::denoise_var_level_gather_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, F);
+        }
+        RT_HIP(hipGetLastError());
+        double *t = ca; ca = cb; cb = t;
+        t = va; va = vb; vb = t;
+    }
+    hipLaunchKernelGGL(rt::denoise_var_finish_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, (const double *)ca, (const double *)mod, npix,
+                       (unsigned long long *)d_out_fix);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_denoise_var(rt_context *ctx, const uint64_t *fix, const uint64_t *half, const uint32_t *count, int64_t spp, const uint64_t *feat,
+                   int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, uint64_t *out_fix, float *kernel_ms)
+{
+    int rc = validate_denoise_var(dn, fix, half, spp, count != nullptr, feat, feat_spp, width, height, out_fix);
+    if (rc) return rc;
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    RT_HIP(hipSetDevice(ctx->device));
+    const size_t npix = (size_t)width * height;
+    Stage st(ctx);
+    const auto sums = st.in(fix, npix * 3), halves = st.in(half, npix * 3), guides = st.in(feat, npix * RT_FEATURE_WORDS);
+    const auto out = st.out(out_fix, npix * 3);
+    const auto work = st.scratch<double>(npix * rt_dn::kVarWorkDoubles);
+    const auto counts = st.in(count, npix);
+    if ((rc = st.commit())) return rc;
+    RT_HIP(st.upload());
+    return timed_section(ctx, "rt_denoise_var", kernel_ms, st, [&] {
+        return rt_denoise_var_device(ctx, st.ptr(sums), st.ptr(halves), st.ptr(counts), spp, st.ptr(guides), feat_spp, width, height, dn,
+                                     st.ptr(work), st.ptr(out), ctx->own_stream);
+    });
+}
+
+// the library's own CPU statement of the filter: the very functions the kernels compile, one pixel after the other
+int rt_denoise_var_host(const uint64_t *fix, const uint64_t *half, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp,
+                        int32_t width, int32_t height, const struct rt_denoise *dn, uint64_t *out_fix)
+{
+    int rc = validate_denoise_var(dn, fix, half, spp, count != nullptr, feat, feat_spp, width, height, out_fix);
+    if (rc) return rc;
+    std::vector<double> work;
+    try {
+        work.resize((size_t)width * height * rt_dn::kVarWorkDoubles);
+    } catch (...) {
+        return fail(RT_ERR_OUT_OF_MEMORY, "rt_denoise_var_host: no memory for the workspace");
+    }
+    rt_dn::filter_var_host(fix, half, count, (long long)spp, feat, (long long)feat_spp, width, height, dn->levels,
+                           (dn->flags & RT_DENOISE_DEMODULATE) != 0, dn->sigma_color, dn->sigma_normal, dn->sigma_depth, work.data(), out_fix);
+    return RT_OK;
+}
+
+} // extern "C"

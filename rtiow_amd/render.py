@@ -75,6 +75,36 @@ def denoise_host(fix, spp, feat, feat_spp, denoise=None, count=None):
     return out
 
 
+DENOISE_VAR_SIGMA_COLOR = 1.0
+
+
+def make_denoise_var(levels=4, sigma_color=DENOISE_VAR_SIGMA_COLOR, sigma_normal=1.0, sigma_depth=0.2, demodulate=True):
+    """The rt_denoise of the variance-guided denoiser (rt_denoise_var*): as make_denoise, but sigma_color is in STANDARD DEVIATIONS of the
+    pixel's own noise and does not halve per level.  Its default is the choice of the sweep in DESIGN.md section 25."""
+    return make_denoise(levels, sigma_color, sigma_normal, sigma_depth, demodulate)
+
+
+def _denoise_var_arrays(fix, half, feat, count):
+    fix, feat, count, h, w = _denoise_arrays(fix, feat, count)
+    half = np.ascontiguousarray(half, dtype=np.uint64)
+    assert half.shape == (h, w, 3)
+    return fix, half, feat, count, h, w
+
+
+def denoise_var_host(fix, half, spp, feat, feat_spp, denoise=None, count=None):
+    """rt_denoise_var_host (no GPU): the library's CPU statement of the variance-guided denoiser.  As denoise_host, with half u64 [H,W,3]:
+    the sums of half of each pixel's samples (render_adaptive's `half`, or the first of two equal accumulated passes)."""
+    lib = _ffi.load()
+    fix, half, feat, count, h, w = _denoise_var_arrays(fix, half, feat, count)
+    dn = denoise if denoise is not None else make_denoise_var()
+    out = np.zeros((h, w, 3), dtype=np.uint64)
+    _ffi.check(lib.rt_denoise_var_host(fix.ctypes.data_as(C.c_void_p), half.ctypes.data_as(C.c_void_p),
+                                       count.ctypes.data_as(C.c_void_p) if count is not None else None, int(spp),
+                                       feat.ctypes.data_as(C.c_void_p), int(feat_spp), w, h, C.byref(dn), out.ctypes.data_as(C.c_void_p)),
+               "rt_denoise_var_host")
+    return out
+
+
 def make_temporal(alpha_min=0.1, sigma_normal=0.5, sigma_depth=0.1, clamp=True, clamp_scale=1.0):
     """rt_temporal: the least weight of the current frame, the widths of the normal and the relative-depth test that a history tap must
     pass, and whether the history is clamped to the box of the current frame's 3 x 3 neighbourhood (scaled about its centre by
@@ -1082,6 +1112,36 @@ class Renderer:
         return int(n.value)
 
     denoise_host = staticmethod(denoise_host)
+
+    # -- variance-guided denoiser: the colour stop in units of the noise the half-sample sums show -------
+    def denoise_var(self, fix, half, spp, feat, feat_spp, denoise=None, count=None):
+        """rt_denoise_var: as denoise, with half u64 [H,W,3], the sums of half of each pixel's samples -> (the denoised ONE-SAMPLE frame
+        u64 [H,W,3], the kernels' time in ms)."""
+        fix, half, feat, count, h, w = _denoise_var_arrays(fix, half, feat, count)
+        dn = denoise if denoise is not None else make_denoise_var()
+        out = np.zeros((h, w, 3), dtype=np.uint64)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_denoise_var(self._h, fix.ctypes.data_as(C.c_void_p), half.ctypes.data_as(C.c_void_p),
+                                            count.ctypes.data_as(C.c_void_p) if count is not None else None, int(spp),
+                                            feat.ctypes.data_as(C.c_void_p), int(feat_spp), w, h, C.byref(dn), out.ctypes.data_as(C.c_void_p),
+                                            C.byref(ms)), "rt_denoise_var")
+        return out, float(ms.value)
+
+    def denoise_var_device(self, d_fix_ptr, d_half_ptr, spp, d_feat_ptr, feat_spp, width, height, denoise, d_work_ptr, d_out_ptr, d_count_ptr=0,
+                           stream=0):
+        """rt_denoise_var_device: device pointers; d_work_ptr: denoise_var_workspace_bytes(width, height) bytes; asynchronous on `stream`."""
+        _ffi.check(self._lib.rt_denoise_var_device(self._h, C.c_void_p(d_fix_ptr), C.c_void_p(d_half_ptr) if d_half_ptr else None,
+                                                   C.c_void_p(d_count_ptr) if d_count_ptr else None, int(spp), C.c_void_p(d_feat_ptr),
+                                                   int(feat_spp), int(width), int(height), C.byref(denoise), C.c_void_p(d_work_ptr),
+                                                   C.c_void_p(d_out_ptr), C.c_void_p(stream)), "rt_denoise_var_device")
+
+    @staticmethod
+    def denoise_var_workspace_bytes(width, height):
+        n = C.c_int64(0)
+        _ffi.check(_ffi.load().rt_denoise_var_workspace_bytes(int(width), int(height), C.byref(n)), "rt_denoise_var_workspace_bytes")
+        return int(n.value)
+
+    denoise_var_host = staticmethod(denoise_var_host)
 
     # -- temporal accumulation: the previous result, reprojected through the first hit ------
     def temporal(self, fix, spp, feat, feat_spp, cam, history=None, temporal=None, count=None):
