@@ -1,10 +1,12 @@
 // rt_denoise_var.hip -- the variance-guided a-trous denoiser fed by the half-sample sums (rtiow_hip.h, "variance-guided denoiser";
 // DESIGN.md section 25).
 //
-// The twelfth translation unit of librtiow_hip.so, a sibling of rt_denoise.hip that leaves that file and every other one as they are, so
-// every existing kernel keeps its machine code.  (It lives in a folder of its own for the reason wavefront/ does: tools/isa_fingerprint.py
-// --all is pinned to the kernels of rtiow_amd/csrc/rt_*.hip.)  The arithmetic lives in rt_denoise_var_core.hpp, once, for the kernels
-// here, for rt_denoise_var_host and for the stand-alone sanitizer program of the tests.
+// The twelfth translation unit of librtiow_hip.so, a sibling of rt_denoise.hip.  (It lives in a folder of its own for the reason
+// wavefront/ does: tools/isa_fingerprint.py --all is pinned to the kernels of rtiow_amd/csrc/rt_*.hip; its own five kernels are pinned by
+// --denoise-var, profiles/isa_fingerprint_denoise_var.txt.)  The arithmetic lives in rt_denoise_var_core.hpp, once, for the kernels here,
+// for rt_denoise_var_host and for the stand-alone sanitizer program of the tests.  What the two denoisers share lives in
+// rt_denoise_shared.hpp and rt_denoise_tile.inc (see rt_denoise.hip); here stay the kernels under their names, the record's eleventh
+// plane, the NULL checks and the measured defaults.
 //
 // Launches of one denoise, 2 + 2 levels: prepare (one lane per pixel: rt_denoise's prepare and the variance of the two half means), then
 // per level the statistics (the 3x3 box mean of the colour and the 3x3 Gaussian of the variance, one pass) and the 5x5 a-trous taps, then
@@ -25,17 +27,11 @@
 
 #include "rt_host.hpp"
 #include "rt_denoise_var_core.hpp"
+#include "rt_denoise_shared.hpp"
 
 using namespace rt_host;
 
 namespace rt {
-
-constexpr int kDvBlock = 256;
-constexpr int kDvTile = 16;                         // a workgroup's tile of one sub-lattice: 16 x 16 pixels
-constexpr int kDvSide = kDvTile + 4;                // ... and its halo of two taps on every side
-constexpr int kDvCells = kDvSide * kDvSide;
-constexpr int kDvPlanes = 11;                       // c 3, g 3, n 3, z, var
-constexpr long long kDvMaxBlocks = 1 << 20;         // grid-stride loops beyond (a launch's work-items fit 32 bits)
 
 // Which form of the level kernel ships for hole step 2^l: the one with the lower SUM of the two measured frames' times, 1200x675 and
 // 1920x1080 (profiles/denoise_var.txt, tools/denoise_var_bench.py; statistics pass + level kernel in ms, gather / tile):
@@ -49,6 +45,7 @@ constexpr long long kDvMaxBlocks = 1 << 20;         // grid-stride loops beyond 
 constexpr bool kDnVarTileDefault[rt_dn::kMaxLevels] = {true, true, true, false, true, true, true, true};
 
 struct DvFrame {
+    using Rec = rt_dn::TapVar;
     const double *guide;            // [npix][4] normal xyz, depth
     const double *cin;              // [npix][3] the level's input colour
     const double *box;              // [npix][3] its 3x3 box mean
@@ -62,17 +59,7 @@ struct DvFrame {
     double sc2;                     // sigma_color^2
 };
 
-__device__ __forceinline__ void dv_load_tap(const DvFrame &F, unsigned long long p, rt_dn::TapVar *t)
-{
-    const double *c = F.cin + 3 * p, *g = F.box + 3 * p, *q = F.guide + 4 * p;
-    t->c[0] = c[0]; t->c[1] = c[1]; t->c[2] = c[2];
-    t->g[0] = g[0]; t->g[1] = g[1]; t->g[2] = g[2];
-    t->n[0] = q[0]; t->n[1] = q[1]; t->n[2] = q[2];
-    t->z = q[3];
-    t->var = F.vin[p];
-}
-
-__global__ __launch_bounds__(kDvBlock) void denoise_var_prepare_kernel(const unsigned long long *__restrict__ fix,
+__global__ __launch_bounds__(kDnBlock) void denoise_var_prepare_kernel(const unsigned long long *__restrict__ fix,
                                                                        const unsigned long long *__restrict__ half,
                                                                        const uint32_t *__restrict__ count, double spp,
                                                                        const unsigned long long *__restrict__ feat, double feat_spp,
@@ -80,8 +67,8 @@ __global__ __launch_bounds__(kDvBlock) void denoise_var_prepare_kernel(const uns
                                                                        double *__restrict__ mod, double *__restrict__ c0,
                                                                        double *__restrict__ var0)
 {
-    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
-    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < npix; p += stride) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kDnBlock;
+    for (unsigned long long p = (unsigned long long)blockIdx.x * kDnBlock + threadIdx.x; p < npix; p += stride) {
         double c[3], m[3], n[3], z;
         const double samples = count ? (double)count[p] : spp;
         rt_dn::prepare((const uint64_t *)fix + 3 * p, samples, (const uint64_t *)feat + 8 * p, feat_spp, demodulate != 0, c, m, n, &z);
@@ -93,12 +80,12 @@ __global__ __launch_bounds__(kDvBlock) void denoise_var_prepare_kernel(const uns
 }
 
 // the level's statistics in one pass: the 3x3 box mean of the colour and the 3x3 Gaussian of the variance
-__global__ __launch_bounds__(kDvBlock) void denoise_var_stats_kernel(const double *__restrict__ cin, const double *__restrict__ vin,
+__global__ __launch_bounds__(kDnBlock) void denoise_var_stats_kernel(const double *__restrict__ cin, const double *__restrict__ vin,
                                                                      uint32_t width, uint32_t height, unsigned long long npix,
                                                                      double *__restrict__ box, double *__restrict__ gv)
 {
-    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
-    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < npix; p += stride) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * kDnBlock;
+    for (unsigned long long p = (unsigned long long)blockIdx.x * kDnBlock + threadIdx.x; p < npix; p += stride) {
         const uint32_t j = (uint32_t)p / width, i = (uint32_t)p - j * width;        // npix <= 2^31: p fits 32 bits
         double g[3];
         rt_dn::box_mean((long long)i, (long long)j, (long long)width, (long long)height,
@@ -114,89 +101,30 @@ __global__ __launch_bounds__(kDvBlock) void denoise_var_stats_kernel(const doubl
 }
 
 // form (a): one lane per pixel, every tap from global memory
-__global__ __launch_bounds__(kDvBlock) void denoise_var_level_gather_kernel(const DvFrame F)
+__global__ __launch_bounds__(kDnBlock) void denoise_var_level_gather_kernel(const DvFrame F) { dn_gather_body(F); }
+
+// form (b): a workgroup per 16 x 16 tile of one sub-lattice, the records staged in LDS (DnTiling; the body is rt_denoise_tile.inc); this
+// is the pixel it filters from its staged taps
+template <class TapAt>
+__device__ __forceinline__ void dn_tile_pixel(const DvFrame &F, long long i, long long j, long long W, long long H, const rt_dn::TapVar &centre,
+                                              TapAt staged)
 {
-    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
-    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < F.npix; p += stride) {
-        const uint32_t j = (uint32_t)p / F.width, i = (uint32_t)p - j * F.width;
-        rt_dn::TapVar centre;
-        dv_load_tap(F, p, &centre);
-        const long long s = F.L.step;
-        double out[3], var;
-        rt_dn::level_pixel_var((long long)i, (long long)j, (long long)F.width, (long long)F.height, F.L, F.sc2, F.gv[p], centre,
-                               [&](int dx, int dy, rt_dn::TapVar *t) {
-                                   // (in-frame: level_pixel_var asks for no other tap)
-                                   const long long q = (long long)p + (s * dy) * (long long)F.width + s * dx;
-                                   dv_load_tap(F, (unsigned long long)q, t);
-                               }, out, &var);
-        F.cout[3 * p + 0] = out[0]; F.cout[3 * p + 1] = out[1]; F.cout[3 * p + 2] = out[2];
-        F.vout[p] = var;
-    }
+    const unsigned long long p = (unsigned long long)(j * W + i);
+    double out[3], var;
+    rt_dn::level_pixel_var(i, j, W, H, F.L, F.sc2, F.gv[p], centre, staged, out, &var);
+    F.cout[3 * p + 0] = out[0]; F.cout[3 * p + 1] = out[1]; F.cout[3 * p + 2] = out[2];
+    F.vout[p] = var;
 }
 
-// form (b): a workgroup per 16 x 16 tile of one sub-lattice (pixels with i % s == ri, j % s == rj), the records staged in LDS.
-// tiles_x, tiles_y: tiles per sub-lattice (of the widest one; narrower ones have empty tiles); nri = min(s, width) residues in x.
-struct DvTiling {
-    uint32_t tiles_x, tiles_y, nri, n_tiles;
-};
-
-__global__ __launch_bounds__(kDvBlock) void denoise_var_level_tile_kernel(const DvFrame F, const DvTiling T)
+__global__ __launch_bounds__(kDnBlock) void denoise_var_level_tile_kernel(const DvFrame F, const DnTiling T)
 {
-    __shared__ double s_rec[kDvPlanes][kDvCells];
-    const long long s = F.L.step;
-    const long long W = (long long)F.width, H = (long long)F.height;
-    const int lx = (int)threadIdx.x & (kDvTile - 1), ly = (int)threadIdx.x >> 4;
-    const uint32_t gx = T.nri * T.tiles_x;
-    for (uint32_t t = blockIdx.x; t < T.n_tiles; t += gridDim.x) {
-        const uint32_t by = t / gx, bx = t - by * gx;
-        const uint32_t ri = bx / T.tiles_x, tx = bx - ri * T.tiles_x;
-        const uint32_t rj = by / T.tiles_y, ty = by - rj * T.tiles_y;
-        // sub-lattice coordinates (u, v) -> pixel (ri + s u, rj + s v); the tile's first cell is (16 tx - 2, 16 ty - 2)
-        const long long u0 = (long long)tx * kDvTile - 2, v0 = (long long)ty * kDvTile - 2;
-        for (int cell = (int)threadIdx.x; cell < kDvCells; cell += kDvBlock) {
-            const int cy = cell / kDvSide, cx = cell - cy * kDvSide;
-            const long long ii = (long long)ri + s * (u0 + cx), jj = (long long)rj + s * (v0 + cy);
-            if (ii < 0 || ii >= W || jj < 0 || jj >= H) continue;           // never read: level_pixel_var skips taps outside the frame
-            rt_dn::TapVar r;
-            dv_load_tap(F, (unsigned long long)(jj * W + ii), &r);
-            s_rec[0][cell] = r.c[0]; s_rec[1][cell] = r.c[1]; s_rec[2][cell] = r.c[2];
-            s_rec[3][cell] = r.g[0]; s_rec[4][cell] = r.g[1]; s_rec[5][cell] = r.g[2];
-            s_rec[6][cell] = r.n[0]; s_rec[7][cell] = r.n[1]; s_rec[8][cell] = r.n[2];
-            s_rec[9][cell] = r.z;
-            s_rec[10][cell] = r.var;
-        }
-        __syncthreads();
-        const long long i = (long long)ri + s * (u0 + 2 + lx), j = (long long)rj + s * (v0 + 2 + ly);
-        if (i < W && j < H) {
-            auto staged = [&](int dx, int dy, rt_dn::TapVar *q) {
-                const int cell = (ly + 2 + dy) * kDvSide + (lx + 2 + dx);
-                q->c[0] = s_rec[0][cell]; q->c[1] = s_rec[1][cell]; q->c[2] = s_rec[2][cell];
-                q->g[0] = s_rec[3][cell]; q->g[1] = s_rec[4][cell]; q->g[2] = s_rec[5][cell];
-                q->n[0] = s_rec[6][cell]; q->n[1] = s_rec[7][cell]; q->n[2] = s_rec[8][cell];
-                q->z = s_rec[9][cell];
-                q->var = s_rec[10][cell];
-            };
-            rt_dn::TapVar centre;
-            staged(0, 0, &centre);
-            const unsigned long long p = (unsigned long long)(j * W + i);
-            double out[3], var;
-            rt_dn::level_pixel_var(i, j, W, H, F.L, F.sc2, F.gv[p], centre, staged, out, &var);
-            F.cout[3 * p + 0] = out[0]; F.cout[3 * p + 1] = out[1]; F.cout[3 * p + 2] = out[2];
-            F.vout[p] = var;
-        }
-        __syncthreads();                                                    // the next tile overwrites the records
-    }
+#include "rt_denoise_tile.inc"
 }
 
-__global__ __launch_bounds__(kDvBlock) void denoise_var_finish_kernel(const double *__restrict__ c, const double *__restrict__ mod,
+__global__ __launch_bounds__(kDnBlock) void denoise_var_finish_kernel(const double *__restrict__ c, const double *__restrict__ mod,
                                                                       unsigned long long npix, unsigned long long *__restrict__ out)
 {
-    const unsigned long long stride = (unsigned long long)gridDim.x * kDvBlock;
-    for (unsigned long long p = (unsigned long long)blockIdx.x * kDvBlock + threadIdx.x; p < npix; p += stride) {
-        uint64_t q[3];
-        rt_dn::finish(c + 3 * p, mod + 3 * p, q);
-        out[3 * p + 0] = q[0]; out[3 * p + 1] = q[1]; out[3 * p + 2] = q[2];
-    }
+    dn_finish_body(c, mod, npix, out);
 }
 
 } // namespace rt
@@ -212,36 +140,7 @@ int validate_denoise_var(const struct rt_denoise *dn, const void *fix, const voi
     if (!fix) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: a buffer is NULL (fix)");
     if (!half) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: the half-sample sums are NULL (half)");
     if (!feat || !out) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: a buffer is NULL (feat or out)");
-    if (dn->levels < 1 || dn->levels > RT_DENOISE_MAX_LEVELS)
-        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: levels must be 1..%d (is %d)", RT_DENOISE_MAX_LEVELS, dn->levels);
-    if (dn->flags & ~RT_DENOISE_DEMODULATE) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: unknown flags 0x%x", dn->flags);
-    if (!(dn->sigma_color > 0.0) || !(dn->sigma_normal > 0.0) || !(dn->sigma_depth > 0.0) || !std::isfinite(dn->sigma_color) ||
-        !std::isfinite(dn->sigma_normal) || !std::isfinite(dn->sigma_depth))
-        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: every sigma must be > 0 and finite (%g, %g, %g)", dn->sigma_color, dn->sigma_normal,
-                    dn->sigma_depth);
-    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: bad width/height (%d, %d)", width, height);
-    if ((long long)width * height > (1ll << 31))
-        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: width * height must be <= 2^31 (is %lld)", (long long)width * height);
-    if (!has_count && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: spp >= 1 without a count buffer (is %lld)", (long long)spp);
-    if (feat_spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var: feat_spp >= 1 (is %lld)", (long long)feat_spp);
-    return RT_OK;
-}
-
-// RTIOW_DENOISE_LEVEL_KERNEL (diagnostic; rt_denoise.hip reads the same variable): -1 not set, 0 gather, 1 tile
-int var_level_kernel_knob()
-{
-    const char *e = getenv("RTIOW_DENOISE_LEVEL_KERNEL");
-    if (!e || !*e) return -1;
-    if (!strcmp(e, "gather")) return 0;
-    if (!strcmp(e, "tile")) return 1;
-    return -1;
-}
-
-unsigned var_blocks_for(unsigned long long items)
-{
-    unsigned long long b = (items + rt::kDvBlock - 1) / rt::kDvBlock;
-    if (b > (unsigned long long)rt::kDvMaxBlocks) b = (unsigned long long)rt::kDvMaxBlocks;
-    return (unsigned)(b < 1 ? 1 : b);
+    return rt::dn_check_settings("denoise_var", dn, spp, has_count, feat_spp, width, height);
 }
 
 } // namespace
@@ -250,12 +149,7 @@ extern "C" {
 
 int rt_denoise_var_workspace_bytes(int32_t width, int32_t height, int64_t *out_bytes)
 {
-    if (!out_bytes) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var workspace: out_bytes is NULL");
-    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var workspace: bad width/height (%d, %d)", width, height);
-    if ((long long)width * height > (1ll << 31))
-        return fail(RT_ERR_INVALID_ARGUMENT, "denoise_var workspace: width * height must be <= 2^31 (is %lld)", (long long)width * height);
-    *out_bytes = (int64_t)width * height * rt_dn::kVarWorkDoubles * (int64_t)sizeof(double);
-    return RT_OK;
+    return rt::dn_workspace_bytes("denoise_var workspace", width, height, rt_dn::kVarWorkDoubles, out_bytes);
 }
 
 int rt_denoise_var_device(rt_context *ctx, const void *d_fix, const void *d_half, const void *d_count, int64_t spp, const void *d_feat,
@@ -270,45 +164,29 @@ int rt_denoise_var_device(rt_context *ctx, const void *d_fix, const void *d_half
     hipStream_t stream = (hipStream_t)stream_v;
     // (no launch slot: rt_last_stats does not report on a denoise; no scene needed)
     const unsigned long long npix = (unsigned long long)width * (unsigned long long)height;
-    double *guide = (double *)d_work, *mod = guide + 4 * npix, *ca = mod + 3 * npix, *cb = ca + 3 * npix, *box = cb + 3 * npix;
-    double *va = box + 3 * npix, *vb = va + npix, *gv = vb + npix;
-    const unsigned grid = var_blocks_for(npix);
-    hipLaunchKernelGGL(rt::denoise_var_prepare_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, (const unsigned long long *)d_fix,
+    rt_dn::Work k = rt_dn::partition((double *)d_work, npix, true);
+    const unsigned grid = rt::dn_blocks_for(npix);
+    hipLaunchKernelGGL(rt::denoise_var_prepare_kernel, dim3(grid), dim3(rt::kDnBlock), 0, stream, (const unsigned long long *)d_fix,
                        (const unsigned long long *)d_half, (const uint32_t *)d_count, (double)spp, (const unsigned long long *)d_feat,
-                       (double)feat_spp, (dn->flags & RT_DENOISE_DEMODULATE) ? 1 : 0, npix, guide, mod, ca, va);
+                       (double)feat_spp, (dn->flags & RT_DENOISE_DEMODULATE) ? 1 : 0, npix, k.guide, k.mod, k.ca, k.va);
     RT_HIP(hipGetLastError());
-    const int knob = var_level_kernel_knob();
+    const int knob = rt::dn_level_kernel_knob();
     for (int l = 0; l < dn->levels; ++l) {
-        hipLaunchKernelGGL(rt::denoise_var_stats_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, (const double *)ca, (const double *)va,
-                           (uint32_t)width, (uint32_t)height, npix, box, gv);
+        hipLaunchKernelGGL(rt::denoise_var_stats_kernel, dim3(grid), dim3(rt::kDnBlock), 0, stream, (const double *)k.ca, (const double *)k.va,
+                           (uint32_t)width, (uint32_t)height, npix, k.box, k.gv);
         RT_HIP(hipGetLastError());
         rt::DvFrame F;
-        F.guide = guide; F.cin = ca; F.box = box; F.vin = va; F.gv = gv; F.cout = cb; F.vout = vb;
+        F.guide = k.guide; F.cin = k.ca; F.box = k.box; F.vin = k.va; F.gv = k.gv; F.cout = k.cb; F.vout = k.vb;
         F.width = (uint32_t)width; F.height = (uint32_t)height; F.npix = npix;
         F.L = rt_dn::level_const(dn->sigma_color, dn->sigma_normal, dn->sigma_depth, l);
         F.sc2 = dn->sigma_color * dn->sigma_color;
-        // the tiling of the sub-lattices: min(s, width) x min(s, height) of them, each ceil(ceil(width / s) / 16) tiles wide
-        const unsigned long long s = (unsigned long long)F.L.step;
-        const unsigned long long nri = s < (unsigned long long)width ? s : (unsigned long long)width;
-        const unsigned long long nrj = s < (unsigned long long)height ? s : (unsigned long long)height;
-        const unsigned long long tiles_x = (((unsigned long long)width + s - 1) / s + rt::kDvTile - 1) / rt::kDvTile;
-        const unsigned long long tiles_y = (((unsigned long long)height + s - 1) / s + rt::kDvTile - 1) / rt::kDvTile;
-        const unsigned long long n_tiles = nri * tiles_x * nrj * tiles_y;
-        bool tile = knob < 0 ? rt::kDnVarTileDefault[l] : knob == 1;
-        if (n_tiles >= (1ull << 31)) tile = false;                          // (the tile number is a 32-bit integer)
-        if (tile) {
-            rt::DvTiling T;
-            T.tiles_x = (uint32_t)tiles_x; T.tiles_y = (uint32_t)tiles_y; T.nri = (uint32_t)nri; T.n_tiles = (uint32_t)n_tiles;
-            const unsigned tgrid = (unsigned)(n_tiles > (unsigned long long)rt::kDvMaxBlocks ? (unsigned long long)rt::kDvMaxBlocks : n_tiles);
-            hipLaunchKernelGGL(rt::denoise_var_level_tile_kernel, dim3(tgrid), dim3(rt::kDvBlock), 0, stream, F, T);
-        } else {
-            hipLaunchKernelGGL(rt::denoise_var_level_gather_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, F);
-        }
+        rt::dn_launch_level(F, knob < 0 ? rt::kDnVarTileDefault[l] : knob == 1, rt::denoise_var_level_tile_kernel,
+                            rt::denoise_var_level_gather_kernel, stream);
         RT_HIP(hipGetLastError());
-        double *t = ca; ca = cb; cb = t;
-        t = va; va = vb; vb = t;
+        double *t = k.ca; k.ca = k.cb; k.cb = t;
+        t = k.va; k.va = k.vb; k.vb = t;
     }
-    hipLaunchKernelGGL(rt::denoise_var_finish_kernel, dim3(grid), dim3(rt::kDvBlock), 0, stream, (const double *)ca, (const double *)mod, npix,
+    hipLaunchKernelGGL(rt::denoise_var_finish_kernel, dim3(grid), dim3(rt::kDnBlock), 0, stream, (const double *)k.ca, (const double *)k.mod, npix,
                        (unsigned long long *)d_out_fix);
     RT_HIP(hipGetLastError());
     return RT_OK;

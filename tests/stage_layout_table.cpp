@@ -23,7 +23,7 @@ static void row(const char *name, const std::vector<size_t> &sizes)
 // block of 0 bytes
 static std::vector<size_t> denoise_blocks(size_t w, size_t h, bool count)
 {
-    const size_t npix = w * h, fix = npix * 3 * 8, feat = npix * 8 * 8, work = npix * 16 * 8;       // (16: kDnWorkDoubles)
+    const size_t npix = w * h, fix = npix * 3 * 8, feat = npix * 8 * 8, work = npix * 16 * 8;       // (16: rt_dn::kWorkDoubles)
     return {fix, feat, fix, work, count ? npix * 4 : 0};
 }
 static std::vector<size_t> temporal_blocks(size_t w, size_t h, bool count, bool hist)

@@ -8,6 +8,7 @@ import os
 import re
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +16,7 @@ import pytest
 import denoise_ref as dr
 import denoise_var_ref as vr
 import rtiow_amd as rt
+from isa_pins import fingerprint_lines
 from rtiow_amd import _ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -337,13 +339,31 @@ def test_the_kernels_use_no_scratch_memory_and_spill_no_vector_register():
 
 
 def test_the_old_denoiser_is_untouched_by_the_new_unit():
-    """The sibling unit restates what it shares with rt_denoise.hip and includes neither that file nor a render kernel's header."""
-    run = subprocess.run(["hipcc", "-MM", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-                          os.path.join(CSRC, "denoise", "rt_denoise_var.hip")], capture_output=True, text=True, cwd=ROOT, timeout=300)
-    assert run.returncode == 0, run.stderr[-2000:]
-    deps = {os.path.basename(d) for d in run.stdout.replace("\\\n", " ").split() if not d.endswith(":")}
-    assert {"rt_host.hpp", "rt_denoise_core.hpp", "rt_denoise_var_core.hpp"} <= deps, deps
+    """Both units state what they share once, in rt_denoise_shared.hpp; the new one includes neither rt_denoise.hip nor a render kernel's
+    header."""
+    def deps_of(unit):
+        run = subprocess.run(["hipcc", "-MM", "-std=c++17", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+                              os.path.join(CSRC, unit)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+        assert run.returncode == 0, run.stderr[-2000:]
+        return {os.path.basename(d) for d in run.stdout.replace("\\\n", " ").split() if not d.endswith(":")}
+    deps = deps_of(os.path.join("denoise", "rt_denoise_var.hip"))
+    assert {"rt_host.hpp", "rt_denoise_core.hpp", "rt_denoise_var_core.hpp", "rt_denoise_shared.hpp", "rt_denoise_tile.inc"} <= deps, deps
     assert not {"rt_kernels.hpp", "rt_launch.hpp", "rt_device.hpp", "rt_denoise.hip"} & deps, sorted(deps)
+    assert {"rt_denoise_shared.hpp", "rt_denoise_tile.inc"} <= deps_of("rt_denoise.hip")
     import __graft_entry__ as g
     import inspect
     assert inspect.getsource(g.build_hip_library).count(".hip\"") >= 12 and "denoise/rt_denoise_var.hip" in inspect.getsource(g.build_hip_library)
+
+
+def test_the_kernels_have_the_machine_code_they_had_before_the_shared_header():
+    """tools/isa_fingerprint.py --denoise-var = profiles/isa_fingerprint_denoise_var.txt, printed by the same flag on the commit before
+    the two denoisers shared a header: the five kernels, by name, instruction counts and opcode hash."""
+    pinned = fingerprint_lines(open(os.path.join(ROOT, "profiles", "isa_fingerprint_denoise_var.txt")).read())
+    assert len(pinned) == 5, sorted(pinned)
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_fingerprint.py"), "--denoise-var"], capture_output=True, text=True,
+                         timeout=600, cwd=ROOT)
+    assert run.returncode == 0, run.stderr[-2000:]
+    now = fingerprint_lines(run.stdout)
+    assert sorted(now) == sorted(pinned)
+    for name in pinned:
+        assert now[name] == pinned[name], (name, now[name], pinned[name])

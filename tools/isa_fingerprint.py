@@ -12,15 +12,19 @@ lines of --paths are pinned by tests that count them); --pixels, with --paths, l
 their adaptive loop, path_begin_pixels_kernel and pass_add_listed_kernel, behind path_begin_kernel (profiles/isa_fingerprint_wavefront_pixels.txt).
 --all: every kernel of every rtiow_amd/csrc/rt_*.hip, whatever its name, sorted by name and without the s_nop padding behind its
 last instruction -- so a line does not depend on which translation unit the kernel lives in, nor on whether it is the last one there
-(profiles/isa_fingerprint_source_split.txt, tests/test_source_layout_host.py).  The other outputs count that padding, as they always did."""
+(profiles/isa_fingerprint_source_split.txt, tests/test_source_layout_host.py).  --denoise-var: the same listing for the five kernels of
+denoise/rt_denoise_var.hip alone (profiles/isa_fingerprint_denoise_var.txt, tests/test_denoise_var_host.py).  The other outputs count
+that padding, as they always did."""
 import collections, glob, hashlib, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(root, "tools"))
 import isa_census as ic
 args = sys.argv[1:]
 defs = [a for a in args if a.startswith("-D")]
-everything = "--all" in args
-if everything:
+everything = "--all" in args or "--denoise-var" in args      # every kernel of the sources, sorted, the padding trimmed
+if "--denoise-var" in args:
+    sources = ["rtiow_amd/csrc/denoise/rt_denoise_var.hip"]
+elif everything:
     sources = sorted(os.path.relpath(p, root) for p in glob.glob(os.path.join(root, "rtiow_amd", "csrc", "rt_*.hip")))
 else:
     sources = ["rtiow_amd/csrc/rt_api.hip"] + [f"rtiow_amd/csrc/rt_{flag[2:]}.hip" for flag in ("--frames", "--dense", "--features", "--trace") if flag in args]
