@@ -35,8 +35,12 @@ bool dense_body_is_capped(bool small_grid, bool large_blocks)
     return capped_by_default(small_grid, large_blocks);
 }
 
-int launch_dense_capped(rt_context *ctx, const rt::KParams &kp, hipStream_t stream, bool small_grid, bool large_blocks, int *grid_out)
+int launch_dense_capped(rt_context *ctx, const rt::KParams &kp_in, hipStream_t stream, bool small_grid, bool large_blocks, int *grid_out)
 {
+    // lane-striped block sums: the three capped kernels whose ring has 16 pixel slots (the large-grid one on blocks of 1 024 keeps 4 x 8 and its code)
+    rt::KParams kp = kp_in;
+    const StripePlan sp = plan_stripes(kp.use_ring != 0, kp.block_items, kp.spp, small_grid || !large_blocks);
+    kp.stripe_mask = sp.mask;
     if (small_grid)
         return large_blocks ? launch_render<5, false, true, false, rt::kItemBlockDenseLarge>(ctx, kp, stream, grid_out)
                             : launch_render<5, false, true, false, rt::kItemBlockDense>(ctx, kp, stream, grid_out);

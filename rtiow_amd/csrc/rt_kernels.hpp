@@ -48,7 +48,7 @@ namespace rt {
 
 // What rt_params.hpp states of the argument block, pinned here: this file is a hashed kernel source (bench.py, kernel_source_sha)
 // and rt_params.hpp is not.
-static_assert(kParamsVersion == 1, "KParams or a launch constant changed: bump kParamsVersion in rt_params.hpp AND this assert, so that "
+static_assert(kParamsVersion == 2, "KParams or a launch constant changed: bump kParamsVersion in rt_params.hpp AND this assert, so that "
               "this file -- a hashed kernel source -- changes with them");
 
 // x / d for a launch constant d >= 1 and a numerator with x < d + 65536 and x < 2^31, without a division (a `/`
@@ -147,6 +147,13 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     // PHASE 1 on wave masks: the capped kernels but the large-grid one on blocks of 1 024, which has no scalar headroom for it (63 parked scalars: 67 with it)
     constexpr bool kMaskHandout = CAPPED && (SMALLGRID || ITEMS == kItemBlockDense);
     static_assert(kRingDepth * kRingSlots == rt::kRingDepth * rt::kRingSlots, "same LDS either way");
+    // LANE-STRIPED BLOCK SUMS (the capped kernels with 16 pixel slots).  At many samples per pixel a block touches few pixels -- at most
+    // S of the 16 slots, S a power of two the host derives (plan_stripes, rt_launch.hpp) -- and the lanes that finish in one pass add to the same three
+    // words, which the LDS serialises.  The unused slots hold R = 16 / S replicas: the refill bakes a replica number, taken from the item's place in the
+    // block, into the slot it writes into the queue's meta word (slot = dq | replica bits; P.stripe_mask = 15 & ~(S - 1) are the replica's bits), the per-pass
+    // phases address the ring with that slot as they always did, and flush_ring sends every replica to its pixel's address.  A lane's pix_local carries the
+    // replica bits too; the one reader, a sample that goes to the frame buffer directly, takes them off.  P.stripe_mask == 0: one replica, nothing moves.
+    constexpr bool kStriped = CAPPED && kRingSlots == 16;
     __shared__ uint16_t cand[MODE == 1 ? kCandCap : 1][MODE == 1 ? kBlock : 1];     // MODE 1: per-lane candidate lists
     constexpr bool MATRIX = (MODE >= 2);
     constexpr bool LIFTED = (MODE == 4);
@@ -243,10 +250,16 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
     static_assert(kRingDepth == 4 || kRingDepth == 2, "the block counters are written out for a ring of 4 or 2");
     // one block's sums -> frame buffer (wave-uniform call; `e` uniform): lane l < 24 holds (pixel slot l/3, channel l%3),
     // which are 24 consecutive u64 of the frame buffer; zero sums (unused slots, black pixels) are not sent
+    // (striped sums: ring word `lane` is slot lane / 3, whose replica bits come off the pixel while the channel stays.  Stated ONCE, as this lane's base
+    //  pointer into the frame buffer: the other arm's P.fix + lane is hoisted out of the bounce loop into a register pair as well, and this one takes its
+    //  place.  Folding at the write-out instead -- per lane, in a loop over the replicas, through a table in LDS -- spills 2 to 15 more scalars in every form tried.)
+    unsigned long long *const fix_lane = kStriped ? P.fix + ((uint32_t)lane - ((((uint32_t)lane * 43u) >> 7) & P.stripe_mask) * 3u) : P.fix;
     auto flush_ring = [&](uint32_t e) {
         if (lane < kRingSlots * 3) {
             const unsigned long long v = ring_w[e * (kRingSlots * 3) + lane];
             if (v != 0ull) {
+                if constexpr (kStriped) atomicAdd(fix_lane + (size_t)rpix_w[e] * 3u, v);
+                else
                 atomicAdd(P.fix + (size_t)rpix_w[e] * 3u + (size_t)lane, v);
                 ring_w[e * (kRingSlots * 3) + lane] = 0ull;
             }
@@ -447,6 +460,15 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     qid_w[1 * 64 + lane] = wy;
                     qid_w[2 * 64 + lane] = g_pix;
                     qid_w[3 * 64 + lane] = g_s;
+                    if constexpr (kStriped) {
+                        // (consecutive items, which finish together, take the replicas in turn: bits 0-1 of the item's number become bits 2-3 of the slot, cut to
+                        //  the replica's bits.  The mask is loaded HERE, from the kernel-argument block: read as P.stripe_mask it is one more scalar parked across
+                        //  the whole pass, and the small-grid pair spills 4 more)
+                        uint32_t sm;
+                        asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(sm) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(offsetof(KParams, stripe_mask)));
+                        qid_w[4 * 64 + lane] = (g_ev << 8) | dq | ((s_rel << 2) & sm);
+                    }
+                    else
                     qid_w[4 * 64 + lane] = (g_ev << 8) | dq;        // (the event counter has 24 bits here: 8 million lens retries)
                 }
                 blk_next += n_gen;
@@ -1586,7 +1608,7 @@ __global__ __launch_bounds__(kBlock, (MODE == 5 && !DIAG) ? 4 : (MODE >= 2) ? 3 
                     unsigned long long *acc = ring_w + ((my_blk >> 4) & (uint32_t)(kRingDepth - 1)) * (kRingSlots * 3) + (my_blk & 15u) * 3u;
                     atomicAdd(acc + 0, q0); atomicAdd(acc + 1, q1); atomicAdd(acc + 2, q2);
                 } else {                                            // too few samples per pixel for block sums, or an orphan of a long-gone block
-                    unsigned long long *px = P.fix + (size_t)pix_local * 3u;
+                    unsigned long long *px = P.fix + (size_t)(kStriped ? pix_local - (my_blk & P.stripe_mask) : pix_local) * 3u;
                     atomicAdd(px + 0, q0); atomicAdd(px + 1, q1); atomicAdd(px + 2, q2);
                 }
             }

@@ -52,6 +52,27 @@ inline LaunchPlan plan_launch(int spp, int ring_min_spp, bool shipped_kernel, bo
     return plan;
 }
 
+// Lane-striped block sums (render_kernel, kStriped: the capped dense kernels whose ring has 16 pixel slots).  A block of block_items consecutive
+// samples touches at most ceil((block_items - 1) / spp) + 1 pixels; S, the smallest power of two that holds them (at least 4), is how many of the 16
+// slots the launch can use at all, and the slots above them hold further copies, R = 16 / S replicas in all: 4 replicas on blocks of 1 024 from 341 samples per
+// pixel, 2 from 147; on blocks of 256 from 85 and from 37.  mask = 15 & ~(S - 1), the replica's bits of a slot number, goes into KParams (stripe_mask).
+// Without block sums, on any other kernel, or where a block may touch more than 8 pixels: one replica, mask = 0, every address as it was.
+struct StripePlan {
+    unsigned slots, replicas;  // S, R
+    unsigned mask;             // KParams::stripe_mask
+};
+inline StripePlan plan_stripes(bool use_ring, unsigned block_items, int spp, bool striped_kernel)
+{
+    StripePlan sp = {2u * (unsigned)rt::kRingSlots, 1u, 0u};
+    if (!use_ring || !striped_kernel || spp < 1 || block_items < 1u) return sp;
+    const unsigned touched = (block_items - 1u + (unsigned)spp - 1u) / (unsigned)spp + 1u;
+    unsigned s = 4u;
+    while (s < touched && s < sp.slots) s <<= 1;
+    if (s >= sp.slots) return sp;
+    sp.replicas = sp.slots / s; sp.slots = s; sp.mask = 15u & ~(s - 1u);
+    return sp;
+}
+
 // The KParams fields every launch path fills the same way (the rest is zero): image size, samples, depth, key, the plan, the item and
 // block counts, the scene's tables and the sums.  The sharding fields say "one shard" (rt_render_device overwrites them); rows,
 // magic_width, magic_tile, the camera(s), pix_list and the frame fields are the caller's.

@@ -13,7 +13,7 @@
 
 namespace rt {
 
-constexpr int kParamsVersion = 1;
+constexpr int kParamsVersion = 2;
 
 struct KCamera {
     double origin[3], llc[3], horizontal[3], vertical[3], u[3], v[3];
@@ -77,6 +77,10 @@ struct KParams {
     // and read where they lie, in the kernel-argument block, with scalar loads (rt_device.hpp, philox4x32_10_table).  The last member, like pix_list and
     // cams before it: the offsets of everything else stay where they were.  No other kernel reads it.
     uint32_t round_keys[20];
+    // the capped dense kernels with 16 pixel slots: lane-striped block sums (plan_stripes, rt_launch.hpp).  A launch whose
+    // blocks touch at most S <= 8 pixels keeps R = 16 / S replicas of every slot's sums: a sample adds to slot dq | replica * S, and
+    // stripe_mask = 15 & ~(S - 1) are the replica's bits of a slot number.  0 (every other kernel and launch): one replica, slot = dq.  The last member.
+    uint32_t stripe_mask;
 };
 
 constexpr int RT_KIND_LAMBERTIAN = 0, RT_KIND_METAL = 1, RT_KIND_DIALECTRIC = 2;

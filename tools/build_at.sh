@@ -6,7 +6,7 @@ REV=$1; NAME=$2
 TMP=$(mktemp -d)
 git archive $REV rtiow_amd/csrc include | tar -x -C $TMP
 # every translation unit the revision has: the loader refuses a library that lacks a symbol it declares
-SRCS=$(ls $TMP/rtiow_amd/csrc/rt_*.hip $TMP/rtiow_amd/csrc/wavefront/*.hip 2>/dev/null || true)   # (a revision before the wavefront path steps has no such folder)
+SRCS=$(ls $TMP/rtiow_amd/csrc/rt_*.hip $TMP/rtiow_amd/csrc/wavefront/*.hip $TMP/rtiow_amd/csrc/denoise/*.hip 2>/dev/null || true)   # (an older revision lacks the folders)
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -mllvm -amdgpu-mfma-vgpr-form \
   -fPIC -shared -I $TMP/include -I $TMP/rtiow_amd/csrc -o tools/var_$NAME.so $SRCS
 rm -rf $TMP

@@ -13,6 +13,8 @@ usage: tools/isa_census.py [--kernel SUBSTR] [--tenk] [--frames] [--dense] [-D..
        --dense: the capped-redraw instantiation of the small-grid kernel on blocks of 1 024 (render_kernelILi5ELb0ELb1ELb0ELin1024, compiled from rt_dense.hip)
        --call-site-lines: an inlined lambda's instructions without a source line go to the line of its call (how the records up to
                           profiles/scalar_trim2_census_after.txt were taken), not to the lambda
+       --lambda-first-line: an inlined lambda's instructions without a source line go to the lambda's first line (the records between the two above and
+                          profiles/handout_trim_census_after.txt), not to the line of the nearest preceding instruction of the same inline frame
        --copies: after the tables, per phase and source line, the static count and the count per wave-bounce of v_mov*, v_cndmask*, v_cmp* and
                  v_accvgpr* -- the instructions a phase's joins cost beside its arithmetic (profiles/vector_trim_census_{before,after}.txt)
 """
@@ -284,14 +286,31 @@ def main():
             if m:
                 lambda_at[m.group(1)] = i + 1
 
+    # ... but the lambda's FIRST line is the wrong place for a lambda that spans several phases: look_tube's recording path ORs the keep masks (the xs[j] of
+    # each half) right in front of the half's asm block, the compiler gives those six v_or per look no line, and on the lambda's first line they counted as
+    # the look itself (16 vector instructions per look where the look has 10, at the looks' rate instead of the halves').  A line-less instruction inside an
+    # inlined lambda now takes the line of the nearest preceding instruction of the SAME inline frame -- the same lambda inlined through the same call
+    # lines -- that has one; the lambda's first line only when there is none yet.  --lambda-first-line: the attribution of the records from
+    # profiles/scalar_trim3_census_after.txt to profiles/handout_trim_census_after.txt.
+    frame_last_line = {}
+    first_line_only = "--lambda-first-line" in args
+
     def helper_lines(stack):
         out = []
         for k, (fn, f, ln) in enumerate(stack[:-1]):
             outer = stack[k + 1]
-            if f == "rt_kernels.hpp" and ln == 0 and outer[1] == "rt_kernels.hpp" and 0 < outer[2] <= len(lines):
+            if f == "rt_kernels.hpp" and outer[1] == "rt_kernels.hpp" and 0 < outer[2] <= len(lines):
                 called = {n for n in lambda_at if re.search(r"\b%s\(" % n, lines[outer[2] - 1]) and lambda_at[n] != outer[2]}
-                if len(called) == 1:
-                    out.append(lambda_at[called.pop()])
+                if len(called) != 1:
+                    continue
+                name = called.pop()
+                frame = (name, tuple((g, l) for _, g, l in stack[k + 1:]))
+                if ln > 0:
+                    frame_last_line[frame] = ln
+                elif first_line_only:
+                    out.append(lambda_at[name])
+                else:
+                    out.append(frame_last_line.get(frame, lambda_at[name]))
         return out
 
     for addr, op, ops in ins:
