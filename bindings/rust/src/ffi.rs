@@ -418,6 +418,34 @@ extern "C" {
                             prev_fix: *const u64, prev_len: *const u32, prev_feat: *const u64, prev_feat_spp: i64,
                             prev_cam: *const rt_camera, width: i32, height: i32, tp: *const rt_temporal, out_fix: *mut u64,
                             out_len: *mut u32) -> i32;
+    /// Temporal accumulation with second moments: `rt_temporal` with `prev_m2` (`[H][W][3]` f64, the previous call's `out_m2`) as a fifth
+    /// part of the history -- all five or none --, and two more outputs: `out_m2`, the accumulated mean of the squared frame means, and
+    /// `out_var`, per channel the variance of the accumulated value.  `out_fix` and `out_len` are `rt_temporal`'s bits.
+    pub fn rt_temporal_var_device(ctx: *mut rt_context, d_fix: *const c_void, d_count: *const c_void, spp: i64, d_feat: *const c_void,
+                                  feat_spp: i64, cam: *const rt_camera, d_prev_fix: *const c_void, d_prev_len: *const c_void,
+                                  d_prev_feat: *const c_void, prev_feat_spp: i64, prev_cam: *const rt_camera, d_prev_m2: *const c_void,
+                                  width: i32, height: i32, tp: *const rt_temporal, d_out_fix: *mut c_void, d_out_len: *mut c_void,
+                                  d_out_m2: *mut c_void, d_out_var: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_temporal_var(ctx: *mut rt_context, fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64,
+                           cam: *const rt_camera, prev_fix: *const u64, prev_len: *const u32, prev_feat: *const u64, prev_feat_spp: i64,
+                           prev_cam: *const rt_camera, prev_m2: *const f64, width: i32, height: i32, tp: *const rt_temporal,
+                           out_fix: *mut u64, out_len: *mut u32, out_m2: *mut f64, out_var: *mut f64, kernel_ms: *mut f32) -> i32;
+    /// The same accumulation on host buffers, no device needed.
+    pub fn rt_temporal_var_host(fix: *const u64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64, cam: *const rt_camera,
+                                prev_fix: *const u64, prev_len: *const u32, prev_feat: *const u64, prev_feat_spp: i64,
+                                prev_cam: *const rt_camera, prev_m2: *const f64, width: i32, height: i32, tp: *const rt_temporal,
+                                out_fix: *mut u64, out_len: *mut u32, out_m2: *mut f64, out_var: *mut f64) -> i32;
+    /// The variance-guided denoiser with the variance given: `rt_denoise_var` with `var` (`[H][W][3]` f64, per channel the variance of the
+    /// pixel's mean: `rt_temporal_var`'s `out_var`) in `half`'s place; the workspace is `rt_denoise_var_workspace_bytes`.
+    pub fn rt_denoise_var_given_device(ctx: *mut rt_context, d_fix: *const c_void, d_var: *const c_void, d_count: *const c_void, spp: i64,
+                                       d_feat: *const c_void, feat_spp: i64, width: i32, height: i32, dn: *const rt_denoise,
+                                       d_work: *mut c_void, d_out_fix: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn rt_denoise_var_given(ctx: *mut rt_context, fix: *const u64, var: *const f64, count: *const u32, spp: i64, feat: *const u64,
+                                feat_spp: i64, width: i32, height: i32, dn: *const rt_denoise, out_fix: *mut u64,
+                                kernel_ms: *mut f32) -> i32;
+    /// The same filter on host buffers, no device needed.
+    pub fn rt_denoise_var_given_host(fix: *const u64, var: *const f64, count: *const u32, spp: i64, feat: *const u64, feat_spp: i64,
+                                     width: i32, height: i32, dn: *const rt_denoise, out_fix: *mut u64) -> i32;
     /// Ray queries: `HittableList::hit(ray, t_min, t_max[k])` of every ray of the batch against the uploaded list (closest hit), and
     /// whether it would hit at all (occlusion, `[n]` u8).  The device forms are asynchronous on `stream`; the structs are host pointers.
     pub fn rt_trace_rays_device(ctx: *mut rt_context, rays: *const rt_rays, t_min: f64, hits: *const rt_hits, stream: *mut c_void) -> i32;

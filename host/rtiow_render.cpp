@@ -41,6 +41,11 @@
 // --temporal-sigma-normal 0.5; --temporal-sigma-depth 0.1; --temporal-clamp X: the scale of the neighbourhood clamp, default 1, a negative X switches
 // it off), with --denoise also rt_denoise on each accumulated frame (spp = 1, the frame's own features), then the one-sample resolve; the
 // frames are written as the batch writes them.  --denoise goes with a batch only together with --temporal.
+// --temporal --denoise-variance (with --cameras / --orbit): the same sequence with second moments: rt_temporal_var in
+// rt_temporal's place, with a fifth history buffer, and on each accumulated frame rt_denoise_var_given with the variance that call returned
+// (spp = 1; --sigma-color in standard deviations, default 1.5 here: the sweep of section 26).  No half sums are needed, so --spp may be odd.  With --wavefront and its --sky,
+// --emit and --direct* switches every frame is rendered through the device path queue (frame f with sample_begin = f S) instead of by the
+// batch launch.  --denoise-variance goes with a batch only together with --temporal.
 // --wavefront: the same frame through the device path queue (rt_render_wavefront: per batch one begin and --depth fused bounce steps, DESIGN.md
 // section 19), then rt_resolve_rgba8: the bytes of the default run.  Single device; with none of the other modes.
 // --sky B_r,B_g,B_b:T_r,T_g,T_b and --emit INDEX:r,g,b (repeatable), both only with --wavefront: the frame lit by a settable sky -- colour B
@@ -64,7 +69,8 @@
 // renders the samples from sample_begin = spp / 2 on top of it, which gives the sums of one pass --; with --adaptive the loop's own half
 // and count buffers go in.  Legal with --wavefront, --sky, --emit, --direct* and --adaptive included (rt_render_wavefront_pixels with
 // RT_FLAG_ACCUMULATE, rt_render_wavefront_adaptive); then rt_render_features, rt_denoise_var and the one-sample resolve.  Not together with
-// --denoise; --wavefront --denoise stays refused.  Single device; not with --uniform53, --passes, --two-calls, --features, --cameras, --orbit.
+// --denoise; --wavefront --denoise stays refused.  Single device; not with --uniform53, --passes, --two-calls, --features; with --cameras or
+// --orbit only together with --temporal (above).
 // --pick I,J: no image; what the book camera's pixel (I, J) (J = 0 the BOTTOM row) of a --width x --height frame shows: the ray through the pixel's
 // centre and the lens centre -- u = (I + 0.5) / (W - 1), v = (J + 0.5) / (H - 1), direction ((lower_left_corner + u horizontal) + v vertical) - origin --
 // in ONE call of rt_trace_rays, printed as "pick I J: index K kind NAME t T point X Y Z" (%.17g; a miss: index -1 kind none t inf).  Single device.
@@ -294,20 +300,20 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--denoise and --denoise-variance are two filters for the same frame: give one of them\n");
         return 2;
     }
-    if (denoise_var && (!devices.empty() || batch || temporal || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
+    if (denoise_var && (!devices.empty() || (batch && !temporal) || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
         std::fprintf(stderr, "--denoise-variance renders on one device and goes with none of --devices, --cameras, --orbit, --temporal, --uniform53, --passes, --two-calls, --features\n");
         return 2;
     }
-    if (denoise_var && !adaptive && (spp < 2 || spp % 2 != 0)) {
+    if (denoise_var && !temporal && !adaptive && (spp < 2 || spp % 2 != 0)) {
         std::fprintf(stderr, "--denoise-variance renders the frame as two passes of spp / 2: --spp must be even and >= 2 (is %d)\n", spp);
         return 2;
     }
-    if (denoise_var && !sigma_color_set) dn.sigma_color = 1.0;
+    if (denoise_var && !sigma_color_set) dn.sigma_color = temporal ? 1.5 : 1.0;      // (the sweeps of DESIGN.md sections 25 and 26)
     if (denoise && (!devices.empty() || (batch && !temporal) || uniform53 || passes > 1 || two_calls || !features_file.empty())) {
         std::fprintf(stderr, "--denoise renders on one device and goes with none of --devices, --cameras, --orbit, --uniform53, --passes, --two-calls, --features\n");
         return 2;
     }
-    if (batch && (!devices.empty() || passes > 1 || adaptive || uniform53 || two_calls || wavefront)) {
+    if (batch && (!devices.empty() || passes > 1 || adaptive || uniform53 || two_calls || (wavefront && !(temporal && denoise_var)))) {
         std::fprintf(stderr, "--cameras / --orbit render a frame batch on one device and go with none of --devices, --passes, --adaptive, --uniform53, --two-calls, --wavefront\n");
         return 2;
     }
@@ -319,7 +325,69 @@ int main(int argc, char **argv)
         std::printf("%zu cameras -> %s\n", cams.size(), dump_cameras.c_str());
         return 0;
     }
+    // what --wavefront's lighting switches must obey, and the emission table they make: asked by the single frame and by the sequence
+    // that renders its frames through the path queue.  0, or the exit code
+    std::vector<double> emission;                // --emit: one (r, g, b) per sphere of the list
+    auto check_lighting = [&]() -> int {
+        if (lit && !wavefront) {
+            std::fprintf(stderr, "--sky and --emit light the frame of the device path queue only: they need --wavefront\n");
+            return 2;
+        }
+        if (direct && (!wavefront || emits.empty())) {
+            std::fprintf(stderr, "--direct samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
+            return 2;
+        }
+        if (direct_cone && direct) {
+            std::fprintf(stderr, "--direct and --direct-cone are two ways to sample the same lights: give one of them\n");
+            return 2;
+        }
+        if (direct_weighted && (direct || direct_cone)) {
+            std::fprintf(stderr, "--direct, --direct-cone and --direct-weighted are three ways to sample the same lights: give one of them\n");
+            return 2;
+        }
+        if (direct_weighted && (!wavefront || emits.empty())) {
+            std::fprintf(stderr, "--direct-weighted samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
+            return 2;
+        }
+        if (direct_cone && (!wavefront || emits.empty())) {
+            std::fprintf(stderr, "--direct-cone samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
+            return 2;
+        }
+        if (!emits.empty()) {
+            emission.assign(flat.size() * 3, 0.0);
+            for (const Emit &e : emits) {
+                if (e.index < 0 || (size_t)e.index >= flat.size()) {
+                    std::fprintf(stderr, "--emit %ld: the scene has %zu spheres\n", e.index, flat.size());
+                    return 2;
+                }
+                for (int c = 0; c < 3; ++c) emission[(size_t)e.index * 3 + c] = e.rgb[c];
+            }
+            light.emission = emission.data(); light.n_emission = (int32_t)flat.size();
+        }
+        return 0;
+    };
+    const bool any_direct = direct || direct_cone || direct_weighted;
+    const uint32_t direct_flags = direct_weighted ? (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) : direct_cone ? RT_DIRECT_CONE : 0u;
+    // one frame through the device path queue, lit and sampled as the switches say
+    auto render_wavefront_frame = [&](rt_context *ctx, const rt_camera *cam, const rt_params *q, uint64_t *fix, uint64_t *rays, float *ms) -> int {
+        int rc = RT_OK;
+        uint64_t shadow = 0;
+        if (direct) {
+            if ((rc = rt_render_wavefront_nee(ctx, cam, q, &light, fix, rays, &shadow, ms))) return die("rt_render_wavefront_nee", rc);
+        } else if (direct_cone || direct_weighted) {
+            if ((rc = rt_render_wavefront_nee_sampled(ctx, cam, q, &light, direct_flags, fix, rays, &shadow, ms)))
+                return die("rt_render_wavefront_nee_sampled", rc);
+        } else if (lit) {
+            if ((rc = rt_render_wavefront_lit(ctx, cam, q, &light, fix, rays, ms))) return die("rt_render_wavefront_lit", rc);
+        } else if ((rc = rt_render_wavefront(ctx, cam, q, fix, rays, ms))) {
+            return die("rt_render_wavefront", rc);
+        }
+        if (any_direct) std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
+        return 0;
+    };
     if (batch) {
+        if (temporal && denoise_var)             // (the one batch that may render through the path queue: its lighting switches are held to their rules)
+            if (const int bad = check_lighting()) return bad;
         std::vector<rt_camera> cams;
         if (orbit > 0) cams = rtiow::orbit_cameras(orbit, width, height);
         else if (!rtiow::load_cameras(cameras_file.c_str(), cams) || cams.empty()) {
@@ -341,12 +409,18 @@ int main(int argc, char **argv)
         if (temporal) {
             // the batch's exact sums in one launch; then frame after frame: the guides of the frame's own camera rays, the accumulation over the
             // previous call's result (two pairs of history buffers, used in turn), optionally the spatial filter, the one-sample resolve
-            std::vector<uint64_t> fix(npix * 3 * cams.size()), feat[2], acc[2], clean;
+            // --denoise-variance: the second moment rides along (a fifth history buffer) and the filter takes the variance the accumulation
+            // returns; --wavefront: every frame through the path queue, one after the other, instead of the batch launch
+            std::vector<uint64_t> fix(npix * 3 * (wavefront ? 1 : cams.size())), feat[2], acc[2], clean;
             std::vector<uint32_t> len[2];
+            std::vector<double> m2[2], var;
             for (int k = 0; k < 2; ++k) { feat[k].resize(npix * RT_FEATURE_WORDS); acc[k].resize(npix * 3); len[k].resize(npix); }
-            if (denoise) clean.resize(npix * 3);
-            rc = rt_render_frames(ctx, cams.data(), (int32_t)cams.size(), stride, &p, fix.data(), &st);
-            if (rc) { die("rt_render_frames", rc); rt_destroy(ctx); return 1; }
+            if (denoise || denoise_var) clean.resize(npix * 3);
+            if (denoise_var) { m2[0].resize(npix * 3); m2[1].resize(npix * 3); var.resize(npix * 3); }
+            if (!wavefront) {
+                rc = rt_render_frames(ctx, cams.data(), (int32_t)cams.size(), stride, &p, fix.data(), &st);
+                if (rc) { die("rt_render_frames", rc); rt_destroy(ctx); return 1; }
+            }
             float tp_ms = 0.0f;
             size_t with_history = 0, hit_pixels = 0;
             for (size_t f = 0; f < cams.size() && !rc; ++f) {
@@ -354,12 +428,27 @@ int main(int argc, char **argv)
                 rt_params fp = p;
                 fp.spp = feature_spp; fp.sample_begin = (int32_t)f * stride;
                 float ms = 0.0f;
+                const uint64_t *frame = fix.data() + (wavefront ? 0 : f * npix * 3);
+                if (wavefront) {
+                    rt_params q = p;
+                    q.sample_begin = (int32_t)f * stride;
+                    uint64_t rays = 0;
+                    if ((rc = render_wavefront_frame(ctx, &cams[f], &q, fix.data(), &rays, &ms))) break;
+                    st.rays_traced += rays; st.kernel_ms += ms; st.samples += (uint64_t)npix * (uint64_t)spp;
+                }
                 rc = rt_render_features(ctx, &cams[f], &fp, feat[w].data(), nullptr, nullptr);
                 if (rc) { die("rt_render_features", rc); break; }
-                rc = rt_temporal(ctx, fix.data() + f * npix * 3, nullptr, spp, feat[w].data(), feature_spp, &cams[f], f ? acc[r].data() : nullptr,
-                                 f ? len[r].data() : nullptr, f ? feat[r].data() : nullptr, feature_spp, f ? &cams[f - 1] : nullptr, width, height, &tp,
-                                 acc[w].data(), len[w].data(), &ms);
-                if (rc) { die("rt_temporal", rc); break; }
+                if (denoise_var) {
+                    rc = rt_temporal_var(ctx, frame, nullptr, spp, feat[w].data(), feature_spp, &cams[f], f ? acc[r].data() : nullptr,
+                                         f ? len[r].data() : nullptr, f ? feat[r].data() : nullptr, feature_spp, f ? &cams[f - 1] : nullptr,
+                                         f ? m2[r].data() : nullptr, width, height, &tp, acc[w].data(), len[w].data(), m2[w].data(), var.data(), &ms);
+                    if (rc) { die("rt_temporal_var", rc); break; }
+                } else {
+                    rc = rt_temporal(ctx, frame, nullptr, spp, feat[w].data(), feature_spp, &cams[f], f ? acc[r].data() : nullptr,
+                                     f ? len[r].data() : nullptr, f ? feat[r].data() : nullptr, feature_spp, f ? &cams[f - 1] : nullptr, width, height,
+                                     &tp, acc[w].data(), len[w].data(), &ms);
+                    if (rc) { die("rt_temporal", rc); break; }
+                }
                 tp_ms += ms;
                 if (f + 1 == cams.size())
                     for (size_t k = 0; k < npix; ++k) { hit_pixels += feat[w][k * RT_FEATURE_WORDS + 7] != 0; with_history += len[w][k] >= 2; }
@@ -367,13 +456,19 @@ int main(int argc, char **argv)
                     rc = rt_denoise(ctx, acc[w].data(), nullptr, 1, feat[w].data(), feature_spp, width, height, &dn, clean.data(), nullptr);
                     if (rc) { die("rt_denoise", rc); break; }
                 }
-                rc = rt_resolve_rgba8(ctx, denoise ? clean.data() : acc[w].data(), width, height, 1, 1, rgba.data() + f * npix * 4);
+                if (denoise_var) {
+                    rc = rt_denoise_var_given(ctx, acc[w].data(), var.data(), nullptr, 1, feat[w].data(), feature_spp, width, height, &dn, clean.data(),
+                                              nullptr);
+                    if (rc) { die("rt_denoise_var_given", rc); break; }
+                }
+                rc = rt_resolve_rgba8(ctx, denoise || denoise_var ? clean.data() : acc[w].data(), width, height, 1, 1, rgba.data() + f * npix * 4);
                 if (rc) die("rt_resolve_rgba8", rc);
             }
             if (rc) { rt_destroy(ctx); return 1; }
             std::printf("temporal: alpha_min %g, sigmas %g / %g, clamp %s %g, features at %d spp%s; accumulation kernels %.3f ms; last frame: %zu of %zu hit pixels with history\n",
                         tp.alpha_min, tp.sigma_normal, tp.sigma_depth, (tp.flags & RT_TEMPORAL_CLAMP) ? "on" : "off", tp.clamp_scale, feature_spp,
-                        denoise ? ", each frame denoised" : "", tp_ms, with_history, hit_pixels);
+                        denoise ? ", each frame denoised" : denoise_var ? ", second moments carried, each frame denoised by its variance" : "", tp_ms,
+                        with_history, hit_pixels);
         } else {
             rc = rt_render_frames_rgba8(ctx, cams.data(), (int32_t)cams.size(), stride, &p, 1, rgba.data(), &st);
             if (rc) { die("rt_render_frames_rgba8", rc); rt_destroy(ctx); return 1; }
@@ -399,8 +494,8 @@ int main(int argc, char **argv)
                 std::fclose(fo);
             }
         }
-        std::printf("%zu frames of %dx%d spp %d, sample stride %d, one launch: %llu rays, kernel %.3f ms (%.1f Msamples/s) -> %s_0000%s ...\n",
-                    cams.size(), width, height, spp, stride, (unsigned long long)st.rays_traced, st.kernel_ms,
+        std::printf("%zu frames of %dx%d spp %d, sample stride %d, %s: %llu rays, kernel %.3f ms (%.1f Msamples/s) -> %s_0000%s ...\n",
+                    cams.size(), width, height, spp, stride, wavefront ? "the path queue" : "one launch", (unsigned long long)st.rays_traced, st.kernel_ms,
                     (double)st.samples / st.kernel_ms / 1e3, prefix.c_str(), ext.c_str());
         return 0;
     }
@@ -422,42 +517,7 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "--wavefront runs on one device and goes with none of --devices, --denoise, --passes, --two-calls, --uniform53, --features\n");
         return 2;
     }
-    if (lit && !wavefront) {
-        std::fprintf(stderr, "--sky and --emit light the frame of the device path queue only: they need --wavefront\n");
-        return 2;
-    }
-    if (direct && (!wavefront || emits.empty())) {
-        std::fprintf(stderr, "--direct samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
-        return 2;
-    }
-    if (direct_cone && direct) {
-        std::fprintf(stderr, "--direct and --direct-cone are two ways to sample the same lights: give one of them\n");
-        return 2;
-    }
-    if (direct_weighted && (direct || direct_cone)) {
-        std::fprintf(stderr, "--direct, --direct-cone and --direct-weighted are three ways to sample the same lights: give one of them\n");
-        return 2;
-    }
-    if (direct_weighted && (!wavefront || emits.empty())) {
-        std::fprintf(stderr, "--direct-weighted samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
-        return 2;
-    }
-    if (direct_cone && (!wavefront || emits.empty())) {
-        std::fprintf(stderr, "--direct-cone samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
-        return 2;
-    }
-    std::vector<double> emission;                // --emit: one (r, g, b) per sphere of the list
-    if (!emits.empty()) {
-        emission.assign(flat.size() * 3, 0.0);
-        for (const Emit &e : emits) {
-            if (e.index < 0 || (size_t)e.index >= flat.size()) {
-                std::fprintf(stderr, "--emit %ld: the scene has %zu spheres\n", e.index, flat.size());
-                return 2;
-            }
-            for (int c = 0; c < 3; ++c) emission[(size_t)e.index * 3 + c] = e.rgb[c];
-        }
-        light.emission = emission.data(); light.n_emission = (int32_t)flat.size();
-    }
+    if (const int bad = check_lighting()) return bad;
     if (!devices.empty()) {
         // one rt_context per listed device, each driven by its own host thread; rows dealt round-robin;
         // one RCCL gather of the exact sums to the first device (main.rs:122-123 + the ordered collect() :139)
@@ -482,8 +542,6 @@ int main(int argc, char **argv)
             // dense kernel or the device path queue --, then the guides, the filter and the one-sample resolve
             std::vector<uint64_t> fix(npix * 3), half(npix * 3);
             std::vector<uint32_t> count;
-            const bool any_direct = direct || direct_cone || direct_weighted;
-            const uint32_t direct_flags = direct_weighted ? (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) : direct_cone ? RT_DIRECT_CONE : 0u;
             uint64_t rays = 0, shadow = 0;
             if (adaptive) {
                 rt_adaptive ad{};
@@ -552,8 +610,6 @@ int main(int argc, char **argv)
             ad.step = step; ad.reserved = 0; ad.threshold = threshold; ad.dark_floor = 0.01;
             std::vector<uint64_t> fix(npix * 3);
             std::vector<uint32_t> count(npix);
-            const bool any_direct = direct || direct_cone || direct_weighted;
-            const uint32_t direct_flags = direct_weighted ? (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) : direct_cone ? RT_DIRECT_CONE : 0u;
             uint64_t rays = 0, shadow = 0;
             rc = rt_render_wavefront_adaptive(ctx, &rc_cam, &p, &ad, lit ? &light : nullptr, any_direct ? 1 : 0, direct_flags, fix.data(), nullptr,
                                               count.data(), &rays, &shadow, &st.kernel_ms);
@@ -628,24 +684,7 @@ int main(int argc, char **argv)
         } else if (wavefront) {                  // the device path queue: the same sums, then the same resolve
             std::vector<uint64_t> fix(npix * 3);
             uint64_t rays = 0;
-            if (direct) {
-                uint64_t shadow = 0;
-                rc = rt_render_wavefront_nee(ctx, &rc_cam, &p, &light, fix.data(), &rays, &shadow, &st.kernel_ms);
-                if (rc) return die("rt_render_wavefront_nee", rc);
-                std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
-            } else if (direct_cone || direct_weighted) {
-                uint64_t shadow = 0;
-                const uint32_t direct_flags = direct_weighted ? (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE) : RT_DIRECT_CONE;
-                rc = rt_render_wavefront_nee_sampled(ctx, &rc_cam, &p, &light, direct_flags, fix.data(), &rays, &shadow, &st.kernel_ms);
-                if (rc) return die("rt_render_wavefront_nee_sampled", rc);
-                std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
-            } else if (lit) {
-                rc = rt_render_wavefront_lit(ctx, &rc_cam, &p, &light, fix.data(), &rays, &st.kernel_ms);
-                if (rc) return die("rt_render_wavefront_lit", rc);
-            } else {
-                rc = rt_render_wavefront(ctx, &rc_cam, &p, fix.data(), &rays, &st.kernel_ms);
-                if (rc) return die("rt_render_wavefront", rc);
-            }
+            if (render_wavefront_frame(ctx, &rc_cam, &p, fix.data(), &rays, &st.kernel_ms)) return 1;
             st.rays_traced = rays; st.samples = (uint64_t)npix * (uint64_t)spp;
             rc = rt_resolve_rgba8(ctx, fix.data(), width, height, spp, 1, rgba.data());
             if (rc) return die("rt_resolve_rgba8", rc);

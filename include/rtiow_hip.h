@@ -611,6 +611,73 @@ int rt_temporal_host(const uint64_t *fix, const uint32_t *count, int64_t spp, co
                      const rt_camera *prev_cam, int32_t width, int32_t height, const struct rt_temporal *tp, uint64_t *out_fix,
                      uint32_t *out_len);
 
+/* ---- temporal accumulation with second moments; the variance-guided denoiser fed by a given variance ---- */
+
+/* rt_temporal with the second moment of the frame means carried beside the colour, and a per-channel variance of the accumulated value as
+ * an output: the temporal half of SVGF (Schied et al., HPG 2017).  DESIGN.md section 26.  Arguments, `struct rt_temporal` and
+ * RT_TEMPORAL_CLAMP are rt_temporal's, and
+ *   history   prev_m2 [H][W][3] double, the previous call's out_m2.  The history is now all FIVE buffers or none.
+ *   outputs   out_m2 [H][W][3] double, the accumulated mean of the squared frame means; out_var [H][W][3] double, per channel the variance
+ *             of the accumulated value out_fix holds, in radiance units squared -- what rt_denoise_var_given takes as `var`.  Like out_fix
+ *             and out_len they must NOT overlap the history.
+ * Doubles, not exact sums: a squared radiance passes the 2^16 sample clamp at c = 256, and a light seen directly is brighter than that.
+ *
+ * The contract: IEEE binary64 throughout, in this operation order, no fused multiply-add.
+ *   Steps 1-7 of rt_temporal are unchanged: out_fix and out_len are rt_temporal's bits for the same inputs.  Below, o_ch is the double of
+ *   step 7 before quantize (c_ch at a "no history" exit) and len is step 7's result.
+ *   s2_ch = c_ch * c_ch.
+ *   No history (step 2 and every "no history" exit): m2_ch = s2_ch, at = 1.0, len = 1.
+ *   Step 5.  Every kept tap also adds acc2_ch = acc2_ch + kw * prev_m2_q,ch, from 0.0;  h2_ch = acc2_ch / ws.
+ *   Step 6, only with the clamp.  hb_ch = h_ch before the two limits; after them h2_ch = (h2_ch - hb_ch * hb_ch) + h_ch * h_ch: the clamp
+ *     moves the history's mean and keeps its central variance.
+ *   Step 7.  m2_ch = h2_ch + at * (s2_ch - h2_ch);  vt_ch = m2_ch - o_ch * o_ch;  vt_ch = vt_ch > 0.0 ? vt_ch : 0.0 (a NaN gives 0).
+ *   Spatial estimate (SVGF's rule for young pixels; always computed).  Over the in-frame pixels q of the 3 x 3 neighbourhood of p in the
+ *     CURRENT frame, the centre included in its place, dy = -1..1 outer, dx = -1..1 inner:  a1_ch = a1_ch + c_q,ch,
+ *     a2_ch = a2_ch + c_q,ch * c_q,ch  and  cnt = cnt + 1.0, all from 0.0.  mu = a1_ch / cnt;  vs_ch = a2_ch / cnt - mu * mu, clipped at 0
+ *     the same way as vt_ch.
+ *   Result.  vf_ch = len < RT_TEMPORAL_VAR_MIN_LEN ? vs_ch : vt_ch;  out_var_ch = vf_ch * at;  out_m2_ch = m2_ch.
+ * vf estimates the variance of ONE frame's mean; multiplying by at makes it the variance of the accumulated value.  That is exact for
+ * the running mean (at = 1 / len); once alpha_min holds at up, the exponential average's variance is at / (2 - at) of one frame's, so
+ * vf * at is conservative by at most 2x.
+ * The result is a pure function of the inputs: the same bits from the device forms and from rt_temporal_var_host.
+ *
+ * RT_ERR_INVALID_ARGUMENT from every form, found before anything is touched and leaving all four outputs untouched: rt_temporal's
+ * checks in its order, with out_m2 and out_var in the NULL check and prev_m2 in the history count (some but not all five is a partial
+ * history); the context check comes last. */
+#define RT_TEMPORAL_VAR_MIN_LEN 4
+
+/* Device form, asynchronous on `stream`: as rt_temporal_device.  Takes NONE of the context's launch slots, rt_last_stats does not report
+ * on it, and it needs no uploaded scene. */
+int rt_temporal_var_device(rt_context *ctx, const void *d_fix, const void *d_count, int64_t spp, const void *d_feat, int64_t feat_spp,
+                           const rt_camera *cam, const void *d_prev_fix, const void *d_prev_len, const void *d_prev_feat, int64_t prev_feat_spp,
+                           const rt_camera *prev_cam, const void *d_prev_m2, int32_t width, int32_t height, const struct rt_temporal *tp,
+                           void *d_out_fix, void *d_out_len, void *d_out_m2, void *d_out_var, void *stream);
+/* Host-buffer form (copies in, accumulates on the device, copies out); synchronous.  kernel_ms (may be NULL): the kernel's time. */
+int rt_temporal_var(rt_context *ctx, const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp,
+                    const rt_camera *cam, const uint64_t *prev_fix, const uint32_t *prev_len, const uint64_t *prev_feat, int64_t prev_feat_spp,
+                    const rt_camera *prev_cam, const double *prev_m2, int32_t width, int32_t height, const struct rt_temporal *tp,
+                    uint64_t *out_fix, uint32_t *out_len, double *out_m2, double *out_var, float *kernel_ms);
+/* The same accumulation on host buffers, no device needed: the library's own CPU statement of the contract (rt_temporal_var_core.hpp). */
+int rt_temporal_var_host(const uint64_t *fix, const uint32_t *count, int64_t spp, const uint64_t *feat, int64_t feat_spp, const rt_camera *cam,
+                         const uint64_t *prev_fix, const uint32_t *prev_len, const uint64_t *prev_feat, int64_t prev_feat_spp,
+                         const rt_camera *prev_cam, const double *prev_m2, int32_t width, int32_t height, const struct rt_temporal *tp,
+                         uint64_t *out_fix, uint32_t *out_len, double *out_m2, double *out_var);
+
+/* rt_denoise_var with `half` replaced by
+ *   var   [H][W][3] double   per channel, the variance of the pixel's mean c_ch in radiance units squared: rt_temporal_var's out_var (then
+ *         fix is its out_fix and spp = 1).
+ * Everything else is rt_denoise_var's: `struct rt_denoise`, the levels, the statistics, the taps, finish, both forms of the level kernel
+ * and their knob, and the workspace of rt_denoise_var_workspace_bytes.  The one new rule is in Prepare:
+ *   x_ch = (var_ch / m_ch) / m_ch;  x_ch = x_ch > 0.0 ? x_ch : 0.0 (a NaN and a negative give 0);  var_p = (x_r + x_g) + x_b.
+ * The checks are rt_denoise_var's in its order, with var in half's place. */
+int rt_denoise_var_given_device(rt_context *ctx, const void *d_fix, const void *d_var, const void *d_count, int64_t spp, const void *d_feat,
+                                int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, void *d_work, void *d_out_fix,
+                                void *stream);
+int rt_denoise_var_given(rt_context *ctx, const uint64_t *fix, const double *var, const uint32_t *count, int64_t spp, const uint64_t *feat,
+                         int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, uint64_t *out_fix, float *kernel_ms);
+int rt_denoise_var_given_host(const uint64_t *fix, const double *var, const uint32_t *count, int64_t spp, const uint64_t *feat,
+                              int64_t feat_spp, int32_t width, int32_t height, const struct rt_denoise *dn, uint64_t *out_fix);
+
 /* ---- ray queries: closest hit and occlusion for rays the caller supplies ---- */
 
 /* HittableList::hit (mod.rs:54-70) for rays that do not come from an rt_camera: picking, visibility between two points, ambient

@@ -100,6 +100,7 @@ RT_DENOISE_MAX_LEVELS = 8
 RT_DENOISE_ALBEDO_FLOOR = 0.015625
 RT_TEMPORAL_CLAMP = 0x1
 RT_TEMPORAL_MAX_LEN = 65535
+RT_TEMPORAL_VAR_MIN_LEN = 4
 RT_PATH_EVENT_DIRECT = 0x80000000
 RT_STEP_NO_DIRECT = 0x1
 RT_DIRECT_CONE = 0x2
@@ -150,6 +151,19 @@ SYMBOLS = [
                               C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, C.POINTER(C.c_float)]),
     ("rt_temporal_host", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
                                    C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP]),
+    # temporal accumulation with second moments: prev_m2 behind prev_cam, out_m2 and out_var behind out_len
+    ("rt_temporal_var_device", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64,
+                                         C.POINTER(rt_camera), _VP, C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, _VP, _VP, _VP]),
+    ("rt_temporal_var", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
+                                  _VP, C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
+    ("rt_temporal_var_host", C.c_int, [_VP, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rt_camera), _VP, _VP, _VP, C.c_int64, C.POINTER(rt_camera),
+                                       _VP, C.c_int32, C.c_int32, C.POINTER(rt_temporal), _VP, _VP, _VP, _VP]),
+    # the variance-guided denoiser with the variance given: rt_denoise_var's arguments, var [H][W][3] f64 in half's place
+    ("rt_denoise_var_given_device", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP, _VP,
+                                              _VP]),
+    ("rt_denoise_var_given", C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP,
+                                       C.POINTER(C.c_float)]),
+    ("rt_denoise_var_given_host", C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, C.c_int32, C.POINTER(rt_denoise), _VP]),
     ("rt_trace_rays_device", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, C.POINTER(rt_hits), _VP]),
     ("rt_trace_rays", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, C.POINTER(rt_hits), C.POINTER(C.c_float)]),
     ("rt_occluded_device", C.c_int, [_VP, C.POINTER(rt_rays), C.c_double, _VP, _VP]),

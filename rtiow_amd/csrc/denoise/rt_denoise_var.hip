@@ -127,6 +127,33 @@ __global__ __launch_bounds__(kDnBlock) void denoise_var_finish_kernel(const doub
     dn_finish_body(c, mod, npix, out);
 }
 
+// What follows prepare, for rt_denoise_var_device and rt_denoise_var_given_device (denoise/rt_temporal_var.hip): per level the statistics
+// and the taps, then finish into d_out_fix, on `stream`.  k: the partitioned workspace, prepared (guide, mod, ca, va).
+int dn_var_levels_device(const struct rt_denoise *dn, rt_dn::Work k, int32_t width, int32_t height, void *d_out_fix, hipStream_t stream)
+{
+    const unsigned long long npix = (unsigned long long)width * (unsigned long long)height;
+    const unsigned grid = dn_blocks_for(npix);
+    const int knob = dn_level_kernel_knob();
+    for (int l = 0; l < dn->levels; ++l) {
+        hipLaunchKernelGGL(denoise_var_stats_kernel, dim3(grid), dim3(kDnBlock), 0, stream, (const double *)k.ca, (const double *)k.va,
+                           (uint32_t)width, (uint32_t)height, npix, k.box, k.gv);
+        RT_HIP(hipGetLastError());
+        DvFrame F;
+        F.guide = k.guide; F.cin = k.ca; F.box = k.box; F.vin = k.va; F.gv = k.gv; F.cout = k.cb; F.vout = k.vb;
+        F.width = (uint32_t)width; F.height = (uint32_t)height; F.npix = npix;
+        F.L = rt_dn::level_const(dn->sigma_color, dn->sigma_normal, dn->sigma_depth, l);
+        F.sc2 = dn->sigma_color * dn->sigma_color;
+        dn_launch_level(F, knob < 0 ? kDnVarTileDefault[l] : knob == 1, denoise_var_level_tile_kernel, denoise_var_level_gather_kernel, stream);
+        RT_HIP(hipGetLastError());
+        double *t = k.ca; k.ca = k.cb; k.cb = t;
+        t = k.va; k.va = k.vb; k.vb = t;
+    }
+    hipLaunchKernelGGL(denoise_var_finish_kernel, dim3(grid), dim3(kDnBlock), 0, stream, (const double *)k.ca, (const double *)k.mod, npix,
+                       (unsigned long long *)d_out_fix);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
 } // namespace rt
 
 namespace {
@@ -170,26 +197,7 @@ int rt_denoise_var_device(rt_context *ctx, const void *d_fix, const void *d_half
                        (const unsigned long long *)d_half, (const uint32_t *)d_count, (double)spp, (const unsigned long long *)d_feat,
                        (double)feat_spp, (dn->flags & RT_DENOISE_DEMODULATE) ? 1 : 0, npix, k.guide, k.mod, k.ca, k.va);
     RT_HIP(hipGetLastError());
-    const int knob = rt::dn_level_kernel_knob();
-    for (int l = 0; l < dn->levels; ++l) {
-        hipLaunchKernelGGL(rt::denoise_var_stats_kernel, dim3(grid), dim3(rt::kDnBlock), 0, stream, (const double *)k.ca, (const double *)k.va,
-                           (uint32_t)width, (uint32_t)height, npix, k.box, k.gv);
-        RT_HIP(hipGetLastError());
-        rt::DvFrame F;
-        F.guide = k.guide; F.cin = k.ca; F.box = k.box; F.vin = k.va; F.gv = k.gv; F.cout = k.cb; F.vout = k.vb;
-        F.width = (uint32_t)width; F.height = (uint32_t)height; F.npix = npix;
-        F.L = rt_dn::level_const(dn->sigma_color, dn->sigma_normal, dn->sigma_depth, l);
-        F.sc2 = dn->sigma_color * dn->sigma_color;
-        rt::dn_launch_level(F, knob < 0 ? rt::kDnVarTileDefault[l] : knob == 1, rt::denoise_var_level_tile_kernel,
-                            rt::denoise_var_level_gather_kernel, stream);
-        RT_HIP(hipGetLastError());
-        double *t = k.ca; k.ca = k.cb; k.cb = t;
-        t = k.va; k.va = k.vb; k.vb = t;
-    }
-    hipLaunchKernelGGL(rt::denoise_var_finish_kernel, dim3(grid), dim3(rt::kDnBlock), 0, stream, (const double *)k.ca, (const double *)k.mod, npix,
-                       (unsigned long long *)d_out_fix);
-    RT_HIP(hipGetLastError());
-    return RT_OK;
+    return rt::dn_var_levels_device(dn, k, width, height, d_out_fix, stream);
 }
 
 int rt_denoise_var(rt_context *ctx, const uint64_t *fix, const uint64_t *half, const uint32_t *count, int64_t spp, const uint64_t *feat,

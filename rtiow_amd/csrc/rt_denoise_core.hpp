@@ -182,22 +182,13 @@ RT_DN_FN double prepare_var(const uint64_t *fix, const uint64_t *half, double sa
 template <class VarAt>
 RT_DN_FN double gauss_var(long long i, long long j, long long width, long long height, VarAt var_at);
 
-// The whole filter on host arrays, one pixel after the other, for either record: prepare, then per level the statistics (the box mean;
-// with a variance, its Gaussian too) and the taps, then finish.  count may be null (every pixel has spp samples); half is read with a
-// variance only.
+// What follows prepare on host arrays, one pixel after the other, for either record: per level the statistics (the box mean; with a
+// variance, its Gaussian too) and the taps, then finish.  k: the partitioned workspace, prepared (guide, mod, ca; with a variance, va).
 template <class Rec>
-inline void filter_walk(const uint64_t *fix, [[maybe_unused]] const uint64_t *half, const uint32_t *count, long long spp, const uint64_t *feat,
-                        long long feat_spp, long long width, long long height, int levels, bool demodulate, double sigma_color,
-                        double sigma_normal, double sigma_depth, double *work, uint64_t *out_fix)
+inline void filter_levels(Work k, long long width, long long height, int levels, double sigma_color, double sigma_normal, double sigma_depth,
+                          uint64_t *out_fix)
 {
     const long long npix = width * height;
-    Work k = partition(work, (unsigned long long)npix, Rec::kVar);
-    for (long long p = 0; p < npix; ++p) {
-        const double samples = count ? (double)count[p] : (double)spp;
-        prepare(fix + 3 * p, samples, feat + 8 * p, (double)feat_spp, demodulate, k.ca + 3 * p, k.mod + 3 * p, k.guide + 4 * p,
-                k.guide + 4 * p + 3);
-        if constexpr (Rec::kVar) k.va[p] = prepare_var(fix + 3 * p, half + 3 * p, samples, k.mod + 3 * p);
-    }
     for (int l = 0; l < levels; ++l) {
         const LevelConst L = level_const(sigma_color, sigma_normal, sigma_depth, l);
         const double *cin = k.ca, *vin = k.va, *box = k.box, *guide = k.guide;
@@ -231,6 +222,24 @@ inline void filter_walk(const uint64_t *fix, [[maybe_unused]] const uint64_t *ha
         if constexpr (Rec::kVar) { t = k.va; k.va = k.vb; k.vb = t; }
     }
     for (long long p = 0; p < npix; ++p) finish(k.ca + 3 * p, k.mod + 3 * p, out_fix + 3 * p);
+}
+
+// The whole filter on host arrays for either record: prepare, then filter_levels.  count may be null (every pixel has spp samples);
+// half is read with a variance only.
+template <class Rec>
+inline void filter_walk(const uint64_t *fix, [[maybe_unused]] const uint64_t *half, const uint32_t *count, long long spp, const uint64_t *feat,
+                        long long feat_spp, long long width, long long height, int levels, bool demodulate, double sigma_color,
+                        double sigma_normal, double sigma_depth, double *work, uint64_t *out_fix)
+{
+    const long long npix = width * height;
+    Work k = partition(work, (unsigned long long)npix, Rec::kVar);
+    for (long long p = 0; p < npix; ++p) {
+        const double samples = count ? (double)count[p] : (double)spp;
+        prepare(fix + 3 * p, samples, feat + 8 * p, (double)feat_spp, demodulate, k.ca + 3 * p, k.mod + 3 * p, k.guide + 4 * p,
+                k.guide + 4 * p + 3);
+        if constexpr (Rec::kVar) k.va[p] = prepare_var(fix + 3 * p, half + 3 * p, samples, k.mod + 3 * p);
+    }
+    filter_levels<Rec>(k, width, height, levels, sigma_color, sigma_normal, sigma_depth, out_fix);
 }
 
 // rt_denoise_host and the stand-alone program

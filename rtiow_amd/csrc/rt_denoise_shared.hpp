@@ -1,5 +1,6 @@
 // rt_denoise_shared.hpp -- what the two a-trous denoisers share beyond their arithmetic (DESIGN.md sections 15 and 25), stated ONCE for
-// rt_denoise.hip and denoise/rt_denoise_var.hip, which include it behind rt_host.hpp and their core header; nothing else does.
+// rt_denoise.hip and denoise/rt_denoise_var.hip, which include it behind rt_host.hpp and their core header; denoise/rt_temporal_var.hip
+// includes it too, for the host part only (its prepare kernel feeds rt_denoise_var's levels).
 //   device  the tile geometry, the tiling of the sub-lattices, the load of a record, the gather form's body, a staged tile's planes
 //           (the tile form's body is rt_denoise_tile.inc, which uses them), the finish body;
 //   host    the diagnostic knob, the grid cap, the checks of a frame's size and of the settings, the tiling arithmetic, one level's launch.
@@ -175,5 +176,10 @@ inline void dn_launch_level(const Frame &F, bool want_tile, void (*tile_kernel)(
         hipLaunchKernelGGL(gather_kernel, dim3(dn_blocks_for(F.npix)), dim3(kDnBlock), 0, stream, F);
     }
 }
+
+// The variance-guided filter behind its prepare kernel -- the statistics and the taps of every level, then finish into d_out_fix -- for
+// the two entries that differ only in where the variance comes from.  Defined in denoise/rt_denoise_var.hip beside its kernels; called
+// from there and from denoise/rt_temporal_var.hip (rt_denoise_var_given_device).  k: the partitioned workspace, prepared.
+int dn_var_levels_device(const struct rt_denoise *dn, rt_dn::Work k, int32_t width, int32_t height, void *d_out_fix, hipStream_t stream);
 
 } // namespace rt

@@ -4,7 +4,8 @@
 // walk over host arrays, which that header writes for either record.  Added here: the record with a variance (TapVar), the variance a
 // pixel's half-sample sums give (prepare_var), its 3x3 Gaussian (gauss_var), and under their names one pixel of one level with the colour
 // stop in units of the local standard deviation and the variance carried along with the squared weights (level_pixel_var) and the whole
-// filter on host arrays (filter_var_host).  rt_denoise_var_host, the kernels of denoise/rt_denoise_var.hip and the stand-alone sanitizer
+// filter on host arrays (filter_var_host); and, for rt_denoise_var_given, the same variance from one the caller
+// gives (prepare_var_given) and the filter behind it (filter_var_given_host).  rt_denoise_var_host, the kernels of denoise/rt_denoise_var.hip and the stand-alone sanitizer
 // program tests/denoise_var_san_main.cpp compile these very functions.
 //
 // A pure header: no HIP header, no library call.  IEEE binary64 throughout, in the written operation order; the translation units that
@@ -31,6 +32,18 @@ RT_DN_FN double prepare_var(const uint64_t *fix, const uint64_t *half, double sa
         e[ch] = (value(d) / samples) / m[ch];
     }
     return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+}
+
+// The same quantity from a variance the caller gives (rt_denoise_var_given): var[ch] = the variance of the pixel's mean c_ch in radiance
+// units; x_ch = (var_ch / m_ch) / m_ch, a NaN or a negative counts 0, (x_r + x_g) + x_b.
+RT_DN_FN double prepare_var_given(const double var[3], const double m[3])
+{
+    double x[3];
+    for (int ch = 0; ch < 3; ++ch) {
+        x[ch] = (var[ch] / m[ch]) / m[ch];
+        x[ch] = x[ch] > 0.0 ? x[ch] : 0.0;
+    }
+    return (x[0] + x[1]) + x[2];
 }
 
 // The 3x3 Gaussian of the level's input variance at pixel (i, j): the in-frame neighbours, dy = -1..1 outer, dx = -1..1 inner, weights
@@ -68,6 +81,21 @@ inline void filter_var_host(const uint64_t *fix, const uint64_t *half, const uin
 {
     filter_walk<TapVar>(fix, half, count, spp, feat, feat_spp, width, height, levels, demodulate, sigma_color, sigma_normal, sigma_depth, work,
                         out_fix);
+}
+
+// ... and with the variance given -- rt_denoise_var_given_host and the stand-alone program tests/temporal_var_san_main.cpp.
+inline void filter_var_given_host(const uint64_t *fix, const double *var, const uint32_t *count, long long spp, const uint64_t *feat,
+                                  long long feat_spp, long long width, long long height, int levels, bool demodulate, double sigma_color,
+                                  double sigma_normal, double sigma_depth, double *work, uint64_t *out_fix)
+{
+    const long long npix = width * height;
+    Work k = partition(work, (unsigned long long)npix, true);
+    for (long long p = 0; p < npix; ++p) {
+        prepare(fix + 3 * p, count ? (double)count[p] : (double)spp, feat + 8 * p, (double)feat_spp, demodulate, k.ca + 3 * p, k.mod + 3 * p,
+                k.guide + 4 * p, k.guide + 4 * p + 3);
+        k.va[p] = prepare_var_given(var + 3 * p, k.mod + 3 * p);
+    }
+    filter_levels<TapVar>(k, width, height, levels, sigma_color, sigma_normal, sigma_depth, out_fix);
 }
 
 } // namespace rt_dn

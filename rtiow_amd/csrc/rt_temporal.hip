@@ -19,19 +19,11 @@
 
 #include "rt_host.hpp"
 #include "rt_temporal_core.hpp"
+#include "rt_temporal_shared.hpp"
 
 using namespace rt_host;
 
 namespace rt {
-
-constexpr int kTpBlock = 256;                       // four waves, each on pixel tiles of its own
-constexpr int kTpWaves = kTpBlock / 64;
-constexpr long long kTpMaxBlocks = 1 << 20;         // the grid-stride loop takes over beyond
-
-struct TpTiling {
-    uint32_t tiles_x;               // pixel tiles per row of tiles: ceil(width / 8)
-    uint32_t n_tiles;               // tiles_x * ceil(height / 8) <= 2^31 / 64 + 2^16
-};
 
 __global__ __launch_bounds__(kTpBlock) void temporal_kernel(const rt_tp::Const K, const rt_tp::Buffers B, const TpTiling T,
                                                             unsigned long long *__restrict__ out_fix, uint32_t *__restrict__ out_len)
@@ -54,16 +46,6 @@ __global__ __launch_bounds__(kTpBlock) void temporal_kernel(const rt_tp::Const K
 
 namespace {
 
-rt_tp::Cam cam_of(const rt_camera *c)
-{
-    rt_tp::Cam k;
-    for (int a = 0; a < 3; ++a) {
-        k.origin[a] = c->origin[a]; k.llc[a] = c->lower_left_corner[a];
-        k.horizontal[a] = c->horizontal[a]; k.vertical[a] = c->vertical[a];
-    }
-    return k;
-}
-
 // What every form checks, before anything is touched; none of it needs a context.  *K: the constants of the call.
 int validate_temporal(const struct rt_temporal *tp, const void *fix, bool has_count, int64_t spp, const void *feat, int64_t feat_spp,
                       const rt_camera *cam, const void *prev_fix, const void *prev_len, const void *prev_feat, int64_t prev_feat_spp,
@@ -75,26 +57,7 @@ int validate_temporal(const struct rt_temporal *tp, const void *fix, bool has_co
     const int n_hist = (prev_fix ? 1 : 0) + (prev_len ? 1 : 0) + (prev_feat ? 1 : 0) + (prev_cam ? 1 : 0);
     if (n_hist != 0 && n_hist != 4)
         return fail(RT_ERR_INVALID_ARGUMENT, "temporal: a partial history (%d of prev_fix, prev_len, prev_feat, prev_cam): all four or none", n_hist);
-    if (tp->flags & ~RT_TEMPORAL_CLAMP) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: unknown flags 0x%x", tp->flags);
-    if (!(tp->alpha_min > 0.0) || !(tp->alpha_min <= 1.0))
-        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: alpha_min must be in (0, 1] (is %g)", tp->alpha_min);
-    if (!(tp->sigma_normal > 0.0) || !(tp->sigma_depth > 0.0) || !std::isfinite(tp->sigma_normal) || !std::isfinite(tp->sigma_depth))
-        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: every sigma must be > 0 and finite (%g, %g)", tp->sigma_normal, tp->sigma_depth);
-    if (!(tp->clamp_scale >= 0.0) || !std::isfinite(tp->clamp_scale))
-        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: clamp_scale must be >= 0 and finite (is %g)", tp->clamp_scale);
-    if (width < 2 || height < 2) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: width and height must be >= 2 (%d, %d)", width, height);
-    if ((long long)width * height > (1ll << 31))
-        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: width * height must be <= 2^31 (is %lld)", (long long)width * height);
-    if (!has_count && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: spp >= 1 without a count buffer (is %lld)", (long long)spp);
-    if (feat_spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "temporal: feat_spp >= 1 (is %lld)", (long long)feat_spp);
-    if (n_hist && prev_feat_spp < 1)
-        return fail(RT_ERR_INVALID_ARGUMENT, "temporal: prev_feat_spp >= 1 with a history (is %lld)", (long long)prev_feat_spp);
-    const rt_tp::Cam cur = cam_of(cam);
-    rt_tp::Cam prev;
-    if (n_hist) prev = cam_of(prev_cam);
-    *K = rt_tp::constants(cur, n_hist ? &prev : nullptr, width, height, has_count ? 1 : (long long)spp, (long long)feat_spp,
-                          n_hist ? (long long)prev_feat_spp : 1, tp->flags, tp->alpha_min, tp->sigma_normal, tp->sigma_depth, tp->clamp_scale);
-    return RT_OK;
+    return rt::tp_check_settings("temporal", tp, has_count, spp, feat_spp, cam, n_hist != 0, prev_feat_spp, prev_cam, width, height, K);
 }
 
 rt_tp::Buffers buffers_of(const void *fix, const void *count, const void *feat, const void *prev_fix, const void *prev_len, const void *prev_feat)
@@ -122,12 +85,8 @@ int rt_temporal_device(rt_context *ctx, const void *d_fix, const void *d_count, 
     RT_HIP(hipSetDevice(ctx->device));
     // (no launch slot: rt_last_stats does not report on an accumulation; no scene needed)
     rt::TpTiling T;
-    T.tiles_x = ((uint32_t)width + 7u) / 8u;
-    const unsigned long long n_tiles = (unsigned long long)T.tiles_x * (((unsigned long long)height + 7ull) / 8ull);
-    T.n_tiles = (uint32_t)n_tiles;                              // width * height <= 2^31: at most 2^31 / 8 + 2^28 tiles of one row or column
-    unsigned long long grid = (n_tiles + rt::kTpWaves - 1) / rt::kTpWaves;
-    if (grid > (unsigned long long)rt::kTpMaxBlocks) grid = (unsigned long long)rt::kTpMaxBlocks;
-    hipLaunchKernelGGL(rt::temporal_kernel, dim3((unsigned)grid), dim3(rt::kTpBlock), 0, (hipStream_t)stream_v, K,
+    const unsigned grid = rt::tp_grid(width, height, &T);
+    hipLaunchKernelGGL(rt::temporal_kernel, dim3(grid), dim3(rt::kTpBlock), 0, (hipStream_t)stream_v, K,
                        buffers_of(d_fix, d_count, d_feat, d_prev_fix, d_prev_len, d_prev_feat), T, (unsigned long long *)d_out_fix,
                        (uint32_t *)d_out_len);
     RT_HIP(hipGetLastError());

@@ -151,6 +151,58 @@ def temporal_host(fix, spp, feat, feat_spp, cam, history=None, temporal=None, co
     return out_fix, out_len
 
 
+# the default sigma_color of render_sequence_var: the swept value with the lowest final-frame RMSE on the night sequence
+# (tools/temporal_var_sweep.py, profiles/temporal_var_sweep.txt)
+TEMPORAL_VAR_SIGMA_COLOR = 1.5
+
+
+def _temporal_var_args(fix, spp, feat, feat_spp, cam, history, count):
+    """_temporal_args with the second moment: history is None or (prev_fix, prev_len, prev_feat, prev_feat_spp, prev_cam, prev_m2 f64 [H,W,3]).
+    -> (head, out_fix, out_len, out_m2, out_var, keep); head ends with prev_m2, width, height."""
+    head, out_fix, out_len, keep = _temporal_args(fix, spp, feat, feat_spp, cam, None if history is None else history[:5], count)
+    h, w = out_len.shape
+    pm2 = None
+    if history is not None:
+        pm2 = np.ascontiguousarray(history[5], dtype=np.float64)
+        assert pm2.shape == (h, w, 3)
+        keep.append(pm2)
+    head = (*head[:-2], pm2.ctypes.data_as(C.c_void_p) if pm2 is not None else None, w, h)
+    return head, out_fix, out_len, np.zeros((h, w, 3), dtype=np.float64), np.zeros((h, w, 3), dtype=np.float64), keep
+
+
+def temporal_var_host(fix, spp, feat, feat_spp, cam, history=None, temporal=None, count=None):
+    """rt_temporal_var_host (no GPU): temporal_host with second moments.  history: None for the first frame, else (prev_fix, prev_len,
+    prev_feat, prev_feat_spp, prev_cam, prev_m2) -- the previous call's out_fix, out_len and out_m2, the previous frame's feature sums and
+    camera.  Returns (out_fix u64 [H,W,3], out_len u32 [H,W], out_m2 f64 [H,W,3], out_var f64 [H,W,3]: the variance of the accumulated value)."""
+    lib = _ffi.load()
+    tp = temporal if temporal is not None else make_temporal()
+    head, out_fix, out_len, out_m2, out_var, keep = _temporal_var_args(fix, spp, feat, feat_spp, cam, history, count)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _ffi.check(lib.rt_temporal_var_host(*head, C.byref(tp), vp(out_fix), vp(out_len), vp(out_m2), vp(out_var)), "rt_temporal_var_host")
+    return out_fix, out_len, out_m2, out_var
+
+
+def _denoise_var_given_arrays(fix, var, feat, count):
+    fix, feat, count, h, w = _denoise_arrays(fix, feat, count)
+    var = np.ascontiguousarray(var, dtype=np.float64)
+    assert var.shape == (h, w, 3)
+    return fix, var, feat, count, h, w
+
+
+def denoise_var_given_host(fix, var, spp, feat, feat_spp, denoise=None, count=None):
+    """rt_denoise_var_given_host (no GPU): denoise_var_host with the variance given -- var f64 [H,W,3], per channel the variance of the
+    pixel's mean in radiance units (temporal_var's out_var, with its out_fix and spp = 1)."""
+    lib = _ffi.load()
+    fix, var, feat, count, h, w = _denoise_var_given_arrays(fix, var, feat, count)
+    dn = denoise if denoise is not None else make_denoise_var()
+    out = np.zeros((h, w, 3), dtype=np.uint64)
+    _ffi.check(lib.rt_denoise_var_given_host(fix.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p),
+                                             count.ctypes.data_as(C.c_void_p) if count is not None else None, int(spp),
+                                             feat.ctypes.data_as(C.c_void_p), int(feat_spp), w, h, C.byref(dn), out.ctypes.data_as(C.c_void_p)),
+               "rt_denoise_var_given_host")
+    return out
+
+
 def shard_rows(params):
     lib = _ffi.load()
     rows = C.c_int32(0)
@@ -1192,6 +1244,88 @@ class Renderer:
             shown = self.denoise(acc, 1, feat, feature_spp, denoise)[0] if denoise is not None else acc
             out[f] = self.resolve_rgba8(shown, 1, flip=flip)
         return out, lengths
+
+    # -- temporal accumulation with second moments, and the variance-guided denoiser fed by its variance ------
+    def temporal_var(self, fix, spp, feat, feat_spp, cam, history=None, temporal=None, count=None):
+        """rt_temporal_var: the arguments of temporal_var_host, on the device -> (out_fix, out_len, out_m2, out_var, the kernel's time in ms).
+        Feed the first three back as the next frame's history (with this frame's feat and camera)."""
+        tp = temporal if temporal is not None else make_temporal()
+        head, out_fix, out_len, out_m2, out_var, keep = _temporal_var_args(fix, spp, feat, feat_spp, cam, history, count)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_temporal_var(self._h, *head, C.byref(tp), vp(out_fix), vp(out_len), vp(out_m2), vp(out_var), C.byref(ms)),
+                   "rt_temporal_var")
+        return out_fix, out_len, out_m2, out_var, float(ms.value)
+
+    def temporal_var_device(self, d_fix_ptr, spp, d_feat_ptr, feat_spp, cam, width, height, temporal, d_out_fix_ptr, d_out_len_ptr, d_out_m2_ptr,
+                            d_out_var_ptr, history=None, d_count_ptr=0, stream=0):
+        """rt_temporal_var_device: device pointers, asynchronous on `stream`; history: None or (d_prev_fix_ptr, d_prev_len_ptr, d_prev_feat_ptr,
+        prev_feat_spp, prev_cam, d_prev_m2_ptr) -- the cameras are host objects.  The outputs must not overlap the history: ping-pong."""
+        vp = lambda q: C.c_void_p(q) if q else None
+        rc = _rt_cam(cam)
+        if history is None:
+            hist = (None, None, None, 0, None, None)
+        else:
+            pc = _rt_cam(history[4])
+            hist = (vp(history[0]), vp(history[1]), vp(history[2]), int(history[3]), C.byref(pc), vp(history[5]))
+        _ffi.check(self._lib.rt_temporal_var_device(self._h, vp(d_fix_ptr), vp(d_count_ptr), int(spp), vp(d_feat_ptr), int(feat_spp), C.byref(rc),
+                                                    *hist, int(width), int(height), C.byref(temporal), vp(d_out_fix_ptr), vp(d_out_len_ptr),
+                                                    vp(d_out_m2_ptr), vp(d_out_var_ptr), C.c_void_p(stream)), "rt_temporal_var_device")
+
+    temporal_var_host = staticmethod(temporal_var_host)
+
+    def denoise_var_given(self, fix, var, spp, feat, feat_spp, denoise=None, count=None):
+        """rt_denoise_var_given: as denoise_var, with var f64 [H,W,3] in half's place -> (the denoised ONE-SAMPLE frame u64 [H,W,3], the
+        kernels' time in ms)."""
+        fix, var, feat, count, h, w = _denoise_var_given_arrays(fix, var, feat, count)
+        dn = denoise if denoise is not None else make_denoise_var()
+        out = np.zeros((h, w, 3), dtype=np.uint64)
+        ms = C.c_float(0.0)
+        _ffi.check(self._lib.rt_denoise_var_given(self._h, fix.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p),
+                                                  count.ctypes.data_as(C.c_void_p) if count is not None else None, int(spp),
+                                                  feat.ctypes.data_as(C.c_void_p), int(feat_spp), w, h, C.byref(dn), out.ctypes.data_as(C.c_void_p),
+                                                  C.byref(ms)), "rt_denoise_var_given")
+        return out, float(ms.value)
+
+    def denoise_var_given_device(self, d_fix_ptr, d_var_ptr, spp, d_feat_ptr, feat_spp, width, height, denoise, d_work_ptr, d_out_ptr, d_count_ptr=0,
+                                 stream=0):
+        """rt_denoise_var_given_device: device pointers; d_work_ptr: denoise_var_workspace_bytes(width, height) bytes; asynchronous on `stream`."""
+        _ffi.check(self._lib.rt_denoise_var_given_device(self._h, C.c_void_p(d_fix_ptr), C.c_void_p(d_var_ptr) if d_var_ptr else None,
+                                                         C.c_void_p(d_count_ptr) if d_count_ptr else None, int(spp), C.c_void_p(d_feat_ptr),
+                                                         int(feat_spp), int(width), int(height), C.byref(denoise), C.c_void_p(d_work_ptr),
+                                                         C.c_void_p(d_out_ptr), C.c_void_p(stream)), "rt_denoise_var_given_device")
+
+    denoise_var_given_host = staticmethod(denoise_var_given_host)
+
+    def render_sequence_var(self, cams, params, sample_stride, feature_spp, temporal=None, denoise=None, lighting=None, direct=False,
+                            sampling="area", flip=True):
+        """render_sequence with second moments and the variance-guided filter: per frame render_features, rt_temporal_var with ping-pong
+        history, rt_denoise_var_given on the accumulated frame with the variance that call returns (spp = 1, the frame's own guides), and the
+        one-sample resolve.  The frames come from render_frames (ONE launch) when lighting is None; otherwise frame f is render_wavefront
+        with sample_begin + f * sample_stride and this lighting, direct and sampling.  temporal: an rt_temporal (None: make_temporal());
+        denoise: an rt_denoise (None: make_denoise_var(sigma_color=TEMPORAL_VAR_SIGMA_COLOR)).  Returns (RGBA8 [F,H,W,4], the last frame's
+        history lengths u32 [H,W], the last frame's out_var f64 [H,W,3])."""
+        a = self._camera_array(cams)
+        tp = temporal if temporal is not None else make_temporal()
+        dn = denoise if denoise is not None else make_denoise_var(sigma_color=TEMPORAL_VAR_SIGMA_COLOR)
+        w, h = params.width, params.height
+        fixes = self.render_frames(a, params, sample_stride)[0] if lighting is None else None
+        out = np.zeros((len(a), h, w, 4), dtype=np.uint8)
+        history, lengths, var = None, np.zeros((h, w), dtype=np.uint32), np.zeros((h, w, 3), dtype=np.float64)
+        for f in range(len(a)):
+            cam = _ffi.rt_camera.from_buffer_copy(a[f].tobytes())
+            begin = params.sample_begin + f * int(sample_stride)
+            if lighting is None:
+                fix = fixes[f]
+            else:
+                fp = make_params(w, h, params.spp, sample_begin=begin, max_depth=params.max_depth, t_min=params.t_min, seed=params.seed)
+                fix = self.render_wavefront(cam, fp, lighting=lighting, direct=direct, sampling=sampling)[0]
+            gp = make_params(w, h, feature_spp, sample_begin=begin, t_min=params.t_min, seed=params.seed)
+            feat, _, _ = self.render_features(cam, gp, want_ids=False)
+            acc, lengths, m2, var, _ = self.temporal_var(fix, params.spp, feat, feature_spp, cam, history, tp)
+            history = (acc, lengths, feat, feature_spp, cam, m2)
+            out[f] = self.resolve_rgba8(self.denoise_var_given(acc, var, 1, feat, feature_spp, dn)[0], 1, flip=flip)
+        return out, lengths, var
 
     # -- to_rgba + flip --------------------------------------------------------
     def resolve_rgba8(self, fix, spp, flip=True):

@@ -13,7 +13,8 @@ their adaptive loop, path_begin_pixels_kernel and pass_add_listed_kernel, behind
 --all: every kernel of every rtiow_amd/csrc/rt_*.hip, whatever its name, sorted by name and without the s_nop padding behind its
 last instruction -- so a line does not depend on which translation unit the kernel lives in, nor on whether it is the last one there
 (profiles/isa_fingerprint_source_split.txt, tests/test_source_layout_host.py).  --denoise-var: the same listing for the five kernels of
-denoise/rt_denoise_var.hip alone (profiles/isa_fingerprint_denoise_var.txt, tests/test_denoise_var_host.py).  The other outputs count
+denoise/rt_denoise_var.hip alone (profiles/isa_fingerprint_denoise_var.txt, tests/test_denoise_var_host.py); --temporal-var: likewise
+for the two kernels of denoise/rt_temporal_var.hip (profiles/isa_fingerprint_temporal_var.txt, tests/test_temporal_var_host.py).  The other outputs count
 that padding, as they always did."""
 import collections, glob, hashlib, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,9 +22,11 @@ sys.path.insert(0, os.path.join(root, "tools"))
 import isa_census as ic
 args = sys.argv[1:]
 defs = [a for a in args if a.startswith("-D")]
-everything = "--all" in args or "--denoise-var" in args      # every kernel of the sources, sorted, the padding trimmed
+everything = "--all" in args or "--denoise-var" in args or "--temporal-var" in args      # every kernel of the sources, sorted, the padding trimmed
 if "--denoise-var" in args:
     sources = ["rtiow_amd/csrc/denoise/rt_denoise_var.hip"]
+elif "--temporal-var" in args:
+    sources = ["rtiow_amd/csrc/denoise/rt_temporal_var.hip"]
 elif everything:
     sources = sorted(os.path.relpath(p, root) for p in glob.glob(os.path.join(root, "rtiow_amd", "csrc", "rt_*.hip")))
 else:

@@ -6,7 +6,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 cmd = ["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
        "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", "-I", "include", "-I", "rtiow_amd/csrc",
        "-Rpass-analysis=kernel-resource-usage", *sys.argv[1:], "-o", "/tmp/_kr.so", *sorted(glob.glob("rtiow_amd/csrc/rt_*.hip", root_dir=root)),
-       "rtiow_amd/csrc/wavefront/rt_shade.hip", "rtiow_amd/csrc/wavefront/rt_paths.hip"]
+       "rtiow_amd/csrc/wavefront/rt_shade.hip", "rtiow_amd/csrc/wavefront/rt_paths.hip", *sorted(glob.glob("rtiow_amd/csrc/denoise/rt_*.hip", root_dir=root))]
 out = subprocess.run(cmd, cwd=root, capture_output=True, text=True)
 cur, rows = None, {}
 for line in (out.stderr + out.stdout).splitlines():
