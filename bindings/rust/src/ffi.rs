@@ -306,6 +306,26 @@ pub struct rt_direct {
 const _: () = assert!(offset_of!(rt_direct, n_lights) == 8);
 const _: () = assert!(offset_of!(rt_direct, flags) == 12);
 const _: () = assert!(16 == size_of::<rt_direct>());
+
+/// The largest `rt_environment.size`.
+pub const RT_ENV_MAX_SIZE: i32 = 1024;
+
+/// An environment cube map for the lit path queue (`rt_paths_step_env_device`, `rt_render_wavefront_env*`): `texels`:
+/// `[6][size][size][3]` radiance, `cdf`: `[6 * size * size]` running sums from `rt_environment_cdf` or null (looked up, never
+/// sampled); DEVICE pointers in the `_device` forms, HOST pointers in `rt_render_wavefront_env`.  `size`: a power of two.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct rt_environment {
+    pub texels: *const f64,
+    pub cdf: *const f64,
+    pub size: i32,
+    pub flags: u32,
+}
+
+const _: () = assert!(offset_of!(rt_environment, cdf) == 8);
+const _: () = assert!(offset_of!(rt_environment, size) == 16);
+const _: () = assert!(offset_of!(rt_environment, flags) == 20);
+const _: () = assert!(24 == size_of::<rt_environment>());
 const _: () = assert!(offset_of!(rt_path_queue, count) == 8);
 const _: () = assert!(offset_of!(rt_path_queue, scratch) == 64);
 const _: () = assert!(72 == size_of::<rt_path_queue>());
@@ -513,6 +533,19 @@ extern "C" {
     pub fn rt_render_wavefront_adaptive(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, a: *const rt_adaptive,
                                         light: *const rt_lighting, direct: i32, direct_flags: u32, out_fix: *mut u64, out_half: *mut u64,
                                         out_count: *mut u32, rays_traced: *mut u64, shadow_rays: *mut u64, kernel_ms: *mut f32) -> i32;
+    /// An environment cube map in the place of the sky: looked up on a miss, importance-sampled at Lambertian hits by the running sums
+    /// `rt_environment_cdf` (a pure host function) builds; the shadow ray is visible iff it meets no sphere.
+    pub fn rt_environment_cdf(texels: *const f64, size: i32, cdf_out: *mut f64) -> i32;
+    pub fn rt_paths_step_env_device(ctx: *mut rt_context, seed: u64, flags: u32, t_min: f64, input: *const rt_path_queue,
+                                    output: *const rt_path_queue, d_fix: *mut c_void, npix: i64, d_rays: *mut c_void,
+                                    light: *const rt_lighting, env: *const rt_environment, step_flags: u32, d_shadow_rays: *mut c_void,
+                                    stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_env_device(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                          env: *const rt_environment, d_fix: *mut c_void, d_rays: *mut c_void, d_shadow_rays: *mut c_void,
+                                          stream: *mut c_void) -> i32;
+    pub fn rt_render_wavefront_env(ctx: *mut rt_context, cam: *const rt_camera, p: *const rt_params, light: *const rt_lighting,
+                                   env: *const rt_environment, sample: i32, fix: *mut u64, rays_traced: *mut u64, shadow_rays: *mut u64,
+                                   kernel_ms: *mut f32) -> i32;
     pub fn rt_last_error() -> *const c_char;
     pub fn rt_backend_name() -> *const c_char;
     pub fn rt_abi_version() -> i32;

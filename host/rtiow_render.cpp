@@ -10,7 +10,8 @@
 //                [--denoise [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--denoise-variance [--feature-spp N] [--denoise-levels L] [--sigma-color X] [--sigma-normal X] [--sigma-depth X]]
 //                [--temporal [--alpha-min X] [--temporal-sigma-normal X] [--temporal-sigma-depth X] [--temporal-clamp X]]
-//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct | --direct-cone | --direct-weighted]]
+//                [--pick I,J] [--wavefront [--sky B_r,B_g,B_b:T_r,T_g,T_b] [--emit INDEX:r,g,b]... [--direct | --direct-cone | --direct-weighted]
+//                 [--env FILE [--env-sample]]]
 //   rtiow_render --reassembly-plan H T N     (no GPU: the strided copies that put N shards' rows back in image order)
 //   rtiow_render --test-png W H out.png      (no GPU: a fixed pattern through the PNG writer -- r = 7x + 13y, g = x ^ y, b = x y, mod 256, alpha 255)
 //
@@ -61,6 +62,9 @@
 // --direct-weighted: --direct-cone with the light chosen by what it can contribute at the hit point -- (r^2 / d^2) max(e) -- instead of
 // uniformly: what a frame lit by many small lights needs (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE).  The rules of
 // --direct; not together with either of the other two.
+// --env FILE: an environment cube map in the place of the sky (rt_render_wavefront_env): raw little-endian f64
+// [6][N][N][3], N -- a power of two -- from the byte count; --env-sample: Lambertian hits importance-sample it with a shadow ray.  Needs
+// --wavefront; --emit still lights; not together with --direct*.  (The single frame and the --temporal --denoise-variance sequence.)
 // --wavefront ... --adaptive THRESHOLD [--step N]: the adaptive loop over the device path queue's frame (rt_render_wavefront_adaptive, DESIGN.md
 // section 24), with --sky, --emit and --direct* as without it; the resolve and the summary line are --adaptive's.  Not with --denoise.
 // --denoise-variance: the variance-guided denoiser (rt_denoise_var) with --denoise's option switches; --sigma-color is then
@@ -137,6 +141,10 @@ int main(int argc, char **argv)
     bool direct_cone = false;                    // --direct-cone: ... sampled by solid angle instead of by area
     bool direct_weighted = false;                // --direct-weighted: ... and chosen by their contribution at the hit point
     bool direct = false;                         // --direct: ... with shadow rays towards the lights (next-event estimation)
+    std::string env_file;                        // --env FILE: an environment cube map (raw little-endian f64 [6][N][N][3]) in the place of the sky
+    bool env_sample = false;                     // --env-sample: ... importance-sampled at Lambertian hits
+    std::vector<double> env_texels;
+    rt_environment env{};
     rt_lighting light{};
     light.sky_bottom[0] = light.sky_bottom[1] = light.sky_bottom[2] = 1.0;
     light.sky_top[0] = 0.5; light.sky_top[1] = 0.7; light.sky_top[2] = 1.0;
@@ -227,6 +235,8 @@ int main(int argc, char **argv)
             emits.push_back(e);
             lit = true;
         }
+        else if (arg("--env")) env_file = argv[++i];
+        else if (!std::strcmp(argv[i], "--env-sample")) env_sample = true;
         else if (arg("--scene")) scene_file = argv[++i];
         else if (arg("--pick")) {
             if (std::sscanf(argv[++i], "%d,%d", &pick_i, &pick_j) != 2) { std::fprintf(stderr, "--pick I,J\n"); return 2; }
@@ -353,6 +363,31 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "--direct-cone samples the lights of the device path queue's frame: it needs --wavefront and at least one --emit\n");
             return 2;
         }
+        if (env_sample && env_file.empty()) {
+            std::fprintf(stderr, "--env-sample samples the map of --env FILE: it needs --env\n");
+            return 2;
+        }
+        if (!env_file.empty() && (!wavefront || direct || direct_cone || direct_weighted)) {
+            std::fprintf(stderr, "--env lights the frame of the device path queue: it needs --wavefront and does not combine with --direct, "
+                         "--direct-cone or --direct-weighted\n");
+            return 2;
+        }
+        if (!env_file.empty()) {                 // the size follows from the byte count: 6 * N * N * 3 doubles
+            FILE *f = std::fopen(env_file.c_str(), "rb");
+            if (!f) { std::perror(env_file.c_str()); return 1; }
+            double buf[4096];
+            size_t got;
+            while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) env_texels.insert(env_texels.end(), buf, buf + got);
+            std::fclose(f);
+            int32_t n = 1;
+            while ((size_t)18 * n * n < env_texels.size() && n < RT_ENV_MAX_SIZE) n *= 2;
+            if (env_texels.empty() || (size_t)18 * n * n != env_texels.size()) {
+                std::fprintf(stderr, "%s: %zu doubles are not 6 * N * N * 3 with N a power of two up to %d\n", env_file.c_str(), env_texels.size(),
+                             RT_ENV_MAX_SIZE);
+                return 1;
+            }
+            env.texels = env_texels.data(); env.cdf = nullptr; env.size = n; env.flags = 0u;
+        }
         if (!emits.empty()) {
             emission.assign(flat.size() * 3, 0.0);
             for (const Emit &e : emits) {
@@ -372,7 +407,11 @@ int main(int argc, char **argv)
     auto render_wavefront_frame = [&](rt_context *ctx, const rt_camera *cam, const rt_params *q, uint64_t *fix, uint64_t *rays, float *ms) -> int {
         int rc = RT_OK;
         uint64_t shadow = 0;
-        if (direct) {
+        if (!env_file.empty()) {
+            if ((rc = rt_render_wavefront_env(ctx, cam, q, &light, &env, env_sample ? 1 : 0, fix, rays, &shadow, ms)))
+                return die("rt_render_wavefront_env", rc);
+            if (env_sample) std::fprintf(stderr, "shadow rays: %llu\n", (unsigned long long)shadow);
+        } else if (direct) {
             if ((rc = rt_render_wavefront_nee(ctx, cam, q, &light, fix, rays, &shadow, ms))) return die("rt_render_wavefront_nee", rc);
         } else if (direct_cone || direct_weighted) {
             if ((rc = rt_render_wavefront_nee_sampled(ctx, cam, q, &light, direct_flags, fix, rays, &shadow, ms)))
@@ -515,6 +554,10 @@ int main(int argc, char **argv)
     }
     if (wavefront && (!devices.empty() || denoise || passes > 1 || two_calls || uniform53 || !features_file.empty())) {
         std::fprintf(stderr, "--wavefront runs on one device and goes with none of --devices, --denoise, --passes, --two-calls, --uniform53, --features\n");
+        return 2;
+    }
+    if (!env_file.empty() && adaptive) {
+        std::fprintf(stderr, "--env is not built for --adaptive: the adaptive loop's frames take no environment\n");
         return 2;
     }
     if (const int bad = check_lighting()) return bad;

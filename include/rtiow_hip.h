@@ -1106,6 +1106,83 @@ int rt_render_wavefront_adaptive(rt_context *ctx, const rt_camera *cam, const rt
                                  int32_t direct, uint32_t direct_flags, uint64_t *out_fix, uint64_t *out_half, uint32_t *out_count,
                                  uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms);
 
+/* ---- environment: a cube map the lit path queue looks up and importance-samples ---- */
+
+/* Image-based lighting for the path queue: a fourth light source beside the sky and the emissive spheres.  A cube map, because a
+ * latitude-longitude map needs atan2 and asin, for which the bit-exact contract has no statement: here the face is chosen by
+ * comparisons and the texel by one division per coordinate, and a direction uniform over a texel's square has the solid-angle density
+ * r^3 / A with r^2 = 1 + a^2 + b^2, so the lookup and the estimator are + - * / in binary64 with ONE stated constant for pi,
+ * PI = 0x400921FB54442D18, and no sqrt per path.  rt_render*, the megakernel, and the unlit, lit and NEE forms know nothing of it.
+ *
+ * Faces: f = 2 * axis + (negative ? 1 : 0), axis 0 = x, 1 = y, 2 = z; the in-face coordinates (a, b) are the other two components in
+ * axis order, divided by the magnitude of the face's own; texel (f, i, j) has the index k = (f * size + i) * size + j, i from a, j from b. */
+#define RT_ENV_MAX_SIZE 1024
+typedef struct {
+    const double *texels;    /* [6][size][size][3] radiance; DEVICE pointer in the _device forms, HOST pointer in the host form        */
+    const double *cdf;       /* [6*size*size] running sums from rt_environment_cdf, same residency; NULL: looked up, never sampled     */
+    int32_t size;            /* texels per face edge: a power of two, 1 .. RT_ENV_MAX_SIZE                                             */
+    uint32_t flags;          /* 0                                                                                                      */
+} rt_environment;            /* 24 bytes */
+
+/* LOOKUP env_lookup(d), for any d, not normalised:
+ *   ax = 0, m = |d.x|;  if (|d.y| > m) ax = 1, m = |d.y|;  if (|d.z| > m) ax = 2, m = |d.z|      (strict: x wins ties over y, y over z; a
+ *                                                                                                  NaN never wins)
+ *   f = 2 * ax + (d[ax] < 0.0 ? 1 : 0);  (a, b) = the other two components in axis order, each divided by m
+ *   x = ((a + 1.0) * 0.5) * (double)size;  i = x >= size ? size - 1 : (x >= 0.0 ? (int)x : 0);  j from b the same way   (a NaN gives 0)
+ *   k = (f * size + i) * size + j
+ * Every bit pattern of d -- zero, infinite and NaN directions included -- names a texel inside the table: no content sends a read
+ * outside it, as with the emission table.
+ *
+ * TABLE: a pure host function.  s = 2.0 / (double)size; for texel k = (f, i, j): ac = ((double)i + 0.5) * s - 1.0, bc likewise from j,
+ * r2 = (1.0 + ac * ac) + bc * bc; mx = the largest channel that compares > 0.0, else 0 (NaN and negative channels count as 0);
+ * W = mx / (r2 * sqrt(r2)); cdf_out[k] = (k ? cdf_out[k - 1] : 0.0) + W, in index order.  A texel whose weight vanishes against the
+ * running sum (below 2^-53 of it) repeats the entry before it and is never chosen.
+ * RT_ERR_INVALID_ARGUMENT: a NULL pointer, a size that is not a power of two in [1, RT_ENV_MAX_SIZE]. */
+int rt_environment_cdf(const double *texels, int32_t size, double *cdf_out);
+
+/* One environment bounce.  Everything rt_paths_step_lit_device promises holds, with these differences.
+ *  - a MISS adds quantize(throughput * texels[env_lookup(dir)]) per channel; the sky colours of `light` are validated and otherwise
+ *    unused.  A path that carries RT_PATH_EVENT_DIRECT adds nothing on a miss: the previous hit's shadow ray already counted the
+ *    environment.  The bit is read, masked off before any Philox use, and written, as in rt_paths_step_nee_device.
+ *  - a HIT on a light always adds, as in the lit step: sphere lights are not sampled in this mode, so no face is suppressed.
+ *  - a HIT on a Lambertian sphere that is not a light is SAMPLED when env->cdf != NULL, step_flags lacks RT_STEP_NO_DIRECT and
+ *    tot = cdf[n - 1], n = 6 * size * size, satisfies tot > 0.0 && tot < inf.  The scatter runs first and unchanged; the path continues
+ *    with event | RT_PATH_EVENT_DIRECT (decided before sampling: also when the sample yields nothing).  Then, with ev_in the masked
+ *    event on entry:
+ *      b = philox(pixel, sample, ev_in, 1)                                      (ONE block, no loop)
+ *      x = u01(b.x) * tot
+ *      lo = 0, hi = n - 1;  while (lo < hi) { mid = (lo + hi) >> 1;  if (cdf[mid] > x) hi = mid; else lo = mid + 1; }   k = lo
+ *                                                        (the first entry above x; NaNs send the search right; it never leaves the table)
+ *      P = (cdf[k] - (k ? cdf[k - 1] : 0.0)) / tot;  nothing follows unless P > 0.0
+ *      (f, i, j) from k;  s = 2.0 / (double)size;  a = ((double)i + u01(b.y)) * s - 1.0;  b' = ((double)j + u01(b.z)) * s - 1.0
+ *      dv: +-1.0 on the face's axis, (a, b') on the other two axes in axis order
+ *      ns = dot(n, dv) (n: the record's normal);  dd = dot(dv, dv);  nothing follows unless ns > 0.0
+ *      w = (ns * (s * s)) / ((PI * P) * (dd * dd));  c = ((throughput * albedo) * texels[k]) * w
+ *      the shadow ray (p, dv) with t_min and t_max = +inf: visible iff the closest-hit scan finds NO sphere;
+ *      if visible and pixel < npix, d_fix[pixel] gains quantize(c).
+ *    For power-of-two sizes every step of a and b' is exact, so env_lookup(dv) == k -- except on the cube's edge: offset word 0 in row 0
+ *    gives the coordinate -1.0, which ties with the face's own +-1.0, and the lookup's strict comparisons give a tie to the lower axis (one
+ *    word in 2^32 per coordinate; the sample takes texels[k] and looks nothing up, so the estimator does not see it).
+ *  - every other scatter clears the bit.
+ * With cdf == NULL or RT_STEP_NO_DIRECT nothing is sampled and no bit is set; with sampling on, every queue array and d_rays after a step
+ * equal the unsampled step's except bit 31 of `event`, and the sums.  d_shadow_rays (may be NULL) gains the shadow rays traced.
+ *
+ * The frame forms run rt_render_wavefront_lit*'s loop with this step, the LAST step of each batch with RT_STEP_NO_DIRECT; sample_begin
+ * and RTIOW_WAVEFRONT_BATCH are honoured; d_shadow_rays / shadow_rays (may be NULL) is zeroed first.  The host form stages the texels
+ * like every host buffer, ignores env->cdf, and with sample != 0 builds the table itself with rt_environment_cdf.
+ *
+ * RT_ERR_INVALID_ARGUMENT, found before anything is touched: first every context-free check of the lit form, in its order; then a NULL
+ * env; env->flags != 0; a size that is not a power of two in [1, RT_ENV_MAX_SIZE]; NULL texels; a step flag other than 0 or
+ * RT_STEP_NO_DIRECT; in the host form, which can see them, a texel that is NaN, infinite or negative; then the context checks and the
+ * emission table's length as in the lit form. */
+int rt_paths_step_env_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                             void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, const rt_environment *env, uint32_t step_flags,
+                             void *d_shadow_rays, void *stream);
+int rt_render_wavefront_env_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_environment *env,
+                                   void *d_fix, void *d_rays, void *d_shadow_rays, void *stream);
+int rt_render_wavefront_env(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_environment *env,
+                            int32_t sample, uint64_t *fix, uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char *rt_last_error(void);
 const char *rt_backend_name(void);     /* "hip-gfx950" */

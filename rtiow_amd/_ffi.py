@@ -88,6 +88,10 @@ class rt_direct(C.Structure):
     _fields_ = [("lights", C.c_void_p), ("n_lights", C.c_int32), ("flags", C.c_uint32)]
 
 
+class rt_environment(C.Structure):
+    _fields_ = [("texels", C.c_void_p), ("cdf", C.c_void_p), ("size", C.c_int32), ("flags", C.c_uint32)]
+
+
 RT_FLAG_ACCUMULATE = 0x1
 RT_FLAG_NO_FILTER = 0x2
 RT_FLAG_DIAG_STATS = 0x4
@@ -105,6 +109,7 @@ RT_PATH_EVENT_DIRECT = 0x80000000
 RT_STEP_NO_DIRECT = 0x1
 RT_DIRECT_CONE = 0x2
 RT_DIRECT_WEIGHTED = 0x8
+RT_ENV_MAX_SIZE = 1024
 RT_SCATTER_ABSORBED, RT_SCATTER_SCATTERED, RT_SCATTER_MISS, RT_SCATTER_BAD_INDEX = 0, 1, 2, 3
 
 # every symbol include/rtiow_hip.h declares: (name, restype, argtypes)
@@ -205,6 +210,14 @@ SYMBOLS = [
     ("rt_render_wavefront_adaptive", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_adaptive), C.POINTER(rt_lighting),
                                                C.c_int32, C.c_uint32, _VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_float)]),
+    # the environment cube map: the pure host table, the step, the two frames (the host form: sample behind env)
+    ("rt_environment_cdf", C.c_int, [_VP, C.c_int32, _VP]),
+    ("rt_paths_step_env_device", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(rt_path_queue), C.POINTER(rt_path_queue), _VP,
+                                           C.c_int64, _VP, C.POINTER(rt_lighting), C.POINTER(rt_environment), C.c_uint32, _VP, _VP]),
+    ("rt_render_wavefront_env_device", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), C.POINTER(rt_environment),
+                                                 _VP, _VP, _VP, _VP]),
+    ("rt_render_wavefront_env", C.c_int, [_VP, C.POINTER(rt_camera), C.POINTER(rt_params), C.POINTER(rt_lighting), C.POINTER(rt_environment),
+                                          C.c_int32, _VP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     ("rt_last_error", C.c_char_p, []),
     ("rt_backend_name", C.c_char_p, []),
     ("rt_abi_version", C.c_int32, []),

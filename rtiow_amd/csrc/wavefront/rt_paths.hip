@@ -1,7 +1,7 @@
 // rt_paths.hip -- the device path queue: a fused bounce step on device-resident paths and the frame rendered from it (rtiow_hip.h, "path
 // queue").
 //
-// The eleventh translation unit of librtiow_hip.so.  Ten kernels of its own:
+// The eleventh translation unit of librtiow_hip.so.  Eleven kernels of its own:
 //   path_begin_kernel     one lane per path, grid-stride: item -> (pixel, sample), the camera ray (sample_ray), throughput 1; *count = n.
 //   path_begin_pixels_kernel  the same body (path_begin<LISTED>, stated once) over a list of pixels: item -> (list index, sample), the pixel
 //                         read from the list (rtiow_hip.h, "wavefront frames over pixel lists").
@@ -19,6 +19,9 @@
 //                         angle").
 //   bounce_weighted_kernel  the cone trip with the light chosen by its contribution at the hit point instead of uniformly (rtiow_hip.h,
 //                         "direct lighting with a weighted choice").
+//   bounce_env_kernel     the NEE trip with an environment cube map in the place of the sky and of the light list: a miss looks it up, a
+//                         Lambertian hit samples it by its running sums and traces a shadow ray that must meet nothing (rtiow_hip.h,
+//                         "environment").
 //   queue_scan_kernel     ONE workgroup: the exclusive scan of the waves' counts, in place; *out->count; d_rays.
 //   queue_compact_kernel  one wave per 64 slots: the survivors move to `out` at offset + rank, so their order is kept.
 // The live count is a word of device memory every kernel reads for itself; the host sizes the grids from the capacity and never waits.
@@ -34,6 +37,7 @@
 
 #include "rt_host.hpp"
 #include "rt_adaptive_check.hpp"
+#include "rt_env_core.hpp"
 #include "rt_first_hit.hpp"
 #include "rt_shade_core.hpp"
 
@@ -141,6 +145,14 @@ struct NeeArgs {
     uint32_t no_direct;
 };
 
+// What an environment step knows beyond L and N (rtiow_hip.h, "environment"): the cube map's texels, [6][size][size][3]
+// device doubles, and its sampling table, [6 size^2] running sums or NULL (looked up, never sampled).  Of N it reads no_direct and
+// shadow_rays; there is no light list.
+struct EnvArgs {
+    const double *texels, *cdf;
+    int32_t size;
+};
+
 // the three 64-bit adds of a path that ends with radiance v (contract C5); g_pix: inside the frame
 __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, const D3 &v)
 {
@@ -155,12 +167,16 @@ __device__ __forceinline__ void add_sample(const KParams &P, uint32_t g_pix, con
 // the wave traces the shadow rays together: only the contribution, the pixel and the light's index are live across that scan.
 // MODE == kNeeCone: the same trip with the light sampled by solid angle (nee_sample_cone).
 // MODE == kNeeWeighted: ... and chosen by its contribution at the hit point (nee_sample_weighted).
+// MODE == kEnv: the NEE trip's shape with the environment E in the place of the sky and of the light list: a miss
+// looks the map up unless the path carries the bit; a light always adds; a Lambertian hit samples the map (env_sample) when env_tot, the
+// table's last entry as the wave read it, says there is something to sample; the shadow ray is visible iff it meets no sphere.
 // The modes are rt_shade_core.hpp's, and so is the choice of the sampler among them (nee_sample_for<MODE>).
 template <int MODE>
 __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays &Q, const unsigned long long npix, const LitArgs &L, const NeeArgs &N,
-                                            uint4 *stage, const int lane, const long long wv, const long long n)
+                                            uint4 *stage, const int lane, const long long wv, const long long n, const EnvArgs &E = {},
+                                            const double env_tot = 0.0)
 {
-    constexpr bool LIT = MODE >= kLit, NEE = MODE >= kNee;
+    constexpr bool LIT = MODE >= kLit, NEE = MODE >= kNee, ENV = MODE == kEnv;
     const long long k = wv * 64 + lane;
     // lanes past the live count stay in the wave: rows that keep nothing, nothing written
     const bool valid = k < n;
@@ -183,7 +199,10 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
         if (fh.hit < 0) {
             // contract C5, as rt_accumulate with sky_dir: the path ends in the sky
             if ((unsigned long long)g_pix < npix) {
-                if constexpr (LIT) add_sample(P, g_pix, sky_blend(thr, d, ld3(L.sky_bottom), ld3(L.sky_top)));
+                if constexpr (ENV) {
+                    // (a path that carries the bit: the previous hit's shadow ray already counted the environment)
+                    if (!was_direct) add_sample(P, g_pix, thr * ld3(E.texels + 3 * (size_t)env_lookup(d, E.size)));
+                } else if constexpr (LIT) add_sample(P, g_pix, sky_blend(thr, d, ld3(L.sky_bottom), ld3(L.sky_top)));
                 else add_sample(P, g_pix, sky_sample(thr, d));
             }
         } else {
@@ -195,7 +214,8 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
                     light = e.x > 0.0 || e.y > 0.0 || e.z > 0.0;    // a NaN or a non-positive channel compares false
                     bool adds = light && (unsigned long long)g_pix < npix;
                     // (NEE: the previous hit's shadow ray already counted a light's front face)
-                    if constexpr (NEE) adds = adds && !(was_direct && light_front(P, o, d, fh.hit, fh.closest));
+                    // (ENV: sphere lights are not sampled, so a light always adds)
+                    if constexpr (NEE && !ENV) adds = adds && !(was_direct && light_front(P, o, d, fh.hit, fh.closest));
                     // both faces emit; no draw; the path ends; a pixel outside the frame adds nothing
                     if (adds) add_sample(P, g_pix, thr * e);
                 }
@@ -207,13 +227,19 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
                 alive = !scatter_path(rec.mrec, d, rec.normal, rec.front, g_pix, g_s, ev, P.k0, P.k1, ndir, albedo);
                 if (alive) {
                     bool direct = false;
-                    if constexpr (NEE) direct = N.n_lights > 0 && !N.no_direct && (int)rec.mrec[5] == RT_KIND_LAMBERTIAN;
+                    if constexpr (ENV) direct = env_tot > 0.0 && (int)rec.mrec[5] == RT_KIND_LAMBERTIAN;
+                    else if constexpr (NEE) direct = N.n_lights > 0 && !N.no_direct && (int)rec.mrec[5] == RT_KIND_LAMBERTIAN;
                     if (direct) ev |= RT_PATH_EVENT_DIRECT;
                     store3(Q.origin, k, rec.p);
                     store3(Q.dir, k, ndir);
                     store3(Q.thr, k, thr * albedo);
                     Q.event[k] = ev;
-                    if constexpr (NEE) {
+                    if constexpr (ENV) {
+                        if (direct) {
+                            shadow = env_sample(P, E.texels, E.cdf, E.size, env_tot, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc);
+                            so = rec.p;
+                        }
+                    } else if constexpr (NEE) {
                         if (direct) {
                             shadow = nee_sample_for<MODE>(P, L.emission, L.n_emission, N.lights, N.n_lights, rec.p, rec.normal, thr * albedo, g_pix, g_s, ev_in, sd, sc, li);
                             so = rec.p;
@@ -236,13 +262,13 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
         FirstHit sh = {__builtin_inf(), -1};
         ScanCounts scnt = {true};
         first_hit_wave<false>(P, stage, lane, so, sd, shadow, sh, scnt);
-        // visible iff the CLOSEST hit is the sampled light itself: no epsilon
-        if (shadow && sh.hit == li && (unsigned long long)g_pix < npix) add_sample(P, g_pix, sc);
+        // visible iff the CLOSEST hit is the sampled light itself: no epsilon (ENV: iff the scan finds no sphere)
+        if (shadow && sh.hit == (ENV ? -1 : li) && (unsigned long long)g_pix < npix) add_sample(P, g_pix, sc);
     }
 }
 
 // the waves' grid-stride loop over the live slots, one trip per 64 of them: the same text in the three kernels, with the LDS stage a kernel's own
-#define RT_BOUNCE_LOOP(MODE, L, N) \
+#define RT_BOUNCE_LOOP(MODE, L, N, ...) \
     __shared__ uint4 s_stage[kPathWaves][64 * 4]; \
     const int lane = (int)threadIdx.x & 63; \
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); \
@@ -250,7 +276,7 @@ __device__ __forceinline__ void bounce_trip(const KParams &P, const QueueArrays 
     const long long n = (long long)live_count(Q); \
     const long long n_trips = (n + 63) >> 6; \
     const long long n_waves = (long long)gridDim.x * kPathWaves; \
-    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) bounce_trip<MODE>(P, Q, npix, L, N, stage, lane, wv, n)
+    for (long long wv = (long long)blockIdx.x * kPathWaves + wave; wv < n_trips; wv += n_waves) bounce_trip<MODE>(P, Q, npix, L, N, stage, lane, wv, n, ##__VA_ARGS__)
 
 // One bounce of the live paths.  P: the scene's tables, t_min, the key (k0, k1) and the sums (fix); npix: entries of P.fix.
 __global__ __launch_bounds__(kPathBlock) void bounce_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix)
@@ -289,6 +315,19 @@ __global__ __launch_bounds__(kPathBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void bounce_weighted_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L, const NeeArgs N)
 {
     RT_BOUNCE_LOOP(kNeeWeighted, L, N);
+}
+
+// ... with an environment cube map in the place of the sky, looked up on a miss and importance-sampled at Lambertian hits
+// (rt_paths_step_env_device): bounce_nee_kernel's shape.  The table's last entry is read once per wave; a table
+// that is absent, switched off by RT_STEP_NO_DIRECT, or whose total is not positive and finite samples nothing and sets no bit.
+// (Defined here, not last, for bounce_cone_kernel's reason.)
+__global__ __launch_bounds__(kPathBlock) __attribute__((amdgpu_waves_per_eu(4)))
+void bounce_env_kernel(const KParams P, const QueueArrays Q, const unsigned long long npix, const LitArgs L, const NeeArgs N, const EnvArgs E)
+{
+    double tot = 0.0;
+    if (E.cdf && !N.no_direct) tot = E.cdf[6 * E.size * E.size - 1];
+    if (!(tot > 0.0 && tot < __builtin_inf())) tot = 0.0;
+    RT_BOUNCE_LOOP(kEnv, L, N, E, tot);
 }
 #undef RT_BOUNCE_LOOP
 
@@ -445,6 +484,34 @@ int check_direct_count(const rt_context *ctx, const char *what, const NeeCall *n
     return RT_OK;
 }
 
+// What an environment call has beyond a lit one; a NULL EnvCall: the call is none.  env->texels and env->cdf: device pointers.
+struct EnvCall {
+    const rt_environment *env;
+    uint32_t step_flags;
+    void *d_shadow_rays;
+};
+
+static_assert(RT_ENV_MAX_SIZE == rt_env::kMaxSize, "the pure header's limit is the ABI's");
+
+// the context-free part of the environment checks, after the lighting's; host_texels: the texels are a host pointer the call may read
+int check_env(const char *what, const EnvCall *call, bool host_texels)
+{
+    const rt_environment *env = call->env;
+    RT_NEED(env, what, "env");
+    if (env->flags) return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown env->flags 0x%x (only 0 is legal)", what, env->flags);
+    if (!rt_env::valid_size(env->size))
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: env->size must be a power of two in [1, %d] (is %d)", what, RT_ENV_MAX_SIZE, env->size);
+    if (!env->texels) return fail(RT_ERR_INVALID_ARGUMENT, "%s: env->texels is NULL", what);
+    if (call->step_flags & ~RT_STEP_NO_DIRECT)
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: unknown step_flags 0x%x (only 0 and RT_STEP_NO_DIRECT are legal)", what, call->step_flags);
+    if (host_texels)
+        for (size_t k = 0; k < 3 * rt_env::texel_count(env->size); ++k)
+            if (!(env->texels[k] >= 0.0) || !std::isfinite(env->texels[k]))
+                return fail(RT_ERR_INVALID_ARGUMENT, "%s: env->texels[%lld][%d] must be finite and >= 0 (is %g)", what, (long long)(k / 3), (int)(k % 3),
+                            env->texels[k]);
+    return RT_OK;
+}
+
 // A list of global pixel numbers as an entry point was handed it.  identity_ok: a NULL list stands for 0, 1, ...,
 // width * height - 1 and n_pixels must be that many (the frame forms); else a NULL list must be empty (the begin).  host: the call may
 // read the entries.
@@ -497,9 +564,10 @@ int check_begin(const rt_context *ctx, const char *what, const rt_camera *cam, i
     return check_context(ctx, what, true, false);
 }
 
-// light: NULL for the unlit step (lit: whether the call is a lit one); nee: NULL unless it is an NEE one
+// light: NULL for the unlit step (lit: whether the call is a lit one); nee: NULL unless it is an NEE one; env: NULL unless it is an
+// environment one
 int check_step(const rt_context *ctx, const char *what, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out, const void *d_fix,
-               int64_t npix, bool lit, const rt_lighting *light, const NeeCall *nee = nullptr)
+               int64_t npix, bool lit, const rt_lighting *light, const NeeCall *nee = nullptr, const EnvCall *env = nullptr)
 {
     if (int rc = check_queue(what, "in", in)) return rc;
     if (int rc = check_queue(what, "out", out)) return rc;
@@ -519,6 +587,8 @@ int check_step(const rt_context *ctx, const char *what, uint32_t flags, double t
         if (int rc = check_light(what, light, false)) return rc;
     if (nee)
         if (int rc = check_direct(what, nee)) return rc;
+    if (env)
+        if (int rc = check_env(what, env, false)) return rc;
     if (int rc = check_context(ctx, what, true, true)) return rc;
     if (lit)
         if (int rc = check_light_count(ctx, what, light)) return rc;
@@ -549,9 +619,9 @@ int launch_begin(const rt_camera *cam, int32_t width, int32_t height, uint64_t s
 }
 
 // light: NULL launches bounce_kernel, else bounce_lit_kernel with the struct's values (light->emission: a device pointer), or with nee
-// bounce_nee_kernel
+// bounce_nee_kernel (or its cone or weighted sibling), or with env bounce_env_kernel
 int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_path_queue *in, const rt_path_queue *out, void *d_fix, int64_t npix,
-                void *d_rays, const rt_lighting *light, const NeeCall *nee, hipStream_t stream)
+                void *d_rays, const rt_lighting *light, const NeeCall *nee, hipStream_t stream, const EnvCall *env = nullptr)
 {
     rt::KParams kp;
     memset(&kp, 0, sizeof(kp));
@@ -571,7 +641,15 @@ int launch_step(const rt_context *ctx, uint64_t seed, double t_min, const rt_pat
         memcpy(la.sky_bottom, light->sky_bottom, sizeof(la.sky_bottom));
         memcpy(la.sky_top, light->sky_top, sizeof(la.sky_top));
         la.emission = light->emission; la.n_emission = light->emission ? light->n_emission : 0;
-        if (nee) {
+        if (env) {
+            rt::NeeArgs na;
+            memset(&na, 0, sizeof(na));
+            na.shadow_rays = (unsigned long long *)env->d_shadow_rays; na.no_direct = env->step_flags & RT_STEP_NO_DIRECT;
+            rt::EnvArgs ea;
+            memset(&ea, 0, sizeof(ea));
+            ea.texels = env->env->texels; ea.cdf = env->env->cdf; ea.size = env->env->size;
+            hipLaunchKernelGGL(rt::bounce_env_kernel, grid, block, 0, stream, kp, qi, (unsigned long long)npix, la, na, ea);
+        } else if (nee) {
             rt::NeeArgs na;
             memset(&na, 0, sizeof(na));
             na.lights = nee->direct->lights; na.n_lights = nee->direct->lights ? nee->direct->n_lights : 0;
@@ -637,10 +715,11 @@ int check_frame_params(const char *what, const rt_params *p, bool accumulate_ok)
 }
 
 // lit / light / host_table / nee as in check_step and check_light; list: the list forms' (RT_FLAG_ACCUMULATE passes), NULL for the others;
-// extra: a check of the caller's own between the context-free ones and the context's (rt_render_wavefront_adaptive), or NULL
+// extra: a check of the caller's own between the context-free ones and the context's (rt_render_wavefront_adaptive), or NULL;
+// env / host_texels: as in check_step and check_env
 int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, const rt_params *p, const void *fix, bool lit = false,
                  const rt_lighting *light = nullptr, bool host_table = false, const NeeCall *nee = nullptr, const PixelList *list = nullptr,
-                 int (*extra)(const char *, const rt_params *, bool) = nullptr)
+                 int (*extra)(const char *, const rt_params *, bool) = nullptr, const EnvCall *env = nullptr, bool host_texels = false)
 {
     RT_NEED(cam, what, "cam");
     RT_NEED(p, what, "params");
@@ -651,6 +730,8 @@ int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, 
         if (int rc = check_light(what, light, host_table)) return rc;
     if (nee)
         if (int rc = check_direct(what, nee)) return rc;
+    if (env)
+        if (int rc = check_env(what, env, host_texels)) return rc;
     if (list)
         if (int rc = check_list(what, *list, (long long)p->width * p->height)) return rc;
     if (extra)
@@ -666,14 +747,16 @@ int check_render(const rt_context *ctx, const char *what, const rt_camera *cam, 
 // nee: the frame's direct lighting (step_flags 0); the LAST step of a batch runs with RT_STEP_NO_DIRECT.
 // d_pixels / n_pixels: the pixels whose samples are rendered -- NULL: all width * height of them, in order --;
 // d_fix is frame-addressed either way.  p->flags & RT_FLAG_ACCUMULATE: nothing is zeroed, the sums and both counters are added to.
+// env: the frame's environment (step_flags 0) in the place of nee, with the same rule for the last step.
 int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const NeeCall *nee, const uint32_t *d_pixels,
-                 long long n_pixels, void *d_fix, void *d_rays, hipStream_t stream)
+                 long long n_pixels, void *d_fix, void *d_rays, hipStream_t stream, const EnvCall *env = nullptr)
 {
     const long long npix = (long long)p->width * p->height, total = n_pixels * p->spp;
     if (!(p->flags & RT_FLAG_ACCUMULATE)) {
         RT_HIP(hipMemsetAsync(d_fix, 0, (size_t)npix * 3 * sizeof(uint64_t), stream));
         if (d_rays) RT_HIP(hipMemsetAsync(d_rays, 0, sizeof(uint64_t), stream));
         if (nee && nee->d_shadow_rays) RT_HIP(hipMemsetAsync(nee->d_shadow_rays, 0, sizeof(uint64_t), stream));
+        if (env && env->d_shadow_rays) RT_HIP(hipMemsetAsync(env->d_shadow_rays, 0, sizeof(uint64_t), stream));
     }
     if (total == 0) return RT_OK;
     const long long batch = batch_items() < total ? batch_items() : total;
@@ -682,12 +765,15 @@ int render_frame(rt_context *ctx, const rt_camera *cam, const rt_params *p, cons
     const rt_path_queue q[2] = {own.queue(ctx->paths.ptr, 0, batch), own.queue(ctx->paths.ptr, 1, batch)};
     NeeCall last = {};
     if (nee) { last = *nee; last.step_flags = RT_STEP_NO_DIRECT; }
+    EnvCall last_env = {};
+    if (env) { last_env = *env; last_env.step_flags = RT_STEP_NO_DIRECT; }
     for (long long first = 0; first < total; first += batch) {
         const long long n = total - first < batch ? total - first : batch;
         if (int rc = launch_begin(cam, p->width, p->height, p->seed, p->spp, p->sample_begin, first, n, &q[0], stream, d_pixels)) return rc;
         for (int depth = 0; depth < p->max_depth; ++depth) {
             const NeeCall *step_nee = nee && depth + 1 == p->max_depth ? &last : nee;
-            if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, light, step_nee, stream)) return rc;
+            const EnvCall *step_env = env && depth + 1 == p->max_depth ? &last_env : env;
+            if (int rc = launch_step(ctx, p->seed, p->t_min, &q[depth & 1], &q[(depth + 1) & 1], d_fix, npix, d_rays, light, step_nee, stream, step_env)) return rc;
         }
     }
     return RT_OK;
@@ -829,6 +915,68 @@ int rt_paths_step_nee_device(rt_context *ctx, uint64_t seed, uint32_t flags, dou
     if (int rc = check_step(ctx, "rt_paths_step_nee", flags, t_min, in, out, d_fix, npix, true, light, &nee)) return rc;
     RT_HIP(hipSetDevice(ctx->device));
     return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, light, &nee, (hipStream_t)stream_v);
+}
+
+int rt_environment_cdf(const double *texels, int32_t size, double *cdf_out)
+{
+    const char *what = "rt_environment_cdf";
+    RT_NEED(texels, what, "texels");
+    RT_NEED(cdf_out, what, "cdf_out");
+    if (!rt_env::valid_size(size))
+        return fail(RT_ERR_INVALID_ARGUMENT, "%s: size must be a power of two in [1, %d] (is %d)", what, RT_ENV_MAX_SIZE, size);
+    rt_env::cdf(texels, size, cdf_out);
+    return RT_OK;
+}
+
+int rt_paths_step_env_device(rt_context *ctx, uint64_t seed, uint32_t flags, double t_min, const rt_path_queue *in, const rt_path_queue *out,
+                             void *d_fix, int64_t npix, void *d_rays, const rt_lighting *light, const rt_environment *env, uint32_t step_flags,
+                             void *d_shadow_rays, void *stream_v)
+{
+    const EnvCall call = {env, step_flags, d_shadow_rays};
+    if (int rc = check_step(ctx, "rt_paths_step_env", flags, t_min, in, out, d_fix, npix, true, light, nullptr, &call)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return launch_step(ctx, seed, t_min, in, out, d_fix, npix, d_rays, light, nullptr, (hipStream_t)stream_v, &call);
+}
+
+int rt_render_wavefront_env_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_environment *env,
+                                   void *d_fix, void *d_rays, void *d_shadow_rays, void *stream_v)
+{
+    const EnvCall call = {env, 0u, d_shadow_rays};
+    if (int rc = check_render(ctx, "rt_render_wavefront_env", cam, p, d_fix, true, light, false, nullptr, nullptr, nullptr, &call, false)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    return render_frame(ctx, cam, p, light, nullptr, nullptr, (long long)p->width * p->height, d_fix, d_rays, (hipStream_t)stream_v, &call);
+}
+
+// The host form: the emission table and the texels staged like every host buffer; sample != 0: the table built here with rt_env::cdf.
+// The counters are counted whether or not the caller asks.
+int rt_render_wavefront_env(rt_context *ctx, const rt_camera *cam, const rt_params *p, const rt_lighting *light, const rt_environment *env,
+                            int32_t sample, uint64_t *fix, uint64_t *rays_traced, uint64_t *shadow_rays, float *kernel_ms)
+{
+    const char *what = "rt_render_wavefront_env";
+    const EnvCall given = {env, 0u, nullptr};
+    if (int rc = check_render(ctx, what, cam, p, fix, true, light, true, nullptr, nullptr, nullptr, &given, true)) return rc;
+    RT_HIP(hipSetDevice(ctx->device));
+    HostLighting lighting(light, true, false, 0u);
+    const size_t n_texels = rt_env::texel_count(env->size);
+    std::vector<double> table(sample ? n_texels : 0);
+    if (sample) rt_env::cdf(env->texels, env->size, table.data());
+    Stage st(ctx);
+    const auto sums = st.out(fix, (size_t)p->width * p->height * 3);
+    const auto rays = rays_traced ? st.out(rays_traced, 1) : st.scratch<uint64_t>(1);
+    const auto shadow = shadow_rays ? st.out(shadow_rays, 1) : st.scratch<uint64_t>(1);
+    if (int rc = lighting.declare(st)) return rc;
+    const auto texels = st.in(env->texels, n_texels * 3);
+    const auto cdf = st.in(static_cast<const double *>(sample ? table.data() : nullptr), table.size());
+    if (int rc = st.commit()) return rc;
+    RT_HIP(st.upload());
+    lighting.resolve(st, nullptr);
+    rt_environment dev = *env;
+    dev.texels = st.ptr(texels); dev.cdf = st.ptr(cdf);
+    const EnvCall call = {&dev, 0u, st.ptr(shadow)};
+    return timed_section(ctx, what, kernel_ms, st, [&] {
+        return render_frame(ctx, cam, p, lighting.frame_light(), nullptr, nullptr, (long long)p->width * p->height, st.ptr(sums), st.ptr(rays),
+                            ctx->own_stream, &call);
+    });
 }
 
 int rt_render_wavefront_device(rt_context *ctx, const rt_camera *cam, const rt_params *p, void *d_fix, void *d_rays, void *stream_v)

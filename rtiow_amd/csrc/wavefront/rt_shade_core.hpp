@@ -308,4 +308,68 @@ __device__ __forceinline__ bool nee_sample_for(const KParams &P, const double *e
 
 #undef RT_NAMES_NO_LIGHT
 
+// ---- the environment: a cube map the path queue looks up on a miss and samples at a Lambertian hit (rtiow_hip.h, "environment"; DESIGN.md
+// section 27).  Stated HERE and nowhere else.  Everything is + - * / in binary64, no contraction, and one constant for pi: no sqrt, no
+// atan2.  size: texels per face edge, a power of two (the host has checked it); texels: [6][size][size][3]; cdf: [6 size^2] running sums.
+constexpr int kEnv = 5;                                                                  // bounce_trip's MODE of the environment step
+
+// one in-face coordinate c in [-1, 1] -> its texel row: a NaN fails both comparisons and gives 0
+__device__ __forceinline__ int env_row(double c, int size)
+{
+    const double x = ((c + 1.0) * 0.5) * (double)size;
+    return x >= (double)size ? size - 1 : (x >= 0.0 ? (int)x : 0);
+}
+
+// The texel a direction names, d not normalised: the face by strict comparisons (x wins ties over y, y over z; a NaN never wins), the
+// texel by one division per coordinate.  Every bit pattern of d names a texel inside the table.
+__device__ __forceinline__ int env_lookup(const D3 &d, int size)
+{
+    int ax = 0;
+    double m = __builtin_fabs(d.x);
+    if (__builtin_fabs(d.y) > m) { ax = 1; m = __builtin_fabs(d.y); }
+    if (__builtin_fabs(d.z) > m) { ax = 2; m = __builtin_fabs(d.z); }
+    const double on = ax == 0 ? d.x : ax == 1 ? d.y : d.z;
+    const int f = 2 * ax + (on < 0.0 ? 1 : 0);
+    const double a = (ax == 0 ? d.y : d.x) / m;                                          // the other two components, in axis order
+    const double b = (ax == 2 ? d.y : d.z) / m;
+    return (f * size + env_row(a, size)) * size + env_row(b, size);
+}
+
+// The environment sample of the path (g_pix, g_s) whose event on entry -- DIRECT bit masked off -- was ev_in, at the hit point with the
+// record's normal n; weight: throughput * albedo; tot = cdf[6 size^2 - 1], > 0 and finite (the caller has decided that).  ONE block,
+// (g_pix, g_s, ev_in, 1): x chooses the texel by a binary search of the running sums -- the first entry above u01(x) tot; NaNs send it
+// right, it never leaves the table --, (y, z) a point of the texel's square.  A direction uniform over that square has the solid-angle
+// density r^3 / s^2, so with the Lambertian BRDF albedo / pi the weight is ns s^2 / (pi P dd^2), dd = r^2 = dot(dv, dv): no sqrt.
+// Returns whether there is a shadow ray to trace -- dv from the hit point, not normalised -- and then c, the radiance to add if that ray
+// meets no sphere.
+__device__ __forceinline__ bool env_sample(const KParams &P, const double *texels, const double *cdf, int size, double tot, const D3 &n,
+                                           const D3 &weight, uint32_t g_pix, uint32_t g_s, uint32_t ev_in, D3 &dv, D3 &c)
+{
+    const U4 b = philox4x32_10(g_pix, g_s, ev_in, 1u, P.k0, P.k1);
+    const double x = u01(b.x) * tot;
+    int lo = 0, hi = 6 * size * size - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid] > x) hi = mid; else lo = mid + 1;
+    }
+    const int k = lo;
+    const double pk = (cdf[k] - (k ? cdf[k - 1] : 0.0)) / tot;
+    if (!(pk > 0.0)) return false;                                                       // a texel of no weight, or a NaN
+    const int sh = __builtin_ctz((unsigned)size);
+    const int f = k >> (2 * sh), i = (k >> sh) & (size - 1), j = k & (size - 1);
+    const double s = 2.0 / (double)size;
+    const double ta = ((double)i + u01(b.y)) * s - 1.0;
+    const double tb = ((double)j + u01(b.z)) * s - 1.0;
+    const double on = (f & 1) ? -1.0 : 1.0;
+    const int ax = f >> 1;
+    dv = ax == 0 ? mk(on, ta, tb) : ax == 1 ? mk(ta, on, tb) : mk(ta, tb, on);
+    const double ns = dot(n, dv);
+    const double dd = dot(dv, dv);
+    if (!(ns > 0.0)) return false;                                                       // below the hit's horizon; a NaN fails this
+    const double pi = __longlong_as_double(0x400921FB54442D18ll);
+    const double w = (ns * (s * s)) / ((pi * pk) * (dd * dd));
+    c = (weight * ld3(texels + 3 * (size_t)k)) * w;
+    return true;
+}
+
 } // namespace rt

@@ -553,6 +553,101 @@ class Lighting:
         return _ffi.rt_lighting((C.c_double * 3)(*self.sky_bottom), (C.c_double * 3)(*self.sky_top), emission_ptr or None, int(n_emission), 0)
 
 
+class Environment:
+    """An environment cube map for the lit path queue (rt_environment): the background the camera sees and the light
+    the scene is lit by.  texels: radiance [6, N, N, 3], N a power of two up to RT_ENV_MAX_SIZE -- a numpy array, or for the device forms a
+    float64 torch tensor on the renderer's device.  Face f = 2 * axis + (negative ? 1 : 0); texel (f, i, j) covers the in-face
+    coordinates a in [2 i / N - 1, 2 (i + 1) / N - 1) and b likewise from j, (a, b) being the other two axes in axis order.
+    sample=True: Lambertian hits importance-sample the map by the running sums of rt_environment_cdf and trace a shadow ray towards
+    it; sample=False: the map is only looked up by the paths that miss.  sums: running sums [6 * N * N] the device forms are to search
+    in the place of rt_environment_cdf's (a numpy array; the host form always builds its own)."""
+
+    def __init__(self, texels, sample=True, sums=None):
+        self.texels, self.sample, self.given_sums = texels, bool(sample), sums
+        shape = tuple(texels.shape)
+        if len(shape) != 4 or shape[0] != 6 or shape[1] != shape[2] or shape[3] != 3:
+            raise ValueError(f"texels must be [6, N, N, 3] (is {shape})")
+        self.size = int(shape[1])
+        if self.size < 1 or self.size > _ffi.RT_ENV_MAX_SIZE or self.size & (self.size - 1):
+            raise ValueError(f"the face edge must be a power of two in [1, {_ffi.RT_ENV_MAX_SIZE}] (is {self.size})")
+        self._device = None
+
+    def _is_tensor(self):
+        return hasattr(self.texels, "data_ptr")
+
+    def table(self):
+        """The texels as a contiguous float64 array [6, N, N, 3] on the host."""
+        t = self.texels.detach().cpu().numpy() if self._is_tensor() else self.texels
+        return np.ascontiguousarray(t, dtype=np.float64)
+
+    def cdf(self):
+        """rt_environment_cdf of the texels: the running sums [6 * N * N] that sampling searches, float64."""
+        t = self.table()
+        out = np.zeros(6 * self.size * self.size, dtype=np.float64)
+        _ffi.check(_ffi.load().rt_environment_cdf(t.ctypes.data, self.size, out.ctypes.data), "rt_environment_cdf")
+        return out
+
+    def save(self, path):
+        """The texels as raw little-endian float64; the size follows from the byte count."""
+        with open(path, "wb") as f:
+            f.write(self.table().astype("<f8").tobytes())
+
+    @classmethod
+    def load(cls, path, sample=True):
+        raw = np.fromfile(path, dtype="<f8")
+        n = int(round((raw.size / 18) ** 0.5)) if raw.size else 0
+        if n < 1 or 18 * n * n != raw.size:
+            raise ValueError(f"{path}: {raw.size * 8} bytes are not 6 * N * N * 3 float64")
+        return cls(raw.astype(np.float64).reshape(6, n, n, 3), sample=sample)
+
+    @classmethod
+    def sun_sky(cls, size, sun_dir=(0.3, 0.8, 0.5), sun_radiance=(400.0, 360.0, 300.0), cos_radius=0.995, bottom=(1.0, 1.0, 1.0),
+                top=(0.5, 0.7, 1.0), sample=True):
+        """A procedural map: at each texel's centre direction u the sky bottom * (1 - t) + top * t with t = (u.y + 1) / 2, and where
+        dot(u, unit(sun_dir)) >= cos_radius the sun's radiance on top of it; if no centre lies inside the sun's disc, the texel that
+        sun_dir names gets it."""
+        n = int(size)
+        centre = (np.arange(n, dtype=np.float64) + 0.5) * (2.0 / n) - 1.0
+        a, b = np.meshgrid(centre, centre, indexing="ij")
+        texels = np.zeros((6, n, n, 3), dtype=np.float64)
+        sun = np.asarray(sun_dir, dtype=np.float64)
+        sun = sun / np.linalg.norm(sun)
+        inside = np.zeros((6, n, n), dtype=bool)
+        for f in range(6):
+            on = np.full_like(a, -1.0 if f & 1 else 1.0)
+            d = np.stack({0: (on, a, b), 1: (a, on, b), 2: (a, b, on)}[f >> 1], axis=-1)
+            u = d / np.linalg.norm(d, axis=-1, keepdims=True)
+            t = 0.5 * (u[..., 1] + 1.0)
+            texels[f] = np.asarray(bottom, dtype=np.float64) * (1.0 - t)[..., None] + np.asarray(top, dtype=np.float64) * t[..., None]
+            inside[f] = u @ sun >= cos_radius
+        if not inside.any():
+            ax = int(np.argmax(np.abs(sun)))
+            m = abs(sun[ax])
+            rest = [sun[k] / m for k in range(3) if k != ax]
+            row = lambda c: min(n - 1, max(0, int((c + 1.0) * 0.5 * n)))
+            inside[2 * ax + (1 if sun[ax] < 0.0 else 0), row(rest[0]), row(rest[1])] = True
+        texels[inside] += np.asarray(sun_radiance, dtype=np.float64)
+        return cls(texels, sample=sample)
+
+    def device(self, renderer, sample=None):
+        """(the texels, the running sums or None) as float64 tensors on the renderer's device, kept alive by this object."""
+        import torch
+        dev = torch.device("cuda", renderer.device_id)
+        if self._device is None or self._device[0] != renderer.device_id:
+            texels = self.texels.contiguous() if self._is_tensor() else torch.from_numpy(self.table()).to(dev)
+            sums = self.cdf() if self.given_sums is None else np.ascontiguousarray(self.given_sums, dtype=np.float64)
+            if sums.shape != (6 * self.size * self.size,):
+                raise ValueError(f"sums must be [{6 * self.size * self.size}] (is {sums.shape})")
+            self._device = (renderer.device_id, texels, torch.from_numpy(sums).to(dev))
+        _, texels, cdf = self._device
+        _torch_check(torch, renderer, [("texels", texels, torch.float64, (6, self.size, self.size, 3))])
+        return texels, (cdf if (self.sample if sample is None else sample) else None)
+
+    def struct(self, texels_ptr, cdf_ptr=None):
+        """The rt_environment naming the two pointers (host or device, as the entry point wants them)."""
+        return _ffi.rt_environment(texels_ptr or None, cdf_ptr or None, self.size, 0)
+
+
 def _direct_flags(sampling, direct):
     """rt_direct.flags of sampling="area" (the light sampled by area: 0), "cone" (by solid angle: RT_DIRECT_CONE) or
     "weighted" (by solid angle, the light chosen by its contribution at the hit point: RT_DIRECT_WEIGHTED | RT_DIRECT_CONE; section 23)."""
@@ -564,13 +659,15 @@ def _direct_flags(sampling, direct):
 
 
 def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, lighting=None, direct=False, no_direct=False, shadow_rays=None,
-                     sampling="area"):
+                     sampling="area", environment=None):
     """rt_paths_step_device on two PathQueues, on torch.cuda.current_stream(): one bounce of the live paths of `qin`; the survivors go to
     `qout` in order.  fix: an int64 tensor [..., 3] holding the u64 sums' bits, added to; rays: an int64 tensor [1] that gains the live
     count, or None.  lighting: a Lighting (rt_paths_step_lit_device; its emission a float64 tensor [n, 3] on the device, or what
     Lighting.device_table makes of it), None: the unlit step.  direct: True (rt_paths_step_nee_device with the lighting's own light
     list) or a list of sphere indices / an int32 tensor on the device; no_direct: RT_STEP_NO_DIRECT; shadow_rays: an int64 tensor [1] that
-    gains the shadow rays traced, or None; sampling: "area", "cone" or "weighted", how direct lighting samples a light.  No host wait."""
+    gains the shadow rays traced, or None; sampling: "area", "cone" or "weighted", how direct lighting samples a light.  environment: an
+    Environment (rt_paths_step_env_device; no_direct and shadow_rays as for direct lighting, with which it does not combine).  No host
+    wait."""
     import torch
     _check_queue(renderer, qin, "qin")
     _check_queue(renderer, qout, "qout")
@@ -582,7 +679,8 @@ def paths_step_torch(renderer, seed, qin, qout, fix, rays=None, t_min=1e-4, ligh
     with torch.cuda.device(qin.device):
         renderer.paths_step_device(seed, qin.struct(), qout.struct(), fix.data_ptr(), fix.numel() // 3, rays.data_ptr() if rays is not None else 0,
                                    t_min, torch.cuda.current_stream().cuda_stream, lighting=lighting, direct=direct, no_direct=no_direct,
-                                   d_shadow_rays_ptr=shadow_rays.data_ptr() if shadow_rays is not None else 0, sampling=sampling)
+                                   d_shadow_rays_ptr=shadow_rays.data_ptr() if shadow_rays is not None else 0, sampling=sampling,
+                                   environment=environment)
 
 
 class Renderer:
@@ -974,15 +1072,30 @@ class Renderer:
         n = int(lights.shape[0])
         return _ffi.rt_direct(lights.data_ptr() if n else None, n, flags), lights
 
+    def _env_lighting(self, lighting, direct, environment):
+        """The Lighting an environment call takes (None: the default one, whose sky the environment replaces and which has no light)."""
+        if direct is not False and direct is not None:
+            raise ValueError("environment= does not combine with direct= (the environment and sphere lights are not sampled in one step)")
+        return lighting if lighting is not None else Lighting()
+
     def paths_step_device(self, seed, qin, qout, d_fix_ptr, npix, d_rays_ptr=0, t_min=1e-4, stream=0, flags=0, lighting=None, direct=False,
-                          no_direct=False, d_shadow_rays_ptr=0, sampling="area"):
+                          no_direct=False, d_shadow_rays_ptr=0, sampling="area", environment=None):
         """rt_paths_step_device, or with a Lighting rt_paths_step_lit_device, or with direct (True: the lighting's own light list, else
         the indices) rt_paths_step_nee_device -- no_direct: RT_STEP_NO_DIRECT; d_shadow_rays_ptr: a device u64 or 0; sampling: "area",
         "cone" (RT_DIRECT_CONE: the light sampled by solid angle) or "weighted" (... and chosen by its contribution at the hit) --; qin, qout:
-        _ffi.rt_path_queue structs of device pointers; asynchronous on `stream`."""
+        _ffi.rt_path_queue structs of device pointers; asynchronous on `stream`.  environment: an Environment: rt_paths_step_env_device
+        with the lighting's emission table (no lighting: no sphere emits), no_direct and d_shadow_rays_ptr as above."""
         direct_flags = _direct_flags(sampling, direct if lighting is not None else False)
         head = (self._h, int(seed), int(flags), float(t_min), C.byref(qin), C.byref(qout), C.c_void_p(d_fix_ptr) if d_fix_ptr else None, int(npix),
                 C.c_void_p(d_rays_ptr) if d_rays_ptr else None)
+        if environment is not None:
+            light, _keep = self._device_lighting(self._env_lighting(lighting, direct, environment))
+            texels, cdf = environment.device(self)
+            env = environment.struct(texels.data_ptr(), cdf.data_ptr() if cdf is not None else None)
+            _ffi.check(self._lib.rt_paths_step_env_device(*head, C.byref(light), C.byref(env), _ffi.RT_STEP_NO_DIRECT if no_direct else 0,
+                                                          C.c_void_p(d_shadow_rays_ptr) if d_shadow_rays_ptr else None, C.c_void_p(stream)),
+                       "rt_paths_step_env_device")
+            return
         if lighting is None:
             _ffi.check(self._lib.rt_paths_step_device(*head, C.c_void_p(stream)), "rt_paths_step_device")
             return
@@ -998,17 +1111,27 @@ class Renderer:
         light, _keep = self._device_lighting(lighting)
         _ffi.check(self._lib.rt_paths_step_lit_device(*head, C.byref(light), C.c_void_p(stream)), "rt_paths_step_lit_device")
 
-    def render_wavefront(self, cam, params, lighting=None, direct=False, sampling="area"):
+    def render_wavefront(self, cam, params, lighting=None, direct=False, sampling="area", environment=None):
         """rt_render_wavefront: the frame through the device path queue -> (the exact sums u64 [H, W, 3], the rays traced): what
         Renderer.render returns as `fix` and as stats["rays_traced"].  lighting: a Lighting (rt_render_wavefront_lit: a settable sky and
         emissive spheres), None: the unlit frame.  direct=True (rt_render_wavefront_nee: shadow rays towards the lighting's lights at
         Lambertian hits) -> (the sums, the rays traced, stats) with stats["shadow_rays"] the shadow rays traced.  sampling="cone"
         (rt_render_wavefront_nee_sampled with RT_DIRECT_CONE): the lights are sampled by solid angle instead of by area;
-        sampling="weighted" (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE): ... and chosen by their contribution at the hit point, not uniformly."""
+        sampling="weighted" (RT_DIRECT_WEIGHTED | RT_DIRECT_CONE): ... and chosen by their contribution at the hit point, not uniformly.
+        environment: an Environment (rt_render_wavefront_env: the cube map in the place of the sky, sampled at Lambertian hits when
+        environment.sample) -> (the sums, the rays traced, stats) as for direct lighting, with which it does not combine."""
         direct_flags = _direct_flags(sampling, direct if direct else False)
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         fix = np.zeros((params.height, params.width, 3), dtype=np.uint64)
         rays = C.c_uint64(0)
+        if environment is not None:
+            light, _keep = self._host_lighting(self._env_lighting(lighting, direct, environment))
+            texels, shadow = environment.table(), C.c_uint64(0)
+            env = environment.struct(texels.ctypes.data)
+            _ffi.check(self._lib.rt_render_wavefront_env(self._h, C.byref(rc), C.byref(params), C.byref(light), C.byref(env), int(environment.sample),
+                                                         fix.ctypes.data_as(C.c_void_p), C.byref(rays), C.byref(shadow), None),
+                       "rt_render_wavefront_env")
+            return fix, int(rays.value), {"rays_traced": int(rays.value), "shadow_rays": int(shadow.value)}
         if direct and lighting is None:
             raise ValueError("direct lighting needs a Lighting")
         if lighting is None:
@@ -1032,14 +1155,22 @@ class Renderer:
         return fix, int(rays.value)
 
     def render_wavefront_device(self, cam, params, d_fix_ptr, d_rays_ptr=0, stream=0, lighting=None, direct=False, d_shadow_rays_ptr=0,
-                                sampling="area"):
+                                sampling="area", environment=None):
         """rt_render_wavefront_device on raw device pointers (d_fix [H][W][3] u64, d_rays one u64 or 0); asynchronous on `stream`.
         lighting: a Lighting (rt_render_wavefront_lit_device; its emission as in paths_step_torch), None: the unlit frame.  direct (as
         in paths_step_device): rt_render_wavefront_nee_device; d_shadow_rays_ptr: a device u64 that receives the shadow rays traced, or 0;
-        sampling: "area", "cone" or "weighted", as in paths_step_device."""
+        sampling: "area", "cone" or "weighted", as in paths_step_device.  environment: an Environment (rt_render_wavefront_env_device)."""
         direct_flags = _direct_flags(sampling, direct if lighting is not None else False)
         rc = cam.to_rt_camera() if hasattr(cam, "to_rt_camera") else cam
         tail = (C.c_void_p(d_fix_ptr) if d_fix_ptr else None, C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream))
+        if environment is not None:
+            light, _keep = self._device_lighting(self._env_lighting(lighting, direct, environment))
+            texels, cdf = environment.device(self)
+            env = environment.struct(texels.data_ptr(), cdf.data_ptr() if cdf is not None else None)
+            _ffi.check(self._lib.rt_render_wavefront_env_device(self._h, C.byref(rc), C.byref(params), C.byref(light), C.byref(env), tail[0], tail[1],
+                                                                C.c_void_p(d_shadow_rays_ptr) if d_shadow_rays_ptr else None, tail[2]),
+                       "rt_render_wavefront_env_device")
+            return
         if lighting is None:
             _ffi.check(self._lib.rt_render_wavefront_device(self._h, C.byref(rc), C.byref(params), *tail), "rt_render_wavefront_device")
             return

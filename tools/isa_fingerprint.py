@@ -10,6 +10,8 @@ path steps (wavefront/rt_shade.hip: a folder of its own, so --all, which is pinn
 --paths, lists bounce_weighted_kernel too, in its place behind bounce_cone_kernel (profiles/isa_fingerprint_weighted.txt: the seven
 lines of --paths are pinned by tests that count them); --pixels, with --paths, likewise lists the two kernels of the wavefront list frames and
 their adaptive loop, path_begin_pixels_kernel and pass_add_listed_kernel, behind path_begin_kernel (profiles/isa_fingerprint_wavefront_pixels.txt).
+--env lists bounce_env_kernel of wavefront/rt_paths.hip and nothing else of that file (profiles/isa_fingerprint_env.txt); with --paths it
+stands in its place behind the other bounce kernels.
 --all: every kernel of every rtiow_amd/csrc/rt_*.hip, whatever its name, sorted by name and without the s_nop padding behind its
 last instruction -- so a line does not depend on which translation unit the kernel lives in, nor on whether it is the last one there
 (profiles/isa_fingerprint_source_split.txt, tests/test_source_layout_host.py).  --denoise-var: the same listing for the five kernels of
@@ -32,7 +34,7 @@ elif everything:
 else:
     sources = ["rtiow_amd/csrc/rt_api.hip"] + [f"rtiow_amd/csrc/rt_{flag[2:]}.hip" for flag in ("--frames", "--dense", "--features", "--trace") if flag in args]
     sources += ["rtiow_amd/csrc/wavefront/rt_shade.hip"] if "--shade" in args else []
-    sources += ["rtiow_amd/csrc/wavefront/rt_paths.hip"] if "--paths" in args else []
+    sources += ["rtiow_amd/csrc/wavefront/rt_paths.hip"] if "--paths" in args or "--env" in args else []
 dis = "\n".join(ic.build(defs, src)[1] for src in sources)
 cur, seqs = None, collections.OrderedDict()
 for line in dis.splitlines():
@@ -47,11 +49,15 @@ for line in dis.splitlines():
     if m and cur:
         seqs[cur].append(m.group(1))
 lines = []
+env_only = not everything and "--env" in args and "--paths" not in args
 for name, ops in seqs.items():
+    if env_only and "bounce_env_kernel" not in name and any(k in name for k in ("path_begin", "pass_add", "bounce_", "queue_")):
+        continue                                           # --env without --paths: of the path queue's file, the one kernel
     if not everything and not any(k in name for k in ("render_kernel", "resolve", "features_kernel", "trace_kernel", "camera_rays_kernel", "scatter_kernel",
                                                             "accumulate_kernel", "path_begin_kernel", "bounce_kernel", "bounce_lit_kernel", "bounce_nee_kernel", "bounce_cone_kernel", "queue_scan_kernel",
                                                             "queue_compact_kernel") + (("bounce_weighted_kernel",) if "--weighted" in args else ())
-                                                           + (("path_begin_pixels_kernel", "pass_add_listed_kernel") if "--pixels" in args else ())):
+                                                           + (("path_begin_pixels_kernel", "pass_add_listed_kernel") if "--pixels" in args else ())
+                                                           + (("bounce_env_kernel",) if "--env" in args else ())):
         continue
     while everything and ops and ops[-1] == "s_nop":       # the padding behind a kernel: longest behind the LAST kernel of a translation unit
         ops.pop()
